@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: upsampled points/s of the Dis-PU generator forward, 256 -> 1024 (4x), fp32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                 (N > 1: launched by torch.distributed.run)
 
 A step = one pass of the hot path over one batch of synthetic patches that already live in HBM:
 BASELINE.json configs[1] (B = 32 patches of 256 points per GPU, generator forward -> 32 x 1024 points),
 and for N > 1 configs[2]: the patch batch is sharded 32 per rank (weak scaling, no data-path collective)
 followed by ONE RCCL all-gather that reassembles the upsampled clouds on every rank.
-Rank 0 prints one JSON line (contract in the task brief) including `roofline` for the dominant kernel
-(HIP events on the launch stream) and `cpu_baseline` (the CPU oracle timed on the host cores, N = 1 only).
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and reports them (`value`,
+`ms_per_step`); --full adds the side figures: the timed loop repeated (`ms_per_step_repeats`), the split-bf16 and
+two-in-flight steps, `roofline` for the dominant kernel (HIP events on the launch stream), the per-op and train-step
+tables and `cpu_baseline` (the CPU oracle timed on the host cores, N = 1 only).
+--dump-outputs DIR writes the clouds of the last timed step as DIR/<name>.npy (float32): `coarse` and `fine` of
+rank 0's patches and, with a collective, `fine_gathered` (every rank's clouds).  Inputs and weights are seeded.
 """
 import argparse
 import json
@@ -197,18 +202,31 @@ def pmc_traffic(kern):
     return row["hbm_bytes_corrected"], src + ")"
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 (a few MB at most: the clouds of one step)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side figures (timed-loop repeats, split-bf16 and two-in-flight steps, roofline, per-op and "
+                         "train-step tables, CPU baseline); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the clouds of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--eager", action="store_true", help="do not capture the forward in a hipGraph")
     ap.add_argument("--graph-only", action="store_true", help="always replay the hipGraph (default: setup picks the faster of replay and eager launches)")
     ap.add_argument("--split-bf16", action="store_true",
                     help="EXPLORATORY, not the headline: after_conv's products as 3-way split-bf16 MFMAs (fp32-accurate, fp32 accumulate)")
     ap.add_argument("--one-stream", action="store_true", help="Generator.branches = False: the non-local cell on the launch stream (profiling passes)")
-    ap.add_argument("--no-ops", action="store_true", help="skip the per-op roofline table (roofline.ops, cpu_baseline.ops)")
+    ap.add_argument("--no-ops", action="store_true", help="with --full: skip the per-op roofline table (roofline.ops, cpu_baseline.ops)")
     args = ap.parse_args()
 
     import numpy as np
@@ -310,6 +328,21 @@ def main():
     gen.fine_out = None
 
     fine_buf = gen._ws[(PATCHES_PER_GPU, NPOINT)]["fine"]
+    coarse_buf = gen._ws[(PATCHES_PER_GPU, NPOINT)]["coarse"]
+
+    def last_outputs():
+        """what a caller of the step receives from its last call, on the host: this rank's coarse and fine clouds and, with a
+        collective, the gathered fine clouds of every rank (all on the workspace / result slots the step wrote)"""
+        res = {"coarse": coarse_buf}
+        if pipe is not None:
+            s = (pipe.steps - 1) % len(pipe.local)
+            res["fine"], res["fine_gathered"] = pipe.local[s], pipe.out[s]
+        else:
+            res["fine"] = fine_buf
+            if gathered is not None:
+                res["fine_gathered"] = gathered
+        torch.cuda.synchronize()
+        return {k: v.detach().to(torch.float32).cpu().numpy() for k, v in res.items()}
 
     def step():
         if graphs is None:
@@ -376,10 +409,12 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # variance of the figure above: the same K-step loop four more times (20 steps are ~20 ms); `value` / `ms_per_step` stay the FIRST
-    # loop's (the contract's timed region), min / median / max of all five ride along
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs())
+    # variance of the figure above (--full): the same K-step loop four more times (20 steps are ~20 ms); `value` / `ms_per_step` stay
+    # the FIRST loop's (the contract's timed region), min / median / max of all five ride along
     loops = [dt]
-    for _ in range(4):
+    for _ in range(4 if args.full else 0):
         if comm:
             dist.barrier()
         torch.cuda.synchronize()
@@ -401,7 +436,7 @@ def main():
     # k, fp32 accumulate: csrc/linear_bf16x3.hip).  fp32-accurate (tests/test_headline_gpu.py) but NOT the fmaf chain of the strict path,
     # so it rides along as a second figure; `value` above stays the strict-fp32 step.
     alt = None
-    if rank == 0 and solo and not args.split_bf16 and not args.eager:
+    if args.full and rank == 0 and solo and not args.split_bf16 and not args.eager:
         try:
             g2 = Generator(params=params, device=dev)
             g2.return_views = True
@@ -452,7 +487,7 @@ def main():
     # batch's latency-bound feature extractor fills the tail of the previous one.  Strict fp32, same kernels, same results per batch;
     # NOT `value` (the contract's step is one batch from its first kernel to its last) -- reported beside it.
     alt2 = None
-    if rank == 0 and solo and not args.split_bf16 and not args.eager:
+    if args.full and rank == 0 and solo and not args.split_bf16 and not args.eager:
         try:
             gens = [gen, Generator(params=params, device=dev)]
             gens[1].return_views = True
@@ -484,7 +519,7 @@ def main():
 
     # ---- roofline of the dominant kernel: HIP events around every launch, on the launch stream (eager pass)
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         reps = 5
         acc = {}
         # every kernel ALONE on the device: the step's second stream (Generator.branches: the non-local cell beside the local cell) is
@@ -540,7 +575,7 @@ def main():
                                 "/ time / %.1f TFLOP/s (fp32 MFMA peak); null = not an MFMA kernel (k-NN selection, gathers, 3-wide heads)"
                                 % FP32_MFMA_PEAK_TFLOPS)
 
-    if rank == 0 and solo:
+    if args.full and rank == 0 and solo:
         # what the matrix pipe of THIS chip sustains for a GEMM-like instruction mix with real data (tools/micro/mfma_power.hip, built by
         # __graft_entry__.build(): 8 accumulator tiles per wave, 2 A + 4 B LDS fragment reads per 8 MFMAs, random operands, no global
         # traffic, no barriers, no loader waves): the practical ceiling next to the datasheet `peak` -- power management, not the kernel
@@ -560,7 +595,8 @@ def main():
                                                       "fragment reads and random operands, 10 launches back to back; `peak` stays the datasheet figure"}
             except Exception as e:                             # noqa: BLE001
                 roof["sustained_peak"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0:
+    side = {}
+    if args.full and rank == 0:
         # step-level fraction of the fp32 MFMA peak: every flop the step executes (dense contractions are 97 % of them)
         ms = dt / args.steps * 1e3
         flops_step = 2.0 * step_macs_per_patch() * PATCHES_PER_GPU
@@ -571,7 +607,6 @@ def main():
                              "TFLOP/s; step_frac_reference_graph prices the same step at the reference graph's %.3f GFLOP "
                              "per patch (work removed by exact algebra counted as done)"
                              % (step_macs_per_patch() / 1e9, PATCHES_PER_GPU, FP32_MFMA_PEAK_TFLOPS, REFERENCE_FLOPS_PER_PATCH / 1e9))
-        side = {}
         if solo and not args.no_ops:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import ops_bench
@@ -589,6 +624,7 @@ def main():
                                  "exp_measured": ops_bench.EXP_PEAK,
                                  "note": "`frac` of a VALU / exp row is against the DATASHEET figure (256 CU x 4 SIMD x 32 lanes x 2.4 GHz); "
                                          "frac_measured_peak against the measured issue rate (tools/micro/valu_rate.hip)"}
+    if rank == 0:
         pts = world * PATCHES_PER_GPU * NPOINT * UP
         out = {"metric": "upsampled points/sec (256->1024, 4x)", "value": pts * args.steps / dt, "unit": "points/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": SETTLE_STEPS, "ms_per_step": dt / args.steps * 1e3,
@@ -606,44 +642,46 @@ def main():
                                           "sync": "all-gather on the compute stream after every step (round-4 behaviour)",
                                           "off": "none (compute-only reference)"}[gather_mode]),
                           "weights": "xavier-uniform seed 1234, zero bias",
-                          "parallelism": "patch-sharded x%d" % world},
-               "roofline": roof}
+                          "parallelism": "patch-sharded x%d" % world}}
+        if roof is not None:
+            out["roofline"] = roof
         if alt is not None:
             out["alt_split_bf16"] = alt
         if alt2 is not None:
             out["alt_two_in_flight"] = alt2
-        srt = sorted(loops)
-        out["ms_per_step_repeats"] = {"n": len(loops), "min": srt[0] / args.steps * 1e3, "median": srt[len(srt) // 2] / args.steps * 1e3,
-                                      "max": srt[-1] / args.steps * 1e3, "note": "the timed K-step loop run 5 times; value / ms_per_step = the first"}
-        if solo and not args.no_cpu_baseline:
+        if args.full:
+            srt = sorted(loops)
+            out["ms_per_step_repeats"] = {"n": len(loops), "min": srt[0] / args.steps * 1e3, "median": srt[len(srt) // 2] / args.steps * 1e3,
+                                          "max": srt[-1] / args.steps * 1e3, "note": "the timed K-step loop run 5 times; value / ms_per_step = the first"}
+        if args.full and solo and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(with_ops=not args.no_ops)
             except Exception as e:                             # noqa: BLE001
                 out["cpu_baseline"] = {"value": None, "unit": "points/s", "cores": 0, "kind": "port", "sample": "failed: %s: %s" % (type(e).__name__, e)}
         # The ONE JSON line stays small enough for the driver to keep it whole (round 3's ~40 KB line lost its nested tables): scalars + the
         # top-8 kernels here; the full per-kernel list, the per-op roofline table, the train-step table and the per-op CPU baseline go to a
-        # side file next to the rocprof summaries.
-        side["kernels"] = roof.pop("kernels")
-        side["kernels_note"] = roof.pop("kernels_note")
-        roof["kernels_top8"] = side["kernels"][:8]
-        if "cpu_baseline" in out and "ops" in out["cpu_baseline"]:
-            side["cpu_baseline_ops"] = out["cpu_baseline"].pop("ops")
-        if "train_step" in side and isinstance(side["train_step"], dict):
-            roof["train_step_ms"] = {k: v.get("ms_per_step") for k, v in side["train_step"].items() if isinstance(v, dict)}
-            roof["train_step_ms_min_median_max"] = {k: [v.get("ms_min"), v.get("ms_per_step"), v.get("ms_max")]
-                                                    for k, v in side["train_step"].items() if isinstance(v, dict) and "ms_min" in v}
-        side["headline"] = {k: out[k] for k in ("value", "ms_per_step", "steps", "warmup", "n_gpus")}
+        # side file, bench_out/bench_side_tables.json (not tracked: tools/collect_profiles.sh copies it into profiles/).
+        if roof is not None:
+            side["kernels"] = roof.pop("kernels")
+            side["kernels_note"] = roof.pop("kernels_note")
+            roof["kernels_top8"] = side["kernels"][:8]
+            if "cpu_baseline" in out and "ops" in out["cpu_baseline"]:
+                side["cpu_baseline_ops"] = out["cpu_baseline"].pop("ops")
+            if "train_step" in side and isinstance(side["train_step"], dict):
+                roof["train_step_ms"] = {k: v.get("ms_per_step") for k, v in side["train_step"].items() if isinstance(v, dict)}
+                roof["train_step_ms_min_median_max"] = {k: [v.get("ms_min"), v.get("ms_per_step"), v.get("ms_max")]
+                                                        for k, v in side["train_step"].items() if isinstance(v, dict) and "ms_min" in v}
+            side["headline"] = {k: out[k] for k in ("value", "ms_per_step", "steps", "warmup", "n_gpus")}
         # only the full run writes the side file: the profiled / counter passes (--no-ops, timings inflated by the profiler) must not
         # overwrite it
-        for d in ((os.path.join(ROOT, "profiles"), os.path.join(ROOT, "gpurun_out")) if (solo and not args.no_ops) else ()):
+        if args.full and solo and not args.no_ops:
             try:
-                os.makedirs(d, exist_ok=True)
-                with open(os.path.join(d, "bench_side_tables.json"), "w") as f:
+                os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+                with open(os.path.join(ROOT, "bench_out", "bench_side_tables.json"), "w") as f:
                     json.dump(side, f, indent=1)
             except OSError:
                 pass
-        if solo and not args.no_ops:
-            roof["side_tables"] = "profiles/bench_side_tables.json (keys: kernels, ops, train_step, ops_peaks, cpu_baseline_ops)"
+            roof["side_tables"] = "bench_out/bench_side_tables.json (keys: kernels, ops, train_step, ops_peaks, cpu_baseline_ops)"
         print(json.dumps(out))
     if pipe is not None:
         pipe.close()

@@ -129,10 +129,32 @@ def chunked_approxmatch_pin():
          cost=O.match_cost(a1, a2, m, contract=1))
 
 
+
+def live_seeds_golden():
+    """ref_live.npz: the inputs of tests/test_oracle.py::test_oracle_vs_reference_live (seeds 1, 2) with the reference's nnsearch,
+    threenn, query_ball_point and OpenMP knn on them, so that the test also runs where oracle/_ref cannot be built."""
+    kw = {}
+    for seed in (1, 2):
+        rng = np.random.default_rng(seed)
+        b, n, m = 2, 257 + seed, 130
+        x1 = rng.standard_normal((b, n, 3)).astype(np.float32)
+        x2 = rng.standard_normal((b, m, 3)).astype(np.float32)
+        u1, u2 = rng.random((b, n, 3)).astype(np.float32), rng.random((b, m, 3)).astype(np.float32)
+        s = "_s%d" % seed
+        kw.update({"x1" + s: x1, "x2" + s: x2, "u1" + s: u1, "u2" + s: u2})
+        kw["nn_d" + s], kw["nn_i" + s] = R.nnsearch(x1, x2)
+        kw["tn_d" + s], kw["tn_i" + s] = R.threenn(x1, x2)
+        kw["qbp" + s] = R.query_ball_point(0.3, 9, u1, u2)
+        kw["knn" + s] = R.knn_batch(x1, x2, 8, omp=True)
+    save("ref_live.npz", **kw)
+
 if __name__ == "__main__":
     import sys
     if len(sys.argv) > 1 and sys.argv[1] == "chunked":
         chunked_approxmatch_pin()
+    elif len(sys.argv) > 1 and sys.argv[1] == "live":
+        live_seeds_golden()
     else:
         main()
         chunked_approxmatch_pin()
+        live_seeds_golden()

@@ -20,6 +20,7 @@ import torch.multiprocessing as mp
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIGURES = os.path.join(ROOT, "bench_out")        # untracked: the dry runs' timings (tools/collect_profiles.sh copies them into profiles/)
 
 
 def _free_port():
@@ -273,7 +274,7 @@ def test_bench_two_ranks_dry_run(dev):
     import sys
     env = dict(os.environ, DISPU_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -395,9 +396,12 @@ def test_bench_two_ranks_overlapped_gather_costs_nothing(dev):
     import sys
     ms = {}
     for mode in ("off", "overlap", "sync"):
-        env = dict(os.environ, DISPU_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", DISPU_BENCH_GATHER=mode)
+        # OMP_WAIT_POLICY=PASSIVE: the host staging wakes OpenMP worker threads that then spin; under a CPU quota smaller than the
+        # cores a rank may run on, two ranks' spinning exhausts the quota and every thread of both is throttled for tens of ms
+        # (measured: gather on the compute stream 14.0 ms per step, 60 s throttled; passive 2.27 ms, as on an unthrottled box)
+        env = dict(os.environ, DISPU_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", DISPU_BENCH_GATHER=mode, OMP_WAIT_POLICY="PASSIVE")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3"]
+               "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--full"]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=ROOT, timeout=900)
         assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
         d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
@@ -405,8 +409,8 @@ def test_bench_two_ranks_overlapped_gather_costs_nothing(dev):
         assert (d["config"]["collective"] is not None) and d["n_gpus"] == 2
     print("two gloo ranks on one GPU, ms per step: compute-only %.3f, pipelined gather %.3f, gather on the compute stream %.3f"
           % (ms["off"], ms["overlap"], ms["sync"]))
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(ROOT, "gpurun_out", "gather_overlap_dry_run.json"), "w") as f:
+    os.makedirs(FIGURES, exist_ok=True)
+    with open(os.path.join(FIGURES, "gather_overlap_dry_run.json"), "w") as f:
         json.dump(ms, f)
     # two processes time-sharing one GPU and host-staged gloo: noisy; the exposed gather costs +25 %, the pipelined one must stay well below
     assert ms["overlap"] <= 1.15 * ms["off"] + 0.02 and ms["overlap"] < ms["sync"], ms
@@ -537,9 +541,9 @@ def test_rccl_branch_on_one_rank(dev):
     _, same, t_plain, t_gather, early, rel, s_plain, s_coll, s_thr, rel_d, t_gather_thr = res[0]
     print("one-rank RCCL dry run (8 patches): forward %.4f ms, + pipelined all-gather %.4f ms (enqueued by a comm thread: %.4f ms); "
           "train step %.4f ms, + bucketed all-reduce %.4f ms (comm thread: %.4f ms)" % (t_plain, t_gather, t_gather_thr, s_plain, s_coll, s_thr))
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+    os.makedirs(FIGURES, exist_ok=True)
     import json
-    with open(os.path.join(ROOT, "gpurun_out", "rccl_world1_dry_run.json"), "w") as f:
+    with open(os.path.join(FIGURES, "rccl_world1_dry_run.json"), "w") as f:
         json.dump({"forward_ms": t_plain, "forward_with_pipelined_all_gather_ms": t_gather, "train_step_ms": s_plain,
                    "train_step_with_bucketed_all_reduce_ms": s_coll, "param_rel_diff_per_step": rel,
                    "forward_with_all_gather_from_comm_thread_ms": t_gather_thr, "train_step_with_all_reduce_from_comm_thread_ms": s_thr,
@@ -552,7 +556,7 @@ def test_rccl_branch_on_one_rank(dev):
     # a collective call costs ~30 us of host time; these steps are launch-bound (8 patches, eager): one call per forward, two per train
     # step.  Bounds = that price + noise; the 32-patch bench step (host idle most of the time) must not move at all (next test).
     # (measured: +0.029 - 0.031 ms and +0.04 - 0.05 ms; the bounds leave 2.5 - 3x for a noisy box -- the figures themselves go to
-    # gpurun_out/rccl_world1_dry_run.json)
+    # bench_out/rccl_world1_dry_run.json)
     assert min(t_gather, t_gather_thr) <= t_plain + 0.08, (t_plain, t_gather, t_gather_thr)
     assert min(s_coll, s_thr) <= s_plain + 0.15, (s_plain, s_coll, s_thr)
 
@@ -570,7 +574,7 @@ def test_bench_one_rank_rccl_dry_run(dev):
         env = dict(os.environ, DISPU_BENCH_BACKEND="nccl", DISPU_BENCH_COLLECTIVES="1", DISPU_BENCH_GATHER=mode, HSA_ENABLE_IPC_MODE_LEGACY="0")
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--full"]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=ROOT, timeout=900)
         assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
         d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
@@ -578,7 +582,8 @@ def test_bench_one_rank_rccl_dry_run(dev):
         assert "cpu_baseline" not in d
         ms[mode], launch[mode] = d["ms_per_step_repeats"]["median"], d["config"]["launch"][:8]
     print("one-rank RCCL bench: compute-only %.4f ms (%s), pipelined all-gather %.4f ms (%s)" % (ms["off"], launch["off"], ms["overlap"], launch["overlap"]))
-    with open(os.path.join(ROOT, "gpurun_out", "rccl_world1_bench.json"), "w") as f:
+    os.makedirs(FIGURES, exist_ok=True)
+    with open(os.path.join(FIGURES, "rccl_world1_bench.json"), "w") as f:
         json.dump({"ms": ms, "launch": launch}, f)
     # what is left is not the collective: tools/debug/gather_cost.py takes the loop apart on the same one-rank group -- one graph 0.915 ms,
     # two alternating graphs 0.917, + an event recorded behind every replay and waited for by an idle side stream 0.927 - 0.931, + a

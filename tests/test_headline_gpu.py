@@ -284,3 +284,32 @@ def test_chain_input_modes_equal_producer_kernels(bench_setup, dev):
         c0, f0 = old(x)
         c1, f1 = s["gen"](x)
         assert np.array_equal(N(c0), N(c1)) and np.array_equal(N(f0), N(f1)), "B = %d" % B
+
+
+def test_bench_plain_run_dumps_the_timed_step(bench_setup, tmp_path):
+    """`bench.py --steps K --dump-outputs DIR` without --full: the headline fields only, K timed steps, and the clouds of the last
+    timed step on disk -- bit-identical to the eager forward of the same seeded patches and weights."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DISPU_BENCH_COLLECTIVES", "DISPU_BENCH_GATHER"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, "one JSON line expected, got %d" % len(lines)
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["unit"] == "points/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["metric"].startswith("upsampled points/sec")
+    assert abs(d["value"] - BENCH_B * BENCH_N * 4 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "alt_split_bf16", "alt_two_in_flight", "ms_per_step_repeats"):
+        assert k not in d, "%s belongs to --full" % k
+    assert sorted(os.listdir(tmp_path)) == ["coarse.npy", "fine.npy"]
+    s = bench_setup
+    for name, ref in (("coarse", s["c"]), ("fine", s["f"])):
+        a = np.load(str(tmp_path / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (BENCH_B, BENCH_N * 4, 3), (name, a.dtype, a.shape)
+        assert np.array_equal(a, ref), "%s.npy differs from the eager forward" % name

@@ -1,6 +1,6 @@
 """CPU tests: the oracle (oracle/dispu_oracle.c) against the committed golden vectors that were produced
 by the REFERENCE's own CPU functions, and -- when oracle/_ref is present -- against those functions
-live on fresh seeded inputs.  Bit-exact for indices and (contract=0) distances."""
+live on seeded inputs.  Bit-exact for indices and (contract=0) distances."""
 import os
 
 import numpy as np
@@ -126,22 +126,28 @@ def test_knn_point_negated_and_ties():
     assert idx[0, 0].tolist() == [1, 2, 0] and val[0, 0].tolist() == [-0.0, -0.0, -1.0]
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("seed", [1, 2])
-def test_oracle_vs_reference_live(seed):
-    rng = np.random.default_rng(seed)
-    b, n, m = 2, 257 + seed, 130
-    x1 = rng.standard_normal((b, n, 3)).astype(np.float32)
-    x2 = rng.standard_normal((b, m, 3)).astype(np.float32)
-    d, i = R.nnsearch(x1, x2)
+def test_oracle_vs_reference_live(seed, golden_dir):
+    """Seeded inputs (b = 2, n = 257 + seed, m = 130) and the reference's outputs on them, stored in ref_live.npz
+    (make_golden.py live); where oracle/_ref is built the reference functions are also run live against the stored outputs."""
+    z = g(golden_dir, "ref_live.npz")
+    s = "_s%d" % seed
+    x1, x2, u1, u2 = (z[k + s] for k in ("x1", "x2", "u1", "u2"))
+    ref = {k: z[k + s] for k in ("nn_d", "nn_i", "tn_d", "tn_i", "qbp", "knn")}
+    if R.available():
+        live = {}
+        live["nn_d"], live["nn_i"] = R.nnsearch(x1, x2)
+        live["tn_d"], live["tn_i"] = R.threenn(x1, x2)
+        live["qbp"] = R.query_ball_point(0.3, 9, u1, u2)
+        live["knn"] = R.knn_batch(x1, x2, 8, omp=True)
+        for k in ref:
+            assert np.array_equal(live[k], ref[k]), "stored reference output %s differs from the live reference" % k
     od, oi, _, _ = O.nn_distance(x1, x2, contract=0)
-    assert np.array_equal(d, od) and np.array_equal(i, oi)
-    d, i = R.threenn(x1, x2)
+    assert np.array_equal(ref["nn_d"], od) and np.array_equal(ref["nn_i"], oi)
     od, oi = O.three_nn(x1, x2, contract=0)
-    assert np.array_equal(d, od) and np.array_equal(i, oi)
-    u1, u2 = rng.random((b, n, 3)).astype(np.float32), rng.random((b, m, 3)).astype(np.float32)
-    assert np.array_equal(R.query_ball_point(0.3, 9, u1, u2), O.query_ball_point(0.3, 9, u1, u2, contract=0)[0])
-    assert np.array_equal(R.knn_batch(x1, x2, 8, omp=True), O.knn_batch(x1, x2, 8))
+    assert np.array_equal(ref["tn_d"], od) and np.array_equal(ref["tn_i"], oi)
+    assert np.array_equal(ref["qbp"], O.query_ball_point(0.3, 9, u1, u2, contract=0)[0])
+    assert np.array_equal(ref["knn"], O.knn_batch(x1, x2, 8))
 
 
 def test_edge_shapes():

@@ -17,7 +17,7 @@ for f in train_b32_bf16_bench.json train_b64_bf16_bench.json train_b64_f32_bench
 for f in stem_stamps.txt knn_stamps.txt x3_lab.txt gather_cost.txt; do [ -f $G/$T/$f ] && cp $G/$T/$f $P/${T}_$f; done
 [ -f $G/${T}_trace_bf16/timeline.txt ] && cp $G/${T}_trace_bf16/timeline.txt $P/${T}_train_bf16_timeline.txt
 [ -f $G/${T}_train_bf16/kernel_stats.csv ] && cp $G/${T}_train_bf16/kernel_stats.csv $P/${T}_train_b8_bf16_kernel_stats.csv
-for f in rccl_world1_dry_run.json rccl_world1_bench.json gather_overlap_dry_run.json; do [ -f $G/$f ] && cp $G/$f $P/${T}_$f; done
+for f in rccl_world1_dry_run.json rccl_world1_bench.json gather_overlap_dry_run.json; do [ -f bench_out/$f ] && cp bench_out/$f $P/${T}_$f; done
 [ -f $G/${T}_valu/valu_summary.json ] && cp $G/${T}_valu/valu_summary.json $P/${T}_valu_summary.json
-[ -f $G/bench_side_tables.json ] && cp $G/bench_side_tables.json $P/bench_side_tables.json
+[ -f bench_out/bench_side_tables.json ] && cp bench_out/bench_side_tables.json $P/bench_side_tables.json
 ls $P | grep ${T}_ | wc -l

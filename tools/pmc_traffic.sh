@@ -4,10 +4,11 @@
 # Usage: tools/pmc_traffic.sh <tag>  -> gpurun_out/<tag>/pmc_summary.json (+ per-pass logs)
 set -e
 TAG=${1:-r01_pmc}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-ops --eager --one-stream"
+CMD="python $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-ops --eager --one-stream"
 i=0
 for CTRS in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
     i=$((i+1))
