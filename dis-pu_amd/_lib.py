@@ -12,6 +12,8 @@ ABI_VERSION = 5       # include/dispu_hip.h: dispu_version()
 ARITH_PLAIN = 0
 ARITH_CONTRACT = 1
 ARITH_PINNED_EXP = 2   # OR-able, approx_match only (bit-reproducible exp; parity mode)
+MESH_BRUTE_FORCE = 8   # OR-able, point_to_mesh only (visit every face tile; A/B tests)
+MESH_TILE = 64         # faces per tile of point_to_mesh's face layout
 
 _vp, _i, _sz, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_long
 
@@ -162,6 +164,12 @@ SIGNATURES = {
     "dispu_pu_loss_finalize": (_i, [_vp, _vp, _l, C.c_float, C.c_float, _vp, _vp]),
     "dispu_augment": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_adam": (_i, [_l, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "dispu_point_to_mesh": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "dispu_disk_count": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dispu_disk_fill": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dispu_disk_uniformity_scratch_bytes": (_sz, [_i, _i]),
+    "dispu_disk_uniformity": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp]),
+    "dispu_row_mean_std": (_i, [_i, _i, _vp, _vp, _vp]),
 }
 
 class TnReduceDesc(C.Structure):

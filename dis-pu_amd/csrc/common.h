@@ -13,6 +13,7 @@
 #define DISPU_ARITH_CONTRACT 1  // fmaf(dz,dz, fmaf(dx,dx, dy*dy)): nvcc-contracted GPU kernels
 #define DISPU_ARITH_PINNED_EXP 2  // OR-able: approx_match uses the bit-reproducible exp (parity mode)
 #define DISPU_KNN_LANE_PER_QUERY 4  // OR-able, dispu_knn_xyz: force the lane-per-query kernel (A/B tests)
+#define DISPU_MESH_BRUTE_FORCE 8    // OR-able, dispu_point_to_mesh: visit every face tile (A/B tests)
 
 #define DISPU_CHECK_LAUNCH()                         \
     do {                                             \

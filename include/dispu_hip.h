@@ -42,6 +42,10 @@ extern "C" {
 /* OR-able, dispu_knn_xyz only: force the lane-per-query kernel instead of the wave-per-query fast path that is
  * used for n <= 1024 (identical results; A/B tests and profiling). */
 #define DISPU_KNN_LANE_PER_QUERY 4
+/* OR-able, dispu_point_to_mesh only: visit every face tile instead of culling tiles by their boxes (identical results; A/B tests). */
+#define DISPU_MESH_BRUTE_FORCE 8
+/* faces per tile of dispu_point_to_mesh's face layout */
+#define DISPU_MESH_TILE 64
 
 /* Library / ABI version.  1 = round 1.  2 = round 2: the *_ws k-NN entries, dispu_attention_project, the bf16 GEMMs (and a
  * scratch argument inserted into dispu_match_cost(_grad) under the same names -- an in-place signature change, withdrawn in 3).
@@ -50,7 +54,8 @@ extern "C" {
  * explicit size), dispu_prob_sample, dispu_selection_sort; the fused training kernels.  A symbol never changes signature again:
  * new forms get new names.  4 = round 4: additions only (dispu_attention_fwd_lse / dispu_attention_bwd, ...).
  * 5 = round 6: dispu_approx_match works inside the reference op's own temp ([b, 2(n+m)] floats; until 4 it needed
- * dispu_approx_match_scratch_bytes and had no way to refuse less); the tiled fast path is dispu_approx_match_ws with an explicit size. */
+ * dispu_approx_match_scratch_bytes and had no way to refuse less); the tiled fast path is dispu_approx_match_ws with an explicit size.
+ * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -636,6 +641,38 @@ int dispu_normalize_patches(int b, int n, const float* in, float* out, float* ce
 /* out = centroid + in * furthest per patch (model.py:310-311). */
 int dispu_denormalize_patches(int b, int m, const float* in, const float* centroid, const float* furthest, float* out,
                               void* stream);
+
+/* ---- evaluator: point-to-surface distance and disk uniformity (evaluation_code/evaluation.cpp, a CGAL + pthreads tool in the
+ * reference, and evaluate.py:53-101) ------------------------------------------------------------------------------------------- */
+/* Per point, the closest point on a triangle mesh: replaces evaluation.cpp:202-214 (AABB-tree `locate`, `point`, squared_distance).
+ * Face layout (dis-pu_amd/mesh.py:Mesh builds it once per mesh): tris [F][12] fp32 = v0.xyz, 0, v1.xyz, 0, v2.xyz, 0 in tile order,
+ * face_ids [F] the original face index of each entry, tile_box [ceil(F/64)][8] = min.xyz, 0, max.xyz, 0 of the DISPU_MESH_TILE
+ * consecutive entries of each tile (NULL: brute force).  Outputs dist [n] (Euclidean), proj [n][3] (closest surface point), face [n]
+ * (original index).  The smallest fp32 squared distance wins, an exact tie goes to the lowest original face index; the winner's
+ * point and distance are recomputed in fp64.  A tile is skipped only when its conservative lower bound is strictly above the best
+ * squared distance found so far, so the pruned path and DISPU_MESH_BRUTE_FORCE give bit-identical outputs. */
+int dispu_point_to_mesh(int n, const float* points, int F, const float* tris, const int* face_ids, const float* tile_box, float* dist,
+                        float* proj, int* face, int flags, void* stream);
+/* Disk membership, evaluation.cpp:68-115 with the EUCLIDEAN distance between the seed and the projected point (CGAL's pre-filter at
+ * :95; CGAL then tests the geodesic distance, :98-100).  Point q is in disk (i, j) iff d2 <= fl32(r_j * r_j), d2 = (dx*dx + dy*dy) + dz*dz,
+ * dx = points[q].x - seeds[i].x.  Two calls: dispu_disk_count writes offsets [S*R + 1] (int64 CSR row starts, rows seed-major
+ * i*R + j = the line order of `_disk_idx.txt`; two launches: counts, then an in-place scan); the caller reads offsets[S*R] back to
+ * size `members`, and dispu_disk_fill writes every row's point indices in ascending order (CGAL's pred_iter loop). */
+int dispu_disk_count(int S, int n, int R, const float* seeds, const float* points, const float* radii, long long* offsets,
+                     void* stream);
+int dispu_disk_fill(int S, int n, int R, const float* seeds, const float* points, const float* radii, const long long* offsets,
+                    int* members, void* stream);
+/* Disk uniformity, evaluate.py:53-101 (analyze_uniform) over a CSR of S*R disks (from dispu_disk_fill or a parsed `_disk_idx.txt`;
+ * members must index points [n][3]).  Per radius j, with expect = pct[j] * N: disks of count c < 5 are skipped; a kept disk adds
+ * (c - expect)^2 / expect * mean_a((nn_a - expect_d)^2 / expect_d), expect_d = sqrt(2 (pi r_j^2 / c) / 1.732), nn_a = the distance to
+ * the nearest OTHER member (sklearn's 2-NN: 0 for duplicates); out[j] (fp64) = the mean over kept disks, NaN if none.  Any disk size;
+ * the reductions run in a fixed order (bit-identical run to run).  scratch >= dispu_disk_uniformity_scratch_bytes(S, R). */
+size_t dispu_disk_uniformity_scratch_bytes(int S, int R);
+int dispu_disk_uniformity(int S, int R, int n, const float* points, const long long* offsets, const int* members, const double* radii,
+                          const double* pct, int N, void* scratch, size_t scratch_bytes, double* out, void* stream);
+/* per-row mean and standard deviation (ddof 0) of x[b, n] over the non-NaN entries, fp64: out [b][2] (np.nanmean / np.nanstd of
+ * evaluate.py:158-159,202-203 on the P2F distances; the std companion of dispu_row_mean_max). */
+int dispu_row_mean_std(int b, int n, const float* x, double* out, void* stream);
 
 #ifdef __cplusplus
 }
