@@ -170,6 +170,12 @@ SIGNATURES = {
     "dispu_disk_uniformity_scratch_bytes": (_sz, [_i, _i]),
     "dispu_disk_uniformity": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp]),
     "dispu_row_mean_std": (_i, [_i, _i, _vp, _vp, _vp]),
+    "dispu_geodesic_scratch_bytes": (_sz, [_i, _i]),
+    "dispu_geodesic_hash_slots": (_i, [_i]),
+    "dispu_geodesic_distances": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _sz, _vp,
+                                      _vp, _vp]),
+    "dispu_geodesic_disk_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dispu_geodesic_disk_fill": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 class TnReduceDesc(C.Structure):

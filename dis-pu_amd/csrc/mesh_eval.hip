@@ -338,6 +338,12 @@ __global__ __launch_bounds__(256) void row_mean_std_kernel(int n, const float* _
     }
 }
 
+// the in-place scan of dispu_disk_count, for the other CSR builders (geodesic.hip)
+int disk_scan_launch(long long M, long long* offsets, hipStream_t st) {
+    hipLaunchKernelGGL(disk_scan_kernel, dim3(1), dim3(SCAN_BS), 0, st, M, offsets);
+    return (int)hipGetLastError();
+}
+
 }  // namespace dispu
 
 using namespace dispu;

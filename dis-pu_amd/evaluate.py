@@ -4,8 +4,9 @@ tf_nndistance and runs one cloud pair per session call; here both clouds are nor
 (dispu_normalize_patches + dispu_nn_distance at (1, 8192, 8192)) and only four scalars travel to the host.
 
 With a mesh (dis-pu_amd/mesh.py) the P2F and uniformity columns of evaluate.py:53-101,163-180 are added: the reference reads them
-from the files of its CGAL tool (evaluation_code/evaluation.cpp); here they are computed on the device, with Euclidean instead of
-geodesic disks (mode "euclidean"), or read from existing CGAL files (mode "cgal_files")."""
+from the files of its CGAL tool (evaluation_code/evaluation.cpp); here they are computed on the device, with Euclidean disks (mode
+"euclidean", the default) or with the CGAL tool's exact geodesic disks (mode "geodesic"), or read from existing CGAL files (mode
+"cgal_files")."""
 import csv
 import os
 from glob import glob
@@ -19,11 +20,13 @@ from .tf_nndistance import nn_distance
 from .upsample import normalize_patches
 
 
-def evaluate_pair(pred, gt, mesh=None, seeds=1000, seed=0, percentages=M.DEFAULT_PERCENTAGES):
+def evaluate_pair(pred, gt, mesh=None, seeds=1000, seed=0, percentages=M.DEFAULT_PERCENTAGES, disks="euclidean"):
     """pred [n,3], gt [m,3] device tensors or arrays -> {"CD": mean fwd + mean bwd, "hausdorff": max fwd + max bwd}.
     With mesh (a mesh.Mesh of the ground-truth surface) the dict also holds "p2f avg" / "p2f std" (P2F of the raw predicted
-    points) and "uniform_<j>" per percentage, with "uniformity_mode": "euclidean" (Euclidean disks, see mesh.py); seeds is a
+    points) and "uniform_<j>" per percentage, with "uniformity_mode": disks ("euclidean" or "geodesic", see mesh.py); seeds is a
     count drawn with `seed` or user-given (face_id, b0, b1, b2) rows (mesh.mesh_metrics)."""
+    if disks not in M.DISK_MODES:
+        raise ValueError("disks must be one of %s, got %r" % (M.DISK_MODES, disks))
     dev = pred.device if isinstance(pred, torch.Tensor) else torch.device("cuda:0")
     p = (pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred[:, :3], np.float32)).to(dev))
     g = (gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt[:, :3], np.float32)).to(dev))
@@ -39,9 +42,9 @@ def evaluate_pair(pred, gt, mesh=None, seeds=1000, seed=0, percentages=M.DEFAULT
     mf, xf, mb, xb = (float(v) for v in out.cpu())
     res = {"CD": mf + mb, "hausdorff": xf + xb, "cd_forward": mf, "cd_backward": mb}
     if mesh is not None:
-        mm = M.mesh_metrics(p, mesh, seeds=seeds, seed=seed, percentages=percentages)
+        mm = M.mesh_metrics(p, mesh, seeds=seeds, seed=seed, percentages=percentages, disks=disks)
         res.update(_mesh_row(mm["p2f avg"], mm["p2f std"], mm["uniform"]))
-        res["uniformity_mode"] = "euclidean"
+        res["uniformity_mode"] = disks
     return res
 
 
@@ -68,14 +71,17 @@ def _from_cgal_files(pred_path, dev, percentages):
 
 
 def evaluate_dirs(pred_dir, gt_dir, csv_name="evaluation.csv", mesh_dir=None, write_cgal_files=False, use_cgal_files=False,
-                  seeds=1000, seed=0, percentages=M.DEFAULT_PERCENTAGES):
+                  seeds=1000, seed=0, percentages=M.DEFAULT_PERCENTAGES, disks="euclidean"):
     """evaluate.py:128-204: every gt/<name>.xyz against pred/<name>.xyz; writes the CSV next to the predictions and returns the
     rows plus the averages.  Without mesh_dir / use_cgal_files: the CD / hausdorff columns only, as before.
-    mesh_dir: where mesh_dir/<name>.off exists the row gains "p2f avg", "p2f std", "uniform_<j>" (Euclidean disks) and the CSV
-    has the reference's seven columns; write_cgal_files writes the CGAL tool's three files beside each such prediction.
+    mesh_dir: where mesh_dir/<name>.off exists the row gains "p2f avg", "p2f std", "uniform_<j>" (disks: "euclidean", the default,
+    or "geodesic", the CGAL tool's membership) and the CSV has the reference's seven columns; write_cgal_files writes the CGAL
+    tool's three files beside each such prediction, `_disk_idx.txt` with the disks of that mode.
     use_cgal_files: where the CGAL tool's files exist beside a prediction, P2F and the disks are read from them instead (the
     reference's route, geodesic disks included).  In the avg row P2F is over all files' distances concatenated (:200-204) and
     uniformity is the mean over files."""
+    if disks not in M.DISK_MODES:
+        raise ValueError("disks must be one of %s, got %r" % (M.DISK_MODES, disks))
     rows = []
     p2f_all, uni_all = [], []
     dev = torch.device("cuda:0")
@@ -94,8 +100,8 @@ def evaluate_dirs(pred_dir, gt_dir, csv_name="evaluation.csv", mesh_dir=None, wr
             row["uniformity_mode"] = "cgal_files"
         elif mesh_path and os.path.isfile(mesh_path):
             p = torch.from_numpy(np.ascontiguousarray(pred, np.float32)).to(dev)
-            mm = M.mesh_metrics(p, M.Mesh.from_off(mesh_path, dev), seeds=seeds, seed=seed, percentages=percentages)
-            row["uniformity_mode"] = "euclidean"
+            mm = M.mesh_metrics(p, M.Mesh.from_off(mesh_path, dev), seeds=seeds, seed=seed, percentages=percentages, disks=disks)
+            row["uniformity_mode"] = disks
             if write_cgal_files:
                 M.write_cgal_files(pred_path, p.cpu().numpy(), mm["dist"].cpu().numpy(), mm["proj"].cpu().numpy(), mm["radii"],
                                    mm["offsets"].cpu().numpy(), mm["members"].cpu().numpy())

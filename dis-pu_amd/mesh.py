@@ -5,12 +5,19 @@ membership, `<pred>_point2mesh_distance.txt` / `_radius.txt` / `_disk_idx.txt`) 
 evaluate.py:53-101 (analyze_uniform).  The geometry runs in csrc/mesh_eval.hip; this module loads meshes, builds the face
 tiles once per mesh, draws seeds on the host and reads / writes the CGAL tool's files.
 
+Disk membership has two modes (mesh_metrics(disks=...), evaluate_pair / evaluate_dirs, tools/evaluate.py --disks):
+  * "euclidean" (the default): q is in disk (i, j) iff the straight-line distance between seed i and the projected point q is at
+    most r_j (disk_members, fp32).  That is CGAL's own pre-filter (evaluation.cpp:95) and a lower bound of the geodesic: on smooth
+    parts at these radii the two agree to about 0.1 % (sphere of radius 0.88, r = 0.157: chord / arc = 0.9987); across creases and
+    thin features a Euclidean disk can hold extra points;
+  * "geodesic": CGAL's membership (Surface_mesh_shortest_path, evaluation.cpp:85-115): the points that pass the straight-line
+    pre-filter at max(radii) are kept iff their exact fp64 geodesic distance on the polyhedral surface from the seed's face location
+    is at most (double)r_j (geodesic_disk_members, csrc/geodesic.hip: Chen-Han / Xin-Wang window propagation, one workgroup per
+    seed).  The `_disk_idx.txt` written in this mode is the one the CGAL tool writes for the same seeds.  It needs an
+    edge-manifold mesh (ValueError otherwise); its tables are built on first use (Mesh.geodesic_tables).
+Where CGAL outputs exist, evaluate.evaluate_dirs(use_cgal_files=True) reads them instead.
+
 Semantics that differ from the CGAL tool, on purpose:
-  * disk membership uses the EUCLIDEAN distance between the seed and a projected point, not CGAL's geodesic distance
-    (Surface_mesh_shortest_path, evaluation.cpp:98-100).  The straight line is CGAL's own pre-filter (:95) and a lower bound of the
-    geodesic: on smooth parts at these radii the two agree to about 0.1 % (sphere of radius 0.88, r = 0.157: chord / arc = 0.9987);
-    across creases and thin features a Euclidean disk can hold extra points.  Exact geodesics are not computed.  Where CGAL
-    outputs exist, evaluate.evaluate_dirs(use_cgal_files=True) reads them instead (geodesic disks included);
   * seeds come from a NumPy generator: CGAL::Random's stream cannot be reproduced, so seeded results match each other, not the
     CGAL tool's, and uniformity is a statistic over a different random set of 1000 disks;
   * the nearest other disk member replaces sklearn's 2-NN (`dis[:, 1]`): the same value, 0 for duplicated points as in sklearn.
@@ -21,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._util import f32, req
+from ._util import f32, i32, req
 
 DEFAULT_PERCENTAGES = (0.008, 0.012)     # evaluation.cpp:259, evaluate.py:46
 
@@ -103,6 +110,59 @@ def face_tiles(verts, faces):
     return tris.reshape(F, 12), order.astype(np.int32), box.reshape(T, 8)
 
 
+def geodesic_tables(verts, faces):
+    """Host tables of the exact geodesic disks (csrc/geodesic.hip), all fp64 geometry:
+      verts64 [V,3] f64; faces [F,3] i32;
+      twin [F,3] i32: for edge k of face f (f[k] -> f[k+1]) the half-edge g*3 + k' of the other face on that edge, -1 on a boundary;
+      edge_geo [F,3,3] f64: (L, cx, cy) of edge k: its length and the opposite vertex f[k+2] in the frame with f[k] at the origin
+        and f[k+1] at (L, 0), cy > 0;
+      angle_sum [V] f64, boundary [V] bool, pseudo [V] i32: 1 where a shortest path may turn (angle sum >= 2 pi, or a boundary
+        vertex: the pseudo-sources of Chen & Han / Xin & Wang);
+      fan_off [V+1] i64, fan [3F] i32: per vertex, the corners f*3 + j (faces[f, j] == v) of the faces around it, ascending.
+    Twins come from sorting the undirected edge keys; an edge shared by more than two faces raises ValueError (CGAL's Surface_mesh
+    cannot hold such a mesh either), and so does a degenerate (zero-area) face."""
+    v = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+    fc = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
+    F, V = fc.shape[0], v.shape[0]
+    a, b = fc, np.roll(fc, -1, axis=1)                               # edge k: f[k] -> f[k+1]
+    key = (np.minimum(a, b) * V + np.maximum(a, b)).reshape(-1)
+    order = np.argsort(key, kind="stable")
+    ks = key[order]
+    start = np.concatenate([[True], ks[1:] != ks[:-1]])
+    gid = np.cumsum(start) - 1
+    cnt = np.bincount(gid)
+    if cnt.size and cnt.max() > 2:
+        e = int(ks[np.argmax(start & (cnt[gid] > 2))])
+        raise ValueError("non-manifold mesh: edge (%d, %d) is shared by %d faces; geodesic disks need an edge-manifold mesh"
+                         % (e // V, e % V, int(cnt.max())))
+    twin = np.full(3 * F, -1, np.int64)
+    pair = np.nonzero(start[:-1] & ~start[1:])[0] if ks.size > 1 else np.zeros(0, np.int64)
+    twin[order[pair]] = order[pair + 1]
+    twin[order[pair + 1]] = order[pair]
+    twin = twin.reshape(F, 3)
+    p0, p1, p2 = v[a], v[b], v[np.roll(fc, -2, axis=1)]             # [F,3,3]: f[k], f[k+1], f[k+2] per edge k
+    e = p1 - p0
+    L = np.linalg.norm(e, axis=2)
+    cr = np.linalg.norm(np.cross(e, p2 - p0), axis=2)
+    if np.any(L <= 0) or np.any(cr <= 0):
+        raise ValueError("degenerate face %d: geodesic disks need faces of positive area" % int(np.nonzero((L <= 0).any(1) | (cr <= 0).any(1))[0][0]))
+    geo = np.stack([L, np.einsum("fkc,fkc->fk", p2 - p0, e) / L, cr / L], axis=2)
+    # corner angle at f[k] between edges k and k-1
+    u, w = p1 - p0, np.roll(p0, 1, axis=1) - p0                      # roll: f[k-1] - f[k]
+    ang = np.arctan2(np.linalg.norm(np.cross(u, w), axis=2), np.einsum("fkc,fkc->fk", u, w))
+    angle_sum = np.bincount(fc.reshape(-1), weights=ang.reshape(-1), minlength=V)
+    boundary = np.zeros(V, bool)
+    bd = (twin < 0)
+    boundary[a[bd]] = True
+    boundary[b[bd]] = True
+    pseudo = ((angle_sum >= 2.0 * np.pi) | boundary).astype(np.int32)
+    corner = np.argsort(fc.reshape(-1), kind="stable")
+    fan_off = np.zeros(V + 1, np.int64)
+    fan_off[1:] = np.cumsum(np.bincount(fc.reshape(-1), minlength=V))
+    return {"verts64": v, "faces": fc.astype(np.int32), "twin": twin.astype(np.int32), "edge_geo": geo, "angle_sum": angle_sum,
+            "boundary": boundary, "pseudo": pseudo, "fan_off": fan_off, "fan": corner.astype(np.int32)}
+
+
 class Mesh(object):
     """A triangle mesh resident on the device in the face layout of dispu_point_to_mesh (include/dispu_hip.h): faces sorted by the
     Morton code of their centroids (a one-time host sort, the counterpart of CGAL's AABB-tree build), tiles of 64 with fp32 boxes.
@@ -141,6 +201,17 @@ class Mesh(object):
     @property
     def num_faces(self):
         return self.faces.shape[0]
+
+    def geodesic_tables(self):
+        """The host tables and device copies of geodesic_tables(verts, faces), built on the first call and cached (Euclidean users
+        never pay for them).  Raises ValueError on a non-manifold mesh."""
+        g = getattr(self, "_geodesic", None)
+        if g is None:
+            g = geodesic_tables(self.verts, self.faces)
+            for k in ("verts64", "faces", "twin", "edge_geo", "pseudo", "fan_off", "fan"):
+                g["dev_" + k] = torch.from_numpy(np.ascontiguousarray(g[k])).to(self.device)
+            self._geodesic = g
+        return g
 
     def surface_points(self, face_ids, bary):
         """b0 v0 + b1 v1 + b2 v2 of each (face, barycentrics) in float64 (CGAL's shortest_paths.point, evaluation.cpp:253)."""
@@ -266,6 +337,99 @@ def uniformity(points, offsets, members, radii, percentages=DEFAULT_PERCENTAGES,
     return out.cpu().numpy()
 
 
+# ------------------------------------------------------------------------------------------------------------- geodesic disks -
+GEODESIC_ARENA = 4096                 # windows per seed in the first pass; an overflowing seed is rerun with 4x as many
+_GEODESIC_ARENA_MAX = 1 << 22
+_GEODESIC_SCRATCH_BUDGET = 256 << 20  # bytes of window arena per launch (seeds are launched in chunks that fit)
+
+
+def _seed_arrays(mesh, seed_faces, seed_bary):
+    fid = np.ascontiguousarray(seed_faces, np.int64).reshape(-1)
+    bary = np.ascontiguousarray(seed_bary, np.float64).reshape(-1, 3)
+    req(fid.shape[0] == bary.shape[0], "seed_faces and seed_bary differ in length")
+    req(fid.size == 0 or (fid.min() >= 0 and fid.max() < mesh.num_faces), "seed face id out of range")
+    req(np.all(bary >= 0.0) and np.all(np.abs(bary.sum(axis=1) - 1.0) <= 1e-9), "seed barycentrics must be >= 0 and sum to 1")
+    return fid.astype(np.int32), bary
+
+
+def _geodesic_launch(T, fid, bary, p, pf, cand_off, cand, a, b, max_dist, cap, dist, status):
+    """seeds [a, b) (consecutive: their candidate rows are a view of the CSR) in chunks whose arenas fit the scratch budget"""
+    L, st, dev = _lib.lib(), _lib.stream_ptr(p.device), p.device
+    per = max(1, _GEODESIC_SCRATCH_BUDGET // max(1, L.dispu_geodesic_scratch_bytes(1, cap)))
+    for c0 in range(a, b, per):
+        c1 = min(b, c0 + per)
+        sf = torch.from_numpy(fid[c0:c1]).to(dev)
+        sb = torch.from_numpy(np.ascontiguousarray(bary[c0:c1])).to(dev)
+        nbytes = L.dispu_geodesic_scratch_bytes(c1 - c0, cap)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.dispu_geodesic_distances(
+            c1 - c0, _lib.ptr(sf), _lib.ptr(sb), _lib.ptr(T["dev_verts64"]), _lib.ptr(T["dev_faces"]), _lib.ptr(T["dev_twin"]),
+            _lib.ptr(T["dev_edge_geo"]), _lib.ptr(T["dev_pseudo"]), _lib.ptr(T["dev_fan_off"]), _lib.ptr(T["dev_fan"]), p.shape[0],
+            _lib.ptr(p), _lib.ptr(pf), _lib.C.c_void_p(cand_off.data_ptr() + 8 * c0), _lib.ptr(cand), float(max_dist), int(cap),
+            _lib.ptr(scratch), nbytes, _lib.ptr(dist), _lib.C.c_void_p(status.data_ptr() + 4 * c0), st), "dispu_geodesic_distances")
+
+
+def geodesic_distances(mesh, seed_faces, seed_bary, points, point_faces, max_dist, arena=GEODESIC_ARENA):
+    """Exact geodesic distances from seeds on the surface (face ids [S], barycentrics [S,3] f64; zeros allowed: a seed on an edge or a
+    vertex) to the points [n,3] (device f32, on the surface: point_to_mesh's proj) in their faces point_faces [n] (device i32) whose
+    straight-line distance to the seed is at most max_dist (widened by 2^-12 relative: the pre-filter must not drop a point the
+    geodesic keeps).  -> (cand_off [S+1] i64, cand i32: per seed its candidate points ascending, dist f64 aligned with cand: the
+    geodesic distance, +inf above max_dist), all on the device.  csrc/geodesic.hip; a seed whose window arena (`arena` windows)
+    overflows is rerun with 4x the arena, never truncated."""
+    T = mesh.geodesic_tables()
+    p, pf = f32(points, "points"), i32(point_faces, "point_faces").reshape(-1)
+    req(p.dim() == 2 and p.shape[1] == 3 and p.shape[0] > 0, "points must be of shape (#points,3)")
+    req(pf.shape[0] == p.shape[0], "point_faces must hold one face per point")
+    req(int(pf.min().item()) >= 0 and int(pf.max().item()) < mesh.num_faces, "point face id out of range")
+    req(p.device == mesh.device and pf.device == mesh.device, "points and mesh live on different devices")
+    req(float(max_dist) >= 0.0, "max_dist must be >= 0")
+    req(int(arena) > 0, "arena must be positive")
+    fid, bary = _seed_arrays(mesh, seed_faces, seed_bary)
+    S, dev = fid.shape[0], p.device
+    seed_pts = torch.from_numpy(mesh.surface_points(fid, bary).astype(np.float32)).to(dev)
+    rc = np.float32(float(max_dist) * (1.0 + 2.0 ** -12))
+    cand_off, cand = disk_members(seed_pts, p, np.array([rc], np.float32)) if S else (torch.zeros(1, dtype=torch.int64, device=dev),
+                                                                                     torch.zeros(0, dtype=torch.int32, device=dev))
+    total = int(cand_off[S].item())
+    dist = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+    cand_buf = cand if cand.numel() > 0 else torch.zeros(1, dtype=torch.int32, device=dev)
+    status = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
+    todo, cap = np.arange(S), int(arena)
+    while todo.size:
+        runs = np.split(todo, np.nonzero(np.diff(todo) != 1)[0] + 1)
+        for r in runs:
+            _geodesic_launch(T, fid, bary, p, pf, cand_off, cand_buf, int(r[0]), int(r[-1]) + 1, max_dist, cap, dist, status)
+        st = status.cpu().numpy()[:S]
+        todo = todo[st[todo] != 0]
+        if todo.size:
+            req(cap < _GEODESIC_ARENA_MAX, "geodesic disks: %d seeds still overflow a %d-window arena" % (todo.size, cap))
+            cap *= 4
+    return cand_off, cand, dist[:total]
+
+
+def geodesic_disk_members(mesh, seed_faces, seed_bary, points, point_faces, radii, arena=GEODESIC_ARENA):
+    """Geodesic disks, the CGAL tool's membership (evaluation.cpp:85-115): point q is in disk (i, j) iff its straight-line distance to
+    seed i passes the pre-filter at max(radii) and geodesic(seed i, q) <= (double)fl32(r_j).  Same arguments as geodesic_distances
+    with the float radii [R]; -> (offsets [S*R+1] i64, members i32) on the device, in disk_members' CSR layout (rows i*R + j,
+    members ascending)."""
+    r = np.asarray(radii, np.float32).reshape(-1)
+    req(r.shape[0] > 0, "at least one radius")
+    cand_off, cand, dist = geodesic_distances(mesh, seed_faces, seed_bary, points, point_faces, float(r.max()), arena)
+    S, R, dev = cand_off.shape[0] - 1, r.shape[0], cand_off.device
+    rd = torch.from_numpy(r).to(dev)
+    offsets = torch.empty(S * R + 1, dtype=torch.int64, device=dev)
+    L, st = _lib.lib(), _lib.stream_ptr(dev)
+    d = dist if dist.numel() > 0 else torch.zeros(1, dtype=torch.float64, device=dev)
+    c = cand if cand.numel() > 0 else torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(L.dispu_geodesic_disk_count(S, R, _lib.ptr(cand_off), _lib.ptr(d), _lib.ptr(rd), _lib.ptr(offsets), st),
+               "dispu_geodesic_disk_count")
+    total = int(offsets[S * R].item())
+    members = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    _lib.check(L.dispu_geodesic_disk_fill(S, R, _lib.ptr(cand_off), _lib.ptr(c), _lib.ptr(d), _lib.ptr(rd), _lib.ptr(offsets),
+                                          _lib.ptr(members), st), "dispu_geodesic_disk_fill")
+    return offsets, members[:total]
+
+
 # ------------------------------------------------------------------------------------------------------------- CGAL files -----
 def cgal_paths(pred_path):
     """the three files the CGAL tool writes beside a prediction (evaluation.cpp:194-197,262,303)."""
@@ -319,10 +483,15 @@ def read_cgal_files(pred_path):
 
 
 # ------------------------------------------------------------------------------------------------------------- one cloud ------
-def mesh_metrics(pred, mesh, seeds=1000, seed=0, percentages=DEFAULT_PERCENTAGES):
+DISK_MODES = ("euclidean", "geodesic")
+
+
+def mesh_metrics(pred, mesh, seeds=1000, seed=0, percentages=DEFAULT_PERCENTAGES, disks="euclidean"):
     """P2F and uniformity of one predicted cloud pred [n,3] (device f32, raw coordinates: the mesh's frame) against `mesh`.
     seeds: a count (sample_surface_seeds(mesh, seeds, seed)) or user-given (face_ids, bary) / an [S,4] array of
-    (face_id, b0, b1, b2) rows.  Returns a dict with the scalars and the device arrays behind them."""
+    (face_id, b0, b1, b2) rows.  disks: "euclidean" (disk_members, the default) or "geodesic" (geodesic_disk_members, CGAL's
+    membership).  Returns a dict with the scalars and the device arrays behind them."""
+    req(disks in DISK_MODES, "disks must be one of %s, got %r" % (DISK_MODES, disks))
     p = f32(pred, "pred")
     if isinstance(seeds, (int, np.integer)):
         fid, bary = sample_surface_seeds(mesh, int(seeds), seed)
@@ -334,7 +503,10 @@ def mesh_metrics(pred, mesh, seeds=1000, seed=0, percentages=DEFAULT_PERCENTAGES
     seed_pts = torch.from_numpy(mesh.surface_points(fid, bary).astype(np.float32)).to(p.device)
     dist, proj, face = point_to_mesh(p, mesh)
     radii = disk_radii(mesh, percentages)
-    offsets, members = disk_members(seed_pts, proj, radii)
+    if disks == "geodesic":
+        offsets, members = geodesic_disk_members(mesh, fid, bary, proj, face, radii)
+    else:
+        offsets, members = disk_members(seed_pts, proj, radii)
     uni = uniformity(proj, offsets, members, radii.astype(np.float64), np.asarray(percentages, np.float64), N=p.shape[0])
     m, s = mean_std(dist)
     return {"p2f avg": m, "p2f std": s, "uniform": uni, "dist": dist, "proj": proj, "face": face, "radii": radii,

@@ -55,7 +55,8 @@ extern "C" {
  * new forms get new names.  4 = round 4: additions only (dispu_attention_fwd_lse / dispu_attention_bwd, ...).
  * 5 = round 6: dispu_approx_match works inside the reference op's own temp ([b, 2(n+m)] floats; until 4 it needed
  * dispu_approx_match_scratch_bytes and had no way to refuse less); the tiled fast path is dispu_approx_match_ws with an explicit size.
- * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std): additions only. */
+ * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std) and its geodesic disks
+ * (dispu_geodesic_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -670,6 +671,30 @@ int dispu_disk_fill(int S, int n, int R, const float* seeds, const float* points
 size_t dispu_disk_uniformity_scratch_bytes(int S, int R);
 int dispu_disk_uniformity(int S, int R, int n, const float* points, const long long* offsets, const int* members, const double* radii,
                           const double* pct, int N, void* scratch, size_t scratch_bytes, double* out, void* stream);
+/* Exact geodesic disks, evaluation.cpp:85-115 (Surface_mesh_shortest_path, one source per seed; shortest_distance_to_source_points for
+ * every projected point that passes the straight-line pre-filter at :95).  Chen-Han / Xin-Wang window propagation in parallel
+ * rounds, one workgroup per seed, fp64 throughout (csrc/geodesic.hip).  Mesh tables (dis-pu_amd/mesh.py:geodesic_tables): verts
+ * [V][3] f64, faces [F][3], twin [F][3] (g*3 + k' of the other face on edge k, -1 on a boundary), edge_geo [F][3][3] f64 (L, cx, cy of
+ * edge k), pseudo [V] (1: saddle or boundary vertex), fan_off [V+1] i64 / fan (corners f*3 + j around each vertex).
+ * Seeds: seed_face [S], seed_bary [S][3] f64 (zeros allowed: a seed on an edge or a vertex).  Targets: points [n][3] with their faces
+ * point_face [n] (dispu_point_to_mesh's proj / face); the candidates of seed i are cand[cand_off[i] .. cand_off[i+1]) (ascending point
+ * indices, e.g. dispu_disk_count / dispu_disk_fill at max_dist widened by a few ulps).  Writes dist[c] (fp64, aligned with cand) = the
+ * geodesic distance from seed i to point cand[c], +inf above max_dist, and status[i] = 0, or 1 / 2 when the seed's window arena
+ * (window_cap windows) or its vertex table (dispu_geodesic_hash_slots(window_cap) slots) overflowed: that seed's distances are then
+ * not written and the caller reruns it with a larger window_cap.  scratch >= dispu_geodesic_scratch_bytes(S, window_cap), refused
+ * (and left untouched) if smaller.  Bit-identical run to run. */
+size_t dispu_geodesic_scratch_bytes(int S, int window_cap);
+int dispu_geodesic_hash_slots(int window_cap);
+int dispu_geodesic_distances(int S, const int* seed_face, const double* seed_bary, const double* verts, const int* faces, const int* twin,
+                             const double* edge_geo, const int* pseudo, const long long* fan_off, const int* fan, int n, const float* points,
+                             const int* point_face, const long long* cand_off, const int* cand, double max_dist, int window_cap,
+                             void* scratch, size_t scratch_bytes, double* dist, int* status, void* stream);
+/* Geodesic disk membership from those distances, evaluation.cpp:98-100: point cand[c] is in disk (i, j) iff dist[c] <= (double)radii[j].
+ * The same two-call CSR as dispu_disk_count / dispu_disk_fill: offsets [S*R + 1] int64, rows seed-major i*R + j, members ascending. */
+int dispu_geodesic_disk_count(int S, int R, const long long* cand_off, const double* dist, const float* radii, long long* offsets,
+                              void* stream);
+int dispu_geodesic_disk_fill(int S, int R, const long long* cand_off, const int* cand, const double* dist, const float* radii,
+                             const long long* offsets, int* members, void* stream);
 /* per-row mean and standard deviation (ddof 0) of x[b, n] over the non-NaN entries, fp64: out [b][2] (np.nanmean / np.nanstd of
  * evaluate.py:158-159,202-203 on the P2F distances; the std companion of dispu_row_mean_max). */
 int dispu_row_mean_std(int b, int n, const float* x, double* out, void* stream);
