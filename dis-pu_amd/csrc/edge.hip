@@ -682,6 +682,10 @@ DISPU_EXPORT int dispu_edge_dense_conv(int npoints, int n_per_cloud, int C, cons
     return (int)hipGetLastError();
 }
 
+DISPU_EXPORT int dispu_linear(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw, int transb,
+                              const float* bias, int act, float* Y, long ldy, long sy, const float* R1, long ldr1, long sr1, const float* R2,
+                              long ldr2, long sr2, void* stream);     // linear.hip
+
 // One dense block of feature_extraction_GCN (Common/ops.py:1437-1486) in one launch: knn_point_2(k + 1, F, F) (tf_util.py:618-651) ->
 // get_edge_feature over neighbours ioff .. ioff + 15 (ops.py:1856-1877) -> dense_conv (:1897-1915).  Same results, bit for bit, as
 // dispu_knn_feat_strided followed by dispu_edge_dense_conv.  Clouds of up to 256 points (n_per_cloud even, >= ksel); idx_out (nullable):
@@ -706,10 +710,13 @@ DISPU_EXPORT int dispu_stem_block(int npoints, int n_per_cloud, int C, const flo
     if (parts > (gpc + 7) / 8) parts = (gpc + 7) / 8;
     if (parts < (gpc + EK_MAXQ / 2 - 1) / (EK_MAXQ / 2)) parts = (gpc + EK_MAXQ / 2 - 1) / (EK_MAXQ / 2);   // at most EK_MAXQ points per workgroup
     const int per = (gpc + parts - 1) / parts;
+    const float* Wp_fused = Wp;
     if (Wp != nullptr) {       // the bottleneck conv's operands reuse LDS regions of the earlier phases: both must fit
         const long wcap = (long)n_per_cloud * (C + 4) + per * 48 + ((n_per_cloud + 3) & ~3) + EK_MAXQ * EK_NP, xcap = (C == 24 ? 84 : 132) * 64;
-        if ((long)(72 + C + k_old) * 48 > wcap || (long)per * 2 * (k_old + 4) > xcap || (ldy & 3) || (((uintptr_t)Y) & 15) || (((uintptr_t)Wp) & 15))
-            return (int)hipErrorInvalidValue;
+        if ((ldy & 3) || (((uintptr_t)Y) & 15) || (((uintptr_t)Wp) & 15)) return (int)hipErrorInvalidValue;
+        // Small clouds leave too little of it (the generator's third block, K = 360, below ~160 points): the conv then runs as a
+        // dispu_linear launch of its own after the block -- the epilogue's arithmetic is dispu_linear's, so the results are the same.
+        if ((long)(72 + C + k_old) * 48 > wcap || (long)per * 2 * (k_old + 4) > xcap) Wp_fused = nullptr;
     }
     const size_t bytes = (size_t)((C == 24 ? 84 : 132) * 64 + EK_MAXQ * (72 + C + 4)) * sizeof(float) + (size_t)n_per_cloud * (C + 4) * sizeof(float) +
                          (size_t)per * 2 * 24 * sizeof(float) + (size_t)((n_per_cloud + 3) & ~3) * sizeof(float) +
@@ -724,9 +731,11 @@ DISPU_EXPORT int dispu_stem_block(int npoints, int n_per_cloud, int C, const flo
     }
     if (C == 24)
         hipLaunchKernelGGL((edge_dense_conv_mfma_kernel<24, true, true, true>), dim3(clouds, parts), dim3(512), bytes, s, npoints, n_per_cloud, F, ldf,
-                           nullptr, 0, ioff, W0, b0, W1, b1, W2, b2, Y, ldy, idx_out, ksel, Wp, bp, k_old, P, ldp, xyz, Wl, bl, Lout, ldl);
+                           nullptr, 0, ioff, W0, b0, W1, b1, W2, b2, Y, ldy, idx_out, ksel, Wp_fused, bp, k_old, P, ldp, xyz, Wl, bl, Lout, ldl);
     else
         hipLaunchKernelGGL((edge_dense_conv_mfma_kernel<48, true, true, true>), dim3(clouds, parts), dim3(512), bytes, s, npoints, n_per_cloud, F, ldf,
-                           nullptr, 0, ioff, W0, b0, W1, b1, W2, b2, Y, ldy, idx_out, ksel, Wp, bp, k_old, P, ldp, xyz, Wl, bl, Lout, ldl);
-    return (int)hipGetLastError();
+                           nullptr, 0, ioff, W0, b0, W1, b1, W2, b2, Y, ldy, idx_out, ksel, Wp_fused, bp, k_old, P, ldp, xyz, Wl, bl, Lout, ldl);
+    const int rc = (int)hipGetLastError();
+    if (rc != 0 || Wp == Wp_fused) return rc;
+    return dispu_linear(1, npoints, 72 + C + k_old, 48, Y, ldy, 0, Wp, 48, 0, 0, bp, 1, P, ldp, 0, nullptr, 0, 0, nullptr, 0, 0, stream);
 }

@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void ps_point_matmul_kernel(long rows, const f
 }
 
 // Row softmax of the attention logits (ops.py:326-338): S <- softmax(S * inv_scale) per row, in place.
-// One wave per row; n <= 64*32.
+// One wave per row; n <= 64*32 (wider rows: softmax_rows_wide_kernel).
 __global__ __launch_bounds__(256) void softmax_rows_kernel(long rows, int n, float mul, float* __restrict__ S, long lds) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -408,6 +408,25 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(long rows, int n, flo
         const int c = lane + q * 64;
         if (c < n) p[c] = v[q] * inv;
     }
+}
+
+// softmax_rows_kernel for rows of more than 64*32 columns (the generator's unfused attention over M > 2048 keys): three passes over
+// the row in memory instead of registers.  Each lane visits its columns in the same order and the wave reduces the same way, so the
+// results are those of softmax_rows_kernel where both apply.
+__global__ __launch_bounds__(256) void softmax_rows_wide_kernel(long rows, int n, float mul, float* __restrict__ S, long lds) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    float* p = S + row * lds;
+    float m = -__builtin_inff();
+    for (int c = lane; c < n; c += 64) m = fmaxf(m, p[c] * mul);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float sum = 0.f;
+    for (int c = lane; c < n; c += 64) sum += expf(p[c] * mul - m);
+    sum = wave_sum_f32(sum);
+    const float inv = 1.0f / sum;
+    for (int c = lane; c < n; c += 64) p[c] = expf(p[c] * mul - m) * inv;
 }
 
 static inline int grid_for(long total, int bs) {
@@ -523,8 +542,11 @@ DISPU_EXPORT int dispu_ps_point_matmul(long rows, int k, int c, int t_n, const f
 }
 
 DISPU_EXPORT int dispu_softmax_rows(long rows, int n, float mul, float* S, long lds, void* stream) {
-    if (rows < 0 || n <= 0 || n > 2048) return (int)hipErrorInvalidValue;
+    if (rows < 0 || n <= 0) return (int)hipErrorInvalidValue;
     if (rows == 0) return 0;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, n, mul, S, lds);
+    if (n > 64 * 32)
+        hipLaunchKernelGGL(softmax_rows_wide_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, n, mul, S, lds);
+    else
+        hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, n, mul, S, lds);
     return (int)hipGetLastError();
 }

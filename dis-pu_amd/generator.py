@@ -58,8 +58,9 @@ class Generator(object):
     by the next call with the same (B, N), and the results (return_views = False) are fresh tensors ordered on the caller's stream.
     Use one Generator per concurrent caller (two in flight: bench.py's alt_two_in_flight holds two)."""
 
-    MAX_BATCH = 2048     # patches per launch sequence: keeps every row*stride product below 2^31 and the workspace
-                         # (~17 MB per patch, dominated by F' [B*1024, 2048]) at ~35 GB; larger batches run in chunks
+    MAX_POINTS = 2048 * 256   # input points (B*N) per launch sequence: keeps every row*stride product below 2^31 and the workspace
+                              # (~17 MB per 256 input points, dominated by F' [B*4N, 2048]) at ~35 GB; larger batches run in chunks
+                              # of max(1, MAX_POINTS // N) patches
 
     def __init__(self, opts=None, is_training=False, name="Generator", params=None, device=None):
         self.opts = opts if opts is not None else _Opts()
@@ -254,11 +255,15 @@ class Generator(object):
             raise ValueError("Generator expects a float32 [B,N,3] tensor on a ROCm device")
         inputs = inputs.contiguous()
         B, N, _ = inputs.shape
+        if N <= K_NEIGH:
+            raise ValueError("Generator needs patches of at least %d points (the dense blocks take the k + 1 = %d nearest "
+                             "neighbours of every point), got N = %d" % (K_NEIGH + 1, K_NEIGH + 1, N))
         M = N * self.up_ratio
-        if B > self.MAX_BATCH:                                  # patches are independent: run the batch in chunks
+        chunk = max(1, self.MAX_POINTS // N)                    # patches per launch sequence
+        if B > chunk:                                           # patches are independent: run the batch in chunks
             if self.return_views:
-                raise ValueError("return_views needs B <= %d (one workspace)" % self.MAX_BATCH)
-            outs = [self.forward(inputs[lo:lo + self.MAX_BATCH]) for lo in range(0, B, self.MAX_BATCH)]
+                raise ValueError("return_views needs B <= %d at N = %d (one workspace)" % (chunk, N))
+            outs = [self.forward(inputs[lo:lo + chunk]) for lo in range(0, B, chunk)]
             return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
         rn, rm, k = B * N, B * M, K_NEIGH
         ws = self._workspace(B, N)

@@ -251,7 +251,8 @@ int dispu_edge_dense_conv(int npoints, int n_per_cloud, int C, const float* F, l
  * >= ksel = ioff + 16 <= 20; npoints a multiple of n_per_cloud); idx_out (nullable): the [npoints, ksel] neighbour table.
  * Wp (nullable) [72 + C + k_old, 48], bp [48]: the NEXT block's bottleneck conv (feature_extraction layer<d+1>_prep, ops.py:1455-1462)
  * in the same launch: P[p, 0:48] = relu([Y[p, 0:72+C] | Y[p, 72+C : 72+C+k_old]] . Wp + bp) -- Y's row continues to the right with the
- * k_old (a multiple of 24) older feature columns; bit-identical to dispu_linear on those rows.
+ * k_old (a multiple of 24) older feature columns; bit-identical to dispu_linear on those rows (where the conv's operands do not fit in
+ * the LDS the cloud leaves -- small clouds, many older columns -- it is a dispu_linear launch after the block).
  * xyz (nullable; C == 24, clouds of <= 680 points) [npoints, 3]: F is not read -- the block's input is feature_extraction's layer0
  * (ops.py:1449-1451) = xyz . Wl [3, 24] + bl, evaluated while the cloud is staged (bit-identical to dispu_linear_small_k) and also
  * written to Lout [npoints, 24] (row stride ldl). */
@@ -305,7 +306,7 @@ int dispu_attention_fwd_lse(int b, int m, int nk, int d, const float* Q, long ld
 int dispu_attention_bwd(int b, int m, int nk, int d, const float* Q, long ldq, const float* K, long ldk, const float* V, long ldv,
                         float scale, const float* O, long ldo, const float* lse2, const float* dO, long lddo, float* dQ, long lddq,
                         float* dK, long lddk, float* dV, long lddv, float* dvec, void* stream);
-/* S <- softmax(S * mul) per row, in place (tf.nn.softmax of PointNonLocalCell, ops.py:338). */
+/* S <- softmax(S * mul) per row of n columns (any n), in place (tf.nn.softmax of PointNonLocalCell, ops.py:338). */
 int dispu_softmax_rows(long rows, int n, float mul, float* S, long lds, void* stream);
 
 /* Fused head chains (one launch, activations stay in LDS): X [rows, K0] -> relu(. W1 + b1) [N1] -> relu(. W2 + b2) [N2]

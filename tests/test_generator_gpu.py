@@ -51,18 +51,24 @@ def test_fine_within_tolerance(setup):
     assert np.abs(setup["f"] - setup["fine"]).max() <= 1e-5
 
 
-def test_fused_local_cell_equals_unfused_chain(dev):
+# (B, N) of the in-generator A/B tests: the bench's patch size, the second pass of 16x upsampling, copy boundaries inside the
+# head chains' row tiles (rm = 1152), and rm = 2000 / M = 1000 (neither a multiple of 128 nor of 32)
+AB_SIZES = [(2, 256), (1, 1024), (1, 288), (2, 250)]
+
+
+@pytest.mark.parametrize("B,n", AB_SIZES)
+def test_fused_local_cell_equals_unfused_chain(dev, B, n):
     """dispu_ps_local (one kernel) vs gather_sub_relu -> dispu_linear -> weight_net -> point_matmul: bit-identical."""
     from dispu_amd import synth
     from dispu_amd.generator import Generator
     P = OG.init_params(seed=7, bias_scale=0.05, bn_random=True)
-    x = torch.from_numpy(synth.patches(2, 256, seed=11)).to(dev)
+    x = torch.from_numpy(synth.patches(B, n, seed=11)).to(dev)
     outs = []
     for fused in (True, False):
         gen = Generator(params=P, device=dev)
         gen.fused_local = fused
         c, f = gen(x)
-        outs.append((N(gen._ws[(2, 256)]["fp"]).copy(), N(c).copy(), N(f).copy()))
+        outs.append((N(gen._ws[(B, n)]["fp"]).copy(), N(c).copy(), N(f).copy()))
     for a, b in zip(outs[0], outs[1]):
         assert np.array_equal(a, b)
 
@@ -128,17 +134,46 @@ def test_fused_attention(dev, b, m):
     assert np.abs(N(out) - want).max() <= 2e-5 * max(1.0, np.abs(want).max())
 
 
-def test_fused_attention_path_equals_unfused_in_generator(dev):
+@pytest.mark.parametrize("rows,n,lds", [(37, 1000, 1000), (37, 2048, 2052), (37, 2049, 2049), (5, 4004, 4004), (6, 4096, 4100), (3, 8192, 8192)])
+def test_softmax_rows(dev, rows, n, lds):
+    """dispu_softmax_rows (the unfused attention's softmax over M keys; M = 4N reaches 4096 in the second pass of 16x upsampling and 8192
+    at N = 2048) against float64, on rows of up to 2048 columns (registers) and wider (three passes through memory).  A wide row whose
+    extra columns are -inf gives the narrow kernel's result bit for bit, and the padding behind each row is left alone."""
+    from dispu_amd import _lib
+    L = _lib.lib()
+    rng = np.random.default_rng(rows * n)
+    s = np.full((rows, lds), -7.0, np.float32)
+    s[:, :n] = rng.standard_normal((rows, n)).astype(np.float32) * 8.0
+    s[0, n // 3] += 40.0                                        # a peaked row
+    t = torch.from_numpy(s).to(dev)
+    _lib.check(L.dispu_softmax_rows(rows, n, 0.125, t.data_ptr(), lds, _lib.stream_ptr(dev)), "dispu_softmax_rows")
+    got = N(t)
+    z = s[:, :n].astype(np.float64) * 0.125
+    e = np.exp(z - z.max(1, keepdims=True))
+    want = e / e.sum(1, keepdims=True)
+    assert np.all(np.abs(got[:, :n] - want) <= 1e-5 * want + 1e-12)
+    assert (got[:, n:] == -7.0).all()
+    if n <= 2048:
+        wide = np.full((rows, 2050), -np.inf, np.float32)
+        wide[:, :n] = s[:, :n]
+        tw = torch.from_numpy(wide).to(dev)
+        _lib.check(L.dispu_softmax_rows(rows, 2050, 0.125, tw.data_ptr(), 2050, _lib.stream_ptr(dev)), "dispu_softmax_rows")
+        assert np.array_equal(N(tw)[:, :n], got[:, :n]) and (N(tw)[:, n:] == 0).all()
+
+
+@pytest.mark.parametrize("B,n", [s for s in AB_SIZES if 4 * s[1] % 32 == 0])    # M % 32 != 0 takes the score buffer either way
+def test_fused_attention_path_equals_unfused_in_generator(dev, B, n):
     from dispu_amd import synth
     from dispu_amd.generator import Generator
     P = OG.init_params(seed=5, bias_scale=0.05)
-    x = torch.from_numpy(synth.patches(2, 256, seed=13)).to(dev)
+    x = torch.from_numpy(synth.patches(B, n, seed=13)).to(dev)
     res = []
     for fused in (True, False):
         gen = Generator(params=P, device=dev)
         gen.fused_attention = fused
         c, f = gen(x)
-        res.append((N(gen._ws[(2, 256)]["nl"]).copy(), N(f).copy()))
+        assert (("scores", B, n) in gen._ws) != fused
+        res.append((N(gen._ws[(B, n)]["nl"]).copy(), N(f).copy()))
     assert np.abs(res[0][0] - res[1][0]).max() <= 1e-5 * max(1.0, np.abs(res[1][0]).max())
     assert np.abs(res[0][1] - res[1][1]).max() <= 1e-6
 
@@ -277,11 +312,15 @@ def test_edge_dense_conv_mfma_equals_valu_and_oracle(dev, C, npts):
 
 @pytest.mark.parametrize("C,nb,n_cloud,kind", [(24, 32, 256, "normal"), (48, 32, 256, "normal"), (48, 1, 256, "normal"), (48, 5, 256, "normal"),
                                                 (48, 8, 256, "normal"), (24, 3, 128, "normal"), (48, 70, 256, "normal"), (48, 2, 64, "normal"),
-                                                (48, 3, 34, "normal"), (48, 2, 256, "dups"), (24, 2, 256, "grid"), (48, 2, 250, "normal")])
+                                                (48, 3, 34, "normal"), (48, 2, 256, "dups"), (24, 2, 256, "grid"), (48, 2, 250, "normal"),
+                                                (48, 2, 18, "wide"), (48, 1, 128, "wide"), (48, 5, 160, "wide"), (48, 3, 162, "wide"),
+                                                (48, 2, 256, "wide")])
 def test_stem_block_equals_search_then_edge_conv(dev, C, nb, n_cloud, kind):
     """dispu_stem_block (neighbour search + edge features + dense_conv in one launch) vs dispu_knn_feat_strided followed by
     dispu_edge_dense_conv: neighbour table and output bit-identical; vs the oracle on the small cases.  'dups': clouds made of 8
-    distinct rows (every distance a 32-way tie: the sort-everything path), 'grid': features on a coarse lattice (many exact ties)."""
+    distinct rows (every distance a 32-way tie: the sort-everything path), 'grid': features on a coarse lattice (many exact ties),
+    'wide': the generator's third block, whose bottleneck conv reads 240 older columns (K = 360) -- below ~160 points per cloud its
+    operands do not fit in the LDS the cloud leaves and it runs as a launch of its own."""
     from dispu_amd import _lib
     from oracle import oracle as O
     L = _lib.lib()
@@ -309,7 +348,7 @@ def test_stem_block_equals_search_then_edge_conv(dev, C, nb, n_cloud, kind):
         idx_b = torch.full((npts, 17), -1, dtype=torch.int32, device=dev)
         y_b = torch.zeros((npts, 72 + C + 3), device=dev)
         # with_idx also exercises the bottleneck-conv epilogue: y rows continue with k_old older columns
-        k_old = 24 * (1 + (nb % 3)) if with_idx else 0
+        k_old = (240 if kind == "wide" else 24 * (1 + (nb % 3))) if with_idx else 0
         ldy = 72 + C + k_old + (4 if with_idx else 3)
         y_b = torch.zeros((npts, ldy), device=dev)
         y_b[:, 72 + C:] = torch.from_numpy(rng.standard_normal((npts, ldy - 72 - C)).astype(np.float32)).to(dev)
@@ -393,37 +432,101 @@ def test_stem_block_refuses_what_it_does_not_cover(dev):
     assert a(1024, 256, 48, 17, 1) == 0
 
 
-def test_fused_head_chains_equal_separate_launches(dev):
+@pytest.mark.parametrize("B,n", [s for s in AB_SIZES if s[0] * 4 * s[1] % 128 == 0])   # otherwise both take the separate launches
+def test_fused_head_chains_equal_separate_launches(dev, B, n):
     """dispu_mlp_chain (one launch per head, activations in LDS) vs the dispu_linear / dispu_linear_small_n launches:
     bit-identical coarse, fine, up128 and aggregation output."""
     from dispu_amd import synth
     from dispu_amd.generator import Generator
     P = OG.init_params(seed=3, bias_scale=0.05, bn_random=True)
-    x = torch.from_numpy(synth.patches(2, 256, seed=13)).to(dev)
+    x = torch.from_numpy(synth.patches(B, n, seed=13)).to(dev)
     outs = []
     for fused in (True, False):
         gen = Generator(params=P, device=dev)
         gen.fused_heads = fused
         gen.keep_intermediates = True
         c, f = gen(x)
-        ws = gen._ws[(2, 256)]
+        ws = gen._ws[(B, n)]
         outs.append([N(c).copy(), N(f).copy(), N(ws["up128"]).copy(), N(ws["agg"]).copy()])
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("B", [1, 5])
-def test_odd_batch_sizes_match_oracle(dev, B):
-    """BASELINE configs[0] (a single 256-point patch) and a batch that is not a multiple of anything: persistent /
-    per-cloud kernels must cope with fewer point groups than CUs and with ragged grids."""
+def _differ(a, b):
+    """how much of a stage diverged: the number of rows (last axis) that are not bit-identical"""
+    a, b = a.reshape(-1, a.shape[-1]), b.reshape(-1, b.shape[-1])
+    return "%d of %d rows differ" % (int((a != b).any(1).sum()), a.shape[0])
+
+
+@pytest.mark.parametrize("B,n", [(1, 256), (5, 256), (1, 1024), (2, 1024), (1, 2048), (1, 288), (1, 520), (2, 250), (1, 255),
+                                 (3, 17), (2, 18)])
+def test_odd_batch_sizes_match_oracle(dev, B, n):
+    """Stage parity with the oracle over patch sizes, each chosen for the paths of Generator.forward it reaches:
+      (1, 256)      BASELINE configs[0], a single patch;
+      (5, 256)      a batch that is not a multiple of anything: persistent / per-cloud kernels with fewer point groups than CUs;
+      (1|2, 1024)   the second pass of 16x upsampling: unfused dense blocks with the chunked feature k-NN (4 chunks), the chunked
+                    xyz k-NN at M = 4096, attention_project over 4096 keys, fused heads;
+      (1, 2048)     the top of the chunked xyz k-NN (M = 8192, 8 chunks), the feature k-NN in 8 chunks, attention over 8192 keys;
+      (1, 288)      the chunked xyz k-NN just past its threshold (M = 1152); fused heads whose 64-row tiles straddle a duplicate_up
+                    copy boundary (copy r starts at row 288 r);
+      (1, 520)      the chunked feature k-NN just past 512 with a short last chunk; rm = 2080: separate head launches;
+      (2, 250)      the fused stem on a cloud that is not a power of two; M = 1000: attention through the score buffer;
+      (1, 255)      odd N: unfused dense blocks at N <= 256, ragged GEMM tiles everywhere;
+      (3, 17)       N = k + 1, the smallest legal cloud (unfused blocks);  (2, 18): N = k + 2 (fused stem).
+    Held to the N = 256 standard: features, neighbour tables, up128 and coarse bit-exact, the fine branch within 1e-5, and every
+    patch of a batch equal to the same patch run alone."""
     from dispu_amd import synth
     from dispu_amd.generator import Generator
     P = OG.init_params(seed=11, bias_scale=0.05, bn_random=True)
-    x = synth.patches(B, 256, seed=40 + B)
-    coarse, fine = OG.generator_forward(P, x)
-    c, f = Generator(params=P, device=dev)(torch.from_numpy(x).to(dev))
-    assert np.array_equal(N(c), coarse)
-    assert np.abs(N(f) - fine).max() <= 1e-5
+    x = synth.patches(B, n, seed=40 + B if n == 256 else 1000 * B + n)
+    tap = {}
+    coarse, fine = OG.generator_forward(P, x, tap)
+    gen = Generator(params=P, device=dev)
+    gen.keep_intermediates = True
+    c, f = gen(torch.from_numpy(x).to(dev))
+    c, f = N(c), N(f)
+    ws, m = gen._ws[(B, n)], 4 * n
+    feat, kidx = N(ws["feat"]).reshape(B, n, 480), N(ws["kidx"])[:, 1:].reshape(B, n, 16)
+    assert np.array_equal(kidx, tap["fe_idx4"]), "fe_idx4: " + _differ(kidx, tap["fe_idx4"])
+    assert np.array_equal(feat, tap["feat480"]), "feat480: " + _differ(feat, tap["feat480"])
+    up128 = N(ws["up128"]).reshape(B, m, 128)
+    assert np.array_equal(up128, tap["up128"]), "up128: " + _differ(up128, tap["up128"])
+    assert np.array_equal(c, coarse), "coarse: " + _differ(c, coarse)
+    psidx = N(ws["psidx"]).reshape(B, m, 16)
+    assert np.array_equal(psidx, tap["ps_idx"]), "ps_idx: " + _differ(psidx, tap["ps_idx"])
+    ff, ref = N(ws["agg"]).reshape(B, m, 256), tap["fine_feat"]
+    assert np.abs(ff - ref).max() <= 1e-5 * max(1.0, np.abs(ref).max())
+    assert np.abs(f - fine).max() <= 1e-5
+    for b in range(B if B > 1 else 0):
+        cb, fb = gen(torch.from_numpy(x[b:b + 1]).to(dev))
+        assert np.array_equal(N(cb)[0], c[b]) and np.array_equal(N(fb)[0], f[b]), "patch %d alone" % b
+
+
+def test_one_instance_serves_several_patch_sizes(dev):
+    """One Generator runs N = 256 -> 1024 -> 250 -> 256 in turn.  Each (B, N) workspace owns its k-NN scratch and attention score
+    buffer, all of them share the auxiliary stream and its events; every result equals a fresh instance's at that size, bit for bit."""
+    from dispu_amd import synth
+    from dispu_amd.generator import Generator
+    P = OG.init_params(seed=19, bias_scale=0.05, bn_random=True)
+    gen = Generator(params=P, device=dev)
+    for i, n in enumerate((256, 1024, 250, 256)):
+        x = torch.from_numpy(synth.patches(2, n, seed=60 + i)).to(dev)
+        c, f = gen(x)
+        c0, f0 = Generator(params=P, device=dev)(x)
+        assert torch.equal(c, c0) and torch.equal(f, f0), "step %d, N = %d" % (i, n)
+    assert "knn_scratch" in gen._ws[(2, 1024)] and "knnf_scratch" in gen._ws[(2, 1024)]
+    assert ("scores", 2, 250) in gen._ws and ("scores", 2, 256) not in gen._ws
+
+
+@pytest.mark.parametrize("n", [16, 1])
+def test_patches_of_at_most_k_points_are_refused(dev, n):
+    """The dense blocks take k + 1 = 17 neighbours per point: smaller patches are refused before anything is allocated or launched."""
+    from dispu_amd.generator import Generator
+    gen = Generator(params=OG.init_params(seed=1), device=dev)
+    x = torch.rand((2, n, 3), device=dev)
+    with pytest.raises(ValueError, match="at least 17 points"):
+        gen(x)
+    assert not gen._ws
 
 
 @pytest.mark.parametrize("b,m", [(2, 1024), (3, 160), (1, 4096)])
@@ -458,16 +561,17 @@ def test_fused_attention_project(dev, b, m):
     assert np.abs(N(y).reshape(-1, 256) - N(y2)).max() <= 1e-5 * max(1.0, np.abs(want).max())
 
 
-def test_projection_epilogue_equals_separate_gemm_in_generator(dev):
+@pytest.mark.parametrize("B,n", [s for s in AB_SIZES if 4 * s[1] % 32 == 0])    # M % 32 != 0 takes the score buffer either way
+def test_projection_epilogue_equals_separate_gemm_in_generator(dev, B, n):
     from dispu_amd import synth
     from dispu_amd.generator import Generator
     P = OG.init_params(seed=5, bias_scale=0.05)
-    x = torch.from_numpy(synth.patches(2, 256, seed=13)).to(dev)
+    x = torch.from_numpy(synth.patches(B, n, seed=13)).to(dev)
     res = []
     for fused in (True, False):
         gen = Generator(params=P, device=dev)
         gen.fused_project = fused
         c, f = gen(x)
-        res.append((N(gen._ws[(2, 256)]["nl"]).copy(), N(f).copy()))
+        res.append((N(gen._ws[(B, n)]["nl"]).copy(), N(f).copy()))
     assert np.abs(res[0][0] - res[1][0]).max() <= 1e-5 * max(1.0, np.abs(res[1][0]).max())
     assert np.abs(res[0][1] - res[1][1]).max() <= 1e-6

@@ -253,18 +253,29 @@ def test_two_stream_forward_equals_single_stream(bench_setup, dev):
     assert np.array_equal(outs[0][0], s["c"]) and np.array_equal(outs[0][1], s["f"])
 
 
-def test_oversize_batches_run_in_chunks(dev):
-    """Batches above Generator.MAX_BATCH (2048: keeps row * stride products below 2^31) are processed in chunks; patches are
-    independent, so the result is the unchunked one.  Exercised here with a tiny limit."""
+@pytest.mark.parametrize("n", [BENCH_N, 1024])
+def test_oversize_batches_run_in_chunks(dev, n):
+    """Batches above Generator.MAX_POINTS input points (2048 x 256: keeps row * stride products below 2^31) are processed in chunks
+    of whole patches; patches are independent, so the result is the unchunked one.  The budget counts points, not patches: with the
+    same budget and B, 1024-point patches (the second pass of 16x upsampling) run in more chunks than 256-point ones.  Exercised here
+    with tiny budgets of three 1024-point and three 256-point patches."""
     from dispu_amd import synth
     from dispu_amd.generator import Generator
     from dispu_amd.params import init_params
     gen = Generator(params=init_params(seed=1234), device=dev)
-    x = torch.from_numpy(synth.patches(7, BENCH_N, seed=5)).to(dev)
+    x = torch.from_numpy(synth.patches(7, n, seed=5)).to(dev)
     c7, f7 = gen(x)
-    gen.MAX_BATCH = 3
-    c, f = gen(x)
-    assert torch.equal(c, c7) and torch.equal(f, f7)
+    seq = []                                          # the (B, N) of every launch sequence
+    ws = gen._workspace
+    gen._workspace = lambda b, n_: seq.append((b, n_)) or ws(b, n_)
+    chunks = {(BENCH_N, 3 * 1024): [7], (1024, 3 * 1024): [3, 3, 1],
+              (BENCH_N, 3 * BENCH_N): [3, 3, 1], (1024, 3 * BENCH_N): [1] * 7}      # a patch above the budget runs alone
+    for budget in (3 * 1024, 3 * BENCH_N):
+        gen.MAX_POINTS = budget
+        del seq[:]
+        c, f = gen(x)
+        assert seq == [(b, n) for b in chunks[(n, budget)]], budget
+        assert torch.equal(c, c7) and torch.equal(f, f7)
     gen.return_views = True
     with pytest.raises(ValueError):
         gen(x)

@@ -38,8 +38,13 @@ def test_config4_16x_with_cd_and_emd(dev):
     x, gt = synth.patch_with_gt(1, 256, 4096, seed=21)
     P = OG.init_params(seed=2)
     gen = Generator(params=P, device=dev)
-    coarse, fine = U.generator_chain(gen, torch.from_numpy(x).to(dev), final_ratio=16)
+    tx = torch.from_numpy(x).to(dev)
+    coarse, fine = U.generator_chain(gen, tx, final_ratio=16)
     assert tuple(fine.shape) == (1, 4096, 3)
+    # the chain is two generator calls, the second on the first one's fine cloud
+    _, f1_dev = gen(tx)
+    c2_dev, f2_dev = gen(f1_dev)
+    assert torch.equal(c2_dev, coarse) and torch.equal(f2_dev, fine)
     c1, f1 = OG.generator_forward(P, x)
     c2, f2 = OG.generator_forward(P, f1)
     # pass 1 is bit-exact up to `coarse`; pass 2 starts from fine (1e-5) so its k-NN decisions may flip on near-ties:
@@ -47,6 +52,12 @@ def test_config4_16x_with_cd_and_emd(dev):
     assert np.abs(N(coarse) - c2).max() < 5e-2
     d1, _, d2, _ = O.nn_distance(N(fine), f2, contract=0)
     assert np.median(d1) < 1e-8 and np.median(d2) < 1e-8
+    # pass 2 against the oracle on the device's own pass-1 output: the N = 256 standard at N = 1024
+    tap = {}
+    c2_own, f2_own = OG.generator_forward(P, N(f1_dev), tap)
+    assert np.array_equal(N(coarse), c2_own)
+    assert np.array_equal(N(gen._ws[(1, 1024)]["psidx"]).reshape(1, 4096, 16), tap["ps_idx"])
+    assert np.abs(N(fine) - f2_own).max() <= 1e-5
     tf, tg = fine.clone(), torch.from_numpy(gt).to(dev)
     cd, emd = float(LU.chamfer(tf, tg)), float(LU.earth_mover(tf, tg))
     assert abs(cd - OM.chamfer(N(tf), gt)) <= 1e-5 * max(1.0, OM.chamfer(N(tf), gt))
@@ -123,6 +134,43 @@ def test_upsample_cloud_stage_parity(dev):
     # end to end against the independent oracle run: same point set up to float noise unless a near-tie flipped
     d1, _, d2, _ = O.nn_distance(out[None], want[None], contract=0)
     assert np.median(d1) < 1e-9 and np.median(d2) < 1e-9
+
+
+def test_upsample_cloud_16x_stage_parity(dev):
+    """BASELINE configs[3] on a whole cloud: upsample_clouds(final_ratio=16) on 1024 points -> 12 patches, two generator passes
+    (256 -> 1024 -> 4096 points per patch), 49152 merged points, FPS to 16384.  Like test_upsample_cloud_stage_parity, every stage
+    is checked against the oracle on the device's own input to that stage: seeds and patch indices exact, both generator passes of
+    all 12 patches at the N = 256 standard (coarse bit-exact, xyz neighbours index-exact, fine 1e-5), the final FPS exact."""
+    from dispu_amd import upsample as U
+    from dispu_amd.generator import Generator
+    rng = np.random.default_rng(4)
+    g = rng.standard_normal((1024, 3))
+    pc = (g / np.linalg.norm(g, axis=1, keepdims=True) * np.array([0.5, 1.2, 0.8]) - 3.0).astype(np.float32)   # an ellipsoid, off-centre
+    P = OG.init_params(seed=6, bias_scale=0.05, bn_random=True)
+    gen = Generator(params=P, device=dev)
+    out, st = U.upsample_cloud(gen, pc, final_ratio=16, return_stages=True)
+    assert out.shape == (16384, 3)
+    cn = N(st["cloud_n"])
+    assert np.array_equal(N(st["seeds"]), O.farthest_point_sample(12, cn))
+    seeds_xyz = cn[0][N(st["seeds"])[0]]
+    assert np.array_equal(N(st["pidx"])[0], OU.extract_knn_patch_idx(seeds_xyz, cn[0], 256))
+    pn = N(st["patches_n"])
+    assert np.allclose(pn, OU.normalize_point_cloud(cn[0][N(st["pidx"])[0]])[0], atol=2e-6)
+    # return_stages keeps the last pass's fine cloud only: run the two passes again, the second must give what the chain gave
+    c1, f1 = gen(st["patches_n"])
+    c2, f2 = gen(f1)
+    assert tuple(f2.shape) == (12, 4096, 3) and torch.equal(f2, st["fine"])
+    c1_want, f1_want = OG.generator_forward(P, pn)
+    assert np.array_equal(N(c1), c1_want) and np.abs(N(f1) - f1_want).max() <= 1e-5
+    tap = {}
+    c2_want, f2_want = OG.generator_forward(P, N(f1), tap)
+    assert np.array_equal(N(c2), c2_want)
+    assert np.array_equal(N(gen._ws[(12, 1024)]["psidx"]).reshape(12, 4096, 16), tap["ps_idx"])
+    assert np.abs(N(f2) - f2_want).max() <= 1e-5
+    merged = N(st["merged"])
+    assert merged.shape == (1, 49152, 3)
+    assert np.array_equal(N(st["sel"]), O.farthest_point_sample(16384, merged))
+    assert np.array_equal(out, merged[0][N(st["sel"])[0]])
 
 
 def test_upsample_clouds_batch_equals_single(dev):
