@@ -27,6 +27,8 @@ SIGNATURES = {
     "dispu_fps_scratch_bytes": (_sz, [_i, _i, _i]),
     "dispu_fps": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "dispu_fps_ws": (_i, [_i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp]),
+    "dispu_fps_segments_scratch_bytes": (_sz, [_i, _vp, _vp]),
+    "dispu_fps_segments": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _vp]),
     "dispu_prob_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dispu_selection_sort": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dispu_gather_point": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -88,6 +90,8 @@ SIGNATURES = {
     "dispu_knn_patch": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dispu_normalize_patches": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dispu_denormalize_patches": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dispu_knn_patch_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dispu_normalize_segments": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_attention": (_i, [_i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _l, C.c_float, _vp, _l, _vp]),
     "dispu_attention_fwd_lse": (_i, [_i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _l, C.c_float, _vp, _l, _vp, _vp]),
     "dispu_attention_bwd": (_i, [_i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _l, C.c_float, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _l,

@@ -54,6 +54,24 @@ struct DevOnce {
     void done() { mask.fetch_or(1ull << cur(), std::memory_order_release); }
 };
 
+// Extents of workgroup g's cloud in a kernel that serves both batch layouts.  off == nullptr: a uniform batch, cloud g owns the
+// points [g n, (g + 1) n) and the outputs [g m, (g + 1) m).  Otherwise a packed ragged batch (the dispu_*_segments entries): the
+// points [off[g], off[g + 1]) and the outputs [ooff[g], ooff[g + 1]) (device int32 offsets, scalar loads).
+struct SegExt {
+    size_t base, obase;
+    int n, m;
+};
+__device__ __forceinline__ SegExt seg_ext(const int* __restrict__ off, const int* __restrict__ ooff, int g, int n, int m) {
+    if (!off) return {(size_t)g * n, (size_t)g * m, n, m};
+    const int b = off[g], ob = ooff[g];
+    return {(size_t)b, (size_t)ob, off[g + 1] - b, ooff[g + 1] - ob};
+}
+
+// The kernel family a cloud of n points sampled to m takes in dispu_fps_ws (with scratch) and dispu_fps_segments: 0 the register
+// kernels of sampling.hip, 1 the region-skipping kernels of fps_wave.hip, 2 the streaming kernel.  Every family returns the same
+// indices (the tie rule is arithmetic), so the choice only sets the speed.
+__host__ __device__ __forceinline__ int fps_family(int n, int m) { return n > 24576 ? 2 : (n > 4096 && m >= 64) ? 1 : 0; }
+
 template <bool FMA>
 __device__ __forceinline__ float sqdist3(float dx, float dy, float dz) {
     if constexpr (FMA) {

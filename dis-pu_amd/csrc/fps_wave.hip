@@ -84,16 +84,21 @@ __device__ __forceinline__ unsigned fpsw_spread4(unsigned v) { return (v & 1u) |
 // positions (one wave of the sampling kernel) re-sorted by the reference's tie priority (bitonic, 2048 keys), written to perm.
 // The order inside a cell comes from LDS atomics; it only decides which points share a wave (speed), never a result - the
 // second sort makes the final permutation deterministic within a wave's range anyway.
-__global__ __launch_bounds__(1024) void fps_wavesort_kernel(int n, int chunk, const float* __restrict__ xyz, int* __restrict__ perm) {
+// off / moff: a packed ragged batch (seg_ext, common.h); the workgroups of segments outside family 1 return at once.
+__global__ __launch_bounds__(1024) void fps_wavesort_kernel(int n, int chunk, const float* __restrict__ xyz, int* __restrict__ perm,
+                                                            const int* __restrict__ off, const int* __restrict__ moff) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* sorted = reinterpret_cast<int*>(smem);                    // [n]
     unsigned* cnt = reinterpret_cast<unsigned*>(sorted + n);       // [4096]
     unsigned* keys = cnt + 4096;                                   // [2048]
     __shared__ float bb[6][16];
     __shared__ unsigned wsum[16];
-    const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* __restrict__ p = xyz + (size_t)cloud * n * 3;
-    int* __restrict__ pm = perm + (size_t)cloud * n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SegExt e = seg_ext(off, moff, blockIdx.x, n, 0);
+    if (off && fps_family(e.n, e.m) != 1) return;
+    n = e.n;
+    const float* __restrict__ p = xyz + e.base * 3;
+    int* __restrict__ pm = perm + e.base;
     float mn[3] = {3e38f, 3e38f, 3e38f}, mx[3] = {-3e38f, -3e38f, -3e38f};
     for (int k = tid; k < n; k += 1024)
 #pragma unroll
@@ -176,17 +181,21 @@ static_assert(FW_W == 16, "the cross-wave reduction reads one slot per lane of D
 // arrays would need 96 of the 128 registers a 16-wave workgroup gets and the compiler spills coordinates to scratch.
 template <int P, int PL, bool FMA>
 __global__ __launch_bounds__(FW_BS) void fps_wave_kernel(int n, int m, const float* __restrict__ xyz, const int* __restrict__ perm,
-                                                         int* __restrict__ out) {
+                                                         int* __restrict__ out, const int* __restrict__ off, const int* __restrict__ moff) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* perm_l = reinterpret_cast<int*>(smem);                               // [FW_BS * P] original index of a sorted position
     float* slot = reinterpret_cast<float*>(perm_l + FW_BS * P);               // [2][FW_W][8]: d, position, x, y, z
     float* xl = slot + 2 * FW_W * 8;                                          // [PL][3][FW_BS]
     constexpr int PR = P - PL;
-    const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);               // scalar: everything per-wave below lives in SGPRs
-    const float* __restrict__ p = xyz + (size_t)cloud * n * 3;
-    const int* __restrict__ pm = perm + (size_t)cloud * n;
-    int* __restrict__ o = out + (size_t)cloud * m;
+    const SegExt e = seg_ext(off, moff, blockIdx.x, n, m);
+    if (off && fps_family(e.n, e.m) != 1) return;
+    n = e.n;
+    m = e.m;
+    const float* __restrict__ p = xyz + e.base * 3;
+    const int* __restrict__ pm = perm + e.base;
+    int* __restrict__ o = out + e.obase;
     const int wbase = wave * 64 * P;
 
     float x[PR], y[PR], z[PR], td[P];
@@ -319,17 +328,21 @@ __global__ __launch_bounds__(FW_BS) void fps_wave_kernel(int n, int m, const flo
 // rare ties and the final pass only, which frees 96 KB of LDS for the coordinates of 8 of the 24 slots).
 template <int P, int PL, bool FMA, int G = 4>
 __global__ __launch_bounds__(FW_BS) void fps_wave4_kernel(int n, int m, const float* __restrict__ xyz, const int* __restrict__ perm,
-                                                          int* __restrict__ out) {
+                                                          int* __restrict__ out, const int* __restrict__ off, const int* __restrict__ moff) {
     constexpr int PG = P / G, PR = P - PL;                // G = 4 (default) or 8 skip groups per wave (round 3: measured)
     static_assert(P % G == 0, "groups must tile the slots");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* slot = reinterpret_cast<float*>(smem);                             // [2][FW_W][8]: distance key, position, x, y, z
     float* xl = slot + 2 * FW_W * 8;                                          // [PL][3][FW_BS]
-    const int cloud = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const float* __restrict__ p = xyz + (size_t)cloud * n * 3;
-    const int* __restrict__ pm = perm + (size_t)cloud * n;
-    int* __restrict__ o = out + (size_t)cloud * m;
+    const SegExt e = seg_ext(off, moff, blockIdx.x, n, m);
+    if (off && fps_family(e.n, e.m) != 1) return;
+    n = e.n;
+    m = e.m;
+    const float* __restrict__ p = xyz + e.base * 3;
+    const int* __restrict__ pm = perm + e.base;
+    int* __restrict__ o = out + e.obase;
     const int wbase = wave * 64 * P;
 
     float x[PR], y[PR], z[PR], td[P];
@@ -491,7 +504,8 @@ __global__ __launch_bounds__(FW_BS) void fps_wave4_kernel(int n, int m, const fl
 }
 
 template <int P, int PL, int G = 4>
-static int launch_fps_wave4(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s) {
+static int launch_fps_wave4(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s, const int* off,
+                            const int* moff) {
     const size_t sort_bytes = (size_t)n * 4 + 4096 * 4 + 2048 * 4;
     const size_t bytes = 2 * FW_W * 8 * 4 + (size_t)PL * 3 * FW_BS * 4;
     static DevOnce attr;
@@ -501,17 +515,18 @@ static int launch_fps_wave4(int b, int n, int m, const float* xyz, int* perm, in
         DISPU_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fps_wave4_kernel<P, PL, false, G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         attr.done();
     }
-    hipLaunchKernelGGL(fps_wavesort_kernel, dim3(b), dim3(1024), sort_bytes, s, n, 64 * (P / G), xyz, perm);
+    hipLaunchKernelGGL(fps_wavesort_kernel, dim3(b), dim3(1024), sort_bytes, s, n, 64 * (P / G), xyz, perm, off, moff);
     DISPU_CHECK_LAUNCH();
     if ((arith & DISPU_ARITH_CONTRACT))
-        hipLaunchKernelGGL((fps_wave4_kernel<P, PL, true, G>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out);
+        hipLaunchKernelGGL((fps_wave4_kernel<P, PL, true, G>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out, off, moff);
     else
-        hipLaunchKernelGGL((fps_wave4_kernel<P, PL, false, G>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out);
+        hipLaunchKernelGGL((fps_wave4_kernel<P, PL, false, G>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out, off, moff);
     return (int)hipGetLastError();
 }
 
 template <int P, int PL>
-static int launch_fps_wave(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s) {
+static int launch_fps_wave(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s, const int* off,
+                           const int* moff) {
     const size_t sort_bytes = (size_t)n * 4 + 4096 * 4 + 2048 * 4;
     const size_t bytes = (size_t)FW_BS * P * 4 + 2 * FW_W * 8 * 4 + (size_t)PL * 3 * FW_BS * 4;
     static DevOnce attr;      
@@ -521,26 +536,31 @@ static int launch_fps_wave(int b, int n, int m, const float* xyz, int* perm, int
         DISPU_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fps_wave_kernel<P, PL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         attr.done();
     }
-    hipLaunchKernelGGL(fps_wavesort_kernel, dim3(b), dim3(1024), sort_bytes, s, n, 64 * P, xyz, perm);
+    hipLaunchKernelGGL(fps_wavesort_kernel, dim3(b), dim3(1024), sort_bytes, s, n, 64 * P, xyz, perm, off, moff);
     DISPU_CHECK_LAUNCH();
     if ((arith & DISPU_ARITH_CONTRACT))
-        hipLaunchKernelGGL((fps_wave_kernel<P, PL, true>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out);
+        hipLaunchKernelGGL((fps_wave_kernel<P, PL, true>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out, off, moff);
     else
-        hipLaunchKernelGGL((fps_wave_kernel<P, PL, false>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out);
+        hipLaunchKernelGGL((fps_wave_kernel<P, PL, false>), dim3(b), dim3(FW_BS), bytes, s, n, m, xyz, perm, out, off, moff);
     return (int)hipGetLastError();
 }
 
 bool fps_wave_wants_scratch(int n, int m) { return n > 4096 && n <= FW_BS * 24 && m >= 64; }
 
+// b clouds of n <= 24576 points (off / moff: a ragged batch of b segments of at most n points each, of which the kernels serve
+// those of family 1); perm: n ints per cloud (sum of the segment sizes).
+int fps_wave_launch(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s, const int* off, const int* moff) {
+    // n <= 8192: a skip region is a wave; above: four regions per wave.  (Measured and not kept as switches: whole-wave regions above
+    // 8192 points, 9.6 - 10.4 vs 8.5 - 9.5 ms at (8, 24576, 8192); eight regions per wave, -2 %: profiles/EXPERIMENTS.md.)
+    if (n <= FW_BS * 8) return launch_fps_wave<8, 0>(b, n, m, xyz, perm, out, arith, s, off, moff);
+    if (n <= FW_BS * 16) return launch_fps_wave4<16, 0>(b, n, m, xyz, perm, out, arith, s, off, moff);
+    return launch_fps_wave4<24, 8>(b, n, m, xyz, perm, out, arith, s, off, moff);
+}
+
 // -1: shape outside this path (or no scratch for the permutation)
 int fps_wave_dispatch(int b, int n, int m, const float* xyz, void* temp, int* out, int arith, hipStream_t s) {
     if (!temp || !fps_wave_wants_scratch(n, m)) return -1;
-    int* perm = reinterpret_cast<int*>(temp);
-    // n <= 8192: a skip region is a wave; above: four regions per wave.  (Measured and not kept as switches: whole-wave regions above
-    // 8192 points, 9.6 - 10.4 vs 8.5 - 9.5 ms at (8, 24576, 8192); eight regions per wave, -2 %: profiles/EXPERIMENTS.md.)
-    if (n <= FW_BS * 8) return launch_fps_wave<8, 0>(b, n, m, xyz, perm, out, arith, s);
-    if (n <= FW_BS * 16) return launch_fps_wave4<16, 0>(b, n, m, xyz, perm, out, arith, s);
-    return launch_fps_wave4<24, 8>(b, n, m, xyz, perm, out, arith, s);
+    return fps_wave_launch(b, n, m, xyz, reinterpret_cast<int*>(temp), out, arith, s, nullptr, nullptr);
 }
 
 }  // namespace dispu

@@ -229,7 +229,8 @@ int knn_xyz_chunked_dispatch(int b, int n, int m, int k, const float* s, const f
                              size_t scratch_bytes, int arith, hipStream_t st);
 // general path (knn_general.hip): any k <= 4096, c <= 4096, any n; mode 0/1 xyz plain/contract, 2 knn_point, 3 knn_point_2
 int knn_general_launch(int mode, int b, int n, int m, int c, int k, long ldp, long ldq, const float* points, const float* queries,
-                       float* dist, int* idx, int neg, hipStream_t st);
+                       float* dist, int* idx, int neg, hipStream_t st, const int* off = nullptr, const int* qoff = nullptr,
+                       int seg_nmin = 0);
 
 }  // namespace dispu
 

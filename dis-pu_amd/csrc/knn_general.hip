@@ -57,7 +57,8 @@ __device__ __forceinline__ float kg_distance(const float* __restrict__ p, const 
 template <int MODE>
 __global__ __launch_bounds__(256) void knn_general_kernel(int n, int m, int c, int k, int kpad, long ldp, long ldq,
                                                            const float* __restrict__ points, const float* __restrict__ queries,
-                                                           float* __restrict__ dist, int* __restrict__ idx, int neg, int vec4) {
+                                                           float* __restrict__ dist, int* __restrict__ idx, int neg, int vec4,
+                                                           const int* __restrict__ off, const int* __restrict__ qoff, int seg_nmin) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);            // [kpad]
     float* qrow = reinterpret_cast<float*>(keys + kpad);                                 // [c rounded up to 4]
@@ -65,9 +66,12 @@ __global__ __launch_bounds__(256) void knn_general_kernel(int n, int m, int c, i
     __shared__ unsigned sel[3];                   // prefix, remaining rank, survivors written
     __shared__ unsigned wcnt[4];
     __shared__ float srq;
-    const int cloud = blockIdx.y, qi = blockIdx.x, tid = threadIdx.x;
-    const float* __restrict__ pc = points + (size_t)cloud * n * ldp;
-    const float* __restrict__ q = queries + ((size_t)cloud * m + qi) * ldq;
+    const int qi = blockIdx.x, tid = threadIdx.x;
+    const SegExt e = seg_ext(off, qoff, blockIdx.y, n, m);    // off / qoff: a ragged batch; segments of <= seg_nmin points are not ours
+    if (off && (qi >= e.m || e.n <= seg_nmin)) return;
+    n = e.n;
+    const float* __restrict__ pc = points + e.base * ldp;
+    const float* __restrict__ q = queries + (e.obase + qi) * ldq;
     for (int l = tid; l < c; l += 256) qrow[l] = q[l];
     if (tid == 0) { sel[0] = 0u; sel[1] = (unsigned)k; sel[2] = 0u; }
     __syncthreads();
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(256) void knn_general_kernel(int n, int m, int c, i
             __syncthreads();
         }
     }
-    const size_t o = ((size_t)cloud * m + qi) * k;
+    const size_t o = (e.obase + qi) * k;
     for (int t = tid; t < k; t += 256) {
         const unsigned long long kv = keys[t];
         idx[o + t] = (int)(unsigned)kv;
@@ -156,8 +160,9 @@ __global__ __launch_bounds__(256) void knn_general_kernel(int n, int m, int c, i
 }
 
 // mode: KG_*; returns hipErrorInvalidValue outside k <= 4096, c <= 4096
+// off / qoff: a ragged batch of b segments (at most n points and m queries each), of which the kernel serves those above seg_nmin points
 int knn_general_launch(int mode, int b, int n, int m, int c, int k, long ldp, long ldq, const float* points, const float* queries,
-                       float* dist, int* idx, int neg, hipStream_t st) {
+                       float* dist, int* idx, int neg, hipStream_t st, const int* off, const int* qoff, int seg_nmin) {
     if (k > KG_MAXK || c > KG_MAXC || k > n) return (int)hipErrorInvalidValue;
     int kpad = 2;
     while (kpad < k) kpad <<= 1;
@@ -173,7 +178,7 @@ int knn_general_launch(int mode, int b, int n, int m, int c, int k, long ldp, lo
             attr.done();                                                                                                      \
         }                                                                                                                     \
         hipLaunchKernelGGL((knn_general_kernel<M>), grid, dim3(256), bytes, st, n, m, c, k, kpad, ldp, ldq, points, queries, \
-                           dist, idx, neg, vec4);                                                                             \
+                           dist, idx, neg, vec4, off, qoff, seg_nmin);                                                                             \
     } while (0)
     if (mode == KG_XYZ_PLAIN) KG_LAUNCH(KG_XYZ_PLAIN);
     else if (mode == KG_XYZ_FMA) KG_LAUNCH(KG_XYZ_FMA);

@@ -13,6 +13,8 @@
 // whose unsigned maximum is exactly that winner, independent of this kernel's thread layout.
 #include "common.h"
 
+#include <mutex>
+
 namespace dispu {
 
 __device__ __forceinline__ uint32_t fps_tiekey(int k) {
@@ -86,16 +88,21 @@ __device__ __forceinline__ constexpr int fps_visit(int s) {
 }
 
 // BS threads, P points per thread (thread t owns k = t + i*BS), FMA = arithmetic flavour.
+// off / moff: a packed ragged batch (seg_ext); the workgroup of a segment outside family `fam` returns at once.
 template <int BS, int P, bool FMA>
 __global__ __launch_bounds__(BS) void fps_reg_kernel(int n, int m, const float* __restrict__ xyz,
-                                                      int* __restrict__ out) {
+                                                      int* __restrict__ out, const int* __restrict__ off,
+                                                      const int* __restrict__ moff, int fam) {
     static_assert(BS == 64 || BS == 256 || BS == 1024, "visit order is derived for these block sizes");
     static_assert(BS != 64 || P <= 8, "BS=64 needs k < 512");
     constexpr int W = BS / kWave;
     __shared__ uint64_t slot[2][W > 1 ? W : 1];
-    const int cloud = blockIdx.x;
-    const float* __restrict__ p = xyz + (size_t)cloud * n * 3;
-    int* __restrict__ o = out + (size_t)cloud * m;
+    const SegExt e = seg_ext(off, moff, blockIdx.x, n, m);
+    if (off && fps_family(e.n, e.m) != fam) return;
+    n = e.n;
+    m = e.m;
+    const float* __restrict__ p = xyz + e.base * 3;
+    int* __restrict__ o = out + e.obase;
     const int tid = threadIdx.x;
 
     float x[P], y[P], z[P], td[P];
@@ -156,13 +163,17 @@ __global__ __launch_bounds__(BS) void fps_reg_kernel(int n, int m, const float* 
 // caller scratch `temp` [b,n] (same role as the reference's temp, tf_sampling.cpp:115).
 template <bool FMA>
 __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, const float* __restrict__ xyz,
-                                                        float* __restrict__ temp, int* __restrict__ out) {
+                                                        float* __restrict__ temp, int* __restrict__ out,
+                                                        const int* __restrict__ off, const int* __restrict__ moff, int fam) {
     constexpr int BS = 1024, W = BS / kWave;
     __shared__ uint64_t slot[2][W];
-    const int cloud = blockIdx.x;
-    const float* __restrict__ p = xyz + (size_t)cloud * n * 3;
-    float* __restrict__ t = temp + (size_t)cloud * n;
-    int* __restrict__ o = out + (size_t)cloud * m;
+    const SegExt e = seg_ext(off, moff, blockIdx.x, n, m);
+    if (off && fps_family(e.n, e.m) != fam) return;
+    n = e.n;
+    m = e.m;
+    const float* __restrict__ p = xyz + e.base * 3;
+    float* __restrict__ t = temp + e.base;
+    int* __restrict__ o = out + e.obase;
     const int tid = threadIdx.x;
     for (int k = tid; k < n; k += BS) t[k] = 1e38f;
     if (tid == 0) o[0] = 0;
@@ -189,11 +200,12 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, const float
 }
 
 template <int BS, int P>
-static int launch_fps_reg(int b, int n, int m, const float* xyz, int* out, int arith, hipStream_t s) {
+static int launch_fps_reg(int b, int n, int m, const float* xyz, int* out, int arith, hipStream_t s, const int* off, const int* moff,
+                          int fam) {
     if ((arith & DISPU_ARITH_CONTRACT))
-        hipLaunchKernelGGL((fps_reg_kernel<BS, P, true>), dim3(b), dim3(BS), 0, s, n, m, xyz, out);
+        hipLaunchKernelGGL((fps_reg_kernel<BS, P, true>), dim3(b), dim3(BS), 0, s, n, m, xyz, out, off, moff, fam);
     else
-        hipLaunchKernelGGL((fps_reg_kernel<BS, P, false>), dim3(b), dim3(BS), 0, s, n, m, xyz, out);
+        hipLaunchKernelGGL((fps_reg_kernel<BS, P, false>), dim3(b), dim3(BS), 0, s, n, m, xyz, out, off, moff, fam);
     return (int)hipGetLastError();
 }
 
@@ -215,29 +227,32 @@ __global__ void gather_point_grad_kernel(int n, int m, size_t total, const float
     }
 }
 
-// csrc/fps_wave.hip: exact sampling with wave-level skipping for 8192 < n <= 24576 (scratch = the sorted permutation)
+// csrc/fps_wave.hip: exact sampling with wave-level skipping for 4096 < n <= 24576 (scratch = the sorted permutation)
 bool fps_wave_wants_scratch(int n, int m);
 int fps_wave_dispatch(int b, int n, int m, const float* xyz, void* temp, int* out, int arith, hipStream_t s);
+int fps_wave_launch(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s, const int* off, const int* moff);
 
 static bool fps_dense_only() { return false; }     // (the region-skipping kernels of csrc/fps_wave.hip whenever scratch is given)
 
-// the dense (scratch-free for n <= 24576) kernels
-static int fps_dense(int b, int n, int m, const float* inp, float* temp, int* out, int arith, hipStream_t s) {
-    if (n <= 64) return launch_fps_reg<64, 1>(b, n, m, inp, out, arith, s);
-    if (n <= 128) return launch_fps_reg<64, 2>(b, n, m, inp, out, arith, s);
-    if (n <= 256) return launch_fps_reg<64, 4>(b, n, m, inp, out, arith, s);
-    if (n <= 512) return launch_fps_reg<256, 2>(b, n, m, inp, out, arith, s);
-    if (n <= 1024) return launch_fps_reg<256, 4>(b, n, m, inp, out, arith, s);
-    if (n <= 2048) return launch_fps_reg<256, 8>(b, n, m, inp, out, arith, s);
-    if (n <= 4096) return launch_fps_reg<1024, 4>(b, n, m, inp, out, arith, s);
-    if (n <= 8192) return launch_fps_reg<1024, 8>(b, n, m, inp, out, arith, s);
-    if (n <= 16384) return launch_fps_reg<1024, 16>(b, n, m, inp, out, arith, s);
-    if (n <= 24576) return launch_fps_reg<1024, 24>(b, n, m, inp, out, arith, s);
+// the dense (scratch-free for n <= 24576) kernels.  off / moff: a ragged batch of b segments of at most n points each, of which
+// the kernel serves those of family `fam`.
+static int fps_dense(int b, int n, int m, const float* inp, float* temp, int* out, int arith, hipStream_t s,
+                     const int* off = nullptr, const int* moff = nullptr, int fam = 0) {
+    if (n <= 64) return launch_fps_reg<64, 1>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 128) return launch_fps_reg<64, 2>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 256) return launch_fps_reg<64, 4>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 512) return launch_fps_reg<256, 2>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 1024) return launch_fps_reg<256, 4>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 2048) return launch_fps_reg<256, 8>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 4096) return launch_fps_reg<1024, 4>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 8192) return launch_fps_reg<1024, 8>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 16384) return launch_fps_reg<1024, 16>(b, n, m, inp, out, arith, s, off, moff, fam);
+    if (n <= 24576) return launch_fps_reg<1024, 24>(b, n, m, inp, out, arith, s, off, moff, fam);
     if (!temp) return (int)hipErrorInvalidValue;
     if ((arith & DISPU_ARITH_CONTRACT))
-        hipLaunchKernelGGL((fps_mem_kernel<true>), dim3(b), dim3(1024), 0, s, n, m, inp, temp, out);
+        hipLaunchKernelGGL((fps_mem_kernel<true>), dim3(b), dim3(1024), 0, s, n, m, inp, temp, out, off, moff, fam);
     else
-        hipLaunchKernelGGL((fps_mem_kernel<false>), dim3(b), dim3(1024), 0, s, n, m, inp, temp, out);
+        hipLaunchKernelGGL((fps_mem_kernel<false>), dim3(b), dim3(1024), 0, s, n, m, inp, temp, out, off, moff, fam);
     return (int)hipGetLastError();
 }
 
@@ -352,6 +367,92 @@ DISPU_EXPORT int dispu_fps(int b, int n, int m, const float* inp, float* temp, i
         if (r != 0) return r;
     }
     return 0;
+}
+
+// ---- ragged batches: segment c of a packed [sum n_c, 3] cloud gives moff[c + 1] - moff[c] samples ---------------------------------
+// The families of one call (fps_family) run concurrently: the first on the caller's stream, the others on side streams of the
+// device forked from and joined back to it by events (a launch of the register kernels would otherwise wait for the whole of a
+// 24576-point launch, or the other way round).  Streams and events are created on the first mixed call and live with the process.
+namespace dispu {
+
+struct FpsSide {
+    hipStream_t st[2];
+    hipEvent_t fork, join[2];
+};
+static int fps_side(FpsSide** out) {
+    static std::mutex mu;
+    static FpsSide side[64];
+    static bool made[64];
+    int d = 0;
+    DISPU_TRY(hipGetDevice(&d));
+    d &= 63;
+    std::lock_guard<std::mutex> g(mu);
+    if (!made[d]) {
+        FpsSide& f = side[d];
+        DISPU_TRY(hipEventCreateWithFlags(&f.fork, hipEventDisableTiming));
+        for (int i = 0; i < 2; ++i) {
+            DISPU_TRY(hipStreamCreateWithFlags(&f.st[i], hipStreamNonBlocking));
+            DISPU_TRY(hipEventCreateWithFlags(&f.join[i], hipEventDisableTiming));
+        }
+        made[d] = true;
+    }
+    *out = &side[d];
+    return 0;
+}
+
+// -> 0 and the largest segment of every family (0: none), or hipErrorInvalidValue for offsets that are not a ragged batch
+static int fps_segment_families(int C, const int* off_host, const int* moff_host, int nmax[3]) {
+    nmax[0] = nmax[1] = nmax[2] = 0;
+    if (!off_host || !moff_host || off_host[0] != 0 || moff_host[0] != 0) return (int)hipErrorInvalidValue;
+    for (int c = 0; c < C; ++c) {
+        const int n = off_host[c + 1] - off_host[c], m = moff_host[c + 1] - moff_host[c];
+        if (off_host[c + 1] <= off_host[c] || moff_host[c + 1] <= moff_host[c]) return (int)hipErrorInvalidValue;
+        const int f = fps_family(n, m);
+        if (n > nmax[f]) nmax[f] = n;
+    }
+    return 0;
+}
+
+}  // namespace dispu
+
+DISPU_EXPORT size_t dispu_fps_segments_scratch_bytes(int C, const int* off_host, const int* moff_host) {
+    int nmax[3];
+    if (C <= 0 || fps_segment_families(C, off_host, moff_host, nmax) != 0) return 0;
+    return (nmax[1] || nmax[2]) ? (size_t)off_host[C] * sizeof(float) : 0;
+}
+
+DISPU_EXPORT int dispu_fps_segments(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp,
+                                    void* temp, size_t temp_bytes, int* out, int arith, void* stream) {
+    if (C < 0) return (int)hipErrorInvalidValue;
+    if (C == 0) return 0;
+    int nmax[3];
+    if (!off || !moff || !inp || !out || fps_segment_families(C, off_host, moff_host, nmax) != 0) return (int)hipErrorInvalidValue;
+    if ((nmax[1] || nmax[2]) && (!temp || temp_bytes < (size_t)off_host[C] * sizeof(float))) return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    // one launch (sequence) per family, sized for its largest segment: the kernels' results do not depend on their tier
+    auto run = [&](int f, hipStream_t st) -> int {
+        if (f == 1) return fps_wave_launch(C, nmax[1], 0, inp, reinterpret_cast<int*>(temp), out, arith, st, off, moff);
+        return fps_dense(C, nmax[f], 0, inp, reinterpret_cast<float*>(temp), out, arith, st, off, moff, f);
+    };
+    int fams[3], nf = 0;
+    for (int f = 0; f < 3; ++f)
+        if (nmax[f]) fams[nf++] = f;
+    if (nf == 1) return run(fams[0], s);
+    FpsSide* side = nullptr;
+    const int r0 = fps_side(&side);
+    if (r0 != 0) return r0;
+    DISPU_TRY(hipEventRecord(side->fork, s));
+    int r = 0;
+    for (int i = 1; i < nf; ++i) {
+        DISPU_TRY(hipStreamWaitEvent(side->st[i - 1], side->fork, 0));
+        const int ri = run(fams[i], side->st[i - 1]);
+        if (r == 0) r = ri;
+        DISPU_TRY(hipEventRecord(side->join[i - 1], side->st[i - 1]));
+    }
+    const int rm = run(fams[0], s);
+    if (r == 0) r = rm;
+    for (int i = 1; i < nf; ++i) DISPU_TRY(hipStreamWaitEvent(s, side->join[i - 1], 0));
+    return r;
 }
 
 // probsampleLauncher(b,n,m,inp_p,inp_r,temp,out)  tf_sampling.cpp:65,83-89: temp [b, n] receives the cumulative sums.

@@ -81,6 +81,122 @@ def upsample_clouds(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_r
     return result
 
 
+# ---- ragged batches: clouds of different sizes packed into one [sum n_c, 3] array, segment c = points [off[c], off[c + 1]) -----------
+
+def segment_offsets(counts):
+    """counts [C] -> int32 offsets [C + 1] (host), refused (ValueError) when the total does not fit an int32 offset."""
+    off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(np.asarray(counts, np.int64), out=off[1:])
+    if off[-1] >= 2 ** 31:
+        raise ValueError("a packed batch holds at most 2^31 - 1 rows, got %d" % off[-1])
+    return off.astype(np.int32)
+
+
+def _host_ptr(a):
+    return _lib.C.c_void_p(a.ctypes.data)
+
+
+def _dev(a, device):
+    return torch.from_numpy(a).to(device)
+
+
+def fps_segments(inp, off, moff, arith=_lib.ARITH_CONTRACT):
+    """farthest_point_sample per segment: inp [sum n_c, 3] (device), off / moff host offsets of the points and of the samples ->
+    idx [sum m_c] int32, local to each segment.  Segment c equals farthest_point_sample(m_c, cloud_c) bit for bit."""
+    off, moff = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(moff, np.int32)
+    C = len(off) - 1
+    out = torch.empty((int(moff[-1]),), dtype=torch.int32, device=inp.device)
+    L = _lib.lib()
+    nbytes = L.dispu_fps_segments_scratch_bytes(C, _host_ptr(off), _host_ptr(moff))
+    temp = torch.empty((nbytes // 4,), dtype=torch.float32, device=inp.device) if nbytes else None
+    d_off, d_moff = _dev(off, inp.device), _dev(moff, inp.device)
+    _lib.check(L.dispu_fps_segments(C, _lib.ptr(d_off), _lib.ptr(d_moff), _host_ptr(off), _host_ptr(moff), _lib.ptr(inp.contiguous()),
+                                    _lib.ptr(temp), nbytes, _lib.ptr(out), int(arith), _lib.stream_ptr(inp.device)), "dispu_fps_segments")
+    return out
+
+
+def knn_patch_segments(cloud, off, queries, qoff, k):
+    """knn_patch per segment: cloud [sum n_c, 3], queries [sum m_c, 3] (device), host offsets -> idx [sum m_c, k] int32, local."""
+    off, qoff = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(qoff, np.int32)
+    idx = torch.empty((int(qoff[-1]), k), dtype=torch.int32, device=cloud.device)
+    d_off, d_qoff = _dev(off, cloud.device), _dev(qoff, cloud.device)
+    _lib.check(_lib.lib().dispu_knn_patch_segments(len(off) - 1, _lib.ptr(d_off), _lib.ptr(d_qoff), _host_ptr(off), _host_ptr(qoff), k,
+                                                   _lib.ptr(cloud.contiguous()), _lib.ptr(queries.contiguous()), _lib.ptr(idx),
+                                                   _lib.stream_ptr(cloud.device)), "dispu_knn_patch_segments")
+    return idx
+
+
+def normalize_segments(p, off):
+    """normalize_patches over each whole segment: p [sum n_c, 3] -> (normalised [sum n_c, 3], centroid [C, 3], furthest [C])."""
+    off = np.ascontiguousarray(off, np.int32)
+    C = len(off) - 1
+    out = torch.empty_like(p)
+    c = torch.empty((C, 3), dtype=torch.float32, device=p.device)
+    f = torch.empty((C,), dtype=torch.float32, device=p.device)
+    d_off = _dev(off, p.device)
+    _lib.check(_lib.lib().dispu_normalize_segments(C, _lib.ptr(d_off), _host_ptr(off), _lib.ptr(p.contiguous()), _lib.ptr(out), _lib.ptr(c),
+                                                   _lib.ptr(f), _lib.stream_ptr(p.device)), "dispu_normalize_segments")
+    return out, c, f
+
+
+def _gather_rows(points, idx):
+    """points [n, 3], idx [r] int32 global rows -> [r, 3] (dispu_gather_point at b = 1)."""
+    return gather_point(points.reshape(1, -1, 3), idx.reshape(1, -1)).reshape(-1, 3)
+
+
+def upsample_ragged(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_ratio=4, return_stages=False):
+    """Clouds of ANY sizes (a sequence of [n_c, 3] numpy arrays or device tensors) -> a list of [final_ratio * n_c, 3] float32 numpy
+    arrays in input order, each bit-identical to upsample_cloud(gen, clouds[c]) (model.py:343-381 per cloud).  The clouds are packed
+    into one [sum n_c, 3] array; whole-cloud normalisation, both FPS stages and the patch k-NN run as ONE launch (sequence) over all
+    segments, and all patches of all clouds go through one generator batch.  With return_stages also a dict of the packed device
+    stages and their host offsets: cloud_n / off, seeds / seed_off (= rows of pidx, patches_n and fine), merged / merged_off,
+    sel / out_off."""
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError("upsample_ragged needs at least one cloud")
+    for i, c in enumerate(clouds):
+        shape = tuple(c.shape) if hasattr(c, "shape") else np.shape(c)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("cloud %d: expected an [n, 3] array, got shape %s" % (i, shape))
+        if shape[0] < patch_num_point:
+            raise ValueError("cloud %d has %d points, fewer than patch_num_point = %d" % (i, shape[0], patch_num_point))
+        if int(shape[0] / patch_num_point * patch_num_ratio) < 1:
+            raise ValueError("cloud %d: %d points give no patch seed at patch_num_ratio = %g" % (i, shape[0], patch_num_ratio))
+    dev = gen.device
+    sizes = [int(c.shape[0]) for c in clouds]
+    seed_nums = [int(n / patch_num_point * patch_num_ratio) for n in sizes]    # model.py:318, evaluated as upsample_clouds does
+    out_nums = [int(n * final_ratio) for n in sizes]                            # model.py:359
+    per_patch = patch_num_point * gen.up_ratio ** round(math.pow(final_ratio, 1.0 / 4))          # generator_chain's output rows
+    off, soff, ooff = segment_offsets(sizes), segment_offsets(seed_nums), segment_offsets(out_nums)
+    moff = segment_offsets([s * per_patch for s in seed_nums])                  # cloud c's patches: its merged segment
+    if all(not isinstance(c, torch.Tensor) for c in clouds):
+        cloud = torch.from_numpy(np.concatenate([np.asarray(c, np.float32) for c in clouds])).to(dev)
+    else:
+        cloud = torch.cat([torch.as_tensor(c if isinstance(c, torch.Tensor) else np.ascontiguousarray(c, np.float32), dtype=torch.float32,
+                                           device=dev) for c in clouds])
+    cloud = cloud.contiguous()
+    # the segment base of every seed row (local indices -> rows of the packed cloud) and the cloud of every patch
+    sbase = _dev(np.repeat(off[:-1], seed_nums), dev)
+    pcloud = _dev(np.repeat(np.arange(len(sizes)), seed_nums), dev)
+
+    cloud_n, c0, f0 = normalize_segments(cloud, off)                            # model.py:364
+    seeds = fps_segments(cloud_n, off, soff)                                     # model.py:323
+    seed_xyz = _gather_rows(cloud_n, seeds + sbase)
+    pidx = knn_patch_segments(cloud_n, off, seed_xyz, soff, patch_num_point)     # pc_util.extract_knn_patch
+    patches = _gather_rows(cloud_n, (pidx + sbase[:, None]).reshape(-1)).reshape(-1, patch_num_point, 3)
+    pn, pc_c, pc_f = normalize_patches(patches)                                  # model.py:306-308
+    coarse, fine = generator_chain(gen, pn, final_ratio)
+    pred = denormalize_patches(fine, pc_c, pc_f)                                 # model.py:310
+    merged = denormalize_patches(pred, c0[pcloud].contiguous(), f0[pcloud].contiguous()).reshape(-1, 3)   # model.py:371-372
+    sel = fps_segments(merged, moff, ooff)                                       # model.py:375
+    result = _gather_rows(merged, sel + _dev(np.repeat(moff[:-1], out_nums), dev)).cpu().numpy()
+    outs = [result[ooff[c]:ooff[c + 1]] for c in range(len(sizes))]
+    if return_stages:
+        return outs, dict(cloud_n=cloud_n, off=off, seeds=seeds, seed_off=soff, pidx=pidx, patches_n=pn, fine=fine, merged=merged,
+                          merged_off=moff, sel=sel, out_off=ooff)
+    return outs
+
+
 def upsample_cloud(gen, pc, patch_num_point=256, patch_num_ratio=3, final_ratio=4, return_stages=False):
     """pc: [N,3] float32 (numpy or device tensor) -> upsampled [final_ratio*N, 3] numpy array (model.py:343-381).
     `gen` is a dispu_amd.generator.Generator with up_ratio 4 (final_ratio 4: one generator pass, model.py:117-118)."""

@@ -56,7 +56,8 @@ extern "C" {
  * 5 = round 6: dispu_approx_match works inside the reference op's own temp ([b, 2(n+m)] floats; until 4 it needed
  * dispu_approx_match_scratch_bytes and had no way to refuse less); the tiled fast path is dispu_approx_match_ws with an explicit size.
  * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std) and its geodesic disks
- * (dispu_geodesic_*): additions only. */
+ * (dispu_geodesic_*) and the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments):
+ * additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -80,6 +81,18 @@ const char* dispu_error_string(int code);
 size_t dispu_fps_scratch_bytes(int b, int n, int m);
 int dispu_fps(int b, int n, int m, const float* inp, float* temp, int* out, int arith, void* stream);
 int dispu_fps_ws(int b, int n, int m, const float* inp, float* temp, size_t temp_bytes, int* out, int arith, void* stream);
+/* A ragged batch of C clouds, the sampling of DisPU/model.py:315-323 and :375 (farthest_point_sample over each whole cloud) for
+ * clouds of different sizes in one call.  inp [sum n_c, 3] packs the clouds; off [C+1] (device int32, off[0] = 0) holds the
+ * segment offsets, segment c samples m_c = moff[c+1] - moff[c] >= 1 points into out[moff[c] ..] (local indices, out[moff[c]] = 0).
+ * off_host / moff_host are the same offsets in host memory: they choose the kernels and LDS sizes and are never read on the
+ * device.  Every segment's indices are bit-identical to dispu_fps_ws on that cloud alone, in both arithmetic flavours.  Segments
+ * go to the family dispu_fps_ws would pick (register kernels; region-skipping kernels for 4096 < n_c <= 24576 with m_c >= 64;
+ * the streaming kernel above 24576), one launch per family sized for its largest segment; several families run concurrently
+ * on side streams joined back to `stream` by events.  temp_bytes >= dispu_fps_segments_scratch_bytes(C, off_host, moff_host)
+ * (4 * sum n_c when a segment needs the permutation or the running distances, else 0). */
+size_t dispu_fps_segments_scratch_bytes(int C, const int* off_host, const int* moff_host);
+int dispu_fps_segments(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* temp,
+                       size_t temp_bytes, int* out, int arith, void* stream);
 
 /* probsampleLauncher(b,n,m,inp_p,inp_r,temp,out)   tf_sampling.cpp:65,83-89; kernels tf_sampling_g.cu:7-104 (cumulative sums
  * of the weights inp_p[b,n] into temp[b,n], then out[b,m] = the first position whose cumulative weight is >= inp_r * total).
@@ -643,6 +656,20 @@ int dispu_normalize_patches(int b, int n, const float* in, float* out, float* ce
 /* out = centroid + in * furthest per patch (model.py:310-311). */
 int dispu_denormalize_patches(int b, int m, const float* in, const float* centroid, const float* furthest, float* out,
                               void* stream);
+/* Ragged batches of whole clouds (model.py:315-381 for C clouds of different sizes at once; pc_util.py:83-92,147-161).  cloud / in
+ * [sum n_c, 3] packs the clouds, off [C+1] (device int32, off[0] = 0) the segment offsets, off_host the same offsets in host memory
+ * (tiers, LDS sizes, validation; never read on the device).
+ * dispu_knn_patch_segments: extract_knn_patch per segment; queries [sum m_c, 3] packed by qoff / qoff_host, idx [sum m_c, k] local
+ * indices.  Bit-identical to dispu_knn_patch on each cloud alone (segments above 8192 points: the radix-select kernel, k <= 4096);
+ * each query sorts over its own segment's padded size.  C <= 65535.
+ * dispu_normalize_segments: normalize_point_cloud over each whole segment, centroid [C,3], furthest [C]; the sequential float32 mean
+ * of dispu_normalize_patches, so each segment is bit-identical to it on that cloud alone.
+ * (Gathers take global indices through dispu_gather_point at b = 1; de-normalisation is dispu_denormalize_patches with per-patch
+ * copies of a cloud's centroid and radius.) */
+int dispu_knn_patch_segments(int C, const int* off, const int* qoff, const int* off_host, const int* qoff_host, int k, const float* cloud,
+                             const float* queries, int* idx, void* stream);
+int dispu_normalize_segments(int C, const int* off, const int* off_host, const float* in, float* out, float* centroid, float* furthest,
+                             void* stream);
 
 /* ---- evaluator: point-to-surface distance and disk uniformity (evaluation_code/evaluation.cpp, a CGAL + pthreads tool in the
  * reference, and evaluate.py:53-101) ------------------------------------------------------------------------------------------- */

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Command line of the reference's test phase, `dis-pu.py --phase test` (DisPU/model.py:343-381): restore the latest checkpoint of
+--log_dir, upsample every cloud matched by --test_data (default <data_dir>/test/*.xyz) and write <stem>_X<final_ratio>.xyz with
+np.savetxt(fmt='%.6f') into --out_folder (default <data_dir>/test/output) -- the files tools/evaluate.py reads.
+
+Clouds go through dis-pu_amd/upsample.py:upsample_ragged in groups of at most --max-points input points (a larger cloud is a group of
+its own), so clouds of different sizes share launches; the outputs do not depend on the grouping.  Each output has final_ratio * n
+points for its own n (the reference takes n from the first globbed file for all of them, model.py:356-359).  .xyz only: rows of
+>= 3 numbers, read like pc_util.load (np.loadtxt, first three columns)."""
+import argparse
+import glob
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def output_name(path, final_ratio):
+    """model.py:380: point_path.split('/')[-1][:-4] + '_X%d.xyz' % final_ratio."""
+    return os.path.splitext(os.path.basename(path))[0] + "_X%d.xyz" % final_ratio
+
+
+def refuse_unsupported(paths):
+    """ValueError naming the first input that is not an .xyz file (pc_util.load's .ply / .pcd readers are not available)."""
+    for p in paths:
+        if os.path.splitext(p)[1].lower() != ".xyz":
+            raise ValueError("%s: only .xyz point clouds are supported (rows of x y z [...]); convert .ply / .pcd files to .xyz first" % p)
+
+
+def load_xyz(path):
+    """pc_util.load(path)[:, :3] for an .xyz file: np.loadtxt as float32, the first three columns (files with normals work)."""
+    pts = np.loadtxt(path, ndmin=2).astype(np.float32)
+    if pts.shape[1] < 3:
+        raise ValueError("%s: expected at least three columns, got %d" % (path, pts.shape[1]))
+    return np.ascontiguousarray(pts[:, :3])
+
+
+def group_by_budget(sizes, max_points):
+    """Consecutive groups of indices into `sizes` (input order kept, no cloud split) whose point counts sum to at most max_points;
+    a cloud above the budget forms a group of its own."""
+    groups, cur, tot = [], [], 0
+    for i, n in enumerate(sizes):
+        if cur and tot + n > max_points:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(i)
+        tot += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="Upsample point clouds with a trained generator (the reference's --phase test).")
+    ap.add_argument("--log_dir", default="log", help="checkpoint directory (its `checkpoint` file names the latest model)")
+    ap.add_argument("--data_dir", default="data", help="reads <data_dir>/test/*.xyz, writes <data_dir>/test/output")
+    ap.add_argument("--test_data", default=None, help="glob of the input clouds (overrides <data_dir>/test/*.xyz)")
+    ap.add_argument("--out_folder", default=None, help="output directory (overrides <data_dir>/test/output)")
+    ap.add_argument("--final_ratio", type=int, choices=(4, 16), default=4, help="upsampling ratio: 4 (one generator pass) or 16 (two)")
+    ap.add_argument("--patch_num_point", type=int, default=256, help="points per patch")
+    ap.add_argument("--patch_num_ratio", type=int, default=3, help="patch seeds per patch_num_point input points")
+    ap.add_argument("--max-points", dest="max_points", type=int, default=1 << 20,
+                    help="input points per batch of clouds (bounds device memory and keeps packed offsets below 2^31)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    if a.max_points <= 0:
+        sys.exit("--max-points must be positive")
+    pattern = a.test_data or os.path.join(a.data_dir, "test", "*.xyz")
+    out_dir = a.out_folder or os.path.join(a.data_dir, "test", "output")
+    paths = sorted(glob.glob(pattern))
+    if not paths:
+        sys.exit("no input matches %s" % pattern)
+    try:
+        refuse_unsupported(paths)
+    except ValueError as e:
+        sys.exit(str(e))
+    clouds = [load_xyz(p) for p in paths]
+
+    sys.path.insert(0, ROOT)
+    import torch
+    import dispu_amd  # noqa: F401
+    from dispu_amd.checkpoint import restore_generator
+    from dispu_amd.upsample import save_xyz, upsample_ragged
+
+    if not torch.cuda.is_available():
+        sys.exit("no ROCm device")
+    dev = torch.device("cuda:0")
+    epoch, gen = restore_generator(a.log_dir, device=dev)
+    print("restored %s (epoch %d)" % (a.log_dir, epoch))
+    os.makedirs(out_dir, exist_ok=True)
+    t0 = time.time()
+    for group in group_by_budget([c.shape[0] for c in clouds], a.max_points):
+        try:
+            preds = upsample_ragged(gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
+        except ValueError as e:
+            sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
+        for i, pred in zip(group, preds):
+            out = os.path.join(out_dir, output_name(paths[i], a.final_ratio))
+            save_xyz(out, pred)
+            print("%s: %d -> %d points, %s" % (paths[i], clouds[i].shape[0], pred.shape[0], out))
+    print("%d clouds in %.2f s" % (len(paths), time.time() - t0))
+
+
+if __name__ == "__main__":
+    main()
