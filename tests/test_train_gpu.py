@@ -7,7 +7,9 @@ gradient of the affected ROWS by O(1) while everything else agrees to ~1e-6.  Th
 row-wise and robust: median row error <= 1e-5 and <= 1 % of rows off by more than 1e-3 for the activation
 gradients, relative L2 <= 3e-3 (and max <= 2e-2 of the largest entry) for the parameter gradients -- a wrong or
 missing term moves these by orders of magnitude more (the reference's own gradient tests use 1e-4 on single ops,
-tf_grouping_op_test.py:23-25)."""
+tf_grouping_op_test.py:23-25).
+The kernels between the generator's output and its first gradient (Chamfer value / gradient, fused repulsion, pu_loss_finalize,
+transpose_batched, sigmoid_offset, dup_sum_grad, add3) have their own tests against float64 in tests/test_train_loss_gpu.py."""
 import ctypes as C
 
 import numpy as np
