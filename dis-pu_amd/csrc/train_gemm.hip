@@ -679,6 +679,7 @@ DISPU_EXPORT int dispu_act_bias_grad(long rows, int n, const float* dY, long ldd
                                      long lddz, float* dbias, int accumulate, float* scratch, long scratch_floats,
                                      void* stream) {
     if (rows < 0 || n < 0 || (act && Y == nullptr)) return (int)hipErrorInvalidValue;
+    if (dZ != nullptr && dZ == dY && lddz != lddy) return (int)hipErrorInvalidValue;      // in place means the same window, stride included
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (rows == 0) {
@@ -686,7 +687,13 @@ DISPU_EXPORT int dispu_act_bias_grad(long rows, int n, const float* dY, long ldd
         return 0;
     }
     if (!dbias) {
-        if (!act || !dZ) return 0;
+        if (!dZ || (!act && dZ == dY)) return 0;
+        if (!act) {         // dZ = dY into a separate buffer: the strided copy of the header's contract (no mask, no partial sums)
+            int rpb;
+            const int nb = bias_blocks(rows, rpb);
+            hipLaunchKernelGGL(act_bias_grad_kernel, dim3(nb), dim3(256), 0, s, rows, n, rpb, dY, lddy, Y, ldy, 0, dZ, lddz, (float*)nullptr);
+            return (int)hipGetLastError();
+        }
         const size_t total = (size_t)rows * n;
         if ((n & 3) == 0 && (lddy & 3) == 0 && (ldy & 3) == 0 && (lddz & 3) == 0 && total / 4 < 0x7fffffffull && lddy < 0x7fffffffl &&
             ldy < 0x7fffffffl && lddz < 0x7fffffffl && ((((uintptr_t)dY) | ((uintptr_t)Y) | ((uintptr_t)dZ)) & 15) == 0) {

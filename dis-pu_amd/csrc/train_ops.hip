@@ -273,15 +273,18 @@ __global__ void bn_apply_kernel(long rows, int c, const float* __restrict__ X, l
     }
 }
 
-// part[blk][0][c] = sum dz, part[blk][1][c] = sum dz * xhat, dz = dY * (act ? Y > 0 : 1)
+// part[blk][0][c] = sum dz, part[blk][1][c] = sum dz * xhat, part[blk][2][c] = sum xhat, dz = dY * (act ? Y > 0 : 1).
+// xhat is taken about the float32 mean of `stats`; where a column's mean is large against its spread that mean is off by up to half an
+// ulp and every xhat by the same d = (mean - fl32(mean)) / std, which shifts sum dz * xhat by d * sum dz.  sum xhat = rows * d measures
+// d, and bn_grad_finalize_kernel takes it out again.
 __global__ __launch_bounds__(256) void bn_grad_stats_kernel(long rows, int c, int rows_per_block, const float* __restrict__ X,
                                                              long ldx, const float* __restrict__ Y, long ldy,
                                                              const float* __restrict__ dY, long lddy,
                                                              const float* __restrict__ stats, int act, double* __restrict__ part) {
-    __shared__ double red[2][256];
+    __shared__ double red[3][256];
     const int ch = threadIdx.x % c, rr = threadIdx.x / c, step = 256 / c;
     const long r0 = (long)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
-    double s1 = 0.0, s2 = 0.0;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
     if (rr < step) {
         const float mu = stats[ch], is = stats[2 * c + ch];
         for (long r = r0 + rr; r < r1; r += step) {
@@ -290,34 +293,41 @@ __global__ __launch_bounds__(256) void bn_grad_stats_kernel(long rows, int c, in
             const float xh = (X[r * ldx + ch] - mu) * is;
             s1 += (double)g;
             s2 += (double)g * (double)xh;
+            s3 += (double)xh;
         }
     }
     red[0][threadIdx.x] = s1;
     red[1][threadIdx.x] = s2;
+    red[2][threadIdx.x] = s3;
     __syncthreads();
     if (threadIdx.x < c) {
-        double a = 0.0, b = 0.0;
+        double a = 0.0, b = 0.0, d = 0.0;
         for (int g = 0; g < step; ++g) {
             a += red[0][g * c + threadIdx.x];
             b += red[1][g * c + threadIdx.x];
+            d += red[2][g * c + threadIdx.x];
         }
-        part[((size_t)blockIdx.x * 2 + 0) * c + threadIdx.x] = a;
-        part[((size_t)blockIdx.x * 2 + 1) * c + threadIdx.x] = b;
+        part[((size_t)blockIdx.x * 3 + 0) * c + threadIdx.x] = a;
+        part[((size_t)blockIdx.x * 3 + 1) * c + threadIdx.x] = b;
+        part[((size_t)blockIdx.x * 3 + 2) * c + threadIdx.x] = d;
     }
 }
 
-// sums[0:c] = sum dz, sums[c:2c] = sum dz*xhat;  dbeta += sum dz, dgamma += sum dz*xhat
-__global__ __launch_bounds__(64) void bn_grad_finalize_kernel(int c, int nparts, const double* __restrict__ part, float* __restrict__ sums,
+// sums[0:c] = sum dz, sums[c:2c] = sum dz*xhat - (sum xhat / rows) * sum dz;  dbeta += sums[0:c], dgamma += sums[c:2c]
+__global__ __launch_bounds__(64) void bn_grad_finalize_kernel(long rows, int c, int nparts, const double* __restrict__ part, float* __restrict__ sums,
                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
     const int ch = blockIdx.x;
-    double a = 0.0, b = 0.0;
+    double a = 0.0, b = 0.0, d = 0.0;
     for (int s = threadIdx.x; s < nparts; s += 64) {
-        a += part[((size_t)s * 2 + 0) * c + ch];
-        b += part[((size_t)s * 2 + 1) * c + ch];
+        a += part[((size_t)s * 3 + 0) * c + ch];
+        b += part[((size_t)s * 3 + 1) * c + ch];
+        d += part[((size_t)s * 3 + 2) * c + ch];
     }
     a = bn_wave_sum(a);
     b = bn_wave_sum(b);
+    d = bn_wave_sum(d);
     if (threadIdx.x != 0) return;
+    b -= (d / (double)rows) * a;
     sums[ch] = (float)a;
     sums[c + ch] = (float)b;
     if (dbeta) dbeta[ch] += (float)a;
@@ -539,7 +549,7 @@ DISPU_EXPORT int dispu_softmax_rows_grad(long rows, int n, float mul, const floa
 DISPU_EXPORT long dispu_bn_scratch_bytes(long rows, int c) {
     if (rows <= 0 || c <= 0) return 0;
     int rpb;
-    return (long)bn_blocks(rows, rpb) * 2 * c * (long)sizeof(double);
+    return (long)bn_blocks(rows, rpb) * 3 * c * (long)sizeof(double);      // the gradient's three partial sums per block and channel; the forward uses two
 }
 
 DISPU_EXPORT int dispu_bn_train(long rows, int c, const float* X, long ldx, const float* gamma, const float* beta, float eps,
@@ -566,12 +576,12 @@ DISPU_EXPORT int dispu_bn_train_grad(long rows, int c, const float* X, long ldx,
     if (rows <= 0 || c <= 0 || c > 64 || 256 % c != 0 || sums == nullptr) return (int)hipErrorInvalidValue;
     int rpb;
     const int nb = bn_blocks(rows, rpb);
-    if (scratch == nullptr || scratch_bytes < (long)nb * 2 * c * (long)sizeof(double)) return (int)hipErrorInvalidValue;
+    if (scratch == nullptr || scratch_bytes < (long)nb * 3 * c * (long)sizeof(double)) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_grad_stats_kernel, dim3(nb), dim3(256), 0, s, rows, c, rpb, X, ldx, Y, ldy, dY, lddy, stats, act,
                        (double*)scratch);
     DISPU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(c), dim3(64), 0, s, c, nb, (const double*)scratch, sums, dgamma, dbeta);
+    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(c), dim3(64), 0, s, rows, c, nb, (const double*)scratch, sums, dgamma, dbeta);
     DISPU_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_grad_apply_kernel, dim3(tgrid((size_t)rows * c, 256)), dim3(256), 0, s, rows, c, X, ldx, Y, ldy, dY,
                        lddy, stats, gamma, sums, act, dX, lddx);

@@ -437,7 +437,8 @@ typedef struct dispu_tn_reduce_desc {
 int dispu_tn_defer(dispu_tn_reduce_desc* desc);
 int dispu_tn_reduce_grouped(int count, const dispu_tn_reduce_desc* table_host, const dispu_tn_reduce_desc* table_device, void* stream);
 long dispu_act_bias_grad_scratch_floats(long rows, int n);
-/* dZ = dY * (act ? Y > 0 : 1) (relu_grad; dZ may alias dY or be NULL), dbias (+)= column sums of dZ (bias_add_grad;
+/* dZ = dY * (act ? Y > 0 : 1) (relu_grad; dZ may be NULL, or dY itself with lddz == lddy: any other stride under the same pointer is
+ * refused), dbias (+)= column sums of dZ (bias_add_grad;
  * dbias may be NULL).  tf_util.py:100-115,170-185. */
 int dispu_act_bias_grad(long rows, int n, const float* dY, long lddy, const float* Y, long ldy, int act, float* dZ, long lddz,
                         float* dbias, int accumulate, float* scratch, long scratch_floats, void* stream);
@@ -466,13 +467,16 @@ int dispu_ps_point_matmul_grad(long rows, int k, int c, int t_n, const float* X2
                                long ldo, float* dX2, long lddx2, float* dwv, void* stream);
 /* gradient of dispu_softmax_rows: dP <- mul * P * (dP - rowsum(dP * P)), in place. */
 int dispu_softmax_rows_grad(long rows, int n, float mul, const float* P, long ldp, float* dP, long lddp, void* stream);
+/* scratch that serves both entries below: the gradient's three double partial sums per block and channel (the forward needs, and
+ * checks for, two of them). */
 long dispu_bn_scratch_bytes(long rows, int c);
 /* contrib.layers.batch_norm in training mode (tf_util.py:512-531): batch statistics over the rows, eps, optional
  * ReLU; stats[3c] = mean | biased var | 1/sqrt(var+eps); moving statistics updated in place with `decay`. */
 int dispu_bn_train(long rows, int c, const float* X, long ldx, const float* gamma, const float* beta, float eps, float decay,
                    int act, float* Y, long ldy, float* stats, float* moving_mean, float* moving_var, void* scratch,
                    long scratch_bytes, void* stream);
-/* its gradient: dX written, dgamma / dbeta accumulate, sums[2c] receives (sum dz | sum dz*xhat). */
+/* its gradient: dX written, dgamma / dbeta accumulate, sums[2c] receives (sum dz | sum dz*xhat); xhat about the true mean: the
+ * offset of the float32 mean in `stats` is measured (sum xhat) and taken out. */
 int dispu_bn_train_grad(long rows, int c, const float* X, long ldx, const float* Y, long ldy, const float* dY, long lddy,
                         const float* stats, const float* gamma, int act, float* dX, long lddx, float* dgamma, float* dbeta,
                         float* sums, void* scratch, long scratch_bytes, void* stream);

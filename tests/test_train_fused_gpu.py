@@ -3,12 +3,18 @@ float64 torch autograd of the forward op each one differentiates -- 1e-5, like t
 native code here (TF1 autodiff, DisPU/model.py:158-178); the forward ops are Common/ops.py:1012-1087 (PointShuffle2)."""
 import ctypes as C
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import train_oracle as T
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import train_ops_oracle as TO  # noqa: E402
+from train_ops_oracle import Guarded, Strided, same_bits  # noqa: E402
+
+from oracle import train_oracle as T  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -31,6 +37,7 @@ def _release():
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     del _KEEP[:]
+    TO.release()
 
 
 def p(t, off=0):
@@ -81,31 +88,50 @@ def test_linear_masked(dev, L, M, Kc, Nout, mcols, acc, kind):
     close(got, ref, 2e-6 * max(Kc, 8) ** 0.5, "masked dX")
 
 
-def test_mask3(dev, L):
+MASK3_CASES = [
+    # (rows, n, (lddy, ld1, ld2, ld3, ldo))
+    (3000, 256, (256, 256, 256, 256, 256)),        # the shape this test always had
+    (8192, 256, (256, 256, 256, 256, 256)),        # the trainer's: 8 patches of 1024 points
+    (300, 256, (256, 256, 256, 256, 256)),         # 3 clouds of 100 points
+    (1000, 64, (68, 72, 76, 80, 84)),              # every operand with a stride of its own
+    (65537, 256, (256, 256, 256, 256, 256)),       # 4 194 368 quads: second trip of the grid-stride loop
+]
+
+
+@pytest.mark.parametrize("rows,n,ld", MASK3_CASES)
+def test_mask3(dev, L, rows, n, ld):
+    """the Ys are ReLU outputs (half exact +0.0) with a block of -0.0, which is not `> 0` either; outputs between sentinels."""
     rng = np.random.default_rng(1)
-    rows, n = 3000, 256
     d = rng.standard_normal((rows, n)).astype(np.float32)
-    ys = [np.maximum(rng.standard_normal((rows, n)), 0).astype(np.float32) for _ in range(3)]
-    outs = [torch.empty((rows, n), dtype=torch.float32, device=dev) for _ in range(3)]
-    ty = [dv(y, dev) for y in ys]
-    L.check(L.lib().dispu_mask3(rows, n, p(dv(d, dev)), n, p(ty[0]), n, p(ty[1]), n, p(ty[2]), n, p(outs[0]), p(outs[1]), p(outs[2]), n,
-                                L.stream_ptr(dev)), "mask3")
+    ys = [TO.relu_like(rng, (rows, n), (7 * i, 7 * i + 40)) for i in range(3)]
+    sd = Strided(dev, rows, n, ld[0], ld[0] - n, d)
+    sy = [Strided(dev, rows, n, ld[1 + i], 0, ys[i]) for i in range(3)]
+    outs = [Strided(dev, rows, n, ld[4], ld[4] - n) for _ in range(3)]
+    L.check(L.lib().dispu_mask3(rows, n, sd.ptr(), ld[0], sy[0].ptr(), ld[1], sy[1].ptr(), ld[2], sy[2].ptr(), ld[3], outs[0].ptr(), outs[1].ptr(),
+                                outs[2].ptr(), ld[4], L.stream_ptr(dev)), "mask3")
+    torch.cuda.synchronize()
     for o, y in zip(outs, ys):
-        assert np.array_equal(N_(o), np.where(y > 0, d, 0).astype(np.float32))
+        assert same_bits(o.data(), np.where(y > 0, d, 0).astype(np.float32)) and o.rest_untouched()
+    assert sd.untouched() and all(t.untouched() for t in sy)
 
 
 def _cloud(rng, B, n, k):
     xyz = rng.standard_normal((B, n, 3)).astype(np.float32) * 0.3
-    d = ((xyz[:, :, None, :] - xyz[:, None, :, :]) ** 2).sum(-1)
-    idx = np.argsort(d, axis=-1, kind="stable")[:, :, :k].astype(np.int32)
+    idx = np.empty((B, n, k), np.int32)
+    for b in range(B):                                                           # one cloud at a time: [n, n] distances, not [B, n, n]
+        d = ((xyz[b][:, None, :] - xyz[b][None, :, :]) ** 2).sum(-1)
+        idx[b] = np.argsort(d, axis=-1, kind="stable")[:, :k]
     return xyz, idx
 
 
-def test_wnet_bn_stats_and_grad(dev, L):
+# today's shape; the trainer's (8192 rows: the statistics kernels' 1024 workgroups walk eight rows each); 3 clouds of 100; 17408 rows:
+# above the 2048 workgroups x 8 rows of the gradient's apply kernel
+@pytest.mark.parametrize("B,n", [(2, 256), (8, 1024), (3, 100), (17, 1024)])
+def test_wnet_bn_stats_and_grad(dev, L, B, n):
     """weight_net_hidden in training mode (ops.py:181-191) without its stored input: batch statistics / folded scale+shift / moving
     statistics against float64, then every gradient (dWw, dbw ~ 0, dgamma, dbeta, dxyz of both points of a pair)."""
     rng = np.random.default_rng(3)
-    B, n, k, t = 2, 256, 16, 16
+    k, t = 16, 16
     xyz, idx = _cloud(rng, B, n, k)
     Ww = (rng.standard_normal((3, t)) * 2).astype(np.float32)
     bw = (rng.standard_normal(t) * 0.1).astype(np.float32)
@@ -174,11 +200,13 @@ def test_knn_invert(dev, L, B, n, k):
         assert np.array_equal(o[b], np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=n))]).astype(np.int32))
 
 
-def test_conv0_per_source_point_backward(dev, L):
+# today's shape; the trainer's (8192 rows: ps_prep_grad's 256 workgroups of 4 rows go round eight times); 3 clouds of 100
+@pytest.mark.parametrize("B,n", [(2, 256), (8, 1024), (3, 100)])
+def test_conv0_per_source_point_backward(dev, L, B, n):
     """h0 = relu(G[j] - A[i]) with G = feat.Wf + xyz.(Wc + Wr) + b0, A = xyz.Wc (csrc/mlp_misc.hip:ps_prep): dz0 -> dG / dAneg through the
     inverted graph (no atomics: run twice, bit-identical), then dxyz and dW0[0:6] (ps_prep_grad) against float64 autograd."""
     rng = np.random.default_rng(11)
-    B, n, k, c = 2, 256, 16, 128
+    k, c = 16, 128
     xyz, idx = _cloud(rng, B, n, k)
     rows = B * n
     W0 = (rng.standard_normal((134, c)) * 0.2).astype(np.float32)
@@ -234,11 +262,12 @@ def test_conv0_per_source_point_backward(dev, L):
     assert not N_(dW0)[6:].any()
 
 
-def test_skip_max_grad(dev, L):
+@pytest.mark.parametrize("B,n", [(2, 256), (8, 1024), (3, 100)])      # today's; the trainer's 8192 rows; 3 clouds of 100
+def test_skip_max_grad(dev, L, B, n):
     """max over the 16 neighbours of [xyz_j - xyz_i | xyz_j | feat_j] (ops.py:1049) backward without the grouped tensor; duplicate
     neighbours make exact ties, which share the gradient evenly (math_grad._MinOrMaxGrad == oracle max_even)."""
     rng = np.random.default_rng(13)
-    B, n, k, cf = 2, 256, 16, 128
+    k, cf = 16, 128
     xyz, idx = _cloud(rng, B, n, k)
     idx[:, ::3, 5] = idx[:, ::3, 2]                                           # repeated neighbour: every channel it wins is a 2-way tie
     feat = rng.standard_normal((B, n, cf)).astype(np.float32)
@@ -278,21 +307,53 @@ def test_skip_max_grad(dev, L):
     close(outs[1][1], outs[0][1].astype(np.float64), 1e-5, "dxyz")
 
 
-def test_point_matmul_grad_relu(dev, L):
+# today's 37 rows; the trainer's 8192; 16385: one row more than the 16384 workgroups, which walks the first of them round its loop again
+@pytest.mark.parametrize("rows", [37, 8192, 16385])
+def test_point_matmul_grad_relu(dev, L, rows):
     rng = np.random.default_rng(7)
-    rows, k, c, t = 37, 16, 128, 16
+    k, c, t = 16, 128, 16
     X2 = np.maximum(rng.standard_normal((rows * k, c)), 0).astype(np.float32)        # h1 = a ReLU output
+    X2[3 * k:5 * k] = np.float32(-0.0)                                               # ... with two points of -0.0
     wv = rng.standard_normal((rows * k, t)).astype(np.float32)
     do = rng.standard_normal((rows, c * t)).astype(np.float32)
-    dX2 = torch.empty((rows * k, c), dtype=torch.float32, device=dev)
-    dwv = torch.empty((rows * k, t), dtype=torch.float32, device=dev)
-    L.check(L.lib().dispu_ps_point_matmul_grad_relu(rows, k, c, t, p(dv(X2, dev)), c, p(dv(wv, dev)), p(dv(do, dev)), c * t, p(dX2), c,
-                                                    p(dwv), L.stream_ptr(dev)), "point_matmul_grad_relu")
-    xt = torch.tensor(X2.reshape(rows, k, c), dtype=F64, requires_grad=True)
-    wt = torch.tensor(wv.reshape(rows, k, t), dtype=F64, requires_grad=True)
-    (xt.transpose(1, 2) @ wt).reshape(rows, c * t).backward(torch.tensor(do, dtype=F64))
-    close(N_(dX2).reshape(rows, k, c), xt.grad.numpy() * (X2.reshape(rows, k, c) > 0), 1e-5, "dz1")
-    close(N_(dwv).reshape(rows, k, t), wt.grad.numpy(), 1e-5, "dwv")
+    dX2, dwv = Guarded(dev, rows * k * c), Guarded(dev, rows * k * t)                # sentinels: a row that is not written shows
+    L.check(L.lib().dispu_ps_point_matmul_grad_relu(rows, k, c, t, p(dv(X2, dev)), c, p(dv(wv, dev)), p(dv(do, dev)), c * t, dX2.ptr(), c,
+                                                    dwv.ptr(), L.stream_ptr(dev)), "point_matmul_grad_relu")
+    torch.cuda.synchronize()
+    if rows <= 37:
+        xt = torch.tensor(X2.reshape(rows, k, c), dtype=F64, requires_grad=True)
+        wt = torch.tensor(wv.reshape(rows, k, t), dtype=F64, requires_grad=True)
+        (xt.transpose(1, 2) @ wt).reshape(rows, c * t).backward(torch.tensor(do, dtype=F64))
+        rX, rW = xt.grad.numpy(), wt.grad.numpy()
+    else:         # the explicit formulas (tests/test_train_ops_oracle.py holds them to this autograd at 1e-12)
+        rX, rW = TO.point_matmul_grad(X2.reshape(rows, k, c), wv.reshape(rows, k, t), do)
+    keep = X2.reshape(rows, k, c) > 0
+    got = dX2.body().reshape(rows, k, c)
+    close(got, rX * keep, 1e-5, "dz1")
+    assert not got[~keep].any()
+    close(dwv.body().reshape(rows, k, t), rW, 1e-5, "dwv")
+    assert dX2.guards_intact() and dwv.guards_intact()
+
+
+def test_point_matmul_grad_relu_bf16_storage_above_the_cap(dev, L):
+    """the bf16-storage twin at 16385 rows: bit-identical to the fp32-storage kernel on the same (bf16-representable) values, rounded."""
+    rng = np.random.default_rng(8)
+    rows, k, c, t = 16385, 16, 128, 16
+    h1b = torch.relu(dv(rng.standard_normal((rows * k, c)).astype(np.float32), dev)).bfloat16()
+    dob = dv(rng.standard_normal((rows, c * t)).astype(np.float32), dev).bfloat16()
+    wv = dv(rng.standard_normal((rows * k, t)).astype(np.float32), dev)
+    dz_b = torch.full((rows * k, c), 7.0, dtype=torch.bfloat16, device=dev)
+    dz_f, dwv_b, dwv_f = [torch.full(sh, 7.0, device=dev) for sh in ((rows * k, c), (rows * k, t), (rows * k, t))]
+    h1f, dof = h1b.float().contiguous(), dob.float().contiguous()
+    _KEEP.extend([h1b, dob, dz_b, dz_f, dwv_b, dwv_f, h1f, dof])
+    lib, st = L.lib(), L.stream_ptr(dev)
+    L.check(lib.dispu_ps_point_matmul_grad_relu_s(rows, k, c, t, p(h1b), c, p(wv), p(dob), c * t, p(dz_b), c, p(dwv_b), 1, st), "pmg bf16")
+    L.check(lib.dispu_ps_point_matmul_grad_relu_s(rows, k, c, t, p(h1f), c, p(wv), p(dof), c * t, p(dz_f), c, p(dwv_f), 0, st), "pmg f32")
+    torch.cuda.synchronize()
+    assert torch.equal(dz_b, dz_f.bfloat16()) and torch.equal(dwv_b, dwv_f)
+    rX, rW = TO.point_matmul_grad(N_(h1f).reshape(rows, k, c), N_(wv).reshape(rows, k, t), N_(dof))
+    close(N_(dwv_f).reshape(rows, k, t), rW, 1e-5, "dwv")
+    close(N_(dz_f).reshape(rows, k, c), rX * (N_(h1f).reshape(rows, k, c) > 0), 1e-5, "dz1")
 
 
 @pytest.mark.parametrize("rows", [384, 96, 12288, 24576])       # 32-row workgroups (< 192 of 64 rows; 96: only 32 divides), 64-row, 128-row

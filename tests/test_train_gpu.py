@@ -9,7 +9,11 @@ gradients, relative L2 <= 3e-3 (and max <= 2e-2 of the largest entry) for the pa
 missing term moves these by orders of magnitude more (the reference's own gradient tests use 1e-4 on single ops,
 tf_grouping_op_test.py:23-25).
 The kernels between the generator's output and its first gradient (Chamfer value / gradient, fused repulsion, pu_loss_finalize,
-transpose_batched, sigmoid_offset, dup_sum_grad, add3) have their own tests against float64 in tests/test_train_loss_gpu.py."""
+transpose_batched, sigmoid_offset, dup_sum_grad, add3) have their own tests against float64 in tests/test_train_loss_gpu.py.
+The "kernels" section below visits each backward kernel at one small shape; tests/test_train_ops_gpu.py runs the same kernels on every
+path of their launch code (grid caps, float4 / scalar switches, strides, ties, exact zeros, NULL outputs, refusals) against the
+explicit-index float64 formulas of tests/train_ops_oracle.py, and tests/test_train_fused_gpu.py the fused PointShuffle2 backward kernels
+at the trainer's own shapes."""
 import ctypes as C
 
 import numpy as np
