@@ -4,7 +4,7 @@
 // The random draws (clipped Gaussian jitter, angles, scales, shifts) are made by the host with the reference's own
 // numpy call sequence and handed in, so a seeded run reproduces the reference's batches; the HBM-bound transform of
 // the [B, N, 3] coordinate blocks happens here.  noise / shift may be NULL.
-#include "common.h"
+#include "augment_point.h"
 
 namespace dispu {
 
@@ -15,13 +15,9 @@ __global__ void augment_kernel(int b, int n, const float* __restrict__ in, const
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const size_t c = e / n;
         float x = in[e * 3 + 0], y = in[e * 3 + 1], z = in[e * 3 + 2];
-        if (noise) { x += noise[e * 3 + 0]; y += noise[e * 3 + 1]; z += noise[e * 3 + 2]; }
-        const float* R = rot + c * 9;                       // row vector times matrix: p' = p . R (np.dot(points, R))
-        float ox = (x * R[0] + y * R[3]) + z * R[6];
-        float oy = (x * R[1] + y * R[4]) + z * R[7];
-        float oz = (x * R[2] + y * R[5]) + z * R[8];
-        const float s = scale[c];
-        ox *= s; oy *= s; oz *= s;
+        if (noise) augment_jitter(x, y, z, noise[e * 3 + 0], noise[e * 3 + 1], noise[e * 3 + 2]);
+        float ox, oy, oz;                                   // row vector times matrix: p' = p . R (np.dot(points, R))
+        augment_rotate_scale(x, y, z, rot + c * 9, scale[c], ox, oy, oz);
         if (shift) { ox += shift[c * 3 + 0]; oy += shift[c * 3 + 1]; oz += shift[c * 3 + 2]; }
         out[e * 3 + 0] = ox; out[e * 3 + 1] = oy; out[e * 3 + 2] = oz;
     }

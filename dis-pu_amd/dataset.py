@@ -7,6 +7,9 @@ next_batch's off-by-one, which skips the first batch of every epoch).  What diff
 and every batch is produced by two device launches (row gather of the 256-of-1024 sub-sample through
 dispu_group_point, then dispu_augment), returning device tensors ready for Trainer.train_step; the reference does
 this in numpy on a background thread and feeds the result through a TF placeholder.
+
+DeviceFetcher has the same surface but makes every per-batch draw on the device (one dispu_sample_batch launch per batch, Philox
+draws keyed by seed / epoch / position): the reference's distributions, not numpy's sequence.  It is what the training loop uses.
 """
 import numpy as np
 import torch
@@ -125,3 +128,94 @@ class Fetcher(object):
             _lib.check(L.dispu_augment(bsize, gt.shape[1], _lib.ptr(gt), None, _lib.ptr(dr), _lib.ptr(ds), None, _lib.ptr(go), st), "dispu_augment")
             x, gt = xo, go
         return x, gt, radius
+
+
+class DeviceFetcher(object):
+    """Fetcher's surface (len / reset / has_next_batch / next_batch -> device (input, gt, radius)) with every per-batch draw made on
+    the device: next_batch() is ONE launch of dispu_sample_batch (csrc/batch_sampler.hip) -- no host draw, no upload, no device-to-host
+    copy.  The normalised dataset is uploaded once; reset() draws the epoch's row permutation on the host from
+    np.random.Generator(PCG64(seed)), composes it onto the previous epoch's (the reference reshuffles its arrays in place,
+    dataset.py:98-103) and uploads L int32 values.  A patch's sub-sample, jitter, rotation and scale are Philox draws keyed by
+    (seed, epoch, position in the permutation): the batches of a (seed, epoch) do not depend on the batch size.  The distributions are
+    the reference's, the draw sequence is not (Fetcher keeps numpy's for reference-reproducible runs).
+
+    Kept from the reference: next_batch() pre-increments batch_idx, so the first batch of every epoch is skipped; a short batch
+    raises.  The sampler's status word (candidate loop exhausted / bad permutation entry) is read once per epoch, in reset()."""
+
+    def __init__(self, input_patches, gt_patches, batch_size, patch_num_point=256, augment=True, shuffle=True, random=True,
+                 jitter_sigma=0.01, jitter_max=0.03, device=None, seed=0):
+        self.device = torch.device(device if device is not None else "cuda:0")
+        gt = np.asarray(gt_patches)
+        inp = np.asarray(input_patches)
+        # load_h5_data (dataset.py:70-74), exactly as Fetcher does it
+        centroid = np.mean(gt, axis=1, keepdims=True)
+        pc = gt - centroid
+        furthest = np.amax(np.sqrt(np.sum(pc ** 2, axis=-1, keepdims=True)), axis=1, keepdims=True)
+        self.batch_size, self.patch_num_point = int(batch_size), int(patch_num_point)
+        self.length, self.gt_num_point = int(gt.shape[0]), int(gt.shape[1])
+        self.augment, self.shuffle, self.random = bool(augment), bool(shuffle), bool(random)
+        self.jitter_sigma, self.jitter_max = float(jitter_sigma), float(jitter_max)
+        if self.patch_num_point > (self.gt_num_point if self.random else inp.shape[1]):
+            raise ValueError("cannot draw %d distinct points from a patch of %d" % (self.patch_num_point,
+                                                                                   self.gt_num_point if self.random else inp.shape[1]))
+        if not self.random and inp.shape[1] != self.patch_num_point:
+            raise ValueError("random=False needs input patches of patch_num_point = %d points, got %d" % (self.patch_num_point, inp.shape[1]))
+        self.gt_data = torch.from_numpy(np.ascontiguousarray(pc / furthest, np.float32)).to(self.device)      # resident for the whole run
+        self.input_data = None if self.random else torch.from_numpy(np.ascontiguousarray((inp - centroid) / furthest, np.float32)).to(self.device)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._rng = np.random.Generator(np.random.PCG64(self.seed))
+        self._perm = np.arange(self.length, dtype=np.int64)
+        self.perm = torch.zeros(self.length, dtype=torch.int32, device=self.device)
+        self.status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.epoch = -1
+        self.reset()
+
+    def __len__(self):
+        return self.length
+
+    def check_status(self):
+        """the sampler's status word (one device-to-host copy; reset() calls this once per epoch)."""
+        s = self.status.cpu().numpy()
+        if s[0]:
+            raise RuntimeError("dispu_sample_batch ran out of candidate rounds during epoch %d (the set was filled with the lowest "
+                               "unused indices): %d of %d points is too dense for the rejection sampler" %
+                               (self.epoch, self.patch_num_point, self.gt_num_point))
+        if s[1]:
+            raise RuntimeError("dispu_sample_batch met a permutation entry outside [0, %d)" % self.length)
+
+    def reset(self):
+        if self.epoch >= 0:
+            self.check_status()
+        if self.shuffle:
+            self._perm = self._perm[self._rng.permutation(self.length)]
+        self.perm.copy_(torch.from_numpy(self._perm.astype(np.int32)))
+        self.epoch += 1
+        self.num_batches = (self.length + self.batch_size - 1) // self.batch_size
+        self.batch_idx = 0
+
+    def has_next_batch(self):
+        return self.batch_idx < self.num_batches
+
+    def next_batch(self, verify=False):
+        """-> (input [B, P, 3], gt [B, G, 3], radius [B]); verify=True adds a dict of the kernel's verification outputs (tests)."""
+        B, P, G = self.batch_size, self.patch_num_point, self.gt_num_point
+        self.batch_idx += 1
+        start = self.batch_idx * B
+        bsize = max(min((self.batch_idx + 1) * B, self.length) - start, 0)
+        if bsize != B:
+            raise IndexError("short batch (%d of %d): the reference fails here too (dataset.py:131-134 indexes "
+                             "batch_input_data[i] for i < batch_size)" % (bsize, B))
+        dev = self.device
+        buf = torch.empty(B * (P + G) * 3 + B, dtype=torch.float32, device=dev)       # one allocation, three views
+        x, gt, radius = buf[:B * P * 3].view(B, P, 3), buf[B * P * 3:B * (P + G) * 3].view(B, G, 3), buf[B * (P + G) * 3:]
+        v = None
+        if verify:
+            v = dict(idx=torch.empty((B, P), dtype=torch.int32, device=dev), rot=torch.empty((B, 9), device=dev),
+                     scale=torch.empty(B, device=dev), noise=torch.empty((B, P, 3), device=dev) if self.augment else None,
+                     raw=torch.empty((B, 4), dtype=torch.int32, device=dev))
+        q = (lambda k: _lib.ptr(v[k])) if verify else (lambda k: None)
+        _lib.check(_lib.tape_lib().dispu_sample_batch(
+            self.length, G, P, _lib.ptr(self.gt_data), _lib.ptr(self.input_data), _lib.ptr(self.perm), start, B, self.seed, self.epoch,
+            self.jitter_sigma, self.jitter_max, int(self.augment), _lib.ptr(x), _lib.ptr(gt), _lib.ptr(radius), _lib.ptr(self.status),
+            q("idx"), q("rot"), q("scale"), q("noise"), q("raw"), _lib.stream_ptr(dev)), "dispu_sample_batch")
+        return (x, gt, radius, v) if verify else (x, gt, radius)

@@ -1403,3 +1403,112 @@ class Trainer(object):
         self.adam(world)
         self.global_step += 1
         return terms
+
+
+# ------------------------------------------------------------------------------------------------------ train phase ----
+# Counterpart of Model.train / Model.train_one_epoch (DisPU/model.py:181-303): the epoch loop around Trainer.train_step.
+LOG_FORMAT = "epoch %04d g_loss=%.9f  coarse_cd=%.9f  coarse_hd=%.9f  fine_cd=%.9f fine_hd=%.9f  time=%.4f"
+
+
+def format_log_line(epoch, g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds):
+    """the per-epoch line of log_train.txt (model.py:220-222; the last field is the epoch's duration in MINUTES)."""
+    return LOG_FORMAT % (epoch, g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds / 60.0)
+
+
+def format_args(opts):
+    """args.txt (model.py:198-200): one `name: value` line per option, sorted by name."""
+    d = opts if isinstance(opts, dict) else {k: getattr(opts, k) for k in dir(opts) if not k.startswith("_") and not callable(getattr(opts, k))}
+    return "".join("%s: %s\n" % (k, d[k]) for k in sorted(d))
+
+
+def steps_per_epoch(n_examples, batch_size):
+    """model.py:239: int(n / B) - 1 (one batch fewer than fit: Fetcher.next_batch skips the first batch of every epoch)."""
+    return int(int(n_examples) / int(batch_size)) - 1
+
+
+def _hausdorff_terms(trainer, inputs, gt, radius):
+    """100 * hausdorff_loss of the step's coarse and fine clouds (model.py:76,79: logged, never differentiated)."""
+    from . import loss_utils
+    ws = trainer._workspace(inputs.shape[0], inputs.shape[1])
+    with torch.no_grad():
+        return 100.0 * loss_utils.hausdorff_loss(ws["coarse"], gt, radius=radius), 100.0 * loss_utils.hausdorff_loss(ws["fine"], gt, radius=radius)
+
+
+def train_one_epoch(trainer, fetcher, batch_size, train_step_fn="eager", hd_fn=_hausdorff_terms):
+    """model.py:229-303 -> (g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds, steps): the epoch's means and its duration.
+    The five sums are accumulated in a device tensor and read ONCE, after the last step: no per-step host synchronisation."""
+    import time
+    if train_step_fn not in ("eager", "taped"):
+        raise ValueError("train_step_fn must be 'eager' or 'taped'")
+    step = trainer.train_step if train_step_fn == "eager" else trainer.train_step_taped
+    n = steps_per_epoch(len(fetcher), batch_size)
+    acc = None
+    t0 = time.time()
+    for _ in range(n):
+        x, gt, radius = fetcher.next_batch()
+        terms = step(x, gt, radius)
+        chd, fhd = hd_fn(trainer, x, gt, radius)
+        row = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(())
+                           for v in (terms["pu_loss"], terms["dis_coarse_cd"], chd, terms["dis_fine_cd"], fhd)])
+        acc = row if acc is None else acc.to(row.device) + row
+    if acc is None:
+        vals = [0.0] * 5                                 # AverageMeter.avg of an empty epoch
+    else:
+        vals = (acc / n).tolist()                        # the epoch's one read-back (also waits for its last step)
+    return tuple(vals) + (time.time() - t0, n)
+
+
+def fit(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", save_fn=None, restore_fn=None, hd_fn=_hausdorff_terms,
+        log=None):
+    """Model.train (model.py:181-227): epochs restore_epoch .. opts.training_epoch - 1 of int(len / B) - 1 steps each; after every epoch
+    fetcher.reset(), trainer.epoch += 1 (weight_fine and the learning rate follow it), one line in <log_dir>/log_train.txt ('w', or
+    'a' when restoring), and checkpoint.save_train_state when epoch % opts.epoch_per_save == 0 and the epoch's mean fine_cd is
+    strictly below the best one saved so far.  args.txt lists the options.  Returns the per-epoch records.  On restore a fetcher
+    with an `epoch` counter is reset() up to the restored epoch (the host Fetcher has none: it goes on from numpy's global state).
+
+    Single process only: data-parallel fit is not implemented (it raises when a process group of more than one rank is active;
+    the sampler's position-keyed draws are what will let ranks take disjoint positions of one epoch).
+    save_fn(log_dir, trainer, epoch) / restore_fn(log_dir, trainer) -> restore epoch / hd_fn default to the checkpoint module and
+    loss_utils.hausdorff_loss; `log` is called with every line written."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("fit() is single-process: data-parallel training loops are out of scope")
+    from . import checkpoint
+    save_fn = checkpoint.save_train_state if save_fn is None else save_fn
+    restore_fn = checkpoint.restore_train_state if restore_fn is None else restore_fn
+    B = int(getattr(opts, "batch_size", getattr(fetcher, "batch_size", 0)))
+    if B <= 0:
+        raise ValueError("opts.batch_size (or fetcher.batch_size) must be positive")
+    os.makedirs(log_dir, exist_ok=True)
+    restore_epoch = 0
+    if restore:
+        restore_epoch = int(restore_fn(log_dir, trainer))
+        # a fetcher that counts its epochs (DeviceFetcher: permutation stream and draws keyed by the epoch) is brought to the restored
+        # one, so a resumed run sees the batches the uninterrupted run would have seen
+        while getattr(fetcher, "epoch", restore_epoch) < restore_epoch:
+            fetcher.reset()
+    records, best = [], math.inf
+    with open(os.path.join(log_dir, "log_train.txt"), "a" if restore else "w") as fout:
+        with open(os.path.join(log_dir, "args.txt"), "w") as f:
+            f.write(format_args(opts))
+
+        def emit(line):
+            fout.write(line + "\n")
+            fout.flush()
+            if log is not None:
+                log(line)
+
+        emit("train_dataset: %d" % len(fetcher))
+        for _ in range(restore_epoch, int(opts.training_epoch)):
+            g, ccd, chd, fcd, fhd, seconds, steps = train_one_epoch(trainer, fetcher, B, train_step_fn, hd_fn)
+            fetcher.reset()
+            trainer.epoch += 1
+            epoch = int(trainer.epoch)
+            emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds))
+            saved = None
+            if epoch % int(opts.epoch_per_save) == 0 and fcd < best:
+                best = fcd
+                saved = save_fn(log_dir, trainer, epoch)
+            records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
+                                steps=steps, saved=saved))
+    return records

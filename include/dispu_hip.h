@@ -650,6 +650,31 @@ int dispu_ps_point_matmul_grad_relu(long rows, int k, int c, int t_n, const floa
 int dispu_augment(int b, int n, const float* in, const float* noise, const float* rot, const float* scale,
                   const float* shift, float* out, void* stream);
 
+/* One training batch in ONE launch, every random draw made on the device.  Replaces, per batch, the host side of
+ * DisPU/dataset.py:113-143 (Fetcher.next_batch) and what it calls in Common/point_operation.py: nonuniform_sampling :10-18,
+ * rotate_point_cloud_and_gt :32-71 (z rotation), jitter_perturbation_point_cloud :74-86, random_scale_point_cloud_and_gt :107-123.
+ * Patch i of the batch is POSITION p = start + i of the epoch: it uses dataset row perm[p] and Philox4x32-10 draws keyed by
+ * (seed, epoch, p) -- independent of B and of the launch shape (counter layout: DESIGN.md, "Train phase").
+ *   gt_data [L, G, 3]   normalised ground-truth patches, resident;  perm [L] int32 row permutation, resident
+ *   input_data          NULL: the input is a sub-sample of P of the G ground-truth points, indices ascending (`random=True`);
+ *                       else [L, P, 3]: the input is row perm[p] of it (`random=False`)
+ *   augment != 0        clipped Gaussian jitter (input only), z rotation, scale in [0.8, 1.2] (both clouds): the arithmetic of
+ *                       dispu_augment on the device's own draws, bit for bit
+ *   input [B, P, 3], gt [B, G, 3], radius [B] (ones)                         outputs
+ *   status [2] int32    status[0] = 1: the bounded candidate loop ran out (DISPU_SAMPLER_MAX_ROUNDS rounds of 64 draws; the set was
+ *                       filled with the lowest unused indices);  status[1] = 1: a perm entry outside [0, L) (row 0 was used).
+ *                       Only ever SET here (plain stores, no atomics): the caller clears it and reads it when it likes.
+ *   idx_out [B, P], rot_out [B, 9], scale_out [B], noise_out [B, P, 3], raw_out [B, 4] (the patch-scalar Philox block)
+ *                       verification outputs, each may be NULL (noise_out needs augment != 0).
+ * Refused before any launch (hipErrorInvalidValue): P > G, G > DISPU_SAMPLER_MAX_G (membership bitmap + owner slots live in LDS),
+ * start + B > L, a missing required pointer, augment with jitter_clip <= 0. */
+#define DISPU_SAMPLER_MAX_ROUNDS 4096
+#define DISPU_SAMPLER_MAX_G 8192
+int dispu_sample_batch(int L, int G, int P, const float* gt_data, const float* input_data, const int* perm, int start, int B,
+                       unsigned long long seed, int epoch, float jitter_sigma, float jitter_clip, int augment, float* input, float* gt,
+                       float* radius, int* status, int* idx_out, float* rot_out, float* scale_out, float* noise_out,
+                       unsigned int* raw_out, void* stream);
+
 /* ---- whole-cloud inference glue (DisPU/model.py:306-381, Common/pc_util.py:83-92,147-161; host numpy/sklearn in
  * the reference, one patch at a time) -------------------------------------------------------------------------- */
 /* extract_knn_patch: for each of m queries the k nearest of the cloud's n points (k up to n; n > 8192: the radix-select kernel, k <= 4096), ascending
