@@ -140,10 +140,24 @@ class DeviceFetcher(object):
     the reference's, the draw sequence is not (Fetcher keeps numpy's for reference-reproducible runs).
 
     Kept from the reference: next_batch() pre-increments batch_idx, so the first batch of every epoch is skipped; a short batch
-    raises.  The sampler's status word (candidate loop exhausted / bad permutation entry) is read once per epoch, in reset()."""
+    raises.  The sampler's status word (candidate loop exhausted / bad permutation entry) is read once per epoch, in reset().
+
+    shard=(rank, world): this process is one of `world` data-parallel ranks.  batch_size stays the GLOBAL batch B (it must divide by
+    world); next_batch() draws the B / world patches at positions [batch_idx * B + rank * B / world, ...) of the epoch, i.e. rows
+    [rank * B / world, (rank + 1) * B / world) of the unsharded fetcher's batch, bit for bit.  Everything else (len, the permutation
+    stream, the skipped first batch, the short-batch error, the epoch counting) is that of the unsharded fetcher: ranks built with
+    the same seed need no communication."""
 
     def __init__(self, input_patches, gt_patches, batch_size, patch_num_point=256, augment=True, shuffle=True, random=True,
-                 jitter_sigma=0.01, jitter_max=0.03, device=None, seed=0):
+                 jitter_sigma=0.01, jitter_max=0.03, device=None, seed=0, shard=None):
+        self.shard = None
+        if shard is not None:
+            rank, world = int(shard[0]), int(shard[1])
+            if world <= 0 or not 0 <= rank < world:
+                raise ValueError("shard=(rank, world) needs 0 <= rank < world, got %r" % (tuple(shard),))
+            if int(batch_size) % world:
+                raise ValueError("the global batch of %d patches does not divide over %d ranks" % (int(batch_size), world))
+            self.shard = (rank, world)
         self.device = torch.device(device if device is not None else "cuda:0")
         gt = np.asarray(gt_patches)
         inp = np.asarray(input_patches)
@@ -183,6 +197,11 @@ class DeviceFetcher(object):
         if s[1]:
             raise RuntimeError("dispu_sample_batch met a permutation entry outside [0, %d)" % self.length)
 
+    def status_flags(self):
+        """the sampler's two status words as they are on the device (int32 [2], no copy, nothing raised): a data-parallel loop
+        gathers every rank's and decides for all of them (train.fit_parallel)."""
+        return self.status
+
     def reset(self):
         if self.epoch >= 0:
             self.check_status()
@@ -205,6 +224,9 @@ class DeviceFetcher(object):
         if bsize != B:
             raise IndexError("short batch (%d of %d): the reference fails here too (dataset.py:131-134 indexes "
                              "batch_input_data[i] for i < batch_size)" % (bsize, B))
+        if self.shard is not None:                       # this rank's rows of the global batch
+            B //= self.shard[1]
+            start += self.shard[0] * B
         dev = self.device
         buf = torch.empty(B * (P + G) * 3 + B, dtype=torch.float32, device=dev)       # one allocation, three views
         x, gt, radius = buf[:B * P * 3].view(B, P, 3), buf[B * P * 3:B * (P + G) * 3].view(B, G, 3), buf[B * (P + G) * 3:]

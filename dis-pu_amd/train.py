@@ -1466,8 +1466,7 @@ def fit(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", s
     strictly below the best one saved so far.  args.txt lists the options.  Returns the per-epoch records.  On restore a fetcher
     with an `epoch` counter is reset() up to the restored epoch (the host Fetcher has none: it goes on from numpy's global state).
 
-    Single process only: data-parallel fit is not implemented (it raises when a process group of more than one rank is active;
-    the sampler's position-keyed draws are what will let ranks take disjoint positions of one epoch).
+    Single process only: it raises when a process group of more than one rank is active (fit_parallel is the data-parallel loop).
     save_fn(log_dir, trainer, epoch) / restore_fn(log_dir, trainer) -> restore epoch / hd_fn default to the checkpoint module and
     loss_utils.hausdorff_loss; `log` is called with every line written."""
     import torch.distributed as dist
@@ -1511,4 +1510,167 @@ def fit(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", s
                 saved = save_fn(log_dir, trainer, epoch)
             records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
                                 steps=steps, saved=saved))
+    return records
+
+
+# -------------------------------------------------------------------------------------- data-parallel train phase ----
+_HD_COLUMNS = (2, 4)       # of a step-meter row [g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd]: max over ranks; the others: mean
+
+
+def step_meters(trainer, inputs, radius, row):
+    """row[0:5] = [pu_loss, 1000 CD_coarse, 100 HD_coarse, 1000 CD_fine, 100 HD_fine] of the step `trainer` has just run on
+    `inputs` / `radius` (train_step or train_step_taped), in ONE launch on the current stream (dispu_step_meters,
+    csrc/step_meters.hip): the loss values are copied from the step's loss_vals, the Hausdorff terms are reduced from the
+    nearest-neighbour distances the step's Chamfer terms left in the workspace -- bit-equal to what _hausdorff_terms recomputes
+    with two more nn_distance launches.  `row`: 5 contiguous float32 on the trainer's device (a row of the epoch's table).
+    Never part of a launch tape: the row pointer changes with every step."""
+    B, N = int(inputs.shape[0]), int(inputs.shape[1])
+    M = N * trainer.up_ratio
+    req(isinstance(row, torch.Tensor) and row.dtype == torch.float32 and row.numel() == 5 and row.is_contiguous()
+        and row.device == trainer.device, "row must be 5 contiguous float32 on %s" % trainer.device)
+    radius = f32(radius, "radius")
+    req(radius.dim() == 1 and radius.shape[0] == B and radius.device == trainer.device and radius.is_contiguous(),
+        "radius must be a contiguous (%d,) tensor on %s" % (B, trainer.device))
+    if (B, N) not in trainer._ws:
+        raise RuntimeError("step_meters: no step has run on a (%d, %d) batch" % (B, N))
+    ws = trainer._ws[(B, N)]
+    c, f = ws["cd"]
+    _lib.check(_lib.lib().dispu_step_meters(B, M, M, _p(c["d_gt"]), _p(c["d_pred"]), _p(f["d_gt"]), _p(f["d_pred"]), _p(radius),
+                                            _p(ws["loss_vals"], 2), _p(row), _lib.stream_ptr(trainer.device)), "dispu_step_meters")
+    return row
+
+
+def _step_meters_fn(trainer, x, gt, radius, row):
+    step_meters(trainer, x, radius, row)
+
+
+def reduce_meter_tables(tables, steps):
+    """tables [world, steps * 5] (every rank's step-meter table) -> the epoch's five logged values, in float64: per step the mean
+    over ranks of the loss / CD columns and the MAX over ranks of the two Hausdorff columns (hausdorff_loss is a max over the
+    batch, and the global batch is the union of the ranks' shards), then the mean over steps."""
+    if steps <= 0:
+        return [0.0] * 5                                 # AverageMeter.avg of an empty epoch
+    t = np.asarray(tables, np.float64).reshape(-1, steps, 5)
+    per_step = t.mean(axis=0)
+    per_step[:, _HD_COLUMNS] = t[:, :, _HD_COLUMNS].max(axis=0)
+    return [float(v) for v in per_step.mean(axis=0)]
+
+
+def fill_meter_table(trainer, fetcher, table, steps, step, meter_fn=_step_meters_fn):
+    """the steps of one epoch as fit_parallel runs them: next_batch, the step function, meter_fn into row s of `table`
+    ([steps * 5 + 2] float32 on the trainer's device); the fetcher's two status flags go behind the rows (zeros for a fetcher
+    without status_flags()).  Launches only: nothing here waits for the device."""
+    for s in range(steps):
+        x, gt, radius = fetcher.next_batch()
+        step(x, gt, radius)
+        meter_fn(trainer, x, gt, radius, table[s * 5:s * 5 + 5])
+    flags_of = getattr(fetcher, "status_flags", None)
+    table[steps * 5:].copy_(torch.as_tensor(flags_of() if flags_of is not None else (0, 0)))
+
+
+def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", group=None, save_fn=None, restore_fn=None,
+                 meter_fn=None, log=None):
+    """Model.train (model.py:181-227) for world >= 1 ranks of `group` (None: the default process group; no group initialised: one
+    rank, a complete single-process loop).  Every rank calls it with its own replica and its own shard of the fetcher.
+
+    Sharding.  opts.batch_size is the GLOBAL batch B (the reference's --batch_size); rank r draws positions
+    [batch * B + r * B / world, + B / world) of the epoch (dataset.DeviceFetcher(shard=(r, world)): same seed and permutation on
+    every rank, no communication).  Every rank runs steps_per_epoch(len(fetcher), B) steps per epoch.
+    Per step: fetcher.next_batch(), the step function (its gradient all-reduce keeps the replicas bit-identical), and
+    meter_fn(trainer, x, gt, radius, row) -- default step_meters, one launch -- into row `step` of a device table.  Nothing in the
+    epoch waits for the device.
+    Epoch end: ONE collective, an all-gather of the rank's [steps * 5 + 2] floats (the table and the fetcher's two status flags).
+    Every rank reduces on the host in float64 (reduce_meter_tables: mean over ranks, max over ranks for the Hausdorff columns, per
+    step; then the mean over steps), so all ranks hold identical values and take the same save decision.  A status flag set on ANY
+    rank raises the same RuntimeError on EVERY rank in that epoch.
+    Artefacts: rank 0 alone writes log_train.txt, args.txt and checkpoints (fit's formats and save rule: epoch % epoch_per_save
+    == 0 and fine_cd < best); a barrier follows each save.  trainer.epoch += 1 and fetcher.reset() happen on every rank; every
+    rank returns the same records (`saved` is rank 0's; `seconds` alone is each rank's own clock).
+    Restore: EVERY rank calls restore_fn(log_dir, trainer).  It only reads, and the calls must be symmetric: Trainer.load_params
+    builds the gradient reducer eagerly, which under gloo creates a process group -- a collective every rank has to reach.  The
+    fetcher is then reset() up to the restored epoch, as in fit.
+
+    ValueError on every rank before the first step: B % world != 0; world > 1 with a fetcher whose `shard` is not (rank, world)
+    (the host Fetcher has none); a trainer whose process group is not `group`."""
+    import time
+    import torch.distributed as dist
+    if train_step_fn not in ("eager", "taped"):
+        raise ValueError("train_step_fn must be 'eager' or 'taped'")
+    active = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if active else 1
+    rank = dist.get_rank(group) if active else 0
+    B = int(getattr(opts, "batch_size", getattr(fetcher, "batch_size", 0)))
+    if B <= 0:
+        raise ValueError("opts.batch_size (or fetcher.batch_size) must be positive")
+    if B % world:
+        raise ValueError("the global batch of %d patches does not divide over %d ranks" % (B, world))
+    if world > 1:
+        shard = getattr(fetcher, "shard", None)
+        if shard is None or tuple(shard) != (rank, world):
+            raise ValueError("rank %d of %d needs a fetcher with shard=(%d, %d), got %r" % (rank, world, rank, world, shard))
+        norm = lambda g: None if g is dist.group.WORLD else g          # None names the default group
+        if norm(getattr(trainer, "pg", None)) is not norm(group):
+            raise ValueError("the trainer all-reduces over another process group than the loop's")
+    from . import checkpoint
+    save_fn = checkpoint.save_train_state if save_fn is None else save_fn
+    restore_fn = checkpoint.restore_train_state if restore_fn is None else restore_fn
+    meter_fn = _step_meters_fn if meter_fn is None else meter_fn
+    step = trainer.train_step if train_step_fn == "eager" else trainer.train_step_taped
+    if rank == 0:
+        os.makedirs(log_dir, exist_ok=True)
+    restore_epoch = 0
+    if restore:
+        restore_epoch = int(restore_fn(log_dir, trainer))
+        while getattr(fetcher, "epoch", restore_epoch) < restore_epoch:
+            fetcher.reset()
+    n = max(steps_per_epoch(len(fetcher), B), 0)
+    table = torch.zeros(n * 5 + 2, dtype=torch.float32, device=getattr(trainer, "device", "cpu"))
+    records, best = [], math.inf
+    fout = open(os.path.join(log_dir, "log_train.txt"), "a" if restore else "w") if rank == 0 else None
+    try:
+        if rank == 0:
+            with open(os.path.join(log_dir, "args.txt"), "w") as f:
+                f.write(format_args(opts))
+
+        def emit(line):
+            if rank == 0:
+                fout.write(line + "\n")
+                fout.flush()
+                if log is not None:
+                    log(line)
+
+        emit("train_dataset: %d" % len(fetcher))
+        for _ in range(restore_epoch, int(opts.training_epoch)):
+            t0 = time.time()
+            fill_meter_table(trainer, fetcher, table, n, step, meter_fn)
+            if world > 1:
+                from . import parallel
+                every = parallel._all_gather_rows(table.view(1, -1), world, group).cpu().numpy()      # the epoch's one collective
+            else:
+                every = table.view(1, -1).cpu().numpy()                                               # ... and its one read-back
+            bad = [(r, int(every[r, n * 5] != 0), int(every[r, n * 5 + 1] != 0)) for r in range(world) if every[r, n * 5:].any()]
+            if bad:
+                raise RuntimeError("epoch %d: the batch sampler reported a failure on rank(s) %s (rank, candidate rounds exhausted, "
+                                   "permutation entry out of range)" % (int(trainer.epoch), bad))
+            g, ccd, chd, fcd, fhd = reduce_meter_tables(every[:, :n * 5], n)
+            seconds = time.time() - t0
+            fetcher.reset()
+            trainer.epoch += 1
+            epoch = int(trainer.epoch)
+            emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds))
+            saved = None
+            if epoch % int(opts.epoch_per_save) == 0 and fcd < best:
+                best = fcd
+                if rank == 0:
+                    saved = save_fn(log_dir, trainer, epoch)
+                if world > 1:
+                    box = [saved]
+                    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+                    saved = box[0]
+                    dist.barrier(group=group)              # no rank runs ahead of a checkpoint another process may read
+            records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
+                                steps=n, saved=saved))
+    finally:
+        if fout is not None:
+            fout.close()
     return records

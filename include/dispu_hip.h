@@ -616,6 +616,15 @@ int dispu_chamfer_loss_grad(int b, int n_gt, const float* gt, int n_pred, const 
 /* out[5] = 1000 CD_coarse | 1000 CD_fine | repulsion_w * mean(rep) / 4 | pu_loss (model.py:87) | weight_fine; cd[2] = the two
  * values of dispu_chamfer_loss_grad, rep [nrep] = dispu_repulsion's per-point sums (NULL: no repulsion term). */
 int dispu_pu_loss_finalize(const float* cd, const float* rep, long nrep, float wf, float rep_w, float* out, void* stream);
+/* the train loop's five per-step meters (model.py:215-222) in one launch:
+ *   row[5] = pu_loss | 1000 CD_coarse | 100 HD_coarse | 1000 CD_fine | 100 HD_fine
+ * loss_out = dispu_pu_loss_finalize's out (its entries 3, 0, 1 are copied); d_gt_* [b, n_gt] / d_pred_* [b, n_pred] = the distances
+ * dispu_nn_distance(gt, pred) left for the coarse (_c) and the fine (_f) cloud; radius [b].  Per term, hausdorff_loss
+ * (loss_utils.py:67-84): 100.0f * max_b[(1.0f * max_j d_gt[b,j] + max_j d_pred[b,j]) / radius[b]] with an IEEE fp32 division.  `row` is
+ * any 5 floats of a caller-owned table; nothing else is written.  b <= 0, n_* <= 0 or a NULL pointer: hipErrorInvalidValue, no
+ * launch. */
+int dispu_step_meters(int b, int n_gt, int n_pred, const float* d_gt_c, const float* d_pred_c, const float* d_gt_f,
+                      const float* d_pred_f, const float* radius, const float* loss_out, float* row, void* stream);
 /* get_repulsion_loss (loss_utils.py:271-298) value and gradient in one launch (= dispu_repulsion + dispu_repulsion_grad): out [rows]
  * per-point hinge sums, dpred [rows, 3] accumulates scale * d loss / d pred (atomics).  ns == 20. */
 int dispu_repulsion_loss_grad(long rows, int n_per_cloud, int ns, float h, float scale, const float* pred, const int* idx, float* out,

@@ -9,6 +9,13 @@ at 8 and 32 patches per batch on a seeded synthetic dataset of 2048 patches (102
 --steps steps (>= 200) timed with the host clock around a final device synchronise; fetchers are reset where their epoch ends
 (inside the window: that cost belongs to the loop).  Also times bare DeviceFetcher.next_batch calls back to back.
 
+At 8 patches it also compares the two meter paths of the epoch loop, on the same trainer, fetcher and batches, eager and taped:
+  (e) train.train_one_epoch            -- fit's path: train._hausdorff_terms after every step (two nn_distance launches, four row
+                                          reductions, torch glue) + stack / add into the epoch's accumulator
+  (f) train.fill_meter_table + reduce  -- fit_parallel's path: ONE dispu_step_meters launch per step into a device table, one
+                                          read-back and a host reduction per epoch
+(--meters-only: just this comparison.)
+
 Prints one JSON line and writes it to --out (default profiles/epoch_bench.json).
 --sampler-only: just the bare next_batch calls (for a kernel trace of the sampler alone)."""
 import argparse
@@ -68,6 +75,62 @@ def epochs_window(dev, steps, trainer, fetcher, loop, batch):
     return (time.perf_counter() - t0) * 1e3 / done
 
 
+def meter_epochs_window(dev, steps, trainer, fetcher, batch, step_fn):
+    """whole epochs as train.fit_parallel runs them at world 1 (fill_meter_table, the table's read-back, the host reduction, the
+    reset) until at least `steps` steps ran -> ms per step"""
+    from dispu_amd import train
+    fetcher.reset()
+    n = train.steps_per_epoch(len(fetcher), batch)
+    table = torch.zeros(n * 5 + 2, dtype=torch.float32, device=dev)
+    step = trainer.train_step if step_fn == "eager" else trainer.train_step_taped
+    done = 0
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    while done < steps:
+        train.fill_meter_table(trainer, fetcher, table, n, step)
+        train.reduce_meter_tables(table.view(1, -1).cpu().numpy()[:, :n * 5], n)
+        fetcher.reset()
+        done += n
+    torch.cuda.synchronize(dev)
+    return (time.perf_counter() - t0) * 1e3 / done
+
+
+def old_epochs_window(dev, steps, trainer, fetcher, batch, step_fn):
+    from dispu_amd import train
+    fetcher.reset()
+    done = 0
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    while done < steps:
+        done += train.train_one_epoch(trainer, fetcher, batch, step_fn)[-1]
+        fetcher.reset()
+    torch.cuda.synchronize(dev)
+    return (time.perf_counter() - t0) * 1e3 / done
+
+
+def meters_row(dev, a, gt, P, B=8):
+    """(e) against (f), eager and taped, alternating windows"""
+    from dispu_amd import dataset
+    from dispu_amd.params import init_params
+    from dispu_amd.train import Trainer
+    fetch = dataset.DeviceFetcher(gt, gt, B, patch_num_point=P, device=dev, seed=1)
+    tr = Trainer(params=init_params(1234), device=dev)
+    paths = {"e_hausdorff_terms": old_epochs_window, "f_step_meters": meter_epochs_window}
+    times = {(k, fn): [] for fn in ("eager", "taped") for k in paths}
+    for (k, fn) in times:
+        paths[k](dev, a.warmup, tr, fetch, B, fn)
+    for _ in range(a.windows):
+        for (k, fn), v in times.items():
+            v.append(paths[k](dev, a.steps, tr, fetch, B, fn))
+    fetch.check_status()
+    row = {"batch": B}
+    for fn in ("eager", "taped"):
+        row[fn] = {k: summary(times[(k, fn)]) for k in paths}
+        row[fn]["f_minus_e_ms"] = row[fn]["f_step_meters"]["median_ms"] - row[fn]["e_hausdorff_terms"]["median_ms"]
+        row[fn]["f_faster_in_every_window"] = bool(max(times[("f_step_meters", fn)]) < min(times[("e_hausdorff_terms", fn)]))
+    return row
+
+
 def summary(v):
     return {"median_ms": float(np.median(v)), "min_ms": float(min(v)), "max_ms": float(max(v)), "windows": [round(x, 4) for x in v]}
 
@@ -81,6 +144,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 32])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "epoch_bench.json"))
     ap.add_argument("--sampler-only", action="store_true")
+    ap.add_argument("--meters-only", action="store_true", help="only the meter-path comparison at 8 patches")
     a = ap.parse_args()
     if a.steps < 200 and not a.sampler_only:
         sys.exit("--steps must be at least 200")
@@ -95,7 +159,9 @@ def main():
     gt = synthetic_patches(a.patches, G, seed=2024)
     res = {"bench": "epoch_bench", "device": torch.cuda.get_device_name(0), "patches": a.patches, "points": [P, G], "steps_per_window": a.steps,
            "dtype": "f32", "batch": {}}
-    for B in a.batches:
+    if not a.sampler_only:
+        res["meters"] = meters_row(dev, a, gt, P)
+    for B in ([] if a.meters_only else a.batches):
         dfetch = dataset.DeviceFetcher(gt, gt, B, patch_num_point=P, device=dev, seed=1)
         dloop = Looping(dfetch, B)
         # bare sampler calls, back to back (launch + kernel; the queue never drains)

@@ -3,7 +3,9 @@
 <data_dir>/PUGAN_poisson_<P>_poisson_<4P>.h5, train the generator for --training_epoch epochs (dis-pu_amd/train.py:fit) and leave
 log_train.txt, args.txt and the `model-<epoch>` checkpoints (+ the `checkpoint` state file) in --log_dir; --restore resumes from the
 latest checkpoint there.  Flags and defaults are those of DisPU/configs.py that the train phase reads; --seed, --dtype, --sampler and
---tape are this project's own.  `--sampler device` (default) draws every batch on the GPU in one launch (dataset.DeviceFetcher);
+--tape are this project's own.  Under `python -m torch.distributed.run --nproc-per-node N tools/train.py ...` it is one of N data-parallel
+ranks (train.py:fit_parallel): --batch_size stays the global batch, rank r trains on device LOCAL_RANK over RCCL (DISPU_TRAIN_BACKEND=gloo
+lets ranks share devices), rank 0 alone prints and writes the artefacts.  `--sampler device` (default) draws every batch on the GPU in one launch (dataset.DeviceFetcher);
 `--sampler host` is dataset.Fetcher, which repeats the reference's numpy draw sequence (np.random.seed(--seed))."""
 import argparse
 import os
@@ -73,6 +75,13 @@ def main(argv=None):
         refuse_unsupported(a)
     except ValueError as e:
         sys.exit(str(e))
+    # started by `python -m torch.distributed.run --nproc-per-node N tools/train.py ...`: one data-parallel rank of N
+    world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
+    if world > 1 and a.sampler == "host":
+        sys.exit("--sampler host draws whole batches from numpy's global state and cannot be sharded: use --sampler device with "
+                 "%d ranks" % world)
+    if world > 1 and a.batch_size % world:
+        sys.exit("--batch_size %d (the global batch) does not divide over %d ranks" % (a.batch_size, world))
     path = data_file(a)
     if not os.path.isfile(path):
         sys.exit("no training data at %s" % path)
@@ -85,22 +94,43 @@ def main(argv=None):
 
     if not torch.cuda.is_available():
         sys.exit("no ROCm device")
-    dev = torch.device("cuda:0")
-    P, G = a.patch_num_point, a.patch_num_point * a.up_ratio
-    inp, gt = dataset.load_patches(path, P, G, random=a.random)
-    kw = dict(batch_size=a.batch_size, patch_num_point=P, augment=a.augment, random=a.random, jitter_sigma=a.jitter_sigma,
-              jitter_max=a.jitter_max, device=dev)
-    if a.sampler == "device":
-        fetcher = dataset.DeviceFetcher(inp, gt, seed=a.seed, **kw)
+    if world == 1:
+        dev = torch.device("cuda:0")
     else:
-        np.random.seed(a.seed)
-        fetcher = dataset.Fetcher(inp, gt, **kw)
-    opts = train.TrainOpts()
-    for k, v in vars(a).items():
-        setattr(opts, k, v)
-    trainer = train.Trainer(opts, params.init_params(seed=a.seed), device=dev, dtype=a.dtype)
-    recs = train.fit(trainer, fetcher, opts, a.log_dir, restore=a.restore, train_step_fn="taped" if a.tape else "eager", log=print)
-    print("%d epochs, %d checkpoints in %s" % (len(recs), sum(r["saved"] is not None for r in recs), a.log_dir))
+        # DISPU_TRAIN_BACKEND=gloo lets a box with fewer GPUs than ranks run the N > 1 loop (ranks share devices, collectives are
+        # staged through the host); real runs use nccl == RCCL, one GPU per rank
+        import torch.distributed as dist
+        backend = os.environ.get("DISPU_TRAIN_BACKEND", "nccl")
+        ndev = torch.cuda.device_count()
+        if backend == "nccl" and local >= ndev:
+            sys.exit("LOCAL_RANK %d but only %d visible GPUs" % (local, ndev))
+        dev = torch.device("cuda", local % ndev)
+        torch.cuda.set_device(dev)
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(backend)
+    try:
+        say = print if rank == 0 else (lambda *args: None)
+        P, G = a.patch_num_point, a.patch_num_point * a.up_ratio
+        inp, gt = dataset.load_patches(path, P, G, random=a.random)
+        kw = dict(batch_size=a.batch_size, patch_num_point=P, augment=a.augment, random=a.random, jitter_sigma=a.jitter_sigma,
+                  jitter_max=a.jitter_max, device=dev)
+        if a.sampler == "device":
+            fetcher = dataset.DeviceFetcher(inp, gt, seed=a.seed, shard=(rank, world) if world > 1 else None, **kw)
+        else:
+            np.random.seed(a.seed)
+            fetcher = dataset.Fetcher(inp, gt, **kw)
+        opts = train.TrainOpts()
+        for k, v in vars(a).items():
+            setattr(opts, k, v)
+        trainer = train.Trainer(opts, params.init_params(seed=a.seed), device=dev, dtype=a.dtype)
+        loop = train.fit_parallel if world > 1 else train.fit
+        recs = loop(trainer, fetcher, opts, a.log_dir, restore=a.restore, train_step_fn="taped" if a.tape else "eager", log=say)
+        say("%d epochs, %d checkpoints in %s" % (len(recs), sum(r["saved"] is not None for r in recs), a.log_dir))
+    finally:
+        if world > 1:
+            dist.destroy_process_group()
 
 
 if __name__ == "__main__":
