@@ -167,6 +167,8 @@ SIGNATURES = {
     "dispu_chamfer_loss_grad": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp]),
     "dispu_pu_loss_finalize": (_i, [_vp, _vp, _l, C.c_float, C.c_float, _vp, _vp]),
     "dispu_step_meters": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dispu_uniform_loss_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "dispu_pu_loss_finalize_u": (_i, [_vp, _vp, _l, C.c_float, C.c_float, _vp, _i, _l, C.c_float, _vp, _vp]),
     "dispu_augment": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_sample_batch": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_ulonglong, _i, C.c_float, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp]),

@@ -43,6 +43,8 @@ class TrainOpts(_Opts):
     lr_clip = 1e-6
     use_repulse = True
     repulsion_w = 1.0
+    use_uniform = False   # model.py:86 (the get_uniform_loss line ships commented out)
+    uniform_w = 10.0      # DisPU/configs.py:42
 
 
 # Streams are shared by every Trainer of a process (per device): HIP maps streams onto a few hardware queues, and a process that
@@ -982,6 +984,33 @@ class Trainer(object):
                                              _p(ws["i_pred"]), _p(radius), coef, _p(full["loss_vals"], slot), _p(dpred), self.st),
                    "chamfer_loss_grad")
 
+    def _uniform_tables(self, B, N):
+        """the level tables of the uniform term for B patches of N points (loss_utils.UniformTables; the gradient carries uniform_w);
+        ValueError for a patch size whose fine cloud leaves a ball with fewer than two slots."""
+        from . import loss_utils
+        M = N * self.up_ratio
+        need = loss_utils.uniform_min_points()
+        if M < need:
+            raise ValueError("use_uniform needs at least %d fine points (int(M * 0.004) >= 2 slots in the smallest ball): a patch size of "
+                             "at least %d at up_ratio %d, got %d (%d fine points)" % (need, -(-need // self.up_ratio), self.up_ratio, N, M))
+        return loss_utils.UniformTables(B, M, scale=float(self.opts.uniform_w))
+
+    def _uniform_workspace(self, ws, B, N):
+        """the uniform term's buffers (csrc/uniform_loss.hip), added to the workspace the first time the term runs at this shape: seeds of
+        the fine cloud, per-ball value partials, and the HOST level tables the launch reads, one per uniform_w -- a launch tape records
+        their addresses, so they live as long as the workspace."""
+        w = float(self.opts.uniform_w)
+        if "utabs" not in ws:
+            tab = self._uniform_tables(B, N)
+            dev, M = self.device, N * self.up_ratio
+            nb = _lib.lib().dispu_fps_scratch_bytes(B, M, tab.npoint)
+            ws.update(utabs={w: tab}, useeds=torch.empty((B, tab.npoint), dtype=torch.int32, device=dev),
+                      upart=torch.empty((tab.nlevels, B * tab.npoint), dtype=torch.float32, device=dev),
+                      ufps_tmp=torch.empty((nb // 4,), dtype=torch.float32, device=dev) if nb else None, ufps_bytes=nb)
+        if w not in ws["utabs"]:
+            ws["utabs"][w] = self._uniform_tables(B, N)
+        return ws["utabs"][w]
+
     def _check_targets(self, gt, radius, B, M):
         """gt [B, 4N, 3] / radius [B] float32 on the device: the loss workspace (d_gt, i_gt, g_gt, ...) is sized [B, 4N]
         and the kernels take raw pointers, so anything else must be refused here (DisPU/model.py:47-49 placeholders)."""
@@ -1000,6 +1029,9 @@ class Trainer(object):
         ws = self._workspace(B, N)
         gt, radius = self._check_targets(gt, radius, B, M)
         wf = weight_fine(self.epoch)
+        uniform = bool(getattr(self.opts, "use_uniform", False))
+        if uniform:
+            tab = self._uniform_workspace(ws, B, N)             # refuses a patch size the term cannot take, before any launch
         # side work is submitted behind the fine term's launches (the chain): the pair tensors of the local cell's backward (needed much
         # later) and the coarse term
         self._defer_branch(2, self._recompute_pair_tensors)    # off the chain: needed by the local cell's backward only
@@ -1007,30 +1039,49 @@ class Trainer(object):
             self._chamfer(ws["coarse"], gt, radius, 1000.0, ws["dcoarse"], 0)
         # fine term: nn_distance, then value + gradient (which zero-fills dfine); the repulsion term's ball query runs next to it and
         # adds its gradient once the Chamfer gradient is in place
+        # the uniform term's seeds (farthest point sampling of the fine cloud) run on the same branch; its fused value + gradient launch
+        # follows the Chamfer gradient like the repulsion gradient does
         rep = None
-        if self.opts.use_repulse:
-            fine = ws["fine"]
+        fine = ws["fine"]
+        if self.opts.use_repulse or uniform:
             with self._branch(1):
-                _lib.check(L.dispu_query_ball(B, M, M, _p(ws["r07"]), 20, _p(fine), _p(fine), _p(ws["ball"]), _p(ws["ball_cnt"]),
-                                              _lib.ARITH_CONTRACT, self.st), "query_ball")   # as loss_utils.get_repulsion_loss
+                if self.opts.use_repulse:
+                    _lib.check(L.dispu_query_ball(B, M, M, _p(ws["r07"]), 20, _p(fine), _p(fine), _p(ws["ball"]), _p(ws["ball_cnt"]),
+                                                  _lib.ARITH_CONTRACT, self.st), "query_ball")   # as loss_utils.get_repulsion_loss
+                if uniform:
+                    _lib.check(L.dispu_fps_ws(B, M, tab.npoint, _p(fine), _p(ws["ufps_tmp"]), ws["ufps_bytes"], _p(ws["useeds"]),
+                                              _lib.ARITH_CONTRACT, self.st), "fps")              # as loss_utils.get_uniform_loss
         self._chamfer(ws["fine"], gt, radius, 1000.0 * wf, ws["dfine"], 1)
-        if self.opts.use_repulse:
+        if self.opts.use_repulse or uniform:
             self._merge(1)
+        if self.opts.use_repulse:
             _lib.check(L.dispu_repulsion_loss_grad(B * M, M, 20, 0.001, self.opts.repulsion_w / (B * M * 4.0), _p(fine), _p(ws["ball"]),
                                                    _p(ws["rep"]), _p(ws["dfine"]), self.st), "repulsion_loss_grad")
             rep = ws["rep"]
+        if uniform:
+            _lib.check(L.dispu_uniform_loss_grad(B, M, tab.npoint, tab.nlevels, ctypes.addressof(tab.ns), ctypes.addressof(tab.levels), _p(fine),
+                                                 _p(ws["useeds"]), _p(ws["upart"]), _p(ws["dfine"]), None, None, _lib.ARITH_CONTRACT, self.st),
+                       "uniform_loss_grad")
         self._merge(0)
         out = ws["loss_vals"]
-        _lib.check(L.dispu_pu_loss_finalize(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
-                                            _p(out, 2), self.st), "pu_loss_finalize")
-        terms = self._terms(out, wf)
+        if uniform:
+            _lib.check(L.dispu_pu_loss_finalize_u(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
+                                                  _p(ws["upart"]), tab.nlevels, B * tab.npoint, float(self.opts.uniform_w), _p(out, 2), self.st),
+                       "pu_loss_finalize_u")
+        else:
+            _lib.check(L.dispu_pu_loss_finalize(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
+                                                _p(out, 2), self.st), "pu_loss_finalize")
+        terms = self._terms(out, wf, uniform)
         self._flush(prio=0)                                     # the recompute branch: submitted behind the loss's own launches
         return terms
 
     @staticmethod
-    def _terms(out, wf):
-        vals = out[2:6].clone()                                 # device scalars that survive the next step
-        return {"dis_coarse_cd": vals[0], "dis_fine_cd": vals[1], "repulsion_loss": vals[2], "pu_loss": vals[3], "weight_fine": wf}
+    def _terms(out, wf, uniform=False):
+        vals = out[2:8 if uniform else 6].clone()               # device scalars that survive the next step
+        terms = {"dis_coarse_cd": vals[0], "dis_fine_cd": vals[1], "repulsion_loss": vals[2], "pu_loss": vals[3], "weight_fine": wf}
+        if uniform:
+            terms["uniform_loss"] = vals[5]                     # uniform_w * get_uniform_loss(fine)
+        return terms
 
     # ---------------------------------------------------------------------------------------------- backward ----
     def backward(self):
@@ -1352,7 +1403,11 @@ class Trainer(object):
         B, N = inputs.shape[0], inputs.shape[1]
         gt, radius = self._check_targets(gt, radius, B, N * self.up_ratio)
         wf = weight_fine(self.epoch)
-        key = (B, N, wf, self.opts.use_repulse, torch.cuda.current_stream(self.device).cuda_stream)
+        uniform = bool(getattr(self.opts, "use_uniform", False))
+        if uniform:
+            self._uniform_tables(B, N)                       # refuses a patch size the term cannot take, before any launch
+        key = (B, N, wf, self.opts.use_repulse, uniform, float(getattr(self.opts, "uniform_w", 0.0)) if uniform else None,
+               torch.cuda.current_stream(self.device).cuda_stream)
         t = self._tapes.get(key)
         if t is None:
             st = dict(x=inputs.clone(), gt=gt.clone(), radius=radius.clone())
@@ -1381,7 +1436,7 @@ class Trainer(object):
         t["gt"].copy_(gt)
         t["radius"].copy_(radius)
         t["tape"].replay()
-        terms = self._terms(t["loss_vals"], wf)
+        terms = self._terms(t["loss_vals"], wf, uniform)
         world = self.all_reduce_grads()
         self.adam(world)
         self.global_step += 1
@@ -1391,6 +1446,8 @@ class Trainer(object):
         """one iteration of the loop body of Model.train (model.py:215-232) -> loss terms (device scalars)."""
         if isinstance(inputs, torch.Tensor) and inputs.dim() == 3:       # refuse bad targets before any launch
             self._check_targets(gt, radius, inputs.shape[0], inputs.shape[1] * self.up_ratio)
+            if getattr(self.opts, "use_uniform", False):
+                self._uniform_tables(inputs.shape[0], inputs.shape[1])
         self.zero_grad()
         self.forward(inputs)
         terms = self.loss_backward(gt, radius)

@@ -629,6 +629,27 @@ int dispu_step_meters(int b, int n_gt, int n_pred, const float* d_gt_c, const fl
  * per-point hinge sums, dpred [rows, 3] accumulates scale * d loss / d pred (atomics).  ns == 20. */
 int dispu_repulsion_loss_grad(long rows, int n_per_cloud, int ns, float h, float scale, const float* pred, const int* idx, float* out,
                               float* dpred, void* stream);
+/* get_uniform_loss (loss_utils.py:238-267; model.py:86) on given seeds, value and gradient in one launch.  pcd [b, n, 3]; seeds
+ * [b, npoint] (farthest_point_sample(npoint, pcd)); per level l < nlevels (1..8): ns[l] slots (2..min(64, n)) and levels[l][4] =
+ * { r_l = sqrt(p_l R) | e_l = sqrt(pi R^2 p_l / ns_l) | value factor | gradient factor } -- HOST arrays, read when the entry is
+ * called (a recorded call keeps the pointers: they must outlive the recording).  For every (cloud, seed) and level: the ball query of
+ * dispu_query_ball (r_l, ns_l, same `arith`), every slot's nearest OTHER slot by the squared distance of coordinate differences (the
+ * lowest slot on exact ties, tf.nn.top_k's rule), u = sqrt(D + 1e-8), q = (u - e_l)^2 / (e_l + 1e-8);
+ *   partial [nlevels, b * npoint]  = value factor * sum of q over the ball's slots, in slot order (get_uniform_loss = the mean of all
+ *                                    partials for the value factor (100 p_l)^2 / ns_l);
+ *   dpcd [b, n, 3] (may be NULL)  += gradient factor * ((u - e_l) / ((e_l + 1e-8) u)) * 2 (x_a - x_c) at row a, the negative at the
+ *                                    partner's row c (atomics; nothing where a == c), seeds / slots / partners held fixed;
+ *   idx_out (may be NULL)            the slots, level after level: [b, npoint, ns_0] | [b, npoint, ns_1] | ...; rows without a hit stay
+ *                                    untouched (their partial is NaN);  cnt_out [nlevels, b * npoint] (may be NULL) the hit counts.
+ * Any n >= 1.  b < 0, n < 1, npoint < 1, nlevels outside 1..8, an ns[l] outside 2..min(64, n) or a NULL required pointer:
+ * hipErrorInvalidValue before any device work; b == 0 returns 0 without a launch. */
+int dispu_uniform_loss_grad(int b, int n, int npoint, int nlevels, const int* ns, const float* levels, const float* pcd,
+                            const int* seeds, float* partial, float* dpcd, int* idx_out, int* cnt_out, int arith, void* stream);
+/* dispu_pu_loss_finalize plus the uniform term (model.py:86-87 with the get_uniform_loss line of loss_utils.py:238-267 enabled):
+ * out[0..4] as there, out[5] = uniform_w * mean(upart [nlevels, nu]) (dispu_uniform_loss_grad's partials), and out[3] (pu_loss)
+ * includes out[5].  One workgroup, fixed summation order. */
+int dispu_pu_loss_finalize_u(const float* cd, const float* rep, long nrep, float wf, float rep_w, const float* upart, int nlevels,
+                             long nu, float uniform_w, float* out, void* stream);
 /* dst[off ..] = W^T [N][K] for every weight matrix W [K][N] at src[off ..]; desc [count][3] = {off, K, N} (device int32).  The training
  * step's dX = dZ . W^T products read W^T untransposed (the forward GEMM's fast path). */
 int dispu_transpose_batched(int count, const int* desc, const float* src, float* dst, void* stream);

@@ -44,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument("--epoch_per_save", type=int, default=20)
     ap.add_argument("--use_repulse", type=str2bool, default=True)
     ap.add_argument("--repulsion_w", type=float, default=1.0, help="repulsion_weight")
+    ap.add_argument("--use_uniform", type=str2bool, default=False, help="add uniform_w * get_uniform_loss(fine) to the loss (model.py:86)")
+    ap.add_argument("--uniform_w", type=float, default=10.0, help="uniform_weight")
     ap.add_argument("--visulize", type=str2bool, default=False, help="not supported (refused when true)")
     ap.add_argument("--seed", type=int, default=0, help="initial weights, the epoch permutations and every batch draw")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="Trainer arithmetic")
@@ -60,6 +62,9 @@ def refuse_unsupported(a):
         raise ValueError("--visulize true: the reference's matplotlib three-view plots are not available")
     if a.batch_size <= 0 or a.training_epoch < 0 or a.epoch_per_save <= 0 or a.patch_num_point <= 0:
         raise ValueError("--batch_size, --epoch_per_save and --patch_num_point must be positive, --training_epoch non-negative")
+    if a.use_uniform and a.patch_num_point * a.up_ratio < 500:
+        raise ValueError("--use_uniform true needs at least 500 fine points (two slots in the smallest ball): --patch_num_point >= 125, "
+                         "got %d" % a.patch_num_point)
     if a.augment and not a.jitter_max > 0:
         raise ValueError("--jitter_max must be positive (the reference asserts clip > 0)")
 

@@ -35,10 +35,11 @@ def main():
     ap.add_argument("--bf16-min-macs", type=float, default=0.0, help="Trainer.bf16_min_macs (A/B)")
     ap.add_argument("--no-bf16-tn", action="store_true", help="A/B: Trainer.bf16_tn = False")
     ap.add_argument("--no-group-reduce", action="store_true", help="A/B: every weight-gradient product launches its own split reduction (Trainer.group_reduce = False)")
+    ap.add_argument("--use-uniform", action="store_true", help="the loss with the uniform term (TrainOpts.use_uniform, uniform_w 10)")
     ap.add_argument("--tape", action="store_true", help="forward + loss + backward re-issued from a launch tape (Trainer.train_step_taped)")
     args = ap.parse_args()
     from dispu_amd import synth
-    from dispu_amd.train import Trainer
+    from dispu_amd.train import Trainer, TrainOpts
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -50,7 +51,9 @@ def main():
     # weights: Xavier-uniform, seed 1234 (identical on every rank) -- generated without the oracle package
     from dispu_amd.params import init_params
     P = init_params(1234)
-    tr = Trainer(params=P, device=dev, dtype=args.dtype)
+    opts = TrainOpts()
+    opts.use_uniform = bool(args.use_uniform)
+    tr = Trainer(opts, params=P, device=dev, dtype=args.dtype)
     if args.dw_streams > 0:
         tr.dw_streams = args.dw_streams
     if args.bf16_min_macs > 0:
@@ -128,6 +131,7 @@ def main():
                           "ms_per_step": dt / args.steps * 1e3,
                           "ms_per_step_repeats": {"n": 5, "min": srt[0] / args.steps * 1e3, "median": srt[2] / args.steps * 1e3,
                                                   "max": srt[4] / args.steps * 1e3}, "launch": "tape" if args.tape else "eager",
+                          "use_uniform": bool(args.use_uniform),
                           "dtype": "f32" if args.dtype == "f32" else "bf16 products, f32 accumulate / storage", "pu_loss": float(terms["pu_loss"]), **phases}))
     if world > 1:
         dist.destroy_process_group()
