@@ -109,8 +109,9 @@ class Trainer(object):
         self._scratch = {}                    # per stream: scratch of the split reductions / column sums
         self._bn_scratch = None
         self._stash_ready = False
+        self._fresh = False                   # True between forward() and the first backward() on it (see backward)
         self._tapes = {}
-        self.dw_streams = 2                   # side streams the weight-gradient products are spread over (round-robin)
+        self._packs = {}                      # bf16 images of the weights for the streaming kernel (_stream)
         self._ar = None                       # parallel.BucketedAllReduce over flat_g (data parallel only, see _reducer)
         self._ar_armed = False                # True inside train_step(): backward() may start a bucket's all-reduce as soon as it is complete
         # a ONE-rank process group normally means "no collectives".  True keeps them (a 1-rank RCCL communicator executes the real
@@ -119,60 +120,46 @@ class Trainer(object):
         # None: the transport's default (RCCL: the launching thread enqueues the collectives).  True: a background thread does -- the step
         # is launch-bound at 8 patches per GPU and a collective call costs ~30 us of host time (parallel._Lane)
         self.comm_thread = comm_thread
+
+        # ---- switches: each default is the measured best; the other value is the reference side of a test (profiles/EXPERIMENTS.md
+        # lists the switches that were removed once measurements had settled them)
         # weight-gradient products (dW = X^T dZ) are off the backward chain: only Adam reads them.  They run on a second
         # HIP stream next to the dX products that ARE the chain (both read dZ; at 8 patches neither fills 256 CUs alone).
         self.overlap_dw = True
-        # dense blocks: forward = the fused inference kernel, backward = one recomputing kernel per block (csrc/edge_bwd.hip);
-        # 0 = round 2's path through materialised edge tensors (A/B tests)
-        self.fused_dense = True
-        self.use_wt = True
-        # dtype "bf16": the big activation / gradient tensors of the local cell are STORED as bf16 (0: fp32 storage, bf16 products only)
-        self.bf16_storage = True          # dX products through per-step W^T copies (A/B switch)
-        self._aux = []
-        self._cur = "main"
-        self._sides = []
-        self._side_rr = -1
-        self._fork_ev = None
-        self._join_ev = None
-        self._sched = 1
-        self.fused_heads_bwd = True
+        self.dw_streams = 2                   # side streams the weight-gradient products are spread over (round-robin)
         # non-local cell: flash-style attention forward (+ per-row log-sum-exp) and a recomputing backward (csrc/attention_train.hip);
-        # 0 = round 3's path through a materialised [B, M, M] probability tensor (A/B tests, the parity twin)
+        # False = round 3's path through a materialised [B, M, M] probability tensor (the parity twin)
         self.flash_attn = True
-        self.bf16_min_macs = 1.5e9
-
-        self._side_busy = []
-        self._group = None                  # (event, side streams that already wait for it) inside _fork_group()
-        # Side work (weight-gradient products, the non-local / skip branches) is QUEUED ON THE HOST AFTER the chain's kernels: every
-        # launch costs ~10 us of Python / ctypes, and a chain kernel that is submitted behind a dozen side launches leaves the GPU's
-        # main queue idle for that long (round 4, profiles/r04_a_train_timeline.txt: 145 us before the fused local cell, 137 us before
-        # its backward).  Side work records its fork event where it belongs and is submitted later, at points where the main queue
-        # holds enough work (Trainer._flush); 0 restores the in-place submission (A/B)
-        # (default "auto": on up to 16 patches per step -- at 32 the chip is saturated by the chain's own kernels, side work submitted
-        # later only lengthens the tail: 4.58 -> 4.63 ms; "1" / "0" force it)
-        self.fused_stem = True     # one launch per dense block in the forward pass
-        self.bf16_tn = True        # dtype="bf16": weight-gradient products of fp32-stored operands on the bf16 TN kernel too (False: they stay on the fp32 one)
-        self.bf16_stream = True    # dtype="bf16": the large dense products on the streaming bf16 kernel (csrc/linear_bf16_stream.hip) where its shape rules hold
-        self._packs = {}
         # the split reductions of the weight-gradient products are not launched one by one: every product describes the reduction it left
         # undone (dispu_tn_defer) and a stream's descriptors run as ONE launch when that stream is joined (_join, _bucket_point): ~20
-        # launches of 4 - 25 us per step become 3.  False: every product reduces itself (A/B; bit-identical)
+        # launches of 4 - 25 us per step become 3.  False: every product reduces itself (bit-identical)
         self.group_reduce = True
         # the local cell's backward (feature x weight gradient, conv1's dX, conv0's gather) as ONE recomputing launch (csrc/ps_local_bwd.hip,
         # fp32 storage only): h1 / dz0 / wv / the inverted neighbour graph never exist in HBM.  Correct and tested, but 40 us slower per 8-patch
         # step than the five-launch path (1.595 vs 1.555 ms): OFF by default
         self.fused_local_bwd = False
-        self._rg = {}                      # stream pointer -> [host descriptor array, entries pending, stream c_void_p]
-        self._rg_dev = {}                  # descriptor table bytes -> device copy (content-addressed: tapes keep pointing at theirs)
-        self.tail_on_chain = True  # the first dense block's weight gradients (the LAST work of the backward) stay on the chain's stream: no cross-stream hop in front of Adam
-        self.prep_late = True     # zeroing / W^T copies for the backward behind the non-local branch's own kernels (0: in front of them, round 3)
-        self.prep_on_side = False   # ... or on a weight-gradient stream during the forward (measured slower at 8 patches in fp32: 1.79 vs 1.71 ms)   # backward's zeroing / W^T copies on a dW stream during the forward
-        self._defer_mode = "auto"
-        self.defer_side = self._defer_mode != "0"
+        self.bf16_stream = True    # dtype="bf16": the large dense products on the streaming bf16 kernel (csrc/linear_bf16_stream.hip) where its shape rules hold
+        self.bf16_min_macs = 1.5e9            # dtype="bf16": products below this many multiply-adds stay on the fp32 kernel (_use_bf16)
+
+        # ---- scheduling state of the step in flight
+        self.st = None                        # stream pointer the launches go to (set by forward() / zero_grad(), swapped inside _branch)
+        self._cur = "main"                    # ... and that stream's scratch key
+        self._aux = []                        # branch i -> (auxiliary stream, fork event, completion event)
+        self._sides = []                      # the weight-gradient streams (_side_next)
+        self._side_rr = -1
+        self._side_busy = []
+        self._group = None                    # (event, side streams that already wait for it) inside _fork_group()
+        # Side work (weight-gradient products, the non-local / skip branches) is QUEUED ON THE HOST AFTER the chain's kernels: every
+        # launch costs ~10 us of Python / ctypes, and a chain kernel that is submitted behind a dozen side launches leaves the GPU's
+        # main queue idle for that long (round 4, profiles/r04_a_train_timeline.txt: 145 us before the fused local cell, 137 us before
+        # its backward).  Side work records its fork event where it belongs and is submitted later, at points where the main queue
+        # holds enough work (Trainer._flush).  On up to 16 patches per step (set by forward()): at 32 the chip is saturated by the
+        # chain's own kernels, side work submitted later only lengthens the tail (4.58 -> 4.63 ms)
+        self.defer_side = True
         self._deferred = []
-        self._pending = set()               # branches whose submission is still in _deferred
-        self._cap_events = []               # events created while a hipGraph is being captured (see _ev)
-        self._aux_done = {}                 # branch i -> the completion event recorded at its last exit
+        self._pending = set()                 # branches whose submission is still in _deferred
+        self._rg = {}                         # stream pointer -> [host descriptor array, entries pending, stream c_void_p]
+        self._rg_dev = {}                     # descriptor table bytes -> device copy (content-addressed: tapes keep pointing at theirs)
         self.P = None
         if params is not None:
             self.load_params(params)
@@ -184,10 +171,10 @@ class Trainer(object):
         train_step_taped records afresh instead of replaying launches onto freed memory.  The bf16 images of the weights
         (_stream) are keyed by the weight's address: dropped with the tapes that point at them."""
         self._tapes.clear()
-        if getattr(self, "_packs", None):
+        if self._packs:
             torch.cuda.synchronize(self.device)
             self._packs.clear()
-        if getattr(self, "_rg_dev", None):               # device copies of reduction tables: only tapes (dropped above) and the step being
+        if self._rg_dev:                                 # device copies of reduction tables: only tapes (dropped above) and the step being
             torch.cuda.synchronize(self.device)          # recorded point at them; a moved scratch buffer makes new table contents anyway
             self._rg_dev.clear()
 
@@ -259,7 +246,7 @@ class Trainer(object):
         rn, rm, k = B * N, B * M, K_NEIGH
         E = lambda *shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
         Z = lambda *shape: torch.zeros(shape, dtype=f32, device=dev)
-        pt = torch.bfloat16 if (self.bf16 and self.bf16_storage) else f32      # storage type of the pair tensors / dF'
+        pt = torch.bfloat16 if self.bf16 else f32      # storage type of the pair tensors / dF'
         ws = dict(
             feat=E(rn, 480), dfeat=E(rn, 480),
             prep=[None, None] + [E(rn, 48) for _ in range(2, DENSE_BLOCKS + 1)],
@@ -281,7 +268,7 @@ class Trainer(object):
             hp=E(rm, 2048), dhp=E(rm, 2048, dtype=pt), aft=E(rm, 256), daft=E(rm, 256),
             kv=E(rm, 128), dkv=E(rm, 128), q=E(rm, 64), dq=E(rm, 64), att=E(rm, 64), datt=E(rm, 64), lse=E(rm), dvec=E(rm),
             S=None if self.flash_attn else E(B, M, M), dS=None if self.flash_attn else E(B, M, M),
-            nl=E(rm, 256), dnl=E(rm, 256), sum=E(rm, 256), dsum=E(rm, 256), agg=E(rm, 256), dagg=E(rm, 256),
+            nl=E(rm, 256), dnl=E(rm, 256), sum=E(rm, 256), agg=E(rm, 256), dagg=E(rm, 256),
             f256=E(rm, 256), df256=E(rm, 256), f64=E(rm, 64), df64=E(rm, 64), z=E(rm, 3), dz=E(rm, 3), fine=E(B, M, 3), dfine=E(B, M, 3),
             # loss
             cd=[dict(d_gt=E(B, M), i_gt=E(B, M, dtype=i32), d_pred=E(B, M), i_pred=E(B, M, dtype=i32), g_gt=E(B, M), g_pred=E(B, M),
@@ -295,17 +282,6 @@ class Trainer(object):
         self._ws[key] = ws
         return ws
 
-    def _edge_buffers(self, B, N):
-        """edge tensors [B*N*16, 72 + 2C] and their gradients, one pair per dense block: only the UNFUSED dense-block path
-        (Trainer.fused_dense = False, kept for A/B tests) materialises them."""
-        key = ("edge", B, N)
-        if key not in self._ws:
-            rows = B * N * K_NEIGH
-            mk = lambda: [None, torch.empty((rows, 72 + 48), dtype=torch.float32, device=self.device)] + \
-                [torch.empty((rows, 72 + 96), dtype=torch.float32, device=self.device) for _ in range(2, DENSE_BLOCKS + 1)]
-            self._ws[key] = (mk(), mk())
-        return self._ws[key]
-
     def _scratch_floats(self, n, key=None):
         """scratch of the launches queued on ONE stream (they run in order, so they can share it): a dW stream's (key "dw<i>"), or the
         current stream's (main or a branch)."""
@@ -314,7 +290,7 @@ class Trainer(object):
         if cur is None or cur.numel() < n:
             if cur is not None:
                 torch.cuda.synchronize(self.device)          # a launch on that stream may still be using the old buffer
-                self._invalidate_recordings()                # ... and a tape / graph recorded at a smaller shape points into it
+                self._invalidate_recordings()                # ... and a tape recorded at a smaller shape points into it
             cur = self._scratch[key] = torch.empty(max(int(n), 1 << 20), dtype=torch.float32, device=self.device)
         return cur
 
@@ -323,7 +299,6 @@ class Trainer(object):
         if not self._sides:
             n = max(1, int(self.dw_streams))
             self._sides = [_pool_stream(self.device, "dw", j) for j in range(n)]
-            self._fork_ev = torch.cuda.Event()
             self._join_evs = [torch.cuda.Event() for _ in range(n)]
             self._side_busy = [False] * n
         self._side_rr = (self._side_rr + 1) % len(self._sides)
@@ -385,46 +360,13 @@ class Trainer(object):
         """t.zero_() on the stream launches currently go to, as a memset through the library (a plain C call: tape-able, and cheaper
         than the torch op)."""
         L = _lib.tape_lib()
-        st = self.st if getattr(self, "st", None) is not None else _lib.stream_ptr(self.device)
+        st = self.st if self.st is not None else _lib.stream_ptr(self.device)
         _lib.check(L.dispu_memset_async(_lib.C.c_void_p(t.data_ptr()), 0, t.numel() * t.element_size(), st), "memset")
-
-    def _ev(self, cached):
-        """the event to record at this point: the cached object in eager mode; a FRESH one while a hipGraph is being captured.
-        Re-recording one event object several times inside a capture loses stream order on this runtime (round 4: the fused coarse-head
-        backward and the dup_sum_grad launch after it, separated by five re-records of one fork event, ran unordered in the replayed
-        graph -- stale d(up256), every gradient of the feature extractor wrong from the second replay on; eager order was never
-        affected).  Fresh events are kept alive until the capture ends (train_step_graphed clears the list)."""
-        if torch.cuda.is_current_stream_capturing():
-            ev = torch.cuda.Event()
-            self._cap_events.append(ev)
-            return ev
-        return cached
-
-    def _fork(self):
-        """-> (stream pointer, scratch key) for a dW product that may start once everything queued on the main stream so far is done."""
-        i = self._side_next()
-        if self._group is not None:
-            # inside _fork_group(): every product of the group hangs off ONE event; a side stream waits for it once
-            ev, waited = self._group
-            if i not in waited:
-                self._wait(self._sides[i], ev)
-                waited.add(i)
-        else:
-            main = torch.cuda.current_stream(self.device)
-            ev = self._ev(self._fork_ev)
-            self._rec(ev, main)
-            self._wait(self._sides[i], ev)
-        self._side_busy[i] = True
-        return ctypes.c_void_p(self._sides[i].cuda_stream), "dw%d" % i
 
     @contextlib.contextmanager
     def _fork_group(self):
         """Several dW products that all depend on the SAME point of the current stream (the four weight gradients of a fused head
-        chain): one event, one wait per side stream.  Besides saving events this is what keeps the step correct under hipGraph replay:
-        captured as record / wait / record / wait ... with nothing launched on the main stream in between (redundant edges from one
-        node to a chain of side-stream nodes), the replayed graph ran the NEXT main-stream kernel without waiting for its predecessor
-        (round 4, tools/debug/graph_vs_eager.py: stale d(up256) -> every gradient of the feature extractor wrong from the second
-        replay on; eager launches were never affected)."""
+        chain): one event, one wait per side stream."""
         if not self.overlap_dw:
             yield
             return
@@ -439,8 +381,6 @@ class Trainer(object):
     def _fork_point(self):
         """an event at the current position of the main stream, for a dW product queued later (see _lin_bwd)."""
         ev = torch.cuda.Event()
-        if torch.cuda.is_current_stream_capturing():
-            self._cap_events.append(ev)
         self._rec(ev, torch.cuda.current_stream(self.device))
         return ev
 
@@ -479,8 +419,6 @@ class Trainer(object):
         raw = ctypes.string_at(ctypes.addressof(g[0]), n * ctypes.sizeof(_lib.TnReduceDesc))
         dev = self._rg_dev.get(raw)
         if dev is None:                                  # first step with this table (steady state: the same pointers every step)
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("a new reduction table inside a hipGraph capture: run one eager step with this batch shape first")
             dev = self._rg_dev[raw] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
         _lib.check(_lib.tape_lib().dispu_tn_reduce_grouped(n, ctypes.c_void_p(ctypes.addressof(g[0])), ctypes.c_void_p(dev.data_ptr()), g[2]),
                    "dispu_tn_reduce_grouped")
@@ -497,9 +435,8 @@ class Trainer(object):
         self._rg_flush()                                 # each stream's pending split reductions: one launch per stream, behind its products
         for i, busy in enumerate(self._side_busy if self._sides else []):
             if busy:
-                ev = self._ev(self._join_evs[i])
-                self._rec(ev, self._sides[i])
-                self._wait(torch.cuda.current_stream(self.device), ev)
+                self._rec(self._join_evs[i], self._sides[i])
+                self._wait(torch.cuda.current_stream(self.device), self._join_evs[i])
                 self._side_busy[i] = False
 
     @contextlib.contextmanager
@@ -515,7 +452,7 @@ class Trainer(object):
             self._aux.append((_pool_stream(self.device, "aux", len(self._aux)), torch.cuda.Event(), torch.cuda.Event()))
         aux, ev_fork, ev_done = self._aux[i]
         if after is None:
-            after = self._ev(ev_fork)
+            after = ev_fork
             self._rec(after, torch.cuda.current_stream(self.device))
         self._wait(aux, after)
         old_st, old_cur = self.st, self._cur
@@ -528,21 +465,13 @@ class Trainer(object):
                 # recorded HERE, not in _merge: streams share hardware queues (GPU_MAX_HW_QUEUES = 4), and a marker queued at merge
                 # time lands behind whatever the other streams of that queue were given in between (measured: the local cell's
                 # backward started 0.33 ms late, behind dW products it does not depend on)
-                if self._sched & 1:
-                    done = self._ev(ev_done)
-                    self._rec(done, aux)
-                    self._aux_done[i] = done
+                self._rec(ev_done, aux)
 
     def _merge(self, i):
         if i in self._pending:
             self._flush(prio=0)                          # a branch whose submission is still deferred cannot be waited for
-        if self.overlap_dw and (i < len(self._aux) or i in self._aux_done):
-            aux, _, ev_done = self._aux[i]
-            if not (self._sched & 1):
-                done = self._ev(ev_done)
-                self._rec(done, aux)
-                self._aux_done[i] = done
-            self._wait(torch.cuda.current_stream(self.device), self._aux_done.get(i, ev_done))
+        if self.overlap_dw and i < len(self._aux):
+            self._wait(torch.cuda.current_stream(self.device), self._aux[i][2])
 
     # ----------------------------------------------------------------------------------------------- helpers ----
     def _dl(self, batch, M, K, N, *rest):
@@ -618,7 +547,7 @@ class Trainer(object):
         L = _lib.tape_lib()
         side = side and self.overlap_dw
         sto = (1 if X.dtype == torch.bfloat16 else 0) | (2 if Zt.dtype == torch.bfloat16 else 0)
-        bf = (self.bf16_tn and self._use_bf16(batch, M, K, N)) or bool(sto)
+        bf = self._use_bf16(batch, M, K, N) or bool(sto)
         need = (L.dispu_linear_tn_bf16_scratch_floats if bf else L.dispu_linear_tn_scratch_floats)(batch, M, K, N)
         # the streaming TN kernel where its shape rules hold (after_conv's 2048 x 256: 37 vs 59 us at 8192 rows; the pair tensors' 128 x 128
         # over 131072 bf16-stored rows: 22 vs 47 us)
@@ -686,9 +615,8 @@ class Trainer(object):
                                          dZ.stride(0) if dZ is not None else 0, _p(dbias), 1, _p(sc), sc.numel(), self.st),
                    "dispu_act_bias_grad")
 
-    def _dx(self, M, N, K, dY, dyoff, W, woff, dX, dxoff, acc, mask=None, WT=None):
-        """dX[:, dxoff:dxoff+K] (+)= dY[:, dyoff:dyoff+N] . W^T, then zeroed where mask <= 0: mask = (tensor, column offset, columns) is the
-        ReLU output that fed this layer -- the relu_grad of the layer below rides in the GEMM epilogue (no separate pass over dX).
+    def _dx(self, M, N, K, dY, dyoff, W, woff, dX, dxoff, acc, WT=None):
+        """dX[:, dxoff:dxoff+K] (+)= dY[:, dyoff:dyoff+N] . W^T.
         WT: the step's transposed copy of W ([N, K] row-major): the product then runs untransposed (the forward GEMM's fast path)."""
         L = _lib.tape_lib()
         bf = self._use_bf16(1, M, N, K)
@@ -699,27 +627,21 @@ class Trainer(object):
         else:
             wp, ldw, tb = _p(W, woff), W.stride(0), 1
         sto = (1 if dY.dtype == torch.bfloat16 else 0) | (4 if dX.dtype == torch.bfloat16 else 0)
-        if (sto or bf) and mask is None and not acc and self._stream(M, N, K, dY, dyoff, W, woff, 0, None, 0, dX, dxoff):
+        if (sto or bf) and not acc and self._stream(M, N, K, dY, dyoff, W, woff, 0, None, 0, dX, dxoff):
             return
         if sto:
-            assert self.bf16 and mask is None and not acc and dyoff == 0 and dxoff == 0
+            assert self.bf16 and not acc and dyoff == 0 and dxoff == 0
             _lib.check(L.dispu_linear_bf16s(1, M, N, K, _p(dY), dY.stride(0), 0, wp, ldw, 0, tb, None, 0, _p(dX), dX.stride(0), 0, None, 0, 0,
                                             sto, self.st), "dispu_linear_bf16s(dX)")
             return
-        if mask is None:
-            fn = L.dispu_linear_bf16 if bf else L.dispu_linear
-            _lib.check(fn(1, M, N, K, _p(dY, dyoff), dY.stride(0), 0, wp, ldw, 0, tb, None, 0, _p(dX, dxoff), dX.stride(0), 0,
-                          r1, ldr, 0, None, 0, 0, self.st), "dispu_linear(dX)")
-        else:
-            mt, moff, mcols = mask
-            fn = L.dispu_linear_bf16_masked if bf else L.dispu_linear_masked
-            _lib.check(fn(1, M, N, K, _p(dY, dyoff), dY.stride(0), 0, wp, ldw, 0, tb, None, 0, _p(dX, dxoff), dX.stride(0), 0,
-                          r1, ldr, 0, _p(mt, moff), mt.stride(0), int(mcols), self.st), "dispu_linear_masked(dX)")
+        fn = L.dispu_linear_bf16 if bf else L.dispu_linear
+        _lib.check(fn(1, M, N, K, _p(dY, dyoff), dY.stride(0), 0, wp, ldw, 0, tb, None, 0, _p(dX, dxoff), dX.stride(0), 0,
+                      r1, ldr, 0, None, 0, 0, self.st), "dispu_linear(dX)")
 
     def _lin_bwd(self, X, xoff, K, wname, N, dY, dyoff, dX=None, dxoff=0, acc_dx=False, M=None, bias=True, W=None, dW=None, woff=0,
-                 mask=None, db=None, side=True):
+                 db=None, side=True):
         """backward of _lin given dZ = dY[:, dyoff:dyoff+N] ALREADY multiplied by the layer's own relu' (its producer did that):
-        db += colsum dZ and dW += X^T dZ on the second stream, dX[:, dxoff:dxoff+K] (+)= dZ . W^T with `mask` (see _dx)."""
+        db += colsum dZ and dW += X^T dZ on the second stream, dX[:, dxoff:dxoff+K] (+)= dZ . W^T (see _dx)."""
         M = X.shape[0] if M is None else M
         W = self.P[wname + "/weights"] if W is None else W
         dW = self.G[wname + "/weights"] if dW is None else dW
@@ -729,8 +651,8 @@ class Trainer(object):
         # ordered after dZ by an event recorded BEFORE the dX launch (dX never writes what the dW product reads)
         ev = self._fork_point() if (self.overlap_dw and dX is not None) else None
         if dX is not None:
-            WT = self.PT.get(wname + "/weights") if (wname is not None and woff == 0 and self.use_wt and K == W.shape[0]) else None
-            self._dx(M, N, K, dY, dyoff, W, woff, dX, dxoff, acc_dx, mask, WT)
+            WT = self.PT.get(wname + "/weights") if (wname is not None and woff == 0 and K == W.shape[0]) else None
+            self._dx(M, N, K, dY, dyoff, W, woff, dX, dxoff, acc_dx, WT)
         self._tn(1, M, K, N, X, xoff, X.stride(0), 0, dY, dyoff, dY.stride(0), 0, dW, woff, dW.stride(0), 0, 1, dbias=db, side=side, after=ev,
                  wgrad=True)
 
@@ -755,27 +677,14 @@ class Trainer(object):
         ws = self._workspace(B, N)
         L = _lib.tape_lib()
         self.st = _lib.stream_ptr(x.device)
-        if self._defer_mode == "auto":
-            # not while capturing: in a hipGraph only the dependencies count, and the executor orders the deferred nodes worse
-            # (graphed 8-patch step 1.94 ms with the deferral, 1.88 ms without)
-            self.defer_side = rm <= 16 * 1024 and not torch.cuda.is_current_stream_capturing()
+        self.defer_side = rm <= 16 * 1024                # see __init__
         self._shape = (B, N)
         self._x = x
-        if self.overlap_dw and self.prep_on_side:
-            # what the backward needs and nothing in the forward touches (zeroed accumulators, the W^T copies: ~45 us of kernels) goes to a
-            # weight-gradient stream, idle during the forward, right now; loss_backward() joins it.  (It used to ride at the head of the
-            # non-local branch "because that has slack" -- since the flash attention the main stream waits 75 us for exactly that branch.)
-            st_side, key = self._fork()
-            self._side_rr -= 1                                       # the weight gradients keep their round-robin assignment
-            main_st, self.st = self.st, st_side
-            self._backward_prep(ws)
-            self.st = main_st
-            self._prep_side = int(key[2:])
         P = self.P
         feat = ws["feat"]
         fe = "generator/feature_extraction_coarse/"
-        stem0 = self.fused_dense and self.fused_stem and N <= 256 and N % 2 == 0
-        if not stem0:      # (fused stem: the first block's launch evaluates layer0 while it stages its cloud)
+        stem = N <= 256 and N % 2 == 0      # one launch per dense block (dispu_stem_block's shape rule)
+        if not stem:       # (fused stem: the first block's launch evaluates layer0 while it stages its cloud)
             _lib.check(L.dispu_linear_small_k(rn, 3, 24, _p(x), 3, _p(P[fe + "layer0/weights"]), _p(P[fe + "layer0/biases"]), 0,
                                               _p(feat, 456), 480, self.st), "layer0")
         col = 456
@@ -794,9 +703,6 @@ class Trainer(object):
             width = 3 * GROWTH + C
             in_col = col
             col -= width
-            stem = self.fused_dense and self.fused_stem and N <= 256 and N % 2 == 0
-            if not stem:
-                _lib.check(L.dispu_knn_feat_strided(B, N, N, C, k + 1, _p(F, foff), ldf, _p(F, foff), ldf, None, _p(kidx), self.st), "knn_feat")
             if stem:
                 # search + edge features + dense_conv in one launch (csrc/edge.hip, KNN variant); the neighbour table stays for the backward pass
                 _lib.check(L.dispu_stem_block(rn, N, C, _p(F, foff), ldf, k + 1, 1, _p(P[sc + "/l0/weights"]), _p(P[sc + "/l0/biases"]),
@@ -807,20 +713,14 @@ class Trainer(object):
                                               _p(ws["prep"][d + 1]) if d < DENSE_BLOCKS else None, 48, _p(x) if d == 1 else None,
                                               _p(P[fe + "layer0/weights"]) if d == 1 else None, _p(P[fe + "layer0/biases"]) if d == 1 else None,
                                               _p(feat, 456) if d == 1 else None, 480, self.st), "stem_block")
-            elif self.fused_dense:
+            else:
+                _lib.check(L.dispu_knn_feat_strided(B, N, N, C, k + 1, _p(F, foff), ldf, _p(F, foff), ldf, None, _p(kidx), self.st), "knn_feat")
                 # the inference kernel (csrc/edge.hip): edge features, three chained convs and the max in one launch; nothing is kept
                 # for the backward pass, which recomputes the block on chip (csrc/edge_bwd.hip)
                 _lib.check(L.dispu_edge_dense_conv(rn, N, C, _p(F, foff), ldf, _p(kidx), k + 1, 1, _p(P[sc + "/l0/weights"]),
                                                    _p(P[sc + "/l0/biases"]), _p(P[sc + "/l1/weights"]), _p(P[sc + "/l1/biases"]),
                                                    _p(P[sc + "/l2/weights"]), _p(P[sc + "/l2/biases"]), _p(feat, col), 480, self.st),
                            "edge_dense_conv")
-            else:
-                Eb = self._edge_buffers(B, N)[0][d]
-                _lib.check(L.dispu_edge_feature(rn, N, k, C, _p(F, foff), ldf, _p(kidx), k + 1, 1, _p(Eb, 72), Eb.stride(0), self.st), "edge_feature")
-                self._lin(Eb, 72, 2 * C, sc + "/l0", 1, Eb, 48, 24)
-                self._lin(Eb, 48, 24 + C, sc + "/l1", 1, Eb, 24, 24)
-                self._lin(Eb, 24, 48 + C, sc + "/l2", 0, Eb, 0, 24)
-                _lib.check(L.dispu_max_k(rn, k, width, _p(Eb), Eb.stride(0), _p(feat, col), 480, self.st), "max_k")
             prep_done = stem and d < DENSE_BLOCKS
             self._blocks.append((d, C, col, in_col, width))
         assert col == 0
@@ -867,8 +767,6 @@ class Trainer(object):
         S = ws["S"]
 
         def nl_branch():
-            if not (self.overlap_dw and self.prep_on_side) and not self.prep_late:
-                self._backward_prep(ws)
             self._lin(up128, 0, 128, ps + "PointShuffle/conv_kv", 0, ws["kv"], 0, 128)
             self._lin(up128, 0, 128, ps + "PointShuffle/conv_query", 0, ws["q"], 0, 64)
             if self.flash_attn:
@@ -882,8 +780,9 @@ class Trainer(object):
                 _lib.check(self._dl(B, M, M, 64, _p(S), M, M * M, _p(ws["kv"], 64), 128, M * 128, 0, None, 0, _p(ws["att"]), 64,
                                           M * 64, None, 0, 0, None, 0, 0, self.st), "att.V")
             self._lin(ws["att"], 0, 64, ps + "PointShuffle/conv_back_project", 1, ws["nl"], 0, 256)
-            if not (self.overlap_dw and self.prep_on_side) and self.prep_late:
-                self._backward_prep(ws)
+            # what the backward needs and nothing in the forward touches (zeroed accumulators, the W^T copies: ~45 us of kernels),
+            # behind the branch's own kernels
+            self._backward_prep(ws)
 
         self._defer_branch(0, nl_branch)
         self._merge(2)
@@ -967,7 +866,7 @@ class Trainer(object):
 
     def _fused_local_bwd_ok(self, ws):
         """the one-launch backward of the local cell: fp32 pair-tensor storage, whole 8-point groups, transposed weight copies at hand."""
-        return (self.fused_local_bwd and ws["h0"].dtype == torch.float32 and ws["h0"].shape[0] % 64 == 0 and self.use_wt
+        return (self.fused_local_bwd and ws["h0"].dtype == torch.float32 and ws["h0"].shape[0] % 64 == 0
                 and ("refine/PointShuffle/conv1/weights" in self.PT))
 
     # -------------------------------------------------------------------------------------------------- loss ----
@@ -1086,8 +985,8 @@ class Trainer(object):
     # ---------------------------------------------------------------------------------------------- backward ----
     def backward(self):
         """gradients of pu_loss w.r.t. every trainable variable, accumulated into the flat gradient buffer.
-        ReLU gradients never run as separate passes: the dX product of a layer applies the mask of the layer below in its epilogue
-        (`mask=`), so every dY arriving at _lin_bwd is already the pre-activation gradient dZ."""
+        ReLU gradients never run as separate passes: the kernel that produces a layer's dY applies that layer's mask (the fused head
+        chains, the gathers, _act_bias_grad), so every dY arriving at _lin_bwd is already the pre-activation gradient dZ."""
         L = _lib.tape_lib()
         B, N = self._shape
         M, k = N * self.up_ratio, K_NEIGH
@@ -1098,13 +997,7 @@ class Trainer(object):
         dcoarse, dfine = ws["dcoarse"].view(rm, 3), ws["dfine"].view(rm, 3)
         ps = "refine/PointShuffle/"
         fs = "refine/fine_coordinate_regressor/"
-        if self.overlap_dw and getattr(self, "_prep_side", None) is not None:
-            # the accumulators zeroed and the W^T copies made on a weight-gradient stream during the forward (see forward())
-            i, self._prep_side = self._prep_side, None
-            ev = self._ev(self._join_evs[i])
-            self._rec(ev, self._sides[i])
-            self._wait(torch.cuda.current_stream(self.device), ev)
-        if not getattr(self, "_fresh", False):
+        if not self._fresh:
             # a second backward() on the same forward (new targets / loss weights): the atomics accumulators still hold the previous,
             # already masked gradients -- clear them again, on this stream, before anything accumulates
             self._zero(ws["zeroed"])
@@ -1113,37 +1006,27 @@ class Trainer(object):
             with self._branch(2):
                 self._recompute_pair_tensors()
 
-        if self._sched & 2:
-            self._merge(2)                               # h0 / h1 / wv / the inverted graph: done by the time the loss is (see _branch)
         # fine = coarse + sigmoid(z) - 0.5
         _lib.check(L.dispu_sigmoid_offset_grad(rm * 3, _p(ws["z"]), _p(dfine), _p(ws["dz"]), _p(dcoarse), self.st), "sigmoid_grad")
         ag = ps + "aggregation"
-        if self.fused_heads_bwd:
-            # fc_layer2 -> fc_layer1 -> fc_layer0 -> aggregation backward and the three branch masks of
-            # sum = relu(after) + relu(skip) + relu(nl) in ONE launch (csrc/mlp_chain_bwd.hip); the four dW products follow on the side streams
-            PT = self.PT
-            _lib.check(L.dispu_mlp_chain_grad(rm, 256, 256, 256, _p(ws["dz"]), 3, _p(P[fs + "fc_layer2/weights"]),
-                                              _p(PT[fs + "fc_layer1/weights"]), _p(PT[fs + "fc_layer0/weights"]), _p(PT[ag + "/weights"]),
-                                              _p(ws["f64"]), 64, _p(ws["f256"]), 256, _p(ws["agg"]), 256, None, 0, None, 0,
-                                              _p(ws["df64"]), 64, _p(ws["df256"]), 256, _p(ws["dagg"]), 256,
-                                              _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), 256, _p(ws["daft"]), _p(ws["dskip"]), _p(ws["dnl"]), 256,
-                                              self.st), "mlp_chain_grad[fine]")
-            with self._fork_group():
-                self._lin_bwd(ws["f64"], 0, 64, fs + "fc_layer2", 3, ws["dz"], 0)
-                self._lin_bwd(ws["f256"], 0, 256, fs + "fc_layer1", 64, ws["df64"], 0)
-                self._lin_bwd(ws["agg"], 0, 256, fs + "fc_layer0", 256, ws["df256"], 0)
-                self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0)
-        else:
-            self._lin_bwd(ws["f64"], 0, 64, fs + "fc_layer2", 3, ws["dz"], 0, ws["df64"], mask=(ws["f64"], 0, 64))
-            self._lin_bwd(ws["f256"], 0, 256, fs + "fc_layer1", 64, ws["df64"], 0, ws["df256"], mask=(ws["f256"], 0, 256))
-            self._lin_bwd(ws["agg"], 0, 256, fs + "fc_layer0", 256, ws["df256"], 0, ws["dagg"], mask=(ws["agg"], 0, 256))
-            self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0, ws["dsum"])
-            # sum = relu(after) + relu(skip) + relu(nl): the three branch gradients in one pass
-            _lib.check(L.dispu_mask3(rm, 256, _p(ws["dsum"]), 256, _p(ws["aft"]), 256, _p(ws["skip"]), 256, _p(ws["nl"]), 256, _p(ws["daft"]),
-                                     _p(ws["dskip"]), _p(ws["dnl"]), 256, self.st), "mask3")
+        # fc_layer2 -> fc_layer1 -> fc_layer0 -> aggregation backward and the three branch masks of
+        # sum = relu(after) + relu(skip) + relu(nl) in ONE launch (csrc/mlp_chain_bwd.hip); the four dW products follow on the side streams
+        PT = self.PT
+        _lib.check(L.dispu_mlp_chain_grad(rm, 256, 256, 256, _p(ws["dz"]), 3, _p(P[fs + "fc_layer2/weights"]),
+                                          _p(PT[fs + "fc_layer1/weights"]), _p(PT[fs + "fc_layer0/weights"]), _p(PT[ag + "/weights"]),
+                                          _p(ws["f64"]), 64, _p(ws["f256"]), 256, _p(ws["agg"]), 256, None, 0, None, 0,
+                                          _p(ws["df64"]), 64, _p(ws["df256"]), 256, _p(ws["dagg"]), 256,
+                                          _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), 256, _p(ws["daft"]), _p(ws["dskip"]), _p(ws["dnl"]), 256,
+                                          self.st), "mlp_chain_grad[fine]")
+        with self._fork_group():
+            self._lin_bwd(ws["f64"], 0, 64, fs + "fc_layer2", 3, ws["dz"], 0)
+            self._lin_bwd(ws["f256"], 0, 256, fs + "fc_layer1", 64, ws["df64"], 0)
+            self._lin_bwd(ws["agg"], 0, 256, fs + "fc_layer0", 256, ws["df256"], 0)
+            self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0)
 
         # local cell first: the host needs ~0.1 ms to queue the two branches below, the chain must not sit idle meanwhile; the
-        # branches themselves only need the mask3 outputs, so they are ordered after THIS point of the stream, not after the product
+        # branches themselves only need the head chain's dskip / dnl, so they are ordered after THIS point of the stream, not after the
+        # product
         ev_br = self._fork_point() if self.overlap_dw else None
         self._lin_bwd(ws["hp"], 0, 2048, ps + "after_conv", 256, ws["daft"], 0, ws["dhp"])
         # non-local cell: reads dnl, writes datt / dS / dkv / dq / dup128 -- nothing the local cell or the skip branch touches, so
@@ -1173,7 +1056,7 @@ class Trainer(object):
             self._lin_bwd(ws["up128"], 0, 128, ps + "PointShuffle/conv_query", 64, ws["dq"], 0, dup128, 0, acc_dx=True)
         self._defer_branch(0, nl_backward, ev_br)
         # skip branch (a second branch): 134 -> 256 backward; its max gradient is scattered after the merges below
-        split_skip = self.fused_heads_bwd and self.overlap_dw      # the skip branch's d(up128) in its own buffer, summed in the coarse chain
+        split_skip = self.overlap_dw      # the skip branch's d(up128) in its own buffer, summed in the coarse chain
         def skip_backward():
             self._lin_bwd(ws["gmax"], 0, 134, ps + "skip", 256, ws["dskip"], 0, ws["dgmax"])
             if split_skip:
@@ -1183,8 +1066,7 @@ class Trainer(object):
         # after_conv's dX (0.1 - 0.15 ms on the GPU) is queued: submit the two branches the chain will wait for behind it; the weight
         # gradients stay deferred until the chain's next three kernels are queued too
         self._flush(prio=0)
-        if not (self._sched & 2):
-            self._merge(2)                               # h0 / h1 / wv / the inverted graph are in place
+        self._merge(2)                                   # h0 / h1 / wv / the inverted graph are in place
         fused_lb = self._fused_local_bwd_ok(ws)
         if fused_lb:
             # one launch: dwv, dz1 (for the side-stream dW1), dG (atomics into the zeroed buffer) and -dA; h1 / dz0 / wv stay on chip
@@ -1236,39 +1118,25 @@ class Trainer(object):
         # coarse regressor
         cs = "generator/coarse_coordinate_regressor/"
         c2 = "generator/upshuffle_0/conv2"
-        if self.fused_heads_bwd:
-            # fc_layer2 -> fc_layer1 -> fc_layer0 (+ everything already accumulated in dup128, then conv2's relu') -> conv2 (duplicate_up's
-            # relu') in one launch
-            PT = self.PT
-            _lib.check(L.dispu_mlp_chain_grad(rm, 256, 128, 256, _p(dcoarse), 3, _p(P[cs + "fc_layer2/weights"]),
-                                              _p(PT[cs + "fc_layer1/weights"]), _p(PT[cs + "fc_layer0/weights"]), _p(PT[c2 + "/weights"]),
-                                              _p(ws["c64"]), 64, _p(ws["c256"]), 256, _p(ws["up128"]), 128, _p(dup128), 128,
-                                              _p(ws["dup128s"]) if split_skip else None, 128, _p(ws["dc64"]), 64, _p(ws["dc256"]), 256, _p(dup128), 128,
-                                              _p(ws["up256"]), None, None, 256, _p(ws["dup256"]), None, None, 256, self.st),
-                       "mlp_chain_grad[coarse]")
-            # the chain goes on first (d(up256) summed over the four copies -> the 480-wide product below); the head's four weight
-            # gradients are queued on the side streams after it
-            _lib.check(L.dispu_dup_sum_grad(B, N, 256, self.up_ratio, _p(ws["dup256"]), 256, _p(ws["dh256"]), 256, self.st), "dup_sum_grad")
-            with self._fork_group():
-                self._lin_bwd(ws["c64"], 0, 64, cs + "fc_layer2", 3, dcoarse, 0)
-                self._lin_bwd(ws["c256"], 0, 256, cs + "fc_layer1", 64, ws["dc64"], 0)
-                self._lin_bwd(ws["up128"], 0, 128, cs + "fc_layer0", 256, ws["dc256"], 0)
-                self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0)
-                w1, dw1 = P["generator/upshuffle_0/conv1/weights"], G["generator/upshuffle_0/conv1/weights"]
-                self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
-                         dbias=G["generator/upshuffle_0/conv1/biases"], side=True, wgrad=True)   # read by Adam only: off the chain like every other dW
-        else:
-            self._lin_bwd(ws["c64"], 0, 64, cs + "fc_layer2", 3, dcoarse, 0, ws["dc64"], mask=(ws["c64"], 0, 64))
-            self._lin_bwd(ws["c256"], 0, 256, cs + "fc_layer1", 64, ws["dc64"], 0, ws["dc256"], mask=(ws["c256"], 0, 256))
-            # the last product that accumulates into dup128 applies conv2's relu' (up128 = relu(conv2))
-            self._lin_bwd(ws["up128"], 0, 128, cs + "fc_layer0", 256, ws["dc256"], 0, dup128, 0, acc_dx=True, mask=(ws["up128"], 0, 128))
-            # duplicate_up
-            self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0, ws["dup256"], mask=(ws["up256"], 0, 256))
+        # fc_layer2 -> fc_layer1 -> fc_layer0 (+ everything already accumulated in dup128, then conv2's relu') -> conv2 (duplicate_up's
+        # relu') in one launch
+        _lib.check(L.dispu_mlp_chain_grad(rm, 256, 128, 256, _p(dcoarse), 3, _p(P[cs + "fc_layer2/weights"]),
+                                          _p(PT[cs + "fc_layer1/weights"]), _p(PT[cs + "fc_layer0/weights"]), _p(PT[c2 + "/weights"]),
+                                          _p(ws["c64"]), 64, _p(ws["c256"]), 256, _p(ws["up128"]), 128, _p(dup128), 128,
+                                          _p(ws["dup128s"]) if split_skip else None, 128, _p(ws["dc64"]), 64, _p(ws["dc256"]), 256, _p(dup128), 128,
+                                          _p(ws["up256"]), None, None, 256, _p(ws["dup256"]), None, None, 256, self.st),
+                   "mlp_chain_grad[coarse]")
+        # the chain goes on first (d(up256) summed over the four copies -> the 480-wide product below); the head's four weight
+        # gradients are queued on the side streams after it
+        _lib.check(L.dispu_dup_sum_grad(B, N, 256, self.up_ratio, _p(ws["dup256"]), 256, _p(ws["dh256"]), 256, self.st), "dup_sum_grad")
         w1, dw1 = P["generator/upshuffle_0/conv1/weights"], G["generator/upshuffle_0/conv1/weights"]
-        if not self.fused_heads_bwd:
+        with self._fork_group():
+            self._lin_bwd(ws["c64"], 0, 64, cs + "fc_layer2", 3, dcoarse, 0)
+            self._lin_bwd(ws["c256"], 0, 256, cs + "fc_layer1", 64, ws["dc64"], 0)
+            self._lin_bwd(ws["up128"], 0, 128, cs + "fc_layer0", 256, ws["dc256"], 0)
+            self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0)
             self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
-                     dbias=G["generator/upshuffle_0/conv1/biases"], side=True)     # read by Adam only: off the chain like every other dW
-            _lib.check(L.dispu_dup_sum_grad(B, N, 256, self.up_ratio, _p(ws["dup256"]), 256, _p(ws["dh256"]), 256, self.st), "dup_sum_grad")
+                     dbias=G["generator/upshuffle_0/conv1/biases"], side=True, wgrad=True)   # read by Adam only: off the chain like every other dW
         feat, dfeat = ws["feat"], ws["dfeat"]
         self._lin_bwd(feat, 0, 480, None, 256, ws["dh256"], 0, dfeat, 0, bias=False, W=w1, dW=dw1)
 
@@ -1281,55 +1149,43 @@ class Trainer(object):
                 dF, dfoff, F, foff = dfeat, 456, feat, 456
             else:
                 dF, dfoff, F, foff = ws["dprep"][d], 0, ws["prep"][d], 0         # zero-filled in forward(), off the chain
-            if self.fused_dense:
-                # the block's backward on the chain; its weight-gradient partials (a scratch buffer per block) are summed on a side stream
-                need = L.dispu_edge_dense_conv_grad_scratch_floats(rn, C)
-                scr = self._scratch_floats(need, "edge%d" % d)
-                _lib.check(L.dispu_edge_dense_conv_grad_partials(rn, N, C, _p(F, foff), F.stride(0), _p(ws["kidx"][d]), k + 1, 1,
-                                                                 _p(P[sc + "/l0/weights"]), _p(P[sc + "/l0/biases"]), _p(P[sc + "/l1/weights"]),
-                                                                 _p(P[sc + "/l1/biases"]), _p(P[sc + "/l2/weights"]), _p(P[sc + "/l2/biases"]),
-                                                                 _p(dfeat, col), 480, _p(dF, dfoff), dF.stride(0), _p(scr), scr.numel(), self.st),
-                           "edge_dense_conv_grad_partials")
-                # the block's recomputing backward kernel (40 - 80 us) is queued: submit some of the side work deferred so far behind it
-                # (the coarse head's weight gradients, the previous blocks' reductions and prep gradients) -- a few launches per block,
-                # as many as the kernel's duration hides
-                tail = self.tail_on_chain and d == 1 and self.overlap_dw
-                self._flush(n=None if tail else 5)
-                def reduce_partials(sc=sc, scr=scr, C=C, ev=(self._fork_point() if (self.overlap_dw and not tail) else None)):
-                    st_r = self._fork_after(ev)[0] if ev is not None else self.st
-                    _lib.check(L.dispu_edge_dense_conv_grad_reduce(rn, C, _p(scr), scr.numel(), _p(G[sc + "/l0/weights"]), _p(G[sc + "/l0/biases"]),
-                                                                   _p(G[sc + "/l1/weights"]), _p(G[sc + "/l1/biases"]), _p(G[sc + "/l2/weights"]),
-                                                                   _p(G[sc + "/l2/biases"]), st_r), "edge_dense_conv_grad_reduce")
-                if tail:
-                    # the last block of the backward: everything deferred so far is on the side streams by now; this block's own
-                    # reduction (and layer0's weight gradient below) follow their producer on the chain's stream -- Adam waits for
-                    # them either way, and a hop to a side stream and back costs more than the two launches take
-                    reduce_partials()
-                else:
-                    self._defer(reduce_partials)
+            # the block's backward on the chain; its weight-gradient partials (a scratch buffer per block) are summed on a side stream
+            need = L.dispu_edge_dense_conv_grad_scratch_floats(rn, C)
+            scr = self._scratch_floats(need, "edge%d" % d)
+            _lib.check(L.dispu_edge_dense_conv_grad_partials(rn, N, C, _p(F, foff), F.stride(0), _p(ws["kidx"][d]), k + 1, 1,
+                                                             _p(P[sc + "/l0/weights"]), _p(P[sc + "/l0/biases"]), _p(P[sc + "/l1/weights"]),
+                                                             _p(P[sc + "/l1/biases"]), _p(P[sc + "/l2/weights"]), _p(P[sc + "/l2/biases"]),
+                                                             _p(dfeat, col), 480, _p(dF, dfoff), dF.stride(0), _p(scr), scr.numel(), self.st),
+                       "edge_dense_conv_grad_partials")
+            # the block's recomputing backward kernel (40 - 80 us) is queued: submit some of the side work deferred so far behind it
+            # (the coarse head's weight gradients, the previous blocks' reductions and prep gradients) -- a few launches per block,
+            # as many as the kernel's duration hides
+            tail = d == 1 and self.overlap_dw
+            self._flush(n=None if tail else 5)
+            def reduce_partials(sc=sc, scr=scr, C=C, ev=(self._fork_point() if (self.overlap_dw and not tail) else None)):
+                st_r = self._fork_after(ev)[0] if ev is not None else self.st
+                _lib.check(L.dispu_edge_dense_conv_grad_reduce(rn, C, _p(scr), scr.numel(), _p(G[sc + "/l0/weights"]), _p(G[sc + "/l0/biases"]),
+                                                               _p(G[sc + "/l1/weights"]), _p(G[sc + "/l1/biases"]), _p(G[sc + "/l2/weights"]),
+                                                               _p(G[sc + "/l2/biases"]), st_r), "edge_dense_conv_grad_reduce")
+            if tail:
+                # the last block of the backward: everything deferred so far is on the side streams by now; this block's own
+                # reduction (and layer0's weight gradient below) follow their producer on the chain's stream -- Adam waits for
+                # them either way, and a hop to a side stream and back costs more than the two launches take
+                reduce_partials()
             else:
-                Eb, dE = self._edge_buffers(B, N)[0][d], self._edge_buffers(B, N)[1][d]
-                lde = dE.stride(0)
-                # max gradient into the pooled columns [0, width), zeros into the neighbour half of the edge feature behind them
-                _lib.check(L.dispu_max_k_grad_tail(rn, k, width, C, _p(Eb), Eb.stride(0), _p(feat, col), 480, _p(dfeat, col), 480, _p(dE), lde, self.st),
-                           "max_k_grad")
-                self._lin_bwd(Eb, 24, 48 + C, sc + "/l2", 24, dE, 0, dE, 24, acc_dx=True, mask=(Eb, 24, 24))     # columns 24:48 = l1: relu'
-                self._lin_bwd(Eb, 48, 24 + C, sc + "/l1", 24, dE, 24, dE, 48, acc_dx=True, mask=(Eb, 48, 24))    # columns 48:72 = l0: relu'
-                self._lin_bwd(Eb, 72, 2 * C, sc + "/l0", 24, dE, 48, dE, 72, acc_dx=True)
-                _lib.check(L.dispu_edge_feature_grad(rn, N, k, C, _p(dE, 72), lde, _p(ws["kidx"][d]), k + 1, 1, _p(dF, dfoff), dF.stride(0), self.st),
-                           "edge_feature_grad")
+                self._defer(reduce_partials)
             if d > 1:
                 self._act_bias_grad(rn, 48, dF, 0, ws["prep"][d], 0, 1, dF, 0, None)        # prep = relu(.): its mask (dF came from atomics)
                 self._lin_bwd(feat, in_col, 480 - in_col, fe + "layer%d_prep" % d, 48, dF, 0, dfeat, in_col, acc_dx=True)
         # layer0 (no activation, input has no gradient)
-        self._lin_bwd(self._x.view(rn, 3), 0, 3, fe + "layer0", 24, dfeat, 456, None, side=not (self.tail_on_chain and self.fused_dense))
+        self._lin_bwd(self._x.view(rn, 3), 0, 3, fe + "layer0", 24, dfeat, 456, None, side=False)
         self._join()                     # every dW is in the flat gradient buffer from here on (all-reduce, Adam)
 
     # -------------------------------------------------------------------------------------------------- step ----
     def _backward_prep(self, ws):
         L = _lib.tape_lib()
         self._zero(ws["zeroed"])          # the dense blocks' input gradients, the skip branch's d(up128): accumulated with atomics
-        if (self.use_wt or self.fused_heads_bwd) and self._t_desc.numel():       # W^T copies for the dX products
+        if self._t_desc.numel():          # W^T copies for the dX products and the fused head chains
             _lib.check(L.dispu_transpose_batched(self._t_desc.numel() // 3, _p(self._t_desc), _p(self.flat_p), _p(self.flat_pT), self.st),
                        "transpose_batched")
 
@@ -1355,12 +1211,12 @@ class Trainer(object):
 
     def _bucket_point(self, i):
         """every gradient of bucket i has been QUEUED (main stream, or a weight-gradient stream): start its all-reduce behind them,
-        while the backward pass goes on.  Eager steps only: a launch tape / hipGraph replays kernels, not collectives -- there every
+        while the backward pass goes on.  Eager steps only: a launch tape replays kernels, not collectives -- there every
         bucket is launched by all_reduce_grads() after the replay."""
         if not self._ar_armed:                           # backward() on its own never communicates: only train_step() arms the early launch
             return
         ar = self._reducer()
-        if ar is None or _lib.taping() is not None or torch.cuda.is_current_stream_capturing() or ar.launched(i):
+        if ar is None or _lib.taping() is not None or ar.launched(i):
             return
         self._flush()                                    # deferred weight gradients of the bucket go to their streams first
         self._rg_flush()                                 # ... and their pending split reductions
@@ -1515,6 +1371,70 @@ def train_one_epoch(trainer, fetcher, batch_size, train_step_fn="eager", hd_fn=_
     return tuple(vals) + (time.time() - t0, n)
 
 
+def _step_and_batch(trainer, fetcher, opts, train_step_fn):
+    """-> (the step function train_step_fn names, the batch size B): what both epoch loops refuse before they touch anything."""
+    if train_step_fn not in ("eager", "taped"):
+        raise ValueError("train_step_fn must be 'eager' or 'taped'")
+    B = int(getattr(opts, "batch_size", getattr(fetcher, "batch_size", 0)))
+    if B <= 0:
+        raise ValueError("opts.batch_size (or fetcher.batch_size) must be positive")
+    return (trainer.train_step if train_step_fn == "eager" else trainer.train_step_taped), B
+
+
+@contextlib.contextmanager
+def _run_files(trainer, fetcher, opts, log_dir, restore, save_fn, restore_fn, log, rank=0):
+    """The set-up of fit and fit_parallel -> (restore epoch, save_fn, emit): the checkpoint module's functions where none are given;
+    the restore (on EVERY rank) and the fetcher's catch-up; then, on rank 0 alone, <log_dir>/log_train.txt ('w', or 'a' when
+    restoring: open until the block ends) and args.txt.  emit(line) writes a line to the log and hands it to `log` (rank 0; a
+    no-op elsewhere)."""
+    from . import checkpoint
+    save_fn = checkpoint.save_train_state if save_fn is None else save_fn
+    restore_fn = checkpoint.restore_train_state if restore_fn is None else restore_fn
+    if rank == 0:
+        os.makedirs(log_dir, exist_ok=True)
+    restore_epoch = 0
+    if restore:
+        restore_epoch = int(restore_fn(log_dir, trainer))
+        # a fetcher that counts its epochs (DeviceFetcher: permutation stream and draws keyed by the epoch) is brought to the restored
+        # one, so a resumed run sees the batches the uninterrupted run would have seen
+        while getattr(fetcher, "epoch", restore_epoch) < restore_epoch:
+            fetcher.reset()
+    fout = open(os.path.join(log_dir, "log_train.txt"), "a" if restore else "w") if rank == 0 else None
+    try:
+        if rank == 0:
+            with open(os.path.join(log_dir, "args.txt"), "w") as f:
+                f.write(format_args(opts))
+
+        def emit(line):
+            if rank == 0:
+                fout.write(line + "\n")
+                fout.flush()
+                if log is not None:
+                    log(line)
+
+        yield restore_epoch, save_fn, emit
+    finally:
+        if fout is not None:
+            fout.close()
+
+
+def _end_epoch(trainer, fetcher, opts, emit, save, records, best, vals, seconds, steps):
+    """The epoch tail of fit and fit_parallel, given the epoch's five logged values: fetcher.reset(), trainer.epoch += 1, the log
+    line, save(epoch) when epoch % opts.epoch_per_save == 0 and fine_cd is strictly below `best`, the record.  -> the new best."""
+    g, ccd, chd, fcd, fhd = vals
+    fetcher.reset()
+    trainer.epoch += 1
+    epoch = int(trainer.epoch)
+    emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds))
+    saved = None
+    if epoch % int(opts.epoch_per_save) == 0 and fcd < best:
+        best = fcd
+        saved = save(epoch)
+    records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
+                        steps=steps, saved=saved))
+    return best
+
+
 def fit(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", save_fn=None, restore_fn=None, hd_fn=_hausdorff_terms,
         log=None):
     """Model.train (model.py:181-227): epochs restore_epoch .. opts.training_epoch - 1 of int(len / B) - 1 steps each; after every epoch
@@ -1529,44 +1449,14 @@ def fit(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", s
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise NotImplementedError("fit() is single-process: data-parallel training loops are out of scope")
-    from . import checkpoint
-    save_fn = checkpoint.save_train_state if save_fn is None else save_fn
-    restore_fn = checkpoint.restore_train_state if restore_fn is None else restore_fn
-    B = int(getattr(opts, "batch_size", getattr(fetcher, "batch_size", 0)))
-    if B <= 0:
-        raise ValueError("opts.batch_size (or fetcher.batch_size) must be positive")
-    os.makedirs(log_dir, exist_ok=True)
-    restore_epoch = 0
-    if restore:
-        restore_epoch = int(restore_fn(log_dir, trainer))
-        # a fetcher that counts its epochs (DeviceFetcher: permutation stream and draws keyed by the epoch) is brought to the restored
-        # one, so a resumed run sees the batches the uninterrupted run would have seen
-        while getattr(fetcher, "epoch", restore_epoch) < restore_epoch:
-            fetcher.reset()
+    _, B = _step_and_batch(trainer, fetcher, opts, train_step_fn)
     records, best = [], math.inf
-    with open(os.path.join(log_dir, "log_train.txt"), "a" if restore else "w") as fout:
-        with open(os.path.join(log_dir, "args.txt"), "w") as f:
-            f.write(format_args(opts))
-
-        def emit(line):
-            fout.write(line + "\n")
-            fout.flush()
-            if log is not None:
-                log(line)
-
+    with _run_files(trainer, fetcher, opts, log_dir, restore, save_fn, restore_fn, log) as (restore_epoch, save_fn, emit):
         emit("train_dataset: %d" % len(fetcher))
         for _ in range(restore_epoch, int(opts.training_epoch)):
-            g, ccd, chd, fcd, fhd, seconds, steps = train_one_epoch(trainer, fetcher, B, train_step_fn, hd_fn)
-            fetcher.reset()
-            trainer.epoch += 1
-            epoch = int(trainer.epoch)
-            emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds))
-            saved = None
-            if epoch % int(opts.epoch_per_save) == 0 and fcd < best:
-                best = fcd
-                saved = save_fn(log_dir, trainer, epoch)
-            records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
-                                steps=steps, saved=saved))
+            *vals, seconds, steps = train_one_epoch(trainer, fetcher, B, train_step_fn, hd_fn)
+            best = _end_epoch(trainer, fetcher, opts, emit, lambda epoch: save_fn(log_dir, trainer, epoch), records, best,
+                              vals, seconds, steps)
     return records
 
 
@@ -1651,14 +1541,10 @@ def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="
     (the host Fetcher has none); a trainer whose process group is not `group`."""
     import time
     import torch.distributed as dist
-    if train_step_fn not in ("eager", "taped"):
-        raise ValueError("train_step_fn must be 'eager' or 'taped'")
+    step, B = _step_and_batch(trainer, fetcher, opts, train_step_fn)
     active = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if active else 1
     rank = dist.get_rank(group) if active else 0
-    B = int(getattr(opts, "batch_size", getattr(fetcher, "batch_size", 0)))
-    if B <= 0:
-        raise ValueError("opts.batch_size (or fetcher.batch_size) must be positive")
     if B % world:
         raise ValueError("the global batch of %d patches does not divide over %d ranks" % (B, world))
     if world > 1:
@@ -1668,33 +1554,20 @@ def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="
         norm = lambda g: None if g is dist.group.WORLD else g          # None names the default group
         if norm(getattr(trainer, "pg", None)) is not norm(group):
             raise ValueError("the trainer all-reduces over another process group than the loop's")
-    from . import checkpoint
-    save_fn = checkpoint.save_train_state if save_fn is None else save_fn
-    restore_fn = checkpoint.restore_train_state if restore_fn is None else restore_fn
     meter_fn = _step_meters_fn if meter_fn is None else meter_fn
-    step = trainer.train_step if train_step_fn == "eager" else trainer.train_step_taped
-    if rank == 0:
-        os.makedirs(log_dir, exist_ok=True)
-    restore_epoch = 0
-    if restore:
-        restore_epoch = int(restore_fn(log_dir, trainer))
-        while getattr(fetcher, "epoch", restore_epoch) < restore_epoch:
-            fetcher.reset()
-    n = max(steps_per_epoch(len(fetcher), B), 0)
-    table = torch.zeros(n * 5 + 2, dtype=torch.float32, device=getattr(trainer, "device", "cpu"))
     records, best = [], math.inf
-    fout = open(os.path.join(log_dir, "log_train.txt"), "a" if restore else "w") if rank == 0 else None
-    try:
-        if rank == 0:
-            with open(os.path.join(log_dir, "args.txt"), "w") as f:
-                f.write(format_args(opts))
+    with _run_files(trainer, fetcher, opts, log_dir, restore, save_fn, restore_fn, log, rank) as (restore_epoch, save_fn, emit):
+        n = max(steps_per_epoch(len(fetcher), B), 0)
+        table = torch.zeros(n * 5 + 2, dtype=torch.float32, device=getattr(trainer, "device", "cpu"))
 
-        def emit(line):
-            if rank == 0:
-                fout.write(line + "\n")
-                fout.flush()
-                if log is not None:
-                    log(line)
+        def save(epoch):
+            saved = save_fn(log_dir, trainer, epoch) if rank == 0 else None
+            if world > 1:
+                box = [saved]
+                dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+                saved = box[0]
+                dist.barrier(group=group)              # no rank runs ahead of a checkpoint another process may read
+            return saved
 
         emit("train_dataset: %d" % len(fetcher))
         for _ in range(restore_epoch, int(opts.training_epoch)):
@@ -1709,25 +1582,6 @@ def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="
             if bad:
                 raise RuntimeError("epoch %d: the batch sampler reported a failure on rank(s) %s (rank, candidate rounds exhausted, "
                                    "permutation entry out of range)" % (int(trainer.epoch), bad))
-            g, ccd, chd, fcd, fhd = reduce_meter_tables(every[:, :n * 5], n)
-            seconds = time.time() - t0
-            fetcher.reset()
-            trainer.epoch += 1
-            epoch = int(trainer.epoch)
-            emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds))
-            saved = None
-            if epoch % int(opts.epoch_per_save) == 0 and fcd < best:
-                best = fcd
-                if rank == 0:
-                    saved = save_fn(log_dir, trainer, epoch)
-                if world > 1:
-                    box = [saved]
-                    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-                    saved = box[0]
-                    dist.barrier(group=group)              # no rank runs ahead of a checkpoint another process may read
-            records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
-                                steps=n, saved=saved))
-    finally:
-        if fout is not None:
-            fout.close()
+            vals = reduce_meter_tables(every[:, :n * 5], n)
+            best = _end_epoch(trainer, fetcher, opts, emit, save, records, best, vals, time.time() - t0, n)
     return records

@@ -15,8 +15,7 @@ def wall(fn, reps=20, warm=5):
     torch.cuda.synchronize(); t = time.perf_counter()
     for _ in range(reps): fn()
     torch.cuda.synchronize(); return (time.perf_counter() - t) / reps
-for name, kv in [("default", {}), ("prep_on_side", {"prep_on_side": True}), ("dw_streams=1", {"dw_streams": 1}), ("dw_streams=3", {"dw_streams": 3}),
-                 ("bf16_storage off", {"bf16_storage": False}), ("tail_on_chain off", {"tail_on_chain": False}), ("default again", {})]:
+for name, kv in [("default", {}), ("dw_streams=1", {"dw_streams": 1}), ("dw_streams=3", {"dw_streams": 3}), ("default again", {})]:
     tr = None
     tr = Trainer(params=P, device=dev, dtype="bf16")
     for k, v in kv.items():
