@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from ._util import f32, req
 from .generator import BN_EPS, DENSE_BLOCKS, GROWTH, K_NEIGH, _Opts, gen_grid
+from .schedule import StepSchedule
 
 BN_DECAY = 0.95      # DisPU/generator.py:39 bn_decay
 BN = "refine/PointShuffle/weight_net/wconv0/bn/"
@@ -47,22 +48,6 @@ class TrainOpts(_Opts):
     uniform_w = 10.0      # DisPU/configs.py:42
 
 
-# Streams are shared by every Trainer of a process (per device): HIP maps streams onto a few hardware queues, and a process that
-# builds Trainer after Trainer (bench.py's side table, the test suite) would otherwise keep adding streams to them.  Trainers of one
-# process run one after the other on the host thread, so sharing is safe: events order the work.  (Which of torch's pooled streams
-# the step gets does not matter: skipping 0 - 7 of them first leaves the step at 1.945 ms.)
-_STREAM_POOL = {}
-
-
-def _pool_stream(device, kind, i):
-    key = (torch.device(device).index or 0, kind, i)
-    st = _STREAM_POOL.get(key)
-    if st is None:
-        with torch.cuda.device(device):
-            st = _STREAM_POOL[key] = torch.cuda.Stream(device=device)
-    return st
-
-
 def weight_fine(epoch):
     """model.py:52-54 piecewise_constant(epoch, [10, 20, 30], [0.01, 0.1, 0.5, 1.0])."""
     return 0.01 if epoch <= 10 else 0.1 if epoch <= 20 else 0.5 if epoch <= 30 else 1.0
@@ -79,6 +64,10 @@ def learning_rate(opts, epoch):
 def _p(t, off=0):
     """Device pointer of element `off` of t's storage (in t's own element size: a bf16-stored activation advances 2 bytes per column)."""
     return _lib.C.c_void_p(t.data_ptr() + t.element_size() * off) if t is not None else _lib.C.c_void_p(0)
+
+
+def _sched_attr(name):                                   # a Trainer switch that lives on its StepSchedule
+    return property(lambda self: getattr(self.sched, name), lambda self, v: setattr(self.sched, name, v))
 
 
 class Trainer(object):
@@ -123,46 +112,30 @@ class Trainer(object):
 
         # ---- switches: each default is the measured best; the other value is the reference side of a test (profiles/EXPERIMENTS.md
         # lists the switches that were removed once measurements had settled them)
-        # weight-gradient products (dW = X^T dZ) are off the backward chain: only Adam reads them.  They run on a second
+        # (overlap_dw, dw_streams, group_reduce and defer_side live on the step's schedule, schedule.StepSchedule: the properties below)
+        # overlap_dw: weight-gradient products (dW = X^T dZ) are off the backward chain: only Adam reads them.  They run on a second
         # HIP stream next to the dX products that ARE the chain (both read dZ; at 8 patches neither fills 256 CUs alone).
-        self.overlap_dw = True
-        self.dw_streams = 2                   # side streams the weight-gradient products are spread over (round-robin)
+        # dw_streams: side streams the weight-gradient products are spread over (round-robin)
+        # group_reduce: the split reductions of the weight-gradient products are not launched one by one: every product describes the
+        # reduction it left undone (dispu_tn_defer) and a stream's descriptors run as ONE launch when that stream is joined (join,
+        # _bucket_point): ~20 launches of 4 - 25 us per step become 3.  False: every product reduces itself (bit-identical)
+        # defer_side: side work is submitted behind the chain's kernels (set by forward() from the batch size, see StepSchedule)
+        self.sched = StepSchedule(self.device, overlap_dw=True, dw_streams=2, defer_side=True, group_reduce=True)
         # non-local cell: flash-style attention forward (+ per-row log-sum-exp) and a recomputing backward (csrc/attention_train.hip);
         # False = round 3's path through a materialised [B, M, M] probability tensor (the parity twin)
         self.flash_attn = True
-        # the split reductions of the weight-gradient products are not launched one by one: every product describes the reduction it left
-        # undone (dispu_tn_defer) and a stream's descriptors run as ONE launch when that stream is joined (_join, _bucket_point): ~20
-        # launches of 4 - 25 us per step become 3.  False: every product reduces itself (bit-identical)
-        self.group_reduce = True
         # the local cell's backward (feature x weight gradient, conv1's dX, conv0's gather) as ONE recomputing launch (csrc/ps_local_bwd.hip,
         # fp32 storage only): h1 / dz0 / wv / the inverted neighbour graph never exist in HBM.  Correct and tested, but 40 us slower per 8-patch
         # step than the five-launch path (1.595 vs 1.555 ms): OFF by default
         self.fused_local_bwd = False
         self.bf16_stream = True    # dtype="bf16": the large dense products on the streaming bf16 kernel (csrc/linear_bf16_stream.hip) where its shape rules hold
         self.bf16_min_macs = 1.5e9            # dtype="bf16": products below this many multiply-adds stay on the fp32 kernel (_use_bf16)
-
-        # ---- scheduling state of the step in flight
-        self.st = None                        # stream pointer the launches go to (set by forward() / zero_grad(), swapped inside _branch)
-        self._cur = "main"                    # ... and that stream's scratch key
-        self._aux = []                        # branch i -> (auxiliary stream, fork event, completion event)
-        self._sides = []                      # the weight-gradient streams (_side_next)
-        self._side_rr = -1
-        self._side_busy = []
-        self._group = None                    # (event, side streams that already wait for it) inside _fork_group()
-        # Side work (weight-gradient products, the non-local / skip branches) is QUEUED ON THE HOST AFTER the chain's kernels: every
-        # launch costs ~10 us of Python / ctypes, and a chain kernel that is submitted behind a dozen side launches leaves the GPU's
-        # main queue idle for that long (round 4, profiles/r04_a_train_timeline.txt: 145 us before the fused local cell, 137 us before
-        # its backward).  Side work records its fork event where it belongs and is submitted later, at points where the main queue
-        # holds enough work (Trainer._flush).  On up to 16 patches per step (set by forward()): at 32 the chip is saturated by the
-        # chain's own kernels, side work submitted later only lengthens the tail (4.58 -> 4.63 ms)
-        self.defer_side = True
-        self._deferred = []
-        self._pending = set()                 # branches whose submission is still in _deferred
-        self._rg = {}                         # stream pointer -> [host descriptor array, entries pending, stream c_void_p]
-        self._rg_dev = {}                     # descriptor table bytes -> device copy (content-addressed: tapes keep pointing at theirs)
         self.P = None
         if params is not None:
             self.load_params(params)
+
+    overlap_dw, dw_streams, group_reduce, defer_side = (_sched_attr(n) for n in ("overlap_dw", "dw_streams", "group_reduce", "defer_side"))
+    st = property(lambda self: self.sched.st)            # the stream pointer the launches go to
 
     # --------------------------------------------------------------------------------------------- parameters ----
     def _invalidate_recordings(self):
@@ -171,12 +144,12 @@ class Trainer(object):
         train_step_taped records afresh instead of replaying launches onto freed memory.  The bf16 images of the weights
         (_stream) are keyed by the weight's address: dropped with the tapes that point at them."""
         self._tapes.clear()
-        if self._packs:
+        # the schedule's device copies of reduction tables: only tapes (dropped above) and the step being recorded point at them; a moved
+        # scratch buffer makes new table contents anyway
+        if self._packs or self.sched.tables:
             torch.cuda.synchronize(self.device)
-            self._packs.clear()
-        if self._rg_dev:                                 # device copies of reduction tables: only tapes (dropped above) and the step being
-            torch.cuda.synchronize(self.device)          # recorded point at them; a moved scratch buffer makes new table contents anyway
-            self._rg_dev.clear()
+        self._packs.clear()
+        self.sched.drop_tables()
 
     def load_params(self, params):
         dev = self.device
@@ -285,7 +258,7 @@ class Trainer(object):
     def _scratch_floats(self, n, key=None):
         """scratch of the launches queued on ONE stream (they run in order, so they can share it): a dW stream's (key "dw<i>"), or the
         current stream's (main or a branch)."""
-        key = key if key else self._cur
+        key = key if key else self.sched.key
         cur = self._scratch.get(key)
         if cur is None or cur.numel() < n:
             if cur is not None:
@@ -294,184 +267,12 @@ class Trainer(object):
             cur = self._scratch[key] = torch.empty(max(int(n), 1 << 20), dtype=torch.float32, device=self.device)
         return cur
 
-    # ---- side stream(s) for the weight-gradient products (Trainer.dw_streams of them, used round-robin; each has its own scratch)
-    def _side_next(self):
-        if not self._sides:
-            n = max(1, int(self.dw_streams))
-            self._sides = [_pool_stream(self.device, "dw", j) for j in range(n)]
-            self._join_evs = [torch.cuda.Event() for _ in range(n)]
-            self._side_busy = [False] * n
-        self._side_rr = (self._side_rr + 1) % len(self._sides)
-        return self._side_rr
-
-    def _defer(self, fn, prio=1):
-        """run the side-stream submission `fn` now, or at a later _flush() when deferral is on (only while side streams are in use).
-        prio 0: branches the chain will wait for (non-local / skip / recompute); 1: weight gradients, read by Adam only."""
-        if self.defer_side and self.overlap_dw:
-            self._deferred.append((prio, fn))
-        else:
-            fn()
-
-    def _flush(self, n=None, prio=1):
-        """submit the deferred side launches of priority <= prio, in their order: all of them, or the first n."""
-        i = 0
-        while i < len(self._deferred) and (n is None or n > 0):
-            if self._deferred[i][0] <= prio:
-                self._deferred.pop(i)[1]()                # (may append: a branch defers its own weight gradients)
-                if n is not None:
-                    n -= 1
-            else:
-                i += 1
-        if not any(p == 0 for p, _ in self._deferred):
-            self._pending.clear()
-
-    def _defer_branch(self, i, body, after=None):
-        """`with self._branch(i, after): body()` -- submitted now, or at the next _flush() / _merge(i) when deferral is on.  The branch
-        is ordered after `after`, or after THIS point of the current stream (the event is recorded now, whenever the body is submitted)."""
-        if not (self.defer_side and self.overlap_dw):
-            with self._branch(i, after):
-                body()
-            return
-        ev = after if after is not None else self._fork_point()
-
-        def run():
-            with self._branch(i, ev):
-                body()
-        self._pending.add(i)
-        self._deferred.append((0, run))
-
-    # ---- stream / event operations (recorded on the launch tape as raw HIP calls when one is being taken, see train_step_taped)
-    def _rec(self, ev, stream):
-        ev.record(stream)
-        t = _lib.taping()
-        if t is not None:
-            t.keep += [ev, stream]
-            t.calls.append((_lib.lib().dispu_event_record, (ctypes.c_void_p(ev.cuda_event), ctypes.c_void_p(stream.cuda_stream)), "event_record"))
-
-    def _wait(self, stream, ev):
-        stream.wait_event(ev)
-        t = _lib.taping()
-        if t is not None:
-            t.keep += [ev, stream]
-            t.calls.append((_lib.lib().dispu_stream_wait_event, (ctypes.c_void_p(stream.cuda_stream), ctypes.c_void_p(ev.cuda_event)),
-                            "stream_wait_event"))
-
     def _zero(self, t):
         """t.zero_() on the stream launches currently go to, as a memset through the library (a plain C call: tape-able, and cheaper
         than the torch op)."""
         L = _lib.tape_lib()
         st = self.st if self.st is not None else _lib.stream_ptr(self.device)
         _lib.check(L.dispu_memset_async(_lib.C.c_void_p(t.data_ptr()), 0, t.numel() * t.element_size(), st), "memset")
-
-    @contextlib.contextmanager
-    def _fork_group(self):
-        """Several dW products that all depend on the SAME point of the current stream (the four weight gradients of a fused head
-        chain): one event, one wait per side stream."""
-        if not self.overlap_dw:
-            yield
-            return
-        self._side_next()                                  # make sure the side streams exist
-        self._side_rr -= 1
-        self._group = (self._fork_point(), set())
-        try:
-            yield
-        finally:
-            self._group = None
-
-    def _fork_point(self):
-        """an event at the current position of the main stream, for a dW product queued later (see _lin_bwd)."""
-        ev = torch.cuda.Event()
-        self._rec(ev, torch.cuda.current_stream(self.device))
-        return ev
-
-    def _fork_after(self, ev):
-        i = self._side_next()
-        self._wait(self._sides[i], ev)
-        self._side_busy[i] = True
-        return ctypes.c_void_p(self._sides[i].cuda_stream), "dw%d" % i
-
-    # ---- grouped split reductions (dispu_tn_defer / dispu_tn_reduce_grouped) ----
-    _RG_MAX = 64
-
-    def _rg_slot(self, st, out_ptr, bias_ptr):
-        """-> (address of the next free descriptor of stream `st`, its group, out pointer, bias pointer).  A product whose destination
-        another pending reduction also accumulates into flushes that group first (two descriptors of one launch must not alias)."""
-        for g in self._rg.values():
-            if g[1] and any(o == out_ptr or (bias_ptr and b == bias_ptr) for o, b in g[3]):
-                self._rg_flush_group(g)
-        g = self._rg.get(st.value)
-        if g is None:
-            g = self._rg[st.value] = [(_lib.TnReduceDesc * self._RG_MAX)(), 0, ctypes.c_void_p(st.value), []]
-        if g[1] >= self._RG_MAX:
-            self._rg_flush_group(g)
-        return (ctypes.c_void_p(ctypes.addressof(g[0]) + g[1] * ctypes.sizeof(_lib.TnReduceDesc)), g, out_ptr, bias_ptr)
-
-    def _rg_commit(self, slot):
-        _, g, out_ptr, bias_ptr = slot
-        if g[0][g[1]].splits > 0:                        # the product left a reduction behind (0: it wrote its result itself)
-            g[1] += 1
-            g[3].append((out_ptr, bias_ptr))
-
-    def _rg_flush_group(self, g):
-        n = g[1]
-        if not n:
-            return
-        raw = ctypes.string_at(ctypes.addressof(g[0]), n * ctypes.sizeof(_lib.TnReduceDesc))
-        dev = self._rg_dev.get(raw)
-        if dev is None:                                  # first step with this table (steady state: the same pointers every step)
-            dev = self._rg_dev[raw] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        _lib.check(_lib.tape_lib().dispu_tn_reduce_grouped(n, ctypes.c_void_p(ctypes.addressof(g[0])), ctypes.c_void_p(dev.data_ptr()), g[2]),
-                   "dispu_tn_reduce_grouped")
-        g[1] = 0
-        g[3] = []
-
-    def _rg_flush(self):
-        for g in self._rg.values():
-            self._rg_flush_group(g)
-
-    def _join(self):
-        """the current stream waits for every dW product queued so far (before a buffer they read is overwritten, before Adam)."""
-        self._flush()
-        self._rg_flush()                                 # each stream's pending split reductions: one launch per stream, behind its products
-        for i, busy in enumerate(self._side_busy if self._sides else []):
-            if busy:
-                self._rec(self._join_evs[i], self._sides[i])
-                self._wait(torch.cuda.current_stream(self.device), self._join_evs[i])
-                self._side_busy[i] = False
-
-    @contextlib.contextmanager
-    def _branch(self, i, after=None):
-        """Launches inside run on auxiliary stream i, after everything queued on the current stream so far (or after the event
-        `after`, recorded earlier on it); `_merge(i)` makes
-        the current stream wait for them.  At 8 patches per GPU a chain of 10 us kernels leaves most of the 256 CUs idle:
-        independent sub-graphs (non-local cell | skip + local cell; the two Chamfer terms) run side by side."""
-        if not self.overlap_dw:
-            yield
-            return
-        while len(self._aux) <= i:
-            self._aux.append((_pool_stream(self.device, "aux", len(self._aux)), torch.cuda.Event(), torch.cuda.Event()))
-        aux, ev_fork, ev_done = self._aux[i]
-        if after is None:
-            after = ev_fork
-            self._rec(after, torch.cuda.current_stream(self.device))
-        self._wait(aux, after)
-        old_st, old_cur = self.st, self._cur
-        with torch.cuda.stream(aux):
-            self.st, self._cur = ctypes.c_void_p(aux.cuda_stream), "aux%d" % i
-            try:
-                yield
-            finally:
-                self.st, self._cur = old_st, old_cur
-                # recorded HERE, not in _merge: streams share hardware queues (GPU_MAX_HW_QUEUES = 4), and a marker queued at merge
-                # time lands behind whatever the other streams of that queue were given in between (measured: the local cell's
-                # backward started 0.33 ms late, behind dW products it does not depend on)
-                self._rec(ev_done, aux)
-
-    def _merge(self, i):
-        if i in self._pending:
-            self._flush(prio=0)                          # a branch whose submission is still deferred cannot be waited for
-        if self.overlap_dw and i < len(self._aux):
-            self._wait(torch.cuda.current_stream(self.device), self._aux[i][2])
 
     # ----------------------------------------------------------------------------------------------- helpers ----
     def _dl(self, batch, M, K, N, *rest):
@@ -540,9 +341,9 @@ class Trainer(object):
 
     def _tn(self, batch, M, K, N, X, xoff, ldx, sx, Zt, zoff, ldz, sz, out, ooff, ldo, so, accumulate, dbias=None, side=False, after=None,
             wgrad=False):
-        """out (+)= X^T . Zt.  side=True: on a side stream (the caller guarantees nothing overwrites X / Zt before _join), ordered after
-        `after` / the enclosing _fork_group's event / this point of the current stream; the launch itself may be deferred (_defer).
-        wgrad=True: `out` is a weight gradient -- nothing reads it before _join(), so its split reduction may wait for the stream's
+        """out (+)= X^T . Zt.  side=True: on a side stream (the caller guarantees nothing overwrites X / Zt before join), ordered after
+        `after` (an event or a StepSchedule.fork_group()) / this point of the current stream; the launch itself may be deferred (StepSchedule.defer).
+        wgrad=True: `out` is a weight gradient -- nothing reads it before join(), so its split reduction may wait for the stream's
         grouped launch (Trainer.group_reduce)."""
         L = _lib.tape_lib()
         side = side and self.overlap_dw
@@ -557,19 +358,16 @@ class Trainer(object):
             need = max(need, tn_stream)
 
         def launch(st, key):
-            slot = None
-            if self.group_reduce and wgrad and batch == 1 and (key is not None or self._cur == "main"):
-                # a scratch buffer of this product's own (it must survive until the grouped reduction) and a descriptor slot of its stream
-                key = ("tn", out.data_ptr() + 4 * ooff, K, N)
-                slot = self._rg_slot(st, out.data_ptr() + 4 * ooff, dbias.data_ptr() if dbias is not None else 0)
-            sc = self._scratch_floats(need, key)
-            if slot is not None:
-                _lib.check(L.dispu_tn_defer(slot[0]), "dispu_tn_defer")
+            if not (self.group_reduce and wgrad and batch == 1 and (key is not None or self.sched.key == "main")):
+                return launch_product(st, self._scratch_floats(need, key))
+            # a descriptor slot of its stream and a scratch buffer of this product's own (it must survive until the grouped reduction)
+            slot, grp = self.sched.reduce_slot(st, out.data_ptr() + 4 * ooff, dbias.data_ptr() if dbias is not None else 0)
+            sc = self._scratch_floats(need, ("tn", out.data_ptr() + 4 * ooff, K, N))
+            _lib.check(L.dispu_tn_defer(slot), "dispu_tn_defer")
             try:
                 launch_product(st, sc)
             finally:
-                if slot is not None:
-                    self._rg_commit(slot)
+                grp.commit()
 
         def launch_product(st, sc):
             if tn_stream:
@@ -588,23 +386,8 @@ class Trainer(object):
         if not side:
             launch(self.st, None)
             return
-        grp = self._group
-        ev = after if after is not None else (None if grp is not None else self._fork_point())
-
-        def submit():
-            if ev is not None:
-                st, key = self._fork_after(ev)
-            else:                                          # member of a _fork_group: one wait per side stream for the group's event
-                i = self._side_next()
-                gev, waited = grp
-                if i not in waited:
-                    self._wait(self._sides[i], gev)
-                    waited.add(i)
-                self._side_busy[i] = True
-                st, key = ctypes.c_void_p(self._sides[i].cuda_stream), "dw%d" % i
-            launch(st, key)
-
-        self._defer(submit)
+        ev = after if after is not None else self.sched.fork_point()
+        self.sched.defer(lambda: launch(*self.sched.side_stream(ev)))
 
     def _act_bias_grad(self, M, N, dY, dyoff, Y, yoff, act, dZ, dzoff, dbias):
         L = _lib.tape_lib()
@@ -639,9 +422,9 @@ class Trainer(object):
                       r1, ldr, 0, None, 0, 0, self.st), "dispu_linear(dX)")
 
     def _lin_bwd(self, X, xoff, K, wname, N, dY, dyoff, dX=None, dxoff=0, acc_dx=False, M=None, bias=True, W=None, dW=None, woff=0,
-                 db=None, side=True):
+                 db=None, side=True, after=None):
         """backward of _lin given dZ = dY[:, dyoff:dyoff+N] ALREADY multiplied by the layer's own relu' (its producer did that):
-        db += colsum dZ and dW += X^T dZ on the second stream, dX[:, dxoff:dxoff+K] (+)= dZ . W^T (see _dx)."""
+        db += colsum dZ and dW += X^T dZ on the second stream (ordered after `after`, see _tn), dX[:, dxoff:dxoff+K] (+)= dZ . W^T (see _dx)."""
         M = X.shape[0] if M is None else M
         W = self.P[wname + "/weights"] if W is None else W
         dW = self.G[wname + "/weights"] if dW is None else dW
@@ -649,7 +432,7 @@ class Trainer(object):
             db = self.G[wname + "/biases"]
         # the dX product IS the backward chain: it is queued first; the dW product (read by Adam only) follows on the second stream,
         # ordered after dZ by an event recorded BEFORE the dX launch (dX never writes what the dW product reads)
-        ev = self._fork_point() if (self.overlap_dw and dX is not None) else None
+        ev = self.sched.fork_point() if (self.overlap_dw and dX is not None) else after
         if dX is not None:
             WT = self.PT.get(wname + "/weights") if (wname is not None and woff == 0 and K == W.shape[0]) else None
             self._dx(M, N, K, dY, dyoff, W, woff, dX, dxoff, acc_dx, WT)
@@ -676,7 +459,7 @@ class Trainer(object):
                          % (self.up_ratio, N))
         ws = self._workspace(B, N)
         L = _lib.tape_lib()
-        self.st = _lib.stream_ptr(x.device)
+        self.sched.st = _lib.stream_ptr(x.device)
         self.defer_side = rm <= 16 * 1024                # see __init__
         self._shape = (B, N)
         self._x = x
@@ -749,7 +532,7 @@ class Trainer(object):
         nb = L.dispu_ps_wnet_scratch_bytes(rm)
         if self._bn_scratch is None or self._bn_scratch.numel() * 8 < nb:
             self._bn_scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=self.device)
-        with self._branch(2):
+        with self.sched.branch(2):
             _lib.check(L.dispu_knn_xyz(B, M, M, k, _p(coarse), _p(coarse), _p(ws["psidx"]), None, _lib.ARITH_PLAIN, self.st), "knn_xyz")
             _lib.check(L.dispu_ps_wnet_bn_stats(rm, M, k, 16, _p(ws["psidx"]), _p(coarse), _p(ww), _p(bw), _p(P[BN + "gamma"]), _p(P[BN + "beta"]),
                                                 BN_EPS, BN_DECAY, _p(ws["bn_stats"]), _p(ws["bn_scale"]), _p(ws["bn_shift"]),
@@ -784,15 +567,15 @@ class Trainer(object):
             # behind the branch's own kernels
             self._backward_prep(ws)
 
-        self._defer_branch(0, nl_branch)
-        self._merge(2)
+        self.sched.defer_branch(0, nl_branch)
+        self.sched.merge(2)
 
         # skip (a second branch next to the local cell): gather-max straight from xyz / up128, then 134 -> 256
         def skip_branch():
             _lib.check(L.dispu_ps_skip_max(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(up128), 128, _p(ws["gmax"]), 144, self.st), "skip_max")
             self._lin(ws["gmax"], 0, 134, ps + "skip", 1, ws["skip"], 0, 256)
 
-        self._defer_branch(1, skip_branch)
+        self.sched.defer_branch(1, skip_branch)
         # the fused cell (conv1, weight_net with the folded BatchNorm, feature x weight)
         _lib.check(L.dispu_ps_local(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(ws["gm"]), 128, _p(ws["am"]),
                                     _p(P[ps + "conv1/weights"]), _p(P[ps + "conv1/biases"]), _p(ww), _p(bw), _p(ws["bn_scale"]),
@@ -813,8 +596,8 @@ class Trainer(object):
                        "dispu_linear_splitk_finish")
         else:
             self._lin(ws["hp"], 0, 2048, ps + "after_conv", 1, ws["aft"], 0, 256)
-        self._merge(0)
-        self._merge(1)
+        self.sched.merge(0)
+        self.sched.merge(1)
         _lib.check(L.dispu_add3(rm * 256, _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), _p(ws["sum"]), self.st), "add3")
         # aggregation -> fine regressor (fc_layer0, fc_layer1, fc_layer2) -> coarse + sigmoid(.) - 0.5 in one launch
         fs = "refine/fine_coordinate_regressor/"
@@ -933,8 +716,8 @@ class Trainer(object):
             tab = self._uniform_workspace(ws, B, N)             # refuses a patch size the term cannot take, before any launch
         # side work is submitted behind the fine term's launches (the chain): the pair tensors of the local cell's backward (needed much
         # later) and the coarse term
-        self._defer_branch(2, self._recompute_pair_tensors)    # off the chain: needed by the local cell's backward only
-        with self._branch(0):                                   # the coarse term next to the fine term and the repulsion term
+        self.sched.defer_branch(2, self._recompute_pair_tensors)    # off the chain: needed by the local cell's backward only
+        with self.sched.branch(0):                                   # the coarse term next to the fine term and the repulsion term
             self._chamfer(ws["coarse"], gt, radius, 1000.0, ws["dcoarse"], 0)
         # fine term: nn_distance, then value + gradient (which zero-fills dfine); the repulsion term's ball query runs next to it and
         # adds its gradient once the Chamfer gradient is in place
@@ -943,7 +726,7 @@ class Trainer(object):
         rep = None
         fine = ws["fine"]
         if self.opts.use_repulse or uniform:
-            with self._branch(1):
+            with self.sched.branch(1):
                 if self.opts.use_repulse:
                     _lib.check(L.dispu_query_ball(B, M, M, _p(ws["r07"]), 20, _p(fine), _p(fine), _p(ws["ball"]), _p(ws["ball_cnt"]),
                                                   _lib.ARITH_CONTRACT, self.st), "query_ball")   # as loss_utils.get_repulsion_loss
@@ -952,7 +735,7 @@ class Trainer(object):
                                               _lib.ARITH_CONTRACT, self.st), "fps")              # as loss_utils.get_uniform_loss
         self._chamfer(ws["fine"], gt, radius, 1000.0 * wf, ws["dfine"], 1)
         if self.opts.use_repulse or uniform:
-            self._merge(1)
+            self.sched.merge(1)
         if self.opts.use_repulse:
             _lib.check(L.dispu_repulsion_loss_grad(B * M, M, 20, 0.001, self.opts.repulsion_w / (B * M * 4.0), _p(fine), _p(ws["ball"]),
                                                    _p(ws["rep"]), _p(ws["dfine"]), self.st), "repulsion_loss_grad")
@@ -961,7 +744,7 @@ class Trainer(object):
             _lib.check(L.dispu_uniform_loss_grad(B, M, tab.npoint, tab.nlevels, ctypes.addressof(tab.ns), ctypes.addressof(tab.levels), _p(fine),
                                                  _p(ws["useeds"]), _p(ws["upart"]), _p(ws["dfine"]), None, None, _lib.ARITH_CONTRACT, self.st),
                        "uniform_loss_grad")
-        self._merge(0)
+        self.sched.merge(0)
         out = ws["loss_vals"]
         if uniform:
             _lib.check(L.dispu_pu_loss_finalize_u(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
@@ -971,7 +754,7 @@ class Trainer(object):
             _lib.check(L.dispu_pu_loss_finalize(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
                                                 _p(out, 2), self.st), "pu_loss_finalize")
         terms = self._terms(out, wf, uniform)
-        self._flush(prio=0)                                     # the recompute branch: submitted behind the loss's own launches
+        self.sched.flush(prio=0)                                     # the recompute branch: submitted behind the loss's own launches
         return terms
 
     @staticmethod
@@ -1003,7 +786,7 @@ class Trainer(object):
             self._zero(ws["zeroed"])
         self._fresh = False
         if not self._stash_ready:                       # backward() without loss_backward(): rebuild the pair tensors here
-            with self._branch(2):
+            with self.sched.branch(2):
                 self._recompute_pair_tensors()
 
         # fine = coarse + sigmoid(z) - 0.5
@@ -1018,16 +801,16 @@ class Trainer(object):
                                           _p(ws["df64"]), 64, _p(ws["df256"]), 256, _p(ws["dagg"]), 256,
                                           _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), 256, _p(ws["daft"]), _p(ws["dskip"]), _p(ws["dnl"]), 256,
                                           self.st), "mlp_chain_grad[fine]")
-        with self._fork_group():
-            self._lin_bwd(ws["f64"], 0, 64, fs + "fc_layer2", 3, ws["dz"], 0)
-            self._lin_bwd(ws["f256"], 0, 256, fs + "fc_layer1", 64, ws["df64"], 0)
-            self._lin_bwd(ws["agg"], 0, 256, fs + "fc_layer0", 256, ws["df256"], 0)
-            self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0)
+        grp = self.sched.fork_group()
+        self._lin_bwd(ws["f64"], 0, 64, fs + "fc_layer2", 3, ws["dz"], 0, after=grp)
+        self._lin_bwd(ws["f256"], 0, 256, fs + "fc_layer1", 64, ws["df64"], 0, after=grp)
+        self._lin_bwd(ws["agg"], 0, 256, fs + "fc_layer0", 256, ws["df256"], 0, after=grp)
+        self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0, after=grp)
 
         # local cell first: the host needs ~0.1 ms to queue the two branches below, the chain must not sit idle meanwhile; the
         # branches themselves only need the head chain's dskip / dnl, so they are ordered after THIS point of the stream, not after the
         # product
-        ev_br = self._fork_point() if self.overlap_dw else None
+        ev_br = self.sched.fork_point() if self.overlap_dw else None
         self._lin_bwd(ws["hp"], 0, 2048, ps + "after_conv", 256, ws["daft"], 0, ws["dhp"])
         # non-local cell: reads dnl, writes datt / dS / dkv / dq / dup128 -- nothing the local cell or the skip branch touches, so
         # it runs as a branch next to them; merged before anything else accumulates into dup128
@@ -1054,7 +837,7 @@ class Trainer(object):
                 self._tn(B, M, M, 64, dS, 0, M, M * M, q, 0, 64, M * 64, dkv, 0, 128, M * 128, 0)
             self._lin_bwd(ws["up128"], 0, 128, ps + "PointShuffle/conv_kv", 128, dkv, 0, dup128)
             self._lin_bwd(ws["up128"], 0, 128, ps + "PointShuffle/conv_query", 64, ws["dq"], 0, dup128, 0, acc_dx=True)
-        self._defer_branch(0, nl_backward, ev_br)
+        self.sched.defer_branch(0, nl_backward, ev_br)
         # skip branch (a second branch): 134 -> 256 backward; its max gradient is scattered after the merges below
         split_skip = self.overlap_dw      # the skip branch's d(up128) in its own buffer, summed in the coarse chain
         def skip_backward():
@@ -1062,11 +845,11 @@ class Trainer(object):
             if split_skip:
                 _lib.check(L.dispu_ps_skip_max_grad(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(ws["up128"]), 128, _p(ws["gmax"]), 144,
                                                     _p(ws["dgmax"]), 136, _p(dcoarse), _p(ws["dup128s"]), 128, 1, self.st), "ps_skip_max_grad")
-        self._defer_branch(1, skip_backward, ev_br)
+        self.sched.defer_branch(1, skip_backward, ev_br)
         # after_conv's dX (0.1 - 0.15 ms on the GPU) is queued: submit the two branches the chain will wait for behind it; the weight
         # gradients stay deferred until the chain's next three kernels are queued too
-        self._flush(prio=0)
-        self._merge(2)                                   # h0 / h1 / wv / the inverted graph are in place
+        self.sched.flush(prio=0)
+        self.sched.merge(2)                                   # h0 / h1 / wv / the inverted graph are in place
         fused_lb = self._fused_local_bwd_ok(ws)
         if fused_lb:
             # one launch: dwv, dz1 (for the side-stream dW1), dG (atomics into the zeroed buffer) and -dA; h1 / dz0 / wv stay on chip
@@ -1086,7 +869,7 @@ class Trainer(object):
                                             _p(ws["bn_shift"]), _p(P[BN + "gamma"]), _p(ws["dwv"]), _p(G[ps + "weight_net/wconv0/weights"]),
                                             _p(G[ps + "weight_net/wconv0/biases"]), _p(G[BN + "gamma"]), _p(G[BN + "beta"]), _p(dcoarse),
                                             _p(ws["bn_sums"]), _p(self._bn_scratch), self._bn_scratch.numel() * 8, self.st), "ps_wnet_grad")
-        self._defer_branch(2, wnet_backward)
+        self.sched.defer_branch(2, wnet_backward)
         if fused_lb:
             self._lin_bwd(ws["h0"], 0, 128, ps + "conv1", 128, ws["dz1"], 0, None)            # dW1, db1 only: the dX product ran inside the fused launch
         else:
@@ -1097,22 +880,22 @@ class Trainer(object):
                                                       _p(ws["dG"]), 128, _p(ws["dAneg"]), 128, self.st), "conv0_gather_grad")
         # the main queue now holds after_conv's dX, the feature x weight gradient, conv1's dX and the gather (~0.35 ms of kernels at 8
         # patches): time to submit the side work that piled up behind them (five weight gradients, the non-local and skip branches)
-        self._flush()
+        self.sched.flush()
         w0, dw0 = P[ps + "conv0/weights"], G[ps + "conv0/weights"]
-        self._merge(0)                                   # dup128 holds the non-local cell's part from here on
+        self.sched.merge(0)                                   # dup128 holds the non-local cell's part from here on
         self._lin_bwd(ws["up128"], 0, 128, None, 128, ws["dG"], 0, dup128, 0, acc_dx=True, W=w0, dW=dw0, woff=6 * 128, bias=False,
                       db=G[ps + "conv0/biases"])
         _lib.check(L.dispu_ps_prep_grad(rm, 128, _p(coarse), _p(w0), _p(ws["dG"]), 128, _p(ws["dAneg"]), 128, _p(dcoarse), _p(dw0), self.st),
                    "ps_prep_grad")
-        self._merge(1)
+        self.sched.merge(1)
         if not split_skip:
             _lib.check(L.dispu_ps_skip_max_grad(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(ws["up128"]), 128, _p(ws["gmax"]), 144,
                                                 _p(ws["dgmax"]), 136, _p(dcoarse), _p(dup128), 128, 1, self.st), "ps_skip_max_grad")
-        self._merge(2)                                   # the weight net's share of dcoarse
+        self.sched.merge(2)                                   # the weight net's share of dcoarse
         # the refine branch's weight-gradient products submitted so far (after_conv's 2048 x 256 with its ~100 MB of partials among them)
         # get their grouped reduction HERE, in the shadow of the coarse chain's backward; whatever is left at _join() is small.  (All of
         # them at _join(): 35 us of reductions between the last product and Adam.)
-        self._rg_flush()
+        self.sched.flush_reductions()
         self._bucket_point(0)                            # data parallel: every refine/* gradient is queued -> its all-reduce starts
 
         # coarse regressor
@@ -1130,13 +913,13 @@ class Trainer(object):
         # gradients are queued on the side streams after it
         _lib.check(L.dispu_dup_sum_grad(B, N, 256, self.up_ratio, _p(ws["dup256"]), 256, _p(ws["dh256"]), 256, self.st), "dup_sum_grad")
         w1, dw1 = P["generator/upshuffle_0/conv1/weights"], G["generator/upshuffle_0/conv1/weights"]
-        with self._fork_group():
-            self._lin_bwd(ws["c64"], 0, 64, cs + "fc_layer2", 3, dcoarse, 0)
-            self._lin_bwd(ws["c256"], 0, 256, cs + "fc_layer1", 64, ws["dc64"], 0)
-            self._lin_bwd(ws["up128"], 0, 128, cs + "fc_layer0", 256, ws["dc256"], 0)
-            self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0)
-            self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
-                     dbias=G["generator/upshuffle_0/conv1/biases"], side=True, wgrad=True)   # read by Adam only: off the chain like every other dW
+        grp = self.sched.fork_group()
+        self._lin_bwd(ws["c64"], 0, 64, cs + "fc_layer2", 3, dcoarse, 0, after=grp)
+        self._lin_bwd(ws["c256"], 0, 256, cs + "fc_layer1", 64, ws["dc64"], 0, after=grp)
+        self._lin_bwd(ws["up128"], 0, 128, cs + "fc_layer0", 256, ws["dc256"], 0, after=grp)
+        self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0, after=grp)
+        self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
+                 dbias=G["generator/upshuffle_0/conv1/biases"], side=True, after=grp, wgrad=True)   # read by Adam only: off the chain like every other dW
         feat, dfeat = ws["feat"], ws["dfeat"]
         self._lin_bwd(feat, 0, 480, None, 256, ws["dh256"], 0, dfeat, 0, bias=False, W=w1, dW=dw1)
 
@@ -1161,9 +944,9 @@ class Trainer(object):
             # (the coarse head's weight gradients, the previous blocks' reductions and prep gradients) -- a few launches per block,
             # as many as the kernel's duration hides
             tail = d == 1 and self.overlap_dw
-            self._flush(n=None if tail else 5)
-            def reduce_partials(sc=sc, scr=scr, C=C, ev=(self._fork_point() if (self.overlap_dw and not tail) else None)):
-                st_r = self._fork_after(ev)[0] if ev is not None else self.st
+            self.sched.flush(n=None if tail else 5)
+            def reduce_partials(sc=sc, scr=scr, C=C, ev=(self.sched.fork_point() if (self.overlap_dw and not tail) else None)):
+                st_r = self.sched.side_stream(ev)[0] if ev is not None else self.st
                 _lib.check(L.dispu_edge_dense_conv_grad_reduce(rn, C, _p(scr), scr.numel(), _p(G[sc + "/l0/weights"]), _p(G[sc + "/l0/biases"]),
                                                                _p(G[sc + "/l1/weights"]), _p(G[sc + "/l1/biases"]), _p(G[sc + "/l2/weights"]),
                                                                _p(G[sc + "/l2/biases"]), st_r), "edge_dense_conv_grad_reduce")
@@ -1173,13 +956,13 @@ class Trainer(object):
                 # them either way, and a hop to a side stream and back costs more than the two launches take
                 reduce_partials()
             else:
-                self._defer(reduce_partials)
+                self.sched.defer(reduce_partials)
             if d > 1:
                 self._act_bias_grad(rn, 48, dF, 0, ws["prep"][d], 0, 1, dF, 0, None)        # prep = relu(.): its mask (dF came from atomics)
                 self._lin_bwd(feat, in_col, 480 - in_col, fe + "layer%d_prep" % d, 48, dF, 0, dfeat, in_col, acc_dx=True)
         # layer0 (no activation, input has no gradient)
         self._lin_bwd(self._x.view(rn, 3), 0, 3, fe + "layer0", 24, dfeat, 456, None, side=False)
-        self._join()                     # every dW is in the flat gradient buffer from here on (all-reduce, Adam)
+        self.sched.join()                     # every dW is in the flat gradient buffer from here on (all-reduce, Adam)
 
     # -------------------------------------------------------------------------------------------------- step ----
     def _backward_prep(self, ws):
@@ -1190,7 +973,7 @@ class Trainer(object):
                        "transpose_batched")
 
     def zero_grad(self):
-        self.st = _lib.stream_ptr(self.device)
+        self.sched.st = _lib.stream_ptr(self.device)
         self._zero(self.flat_g)
 
     def _reducer(self):
@@ -1218,10 +1001,9 @@ class Trainer(object):
         ar = self._reducer()
         if ar is None or _lib.taping() is not None or ar.launched(i):
             return
-        self._flush()                                    # deferred weight gradients of the bucket go to their streams first
-        self._rg_flush()                                 # ... and their pending split reductions
+        self.sched.flush_all()                           # deferred weight gradients of the bucket go to their streams first, then their pending split reductions
         evs = []
-        for s in [torch.cuda.current_stream(self.device)] + list(self._sides):
+        for s in [torch.cuda.current_stream(self.device)] + self.sched.side_streams:
             ev = torch.cuda.Event()
             ev.record(s)
             evs.append(ev)

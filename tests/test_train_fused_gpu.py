@@ -665,7 +665,7 @@ def test_trainer_grouped_reductions_equal_single_ones(dev, dtype):
         torch.cuda.synchronize()
         g[on] = tr.flat_g.clone()
         if on:
-            assert len(tr._rg_dev) >= 1 and all(grp[1] == 0 for grp in tr._rg.values())
+            assert len(tr.sched.tables) >= 1 and all(grp.n == 0 for grp in tr.sched.reduce_groups.values())
             for _ in range(3):
                 terms = tr.train_step_taped(x, gt, radius)
             assert np.isfinite(float(terms["pu_loss"]))
