@@ -52,6 +52,9 @@ SIGNATURES = {
     "dispu_approx_match_scratch_bytes": (_sz, [_i, _i, _i]),
     "dispu_approx_match": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "dispu_approx_match_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "dispu_approx_match_levels_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
+    "dispu_emd_loss_grad_scratch_bytes": (_sz, [_i, _i, _i]),
+    "dispu_emd_loss_grad": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _i, _vp]),
     "dispu_match_cost_scratch_bytes": (_sz, [_i, _i, _i]),
     "dispu_match_cost": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "dispu_match_cost_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -169,6 +172,7 @@ SIGNATURES = {
     "dispu_step_meters": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_uniform_loss_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "dispu_pu_loss_finalize_u": (_i, [_vp, _vp, _l, C.c_float, C.c_float, _vp, _i, _l, C.c_float, _vp, _vp]),
+    "dispu_pu_loss_finalize_e": (_i, [_vp, _vp, _l, C.c_float, C.c_float, _vp, _i, _l, C.c_float, _vp, _vp, _i, _i, C.c_float, _vp, _vp]),
     "dispu_augment": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_sample_batch": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_ulonglong, _i, C.c_float, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp]),

@@ -326,6 +326,121 @@ __global__ __launch_bounds__(AM_ROWS) void am_assemble_kernel(int n, int m, AmLe
     am_assemble_body<FMA, PINNED>(blockIdx.z, blockIdx.x, blockIdx.y, tile, n, m, lv, xyz1, xyz2, temp, match);
 }
 
+// ---- the EMD term of the training loss: cost and gradient without `match` ------------------------------------------------------
+// 10 * earth_mover(fine, gt, radius) (DisPU/model.py:77; loss_utils.py:170-176) needs cost_b = sum_{k,l} sqrt(d2) match[l][k] (matchcost,
+// tf_approxmatch_g.cu:183-225) and grad1[k] = sum_l match[l][k] (p1_k - p2_l) rsqrt(max(d2, 1e-20)) (matchcostgrad1, :270-291); approx_match
+// carries no gradient (tf_approxmatch.py:22).  Both are sums over the plan entries am_assemble_body rebuilds in registers, so this kernel
+// IS the assembly -- same tile staging, same finish of the last level's ratioR from pass 2's partials, every entry evaluated in the same
+// order (t ascending, am_exp_level, sqdist3<FMA>) -- with the store of the entry replaced by four accumulations.  `match` never exists.
+// Association (fixed, no float atomics, run-to-run identical):
+//   * a lane (point k) adds its partners of one tile in ascending l, each term one fmaf (CONTRACT) or multiply + add;
+//   * gradient: the per-(tile, k) sums are written to part_g[cloud][c][k][3] and emd_combine_kernel adds them in ascending c, starting AS
+//     tile 0's sum, scales once by coef / radius[cloud] and adds the product to dpred;
+//   * cost: a workgroup adds its 256 lane sums by wave butterfly (xor 32 .. 1), then waves 0..3 ascending -> part_c[cloud][rb][c];
+//     emd_combine_kernel's last workgroup of a cloud adds those in ascending (rb, c) order strided over 256 lanes, butterfly, then
+//     (w0 + w1) + (w2 + w3), like match_cost_final_kernel.
+constexpr int EM_CH = 128;     // partners per workgroup at most; halved (down to 32) until a launch has >= 1024 workgroups: the pair loop is
+                               // bound by the ten exponentials per pair, a workgroup's tile only sets how many waves share a CU
+
+__host__ __device__ inline int em_chunk(int b, int n, int m) {
+    int ch = EM_CH;
+    const long rb = (n + AM_ROWS - 1) / AM_ROWS;
+    while (ch > 32 && rb * ((m + ch - 1) / ch) * b < 1024) ch >>= 1;
+    return ch;
+}
+
+template <bool FMA, bool PINNED>
+__global__ __launch_bounds__(AM_ROWS) void emd_tile_kernel(int n, int m, int ch, AmLevels lv, const float* __restrict__ xyz1,
+                                                            const float* __restrict__ xyz2, float* __restrict__ temp,
+                                                            float* __restrict__ part_g, float* __restrict__ part_c) {
+    __shared__ AmPartner tile[EM_CH];
+    __shared__ float wsum[AM_ROWS / kWave];
+    const int cloud = blockIdx.z, c = blockIdx.y, rb = blockIdx.x, tid = threadIdx.x;
+    const AmView v = am_view(temp, cloud, n, m);
+    const float* __restrict__ p1 = xyz1 + (size_t)cloud * n * 3;
+    const float* __restrict__ p2 = xyz2 + (size_t)cloud * m * 3;
+    const int l0 = c * ch, len = min(ch, m - l0);
+    if (tid < len) {
+        const int l = l0 + tid;
+        AmPartner q;
+        q.x = p2[l * 3 + 0]; q.y = p2[l * 3 + 1]; q.z = p2[l * 3 + 2]; q.pad = 0.f; q.pad2[0] = q.pad2[1] = 0.f;
+#pragma unroll
+        for (int t = 0; t < AM_LEVELS - 1; ++t) q.r[t] = v.ratR[(size_t)t * m + l];
+        float remn;
+        am_finish_col<false>(v, m, am_chunks(n), AM_LEVELS - 1, l, q.r[AM_LEVELS - 1], remn);    // as am_assemble_body
+        tile[tid] = q;
+    }
+    __syncthreads();
+    const int k = rb * AM_ROWS + tid;
+    const bool active = k < n;
+    float x1 = 0.f, y1 = 0.f, z1 = 0.f;
+    float rl[AM_LEVELS];
+#pragma unroll
+    for (int t = 0; t < AM_LEVELS; ++t) rl[t] = 0.f;
+    if (active) {
+        x1 = p1[k * 3 + 0]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2];
+#pragma unroll
+        for (int t = 0; t < AM_LEVELS; ++t) rl[t] = v.ratL[(size_t)t * n + k];
+    }
+    float s = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    if (active) {
+#pragma unroll 2
+        for (int i = 0; i < len; ++i) {
+            const AmPartner& q = tile[i];
+            const float dx = q.x - x1, dy = q.y - y1, dz = q.z - z1;
+            const float d2 = sqdist3<FMA>(dx, dy, dz);
+            float w = am_exp_level<PINNED>(d2, lv.v[0]) * rl[0] * q.r[0];                          // match[l][k], the assembly's order
+#pragma unroll
+            for (int t = 1; t < AM_LEVELS; ++t) w += am_exp_level<PINNED>(d2, lv.v[t]) * rl[t] * q.r[t];
+            const float d = __builtin_amdgcn_sqrtf(d2);                                           // as match_cost_tile_kernel
+            const float g = w * rsqrtf(fmaxf(d2, 1e-20f));                                        // as match_grad1_tile_kernel
+            const float ex = -dx, ey = -dy, ez = -dz;                                             // p1_k - p2_l, exact
+            if constexpr (FMA) {
+                s = __builtin_fmaf(d, w, s);
+                gx = __builtin_fmaf(ex, g, gx); gy = __builtin_fmaf(ey, g, gy); gz = __builtin_fmaf(ez, g, gz);
+            } else {
+                s = s + d * w;
+                gx += ex * g; gy += ey * g; gz += ez * g;
+            }
+        }
+        float* gp = part_g + (((size_t)cloud * gridDim.y + c) * n + k) * 3;
+        gp[0] = gx; gp[1] = gy; gp[2] = gz;
+    }
+    s = wave_sum_f32(s);
+    if ((tid & (kWave - 1)) == 0) wsum[tid / kWave] = s;
+    __syncthreads();
+    if (tid == 0) {
+        float r = wsum[0];
+        for (int w = 1; w < AM_ROWS / kWave; ++w) r += wsum[w];
+        part_c[((size_t)cloud * gridDim.x + rb) * gridDim.y + c] = r;
+    }
+}
+
+// workgroups 0 .. gridDim.x - 2 of a cloud: dpred[k][:] += (coef / radius) * sum_c part_g[c][k][:]; the last one: cost = sum of part_c
+__global__ __launch_bounds__(256) void emd_combine_kernel(int n, int nc, int nparts, const float* __restrict__ part_g,
+                                                           const float* __restrict__ part_c, const float* __restrict__ radius, float coef,
+                                                           float* __restrict__ cost, float* __restrict__ dpred) {
+    __shared__ float wsum[256 / kWave];
+    const int cloud = blockIdx.y;
+    if (blockIdx.x + 1 < gridDim.x) {
+        const int e = blockIdx.x * 256 + threadIdx.x;             // element of [n][3]
+        if (e >= n * 3) return;
+        const float* __restrict__ p = part_g + (size_t)cloud * nc * n * 3 + e;
+        const float tot = am_sum_partials<false>(p, (size_t)n * 3, nc, 0.f, true);
+        const float f = radius ? coef / radius[cloud] : coef;
+        float* d = dpred + (size_t)cloud * n * 3 + e;
+        *d = *d + f * tot;
+        return;
+    }
+    const float* __restrict__ p = part_c + (size_t)cloud * nparts;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += p[i];
+    s = wave_sum_f32(s);
+    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) cost[cloud] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 // ---- the auction inside the reference op's own temp ---------------------------------------------------------------------------
 // approxmatchLauncher's caller allocates temp as [b, 2 (n + m)] floats (tf_approxmatch.cpp:164-170) and nothing more.  This form
 // needs exactly that: ONE workgroup per cloud (as the reference's kernel, tf_approxmatch_g.cu:180: <<<32,512>>> over clouds), a lane
@@ -640,12 +755,12 @@ static AmLevels am_levels() {
     return lv;
 }
 
+// the auction without the assembly: init, ten column passes, 1 + 9 row passes (21 launches); the ratio vectors and pass 2's partials of
+// the last level stay in `temp` for whoever rebuilds the plan (am_assemble_kernel, emd_tile_kernel)
 template <bool FMA, bool PINNED>
-static int run_approx_match(int b, int n, int m, const float* xyz1, const float* xyz2, float* match, float* temp,
-                            hipStream_t s) {
+static void run_am_levels(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, const AmLevels& lv, hipStream_t s) {
     const float multiL = (n >= m) ? 1.0f : (float)(m / n);
     const float multiR = (n >= m) ? (float)(n / m) : 1.0f;
-    const AmLevels lv = am_levels();
     const dim3 blk(AM_ROWS);
     const dim3 grow((n + AM_ROWS - 1) / AM_ROWS, am_chunks(m), b), gcol((m + AM_ROWS - 1) / AM_ROWS, am_chunks(n), b);
     hipLaunchKernelGGL(am_init_kernel, dim3(8, b), dim3(256), 0, s, n, m, multiL, multiR, temp);
@@ -655,8 +770,29 @@ static int run_approx_match(int b, int n, int m, const float* xyz1, const float*
         if (t + 1 < AM_LEVELS)
             hipLaunchKernelGGL((am_row_kernel<false, FMA, PINNED>), grow, blk, 0, s, n, m, t, lv.v[t], lv.v[t + 1], xyz1, xyz2, temp);
     }
+}
+
+template <bool FMA, bool PINNED>
+static int run_approx_match(int b, int n, int m, const float* xyz1, const float* xyz2, float* match, float* temp,
+                            hipStream_t s) {
+    const AmLevels lv = am_levels();
+    run_am_levels<FMA, PINNED>(b, n, m, xyz1, xyz2, temp, lv, s);
     const dim3 gasm((n + AM_ROWS - 1) / AM_ROWS, (m + AM_ACH - 1) / AM_ACH, b);
-    hipLaunchKernelGGL((am_assemble_kernel<FMA, PINNED>), gasm, blk, 0, s, n, m, lv, xyz1, xyz2, temp, match);
+    hipLaunchKernelGGL((am_assemble_kernel<FMA, PINNED>), gasm, dim3(AM_ROWS), 0, s, n, m, lv, xyz1, xyz2, temp, match);
+    return (int)hipGetLastError();
+}
+
+template <bool FMA, bool PINNED>
+static int run_emd_loss_grad(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, const float* radius, float coef,
+                             float* cost, float* dpred, float* scratch, hipStream_t s) {
+    const AmLevels lv = am_levels();
+    const int ch = em_chunk(b, n, m);
+    const int rbn = (n + AM_ROWS - 1) / AM_ROWS, nc = (m + ch - 1) / ch;
+    float* part_g = scratch;
+    float* part_c = scratch + (size_t)b * nc * n * 3;
+    hipLaunchKernelGGL((emd_tile_kernel<FMA, PINNED>), dim3(rbn, nc, b), dim3(AM_ROWS), 0, s, n, m, ch, lv, xyz1, xyz2, temp, part_g, part_c);
+    hipLaunchKernelGGL(emd_combine_kernel, dim3((unsigned)(((size_t)n * 3 + 255) / 256 + 1), b), dim3(256), 0, s, n, nc, rbn * nc, part_g, part_c, radius, coef,
+                       cost, dpred);
     return (int)hipGetLastError();
 }
 
@@ -687,6 +823,47 @@ DISPU_EXPORT int dispu_approx_match_ws(int b, int n, int m, const float* xyz1, c
     if (fma) return run_approx_match<true, false>(b, n, m, xyz1, xyz2, match, temp, s);
     if (pin) return run_approx_match<false, true>(b, n, m, xyz1, xyz2, match, temp, s);
     return run_approx_match<false, false>(b, n, m, xyz1, xyz2, match, temp, s);
+}
+
+// dispu_approx_match_ws without its last launch: the auction's 21 passes; `temp` (same size, same refusals) keeps the ten (ratioL, ratioR)
+// vector pairs and pass 2's partials of the last level -- what dispu_emd_loss_grad reads.
+DISPU_EXPORT int dispu_approx_match_levels_ws(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, size_t temp_bytes,
+                                              int arith, void* stream) {
+    if (const int e = am_check_args(b, n, m)) return e;
+    if (b == 0) return 0;
+    if (!temp || temp_bytes < dispu_approx_match_scratch_bytes(b, n, m)) return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const bool fma = (arith & DISPU_ARITH_CONTRACT) != 0, pin = (arith & DISPU_ARITH_PINNED_EXP) != 0;
+    const AmLevels lv = am_levels();
+    if (fma && pin) run_am_levels<true, true>(b, n, m, xyz1, xyz2, temp, lv, s);
+    else if (fma) run_am_levels<true, false>(b, n, m, xyz1, xyz2, temp, lv, s);
+    else if (pin) run_am_levels<false, true>(b, n, m, xyz1, xyz2, temp, lv, s);
+    else run_am_levels<false, false>(b, n, m, xyz1, xyz2, temp, lv, s);
+    return (int)hipGetLastError();
+}
+
+// floats: b * (nc * n * 3 gradient partials + ceil(n / 256) * nc cost partials), nc = ceil(m / ch) tiles of ch = em_chunk(b, n, m) partners
+DISPU_EXPORT size_t dispu_emd_loss_grad_scratch_bytes(int b, int n, int m) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    const int ch = em_chunk(b, n, m);
+    const size_t rbn = (n + AM_ROWS - 1) / AM_ROWS, nc = (m + ch - 1) / ch;
+    return sizeof(float) * (size_t)b * (nc * (size_t)n * 3 + rbn * nc);
+}
+
+// cost[b] = match_cost and dpred += coef / radius[b] * matchcostgrad1 from the scratch dispu_approx_match_levels_ws left: two launches.
+DISPU_EXPORT int dispu_emd_loss_grad(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, const float* radius, float coef,
+                                     float* cost, float* dpred, float* scratch, size_t scratch_bytes, int arith, void* stream) {
+    if (const int e = am_check_args(b, n, m)) return e;
+    if (b == 0) return 0;
+    if (!xyz1 || !xyz2 || !temp || !cost || !dpred || !scratch || scratch_bytes < dispu_emd_loss_grad_scratch_bytes(b, n, m))
+        return (int)hipErrorInvalidValue;
+    if ((m + em_chunk(b, n, m) - 1) / em_chunk(b, n, m) > 65535) return (int)hipErrorInvalidValue;        // tiles of a cloud: grid.y
+    hipStream_t s = (hipStream_t)stream;
+    const bool fma = (arith & DISPU_ARITH_CONTRACT) != 0, pin = (arith & DISPU_ARITH_PINNED_EXP) != 0;
+    if (fma && pin) return run_emd_loss_grad<true, true>(b, n, m, xyz1, xyz2, temp, radius, coef, cost, dpred, scratch, s);
+    if (fma) return run_emd_loss_grad<true, false>(b, n, m, xyz1, xyz2, temp, radius, coef, cost, dpred, scratch, s);
+    if (pin) return run_emd_loss_grad<false, true>(b, n, m, xyz1, xyz2, temp, radius, coef, cost, dpred, scratch, s);
+    return run_emd_loss_grad<false, false>(b, n, m, xyz1, xyz2, temp, radius, coef, cost, dpred, scratch, s);
 }
 
 // approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (tf_approxmatch.cpp:141): `temp` is the op's own [b, 2 (n + m)] float allocation

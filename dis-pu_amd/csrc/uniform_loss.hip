@@ -162,6 +162,35 @@ __global__ __launch_bounds__(1024) void pu_loss_finalize_u_kernel(const float* _
     }
 }
 
+// the loss head with the EMD term (model.py:77 enabled): the sums of pu_loss_finalize_u_kernel in the same order (upart may be NULL:
+// no uniform term), plus out[6] = e = emd_w * mean_b(cost_b / radius_b / m) (earth_mover, loss_utils.py:170-176; radius NULL: 1) and
+// pu_loss = ((c + wf * (f + e)) + r) [+ u]: the term sits INSIDE the weight_fine parenthesis, next to dis_fine_cd.
+__global__ __launch_bounds__(1024) void pu_loss_finalize_e_kernel(const float* __restrict__ cd, const float* __restrict__ rep, long nrep, float wf,
+                                                                   float rep_w, const float* __restrict__ upart, long nupart, float uniform_w,
+                                                                   const float* __restrict__ emd_cost, const float* __restrict__ radius, int b, int m,
+                                                                   float emd_w, float* __restrict__ out) {
+    __shared__ float red[16];
+    __shared__ float per[1024];
+    const float a = block_sum_1024(rep, nrep, red);
+    const float ua = block_sum_1024(upart, nupart, red);
+    float es = 0.f;
+    for (int i = threadIdx.x; i < b; i += 1024) es += (emd_cost[i] / (radius ? radius[i] : 1.0f)) / (float)m;
+    per[threadIdx.x] = es;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float ea = per[0];
+        const int cnt = b < 1024 ? b : 1024;
+        for (int i = 1; i < cnt; ++i) ea += per[i];                     // clouds in ascending order (b <= 1024: exactly the sequential mean)
+        const float r = rep ? rep_w * (a / ((float)nrep * 4.0f)) : 0.f;
+        const float c = 1000.0f * cd[0], f = 1000.0f * cd[1];
+        const float un = upart ? uniform_w * (ua / (float)nupart) : 0.f;
+        const float e = emd_w * (ea / (float)b);
+        float pu = (c + wf * (f + e)) + r;
+        if (upart) pu = pu + un;
+        out[0] = c; out[1] = f; out[2] = r; out[3] = pu; out[4] = wf; out[5] = un; out[6] = e;
+    }
+}
+
 }  // namespace dispu
 
 using namespace dispu;
@@ -199,5 +228,16 @@ DISPU_EXPORT int dispu_pu_loss_finalize_u(const float* cd, const float* rep, lon
     if (!cd || !out || (rep && nrep <= 0) || !upart || nlevels < 1 || nlevels > UL_MAX_LEVELS || nu < 1) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(pu_loss_finalize_u_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, cd, rep, nrep, wf, rep_w, upart,
                        (long)nlevels * nu, uniform_w, out);
+    return (int)hipGetLastError();
+}
+
+// dispu_pu_loss_finalize(_u) + the EMD term (model.py:77): emd_cost [b] = dispu_emd_loss_grad's raw costs of (fine, gt), m points per cloud.
+DISPU_EXPORT int dispu_pu_loss_finalize_e(const float* cd, const float* rep, long nrep, float wf, float rep_w, const float* upart, int nlevels,
+                                          long nu, float uniform_w, const float* emd_cost, const float* radius, int b, int m, float emd_w,
+                                          float* out, void* stream) {
+    if (!cd || !out || (rep && nrep <= 0) || !emd_cost || b < 1 || m < 1) return (int)hipErrorInvalidValue;
+    if (upart && (nlevels < 1 || nlevels > UL_MAX_LEVELS || nu < 1)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(pu_loss_finalize_e_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, cd, rep, nrep, wf, rep_w, upart,
+                       upart ? (long)nlevels * nu : 0l, uniform_w, emd_cost, radius, b, m, emd_w, out);
     return (int)hipGetLastError();
 }

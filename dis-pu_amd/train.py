@@ -46,6 +46,8 @@ class TrainOpts(_Opts):
     repulsion_w = 1.0
     use_uniform = False   # model.py:86 (the get_uniform_loss line ships commented out)
     uniform_w = 10.0      # DisPU/configs.py:42
+    use_emd = False       # model.py:77 (the dis_fine_emd line ships commented out)
+    emd_w = 10.0          # model.py:77, the literal in front of earth_mover (configs.py has no flag for it)
 
 
 def weight_fine(epoch):
@@ -247,7 +249,7 @@ class Trainer(object):
             cd=[dict(d_gt=E(B, M), i_gt=E(B, M, dtype=i32), d_pred=E(B, M), i_pred=E(B, M, dtype=i32), g_gt=E(B, M), g_pred=E(B, M),
                      dgt_unused=E(B, M, 3), rowmean=E(B), rowmax=E(B)) for _ in range(2)],      # one set per Chamfer term
             ball=E(B, M, 20, dtype=i32), ball_cnt=E(B, M, dtype=i32), rep=E(B, M), rowmean=E(B), rowmax=E(B),
-            loss_vals=Z(8), r07=torch.full((B,), 0.07, dtype=f32, device=dev), zeros=Z(1))
+            loss_vals=Z(9), r07=torch.full((B,), 0.07, dtype=f32, device=dev), zeros=Z(1))
         ws["dprep"] = [None, None] + [ws["zeroed"][i * rn * 48:(i + 1) * rn * 48].view(rn, 48) for i in range(DENSE_BLOCKS - 1)]
         ws["dup128s"] = ws["zeroed"][(DENSE_BLOCKS - 1) * rn * 48:].view(rm, 128)
         # grid code of duplicate_up: row (cloud*up + r)*N + i carries grid[r]
@@ -693,6 +695,16 @@ class Trainer(object):
             ws["utabs"][w] = self._uniform_tables(B, N)
         return ws["utabs"][w]
 
+    def _emd_workspace(self, ws, B, N):
+        """the EMD term's buffers (csrc/approxmatch.hip), added to the workspace the first time the term runs at this shape: the auction's
+        scratch (ratio vectors and chunk partials; no [B, M, M] match), the fused launch's partial sums, one raw cost per cloud."""
+        if "emd_cost" not in ws:
+            L, M, dev = _lib.lib(), N * self.up_ratio, self.device
+            nt, ns = L.dispu_approx_match_scratch_bytes(B, M, M), L.dispu_emd_loss_grad_scratch_bytes(B, M, M)
+            ws.update(emd_temp=torch.empty(((nt + 3) // 4,), dtype=torch.float32, device=dev), emd_temp_bytes=nt,
+                      emd_scratch=torch.empty(((ns + 3) // 4,), dtype=torch.float32, device=dev), emd_scratch_bytes=ns,
+                      emd_cost=torch.zeros((B,), dtype=torch.float32, device=dev))
+
     def _check_targets(self, gt, radius, B, M):
         """gt [B, 4N, 3] / radius [B] float32 on the device: the loss workspace (d_gt, i_gt, g_gt, ...) is sized [B, 4N]
         and the kernels take raw pointers, so anything else must be refused here (DisPU/model.py:47-49 placeholders)."""
@@ -714,6 +726,10 @@ class Trainer(object):
         uniform = bool(getattr(self.opts, "use_uniform", False))
         if uniform:
             tab = self._uniform_workspace(ws, B, N)             # refuses a patch size the term cannot take, before any launch
+        emd = bool(getattr(self.opts, "use_emd", False))
+        if emd:
+            self._emd_workspace(ws, B, N)
+            emd_w = float(self.opts.emd_w)
         # side work is submitted behind the fine term's launches (the chain): the pair tensors of the local cell's backward (needed much
         # later) and the coarse term
         self.sched.defer_branch(2, self._recompute_pair_tensors)    # off the chain: needed by the local cell's backward only
@@ -733,7 +749,15 @@ class Trainer(object):
                 if uniform:
                     _lib.check(L.dispu_fps_ws(B, M, tab.npoint, _p(fine), _p(ws["ufps_tmp"]), ws["ufps_bytes"], _p(ws["useeds"]),
                                               _lib.ARITH_CONTRACT, self.st), "fps")              # as loss_utils.get_uniform_loss
+        # the EMD term's auction (21 launches, reads fine and gt only) runs on a branch of its own next to the Chamfer launches: ordered
+        # after THIS point of the stream, submitted behind the fine term's launches (the chain); its fused cost + gradient launch follows
+        # the Chamfer gradient on the chain (which zero-fills dfine), like the two terms above
+        ev_emd = self.sched.fork_point() if (emd and self.overlap_dw) else None
         self._chamfer(ws["fine"], gt, radius, 1000.0 * wf, ws["dfine"], 1)
+        if emd:
+            with self.sched.branch(3, ev_emd):
+                _lib.check(L.dispu_approx_match_levels_ws(B, M, M, _p(fine), _p(gt), _p(ws["emd_temp"]), ws["emd_temp_bytes"],
+                                                          _lib.ARITH_CONTRACT, self.st), "approx_match_levels_ws")   # as loss_utils.earth_mover
         if self.opts.use_repulse or uniform:
             self.sched.merge(1)
         if self.opts.use_repulse:
@@ -744,25 +768,37 @@ class Trainer(object):
             _lib.check(L.dispu_uniform_loss_grad(B, M, tab.npoint, tab.nlevels, ctypes.addressof(tab.ns), ctypes.addressof(tab.levels), _p(fine),
                                                  _p(ws["useeds"]), _p(ws["upart"]), _p(ws["dfine"]), None, None, _lib.ARITH_CONTRACT, self.st),
                        "uniform_loss_grad")
+        if emd:
+            self.sched.merge(3)
+            _lib.check(L.dispu_emd_loss_grad(B, M, M, _p(fine), _p(gt), _p(ws["emd_temp"]), _p(radius), emd_w * wf / (B * M), _p(ws["emd_cost"]),
+                                             _p(ws["dfine"]), _p(ws["emd_scratch"]), ws["emd_scratch_bytes"], _lib.ARITH_CONTRACT, self.st),
+                       "emd_loss_grad")
         self.sched.merge(0)
         out = ws["loss_vals"]
-        if uniform:
+        if emd:
+            _lib.check(L.dispu_pu_loss_finalize_e(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
+                                                  _p(ws["upart"]) if uniform else None, tab.nlevels if uniform else 0,
+                                                  B * tab.npoint if uniform else 0, float(self.opts.uniform_w) if uniform else 0.0,
+                                                  _p(ws["emd_cost"]), _p(radius), B, M, emd_w, _p(out, 2), self.st), "pu_loss_finalize_e")
+        elif uniform:
             _lib.check(L.dispu_pu_loss_finalize_u(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
                                                   _p(ws["upart"]), tab.nlevels, B * tab.npoint, float(self.opts.uniform_w), _p(out, 2), self.st),
                        "pu_loss_finalize_u")
         else:
             _lib.check(L.dispu_pu_loss_finalize(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
                                                 _p(out, 2), self.st), "pu_loss_finalize")
-        terms = self._terms(out, wf, uniform)
+        terms = self._terms(out, wf, uniform, emd)
         self.sched.flush(prio=0)                                     # the recompute branch: submitted behind the loss's own launches
         return terms
 
     @staticmethod
-    def _terms(out, wf, uniform=False):
-        vals = out[2:8 if uniform else 6].clone()               # device scalars that survive the next step
+    def _terms(out, wf, uniform=False, emd=False):
+        vals = out[2:9 if emd else 8 if uniform else 6].clone()  # device scalars that survive the next step
         terms = {"dis_coarse_cd": vals[0], "dis_fine_cd": vals[1], "repulsion_loss": vals[2], "pu_loss": vals[3], "weight_fine": wf}
         if uniform:
             terms["uniform_loss"] = vals[5]                     # uniform_w * get_uniform_loss(fine)
+        if emd:
+            terms["dis_fine_emd"] = vals[6]                     # emd_w * earth_mover(fine, gt, radius)
         return terms
 
     # ---------------------------------------------------------------------------------------------- backward ----
@@ -1044,8 +1080,9 @@ class Trainer(object):
         uniform = bool(getattr(self.opts, "use_uniform", False))
         if uniform:
             self._uniform_tables(B, N)                       # refuses a patch size the term cannot take, before any launch
+        emd = bool(getattr(self.opts, "use_emd", False))
         key = (B, N, wf, self.opts.use_repulse, uniform, float(getattr(self.opts, "uniform_w", 0.0)) if uniform else None,
-               torch.cuda.current_stream(self.device).cuda_stream)
+               emd, float(self.opts.emd_w) if emd else None, torch.cuda.current_stream(self.device).cuda_stream)
         t = self._tapes.get(key)
         if t is None:
             st = dict(x=inputs.clone(), gt=gt.clone(), radius=radius.clone())
@@ -1074,7 +1111,7 @@ class Trainer(object):
         t["gt"].copy_(gt)
         t["radius"].copy_(radius)
         t["tape"].replay()
-        terms = self._terms(t["loss_vals"], wf, uniform)
+        terms = self._terms(t["loss_vals"], wf, uniform, emd)
         world = self.all_reduce_grads()
         self.adam(world)
         self.global_step += 1
@@ -1105,9 +1142,11 @@ class Trainer(object):
 LOG_FORMAT = "epoch %04d g_loss=%.9f  coarse_cd=%.9f  coarse_hd=%.9f  fine_cd=%.9f fine_hd=%.9f  time=%.4f"
 
 
-def format_log_line(epoch, g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds):
-    """the per-epoch line of log_train.txt (model.py:220-222; the last field is the epoch's duration in MINUTES)."""
-    return LOG_FORMAT % (epoch, g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds / 60.0)
+def format_log_line(epoch, g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds, dis_fine_emd=None):
+    """the per-epoch line of log_train.txt (model.py:220-222; the last field is the epoch's duration in MINUTES).  With the EMD term
+    on (TrainOpts.use_emd) the line gains a `dis_fine_emd=` column at its end; without it the line is the reference's."""
+    line = LOG_FORMAT % (epoch, g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds / 60.0)
+    return line if dis_fine_emd is None else line + "  dis_fine_emd=%.9f" % dis_fine_emd
 
 
 def format_args(opts):
@@ -1131,7 +1170,8 @@ def _hausdorff_terms(trainer, inputs, gt, radius):
 
 def train_one_epoch(trainer, fetcher, batch_size, train_step_fn="eager", hd_fn=_hausdorff_terms):
     """model.py:229-303 -> (g_loss, coarse_cd, coarse_hd, fine_cd, fine_hd, seconds, steps): the epoch's means and its duration.
-    The five sums are accumulated in a device tensor and read ONCE, after the last step: no per-step host synchronisation."""
+    The five sums are accumulated in a device tensor and read ONCE, after the last step: no per-step host synchronisation.
+    A step whose terms hold "dis_fine_emd" (TrainOpts.use_emd) adds that mean as a sixth value in front of `seconds`."""
     import time
     if train_step_fn not in ("eager", "taped"):
         raise ValueError("train_step_fn must be 'eager' or 'taped'")
@@ -1143,8 +1183,10 @@ def train_one_epoch(trainer, fetcher, batch_size, train_step_fn="eager", hd_fn=_
         x, gt, radius = fetcher.next_batch()
         terms = step(x, gt, radius)
         chd, fhd = hd_fn(trainer, x, gt, radius)
-        row = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(())
-                           for v in (terms["pu_loss"], terms["dis_coarse_cd"], chd, terms["dis_fine_cd"], fhd)])
+        cols = (terms["pu_loss"], terms["dis_coarse_cd"], chd, terms["dis_fine_cd"], fhd)
+        if "dis_fine_emd" in terms:
+            cols += (terms["dis_fine_emd"],)
+        row = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(()) for v in cols])
         acc = row if acc is None else acc.to(row.device) + row
     if acc is None:
         vals = [0.0] * 5                                 # AverageMeter.avg of an empty epoch
@@ -1203,17 +1245,20 @@ def _run_files(trainer, fetcher, opts, log_dir, restore, save_fn, restore_fn, lo
 def _end_epoch(trainer, fetcher, opts, emit, save, records, best, vals, seconds, steps):
     """The epoch tail of fit and fit_parallel, given the epoch's five logged values: fetcher.reset(), trainer.epoch += 1, the log
     line, save(epoch) when epoch % opts.epoch_per_save == 0 and fine_cd is strictly below `best`, the record.  -> the new best."""
-    g, ccd, chd, fcd, fhd = vals
+    g, ccd, chd, fcd, fhd = vals[:5]
+    emd = vals[5] if len(vals) > 5 else None         # the EMD term's column (TrainOpts.use_emd)
     fetcher.reset()
     trainer.epoch += 1
     epoch = int(trainer.epoch)
-    emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds))
+    emit(format_log_line(epoch, g, ccd, chd, fcd, fhd, seconds, emd))
     saved = None
     if epoch % int(opts.epoch_per_save) == 0 and fcd < best:
         best = fcd
         saved = save(epoch)
     records.append(dict(epoch=epoch, g_loss=g, coarse_cd=ccd, coarse_hd=chd, fine_cd=fcd, fine_hd=fhd, seconds=seconds,
                         steps=steps, saved=saved))
+    if emd is not None:
+        records[-1]["dis_fine_emd"] = emd
     return best
 
 
@@ -1273,28 +1318,32 @@ def _step_meters_fn(trainer, x, gt, radius, row):
     step_meters(trainer, x, radius, row)
 
 
-def reduce_meter_tables(tables, steps):
-    """tables [world, steps * 5] (every rank's step-meter table) -> the epoch's five logged values, in float64: per step the mean
+def reduce_meter_tables(tables, steps, width=5):
+    """tables [world, steps * width] (every rank's step-meter table) -> the epoch's logged values, in float64: per step the mean
     over ranks of the loss / CD columns and the MAX over ranks of the two Hausdorff columns (hausdorff_loss is a max over the
-    batch, and the global batch is the union of the ranks' shards), then the mean over steps."""
+    batch, and the global batch is the union of the ranks' shards), then the mean over steps.  width 6: the EMD term's column
+    (TrainOpts.use_emd) behind the five, a mean over ranks like the other loss columns."""
     if steps <= 0:
-        return [0.0] * 5                                 # AverageMeter.avg of an empty epoch
-    t = np.asarray(tables, np.float64).reshape(-1, steps, 5)
+        return [0.0] * width                             # AverageMeter.avg of an empty epoch
+    t = np.asarray(tables, np.float64).reshape(-1, steps, width)
     per_step = t.mean(axis=0)
     per_step[:, _HD_COLUMNS] = t[:, :, _HD_COLUMNS].max(axis=0)
     return [float(v) for v in per_step.mean(axis=0)]
 
 
-def fill_meter_table(trainer, fetcher, table, steps, step, meter_fn=_step_meters_fn):
+def fill_meter_table(trainer, fetcher, table, steps, step, meter_fn=_step_meters_fn, width=5):
     """the steps of one epoch as fit_parallel runs them: next_batch, the step function, meter_fn into row s of `table`
-    ([steps * 5 + 2] float32 on the trainer's device); the fetcher's two status flags go behind the rows (zeros for a fetcher
-    without status_flags()).  Launches only: nothing here waits for the device."""
+    ([steps * width + 2] float32 on the trainer's device); the fetcher's two status flags go behind the rows (zeros for a fetcher
+    without status_flags()).  width 6 (TrainOpts.use_emd): the step's dis_fine_emd, a device scalar, is copied behind the five
+    meters.  Launches only: nothing here waits for the device."""
     for s in range(steps):
         x, gt, radius = fetcher.next_batch()
-        step(x, gt, radius)
-        meter_fn(trainer, x, gt, radius, table[s * 5:s * 5 + 5])
+        terms = step(x, gt, radius)
+        meter_fn(trainer, x, gt, radius, table[s * width:s * width + 5])
+        if width > 5:
+            table[s * width + 5:s * width + 6].copy_(torch.as_tensor(terms["dis_fine_emd"], dtype=torch.float32).reshape(1))
     flags_of = getattr(fetcher, "status_flags", None)
-    table[steps * 5:].copy_(torch.as_tensor(flags_of() if flags_of is not None else (0, 0)))
+    table[steps * width:].copy_(torch.as_tensor(flags_of() if flags_of is not None else (0, 0)))
 
 
 def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="eager", group=None, save_fn=None, restore_fn=None,
@@ -1340,7 +1389,8 @@ def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="
     records, best = [], math.inf
     with _run_files(trainer, fetcher, opts, log_dir, restore, save_fn, restore_fn, log, rank) as (restore_epoch, save_fn, emit):
         n = max(steps_per_epoch(len(fetcher), B), 0)
-        table = torch.zeros(n * 5 + 2, dtype=torch.float32, device=getattr(trainer, "device", "cpu"))
+        W = 6 if getattr(getattr(trainer, "opts", None), "use_emd", False) else 5      # the EMD term's column behind the five meters
+        table = torch.zeros(n * W + 2, dtype=torch.float32, device=getattr(trainer, "device", "cpu"))
 
         def save(epoch):
             saved = save_fn(log_dir, trainer, epoch) if rank == 0 else None
@@ -1354,16 +1404,16 @@ def fit_parallel(trainer, fetcher, opts, log_dir, restore=False, train_step_fn="
         emit("train_dataset: %d" % len(fetcher))
         for _ in range(restore_epoch, int(opts.training_epoch)):
             t0 = time.time()
-            fill_meter_table(trainer, fetcher, table, n, step, meter_fn)
+            fill_meter_table(trainer, fetcher, table, n, step, meter_fn, W)
             if world > 1:
                 from . import parallel
                 every = parallel._all_gather_rows(table.view(1, -1), world, group).cpu().numpy()      # the epoch's one collective
             else:
                 every = table.view(1, -1).cpu().numpy()                                               # ... and its one read-back
-            bad = [(r, int(every[r, n * 5] != 0), int(every[r, n * 5 + 1] != 0)) for r in range(world) if every[r, n * 5:].any()]
+            bad = [(r, int(every[r, n * W] != 0), int(every[r, n * W + 1] != 0)) for r in range(world) if every[r, n * W:].any()]
             if bad:
                 raise RuntimeError("epoch %d: the batch sampler reported a failure on rank(s) %s (rank, candidate rounds exhausted, "
                                    "permutation entry out of range)" % (int(trainer.epoch), bad))
-            vals = reduce_meter_tables(every[:, :n * 5], n)
+            vals = reduce_meter_tables(every[:, :n * W], n, W)
             best = _end_epoch(trainer, fetcher, opts, emit, save, records, best, vals, time.time() - t0, n)
     return records

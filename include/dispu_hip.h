@@ -203,6 +203,26 @@ int dispu_approx_match(int b, int n, int m, const float* xyz1, const float* xyz2
                        void* stream);
 int dispu_approx_match_ws(int b, int n, int m, const float* xyz1, const float* xyz2, float* match, float* temp,
                           size_t temp_bytes, int arith, void* stream);
+/* dispu_approx_match_ws without its last launch (the assembly of `match`): init, the ten column passes and the 1 + 9 row passes of the
+ * auction (tf_approxmatch_g.cu:50-160).  `temp` / `temp_bytes` and every refusal as dispu_approx_match_ws; afterwards `temp` holds the ten
+ * (ratioL, ratioR) vector pairs and pass 2's partial sums of the last level, byte for byte what dispu_approx_match_ws leaves there. */
+int dispu_approx_match_levels_ws(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, size_t temp_bytes, int arith,
+                                 void* stream);
+/* The EMD term of the training loss, `10.0 * earth_mover(fine, gt, radius)` (DisPU/model.py:77; loss_utils.py:170-176), value and
+ * gradient without a [b, m, n] `match`: replaces approxmatchLauncher's `match += w` (tf_approxmatch_g.cu:152), matchcost (:183-225) and
+ * matchcostgrad1 (:270-291) behind one entry.  xyz1 [b, n, 3] = the prediction, xyz2 [b, m, 3] = the ground truth, `temp` = the scratch
+ * dispu_approx_match_levels_ws(b, n, m, xyz1, xyz2, ...) filled in the same `arith` mode.  Every plan entry match[l][k] =
+ * sum_t exp(level_t d2) ratioL_t[k] ratioR_t[l] is rebuilt in registers in dispu_approx_match_ws's order and feeds
+ *   cost [b]          = sum_{k,l} sqrt(d2) match[l][k]                                   (written, not scaled)
+ *   dpred [b, n, 3]  += (coef / radius[b]) * sum_l match[l][k] (xyz1_k - xyz2_l) rsqrt(max(d2, 1e-20))     (radius NULL: factor coef)
+ * approx_match carries no gradient (tf_approxmatch.py:22), so this is the whole gradient of the term w.r.t. xyz1.  n != m allowed.
+ * Two launches (tiles, combine); partial sums are combined in ascending tile order, no float atomics: run-to-run identical.
+ * `scratch`: dispu_emd_loss_grad_scratch_bytes(b, n, m) = 4 * b * (nc * n * 3 + ceil(n / 256) * nc) bytes, nc = ceil(m / ch), where
+ * ch = 128 is halved while ch > 32 and ceil(n / 256) * ceil(m / ch) * b < 1024.  b < 0, n or m < 1, a NULL pointer (radius excepted)
+ * or scratch_bytes below that: hipErrorInvalidValue, nothing written; b == 0 returns 0 without a launch. */
+size_t dispu_emd_loss_grad_scratch_bytes(int b, int n, int m);
+int dispu_emd_loss_grad(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, const float* radius, float coef,
+                        float* cost, float* dpred, float* scratch, size_t scratch_bytes, int arith, void* stream);
 /* matchcostLauncher(b,n,m,xyz1,xyz2,match,out)   tf_approxmatch.cpp:142; kernel tf_approxmatch_g.cu:183-228.
  * dispu_match_cost: the launcher's own signature, no scratch (one workgroup per cloud, like the reference's kernel).
  * dispu_match_cost_ws: the fast path; `scratch`: dispu_match_cost_scratch_bytes(b,n,m) bytes (one partial per tile of `match`).
@@ -650,6 +670,15 @@ int dispu_uniform_loss_grad(int b, int n, int npoint, int nlevels, const int* ns
  * includes out[5].  One workgroup, fixed summation order. */
 int dispu_pu_loss_finalize_u(const float* cd, const float* rep, long nrep, float wf, float rep_w, const float* upart, int nlevels,
                              long nu, float uniform_w, float* out, void* stream);
+/* the loss head with the EMD line of DisPU/model.py:77 enabled (`dis_fine_emd = 10.0 * earth_mover(fine, gt, radius)`): the inputs of
+ * dispu_pu_loss_finalize_u with upart NULL-able (NULL: no uniform term, out[5] = 0, nlevels / nu ignored) plus emd_cost [b] =
+ * dispu_emd_loss_grad's costs, radius [b] (NULL: 1) and m points per cloud.  out[0..2], out[4], out[5] as there;
+ * out[6] = dis_fine_emd = emd_w * mean_b(emd_cost[b] / radius[b] / m) (loss_utils.py:170-176);
+ * out[3] = pu_loss = ((out[0] + wf * (out[1] + out[6])) + out[2]) [+ out[5] with upart] in fp32, in this order: the term is weighted by
+ * weight_fine like dis_fine_cd (the reference never sums it: INTEGRATION.md).  One workgroup, fixed summation order. */
+int dispu_pu_loss_finalize_e(const float* cd, const float* rep, long nrep, float wf, float rep_w, const float* upart, int nlevels,
+                             long nu, float uniform_w, const float* emd_cost, const float* radius, int b, int m, float emd_w,
+                             float* out, void* stream);
 /* dst[off ..] = W^T [N][K] for every weight matrix W [K][N] at src[off ..]; desc [count][3] = {off, K, N} (device int32).  The training
  * step's dX = dZ . W^T products read W^T untransposed (the forward GEMM's fast path). */
 int dispu_transpose_batched(int count, const int* desc, const float* src, float* dst, void* stream);

@@ -46,6 +46,8 @@ def parse_args(argv=None):
     ap.add_argument("--repulsion_w", type=float, default=1.0, help="repulsion_weight")
     ap.add_argument("--use_uniform", type=str2bool, default=False, help="add uniform_w * get_uniform_loss(fine) to the loss (model.py:86)")
     ap.add_argument("--uniform_w", type=float, default=10.0, help="uniform_weight")
+    ap.add_argument("--use_emd", type=str2bool, default=False, help="add weight_fine * emd_w * earth_mover(fine, gt, radius) to the loss (model.py:77)")
+    ap.add_argument("--emd_w", type=float, default=10.0, help="the factor in front of earth_mover (model.py:77)")
     ap.add_argument("--visulize", type=str2bool, default=False, help="not supported (refused when true)")
     ap.add_argument("--seed", type=int, default=0, help="initial weights, the epoch permutations and every batch draw")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="Trainer arithmetic")

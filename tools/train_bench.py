@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--bf16-min-macs", type=float, default=0.0, help="Trainer.bf16_min_macs (A/B)")
     ap.add_argument("--no-group-reduce", action="store_true", help="A/B: every weight-gradient product launches its own split reduction (Trainer.group_reduce = False)")
     ap.add_argument("--use-uniform", action="store_true", help="the loss with the uniform term (TrainOpts.use_uniform, uniform_w 10)")
+    ap.add_argument("--use-emd", action="store_true", help="the loss with the EMD term (TrainOpts.use_emd, emd_w 10)")
     ap.add_argument("--tape", action="store_true", help="forward + loss + backward re-issued from a launch tape (Trainer.train_step_taped)")
     args = ap.parse_args()
     from dispu_amd import synth
@@ -51,6 +52,7 @@ def main():
     P = init_params(1234)
     opts = TrainOpts()
     opts.use_uniform = bool(args.use_uniform)
+    opts.use_emd = bool(args.use_emd)
     tr = Trainer(opts, params=P, device=dev, dtype=args.dtype)
     if args.dw_streams > 0:
         tr.dw_streams = args.dw_streams
@@ -125,7 +127,7 @@ def main():
                           "ms_per_step": dt / args.steps * 1e3,
                           "ms_per_step_repeats": {"n": 5, "min": srt[0] / args.steps * 1e3, "median": srt[2] / args.steps * 1e3,
                                                   "max": srt[4] / args.steps * 1e3}, "launch": "tape" if args.tape else "eager",
-                          "use_uniform": bool(args.use_uniform),
+                          "use_uniform": bool(args.use_uniform), "use_emd": bool(args.use_emd),
                           "dtype": "f32" if args.dtype == "f32" else "bf16 products, f32 accumulate / storage", "pu_loss": float(terms["pu_loss"]), **phases}))
     if world > 1:
         dist.destroy_process_group()
