@@ -14,6 +14,7 @@ ARITH_CONTRACT = 1
 ARITH_PINNED_EXP = 2   # OR-able, approx_match only (bit-reproducible exp; parity mode)
 MESH_BRUTE_FORCE = 8   # OR-able, point_to_mesh only (visit every face tile; A/B tests)
 MESH_TILE = 64         # faces per tile of point_to_mesh's face layout
+LINEAR_PLAN_INTS = 21  # include/dispu_hip.h: DISPU_LINEAR_PLAN_INTS
 
 _vp, _i, _sz, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_long
 
@@ -67,6 +68,9 @@ SIGNATURES = {
     "dispu_linear_tile": (_i, [_i, _i, _i]),
     "dispu_linear_tile2": (_i, [_i, _i, _i, _i, _i]),
     "dispu_debug_linear_tile": (None, [_i]),
+    "dispu_linear_plan": (_i, [_i, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i,
+                               _vp]),
+    "dispu_linear_bf16_plan": (_i, [_i, _i, _i, _i]),
     "dispu_sa_fused": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_edge_conv_fused": (_i, [_i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "dispu_group_center": (_i, [_l, _i, _i, _vp, _vp, _vp]),
@@ -246,7 +250,7 @@ class Tape(object):
 
 
 _TAPE = None                     # the Tape being recorded, if any
-_NO_TAPE = ("dispu_version", "dispu_error_string", "dispu_linear_tile", "dispu_linear_tile2")
+_NO_TAPE = ("dispu_version", "dispu_error_string", "dispu_linear_tile", "dispu_linear_tile2", "dispu_linear_plan", "dispu_linear_bf16_plan")
 
 
 class _TapeLib(object):
@@ -307,6 +311,20 @@ def check(code, what):
     if code != 0:
         msg = lib().dispu_error_string(code)
         raise DispuError("%s failed: hip error %d (%s)" % (what, code, msg.decode() if msg else "?"))
+
+
+def linear_plan(batch, M, K, N, X, ldx, sx, W, ldw, sw, transb, bias, scale, shift, act, Y, ldy, sy, R1, ldr1, sr1, R2, ldr2, sr2, Mk, ldm,
+                mcols):
+    """dispu_linear_plan as a list of launches: ("skinny", n0, n1, NG, transb) or ("tiled", n0, n1, BM, BN, BK, transb, edge, EPI).
+    Pointers are addresses (int) or None; nothing is dereferenced and no device is needed."""
+    buf = (_i * LINEAR_PLAN_INTS)()
+    check(lib().dispu_linear_plan(batch, M, K, N, X, ldx, sx, W, ldw, sw, transb, bias, scale, shift, act, Y, ldy, sy, R1, ldr1, sr1, R2, ldr2,
+                                  sr2, Mk, ldm, mcols, buf), "dispu_linear_plan")
+    out = []
+    for i in range(buf[0]):
+        kind, n0, n1, bm, bn, bk, tb, edge, epi, ng = buf[1 + 10 * i:11 + 10 * i]
+        out.append(("tiled", n0, n1, bm, bn, bk, tb, edge, epi) if kind else ("skinny", n0, n1, ng, tb))
+    return out
 
 
 def stream_ptr(device=None):

@@ -563,44 +563,28 @@ static int launch_epi(const LinearArgs& a, dim3 grid, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, int BK, bool TRANSB, bool EDGE>
-static int launch_one(const LinearArgs& a, dim3 grid, hipStream_t s) {
-    if (!a.scale && !a.R1 && !a.R2 && !a.Mk) {
-        if constexpr (BM == 128 && BN == 256 && BK == 16 && !TRANSB && !EDGE) {
-            if (a.K >= 1024) return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 6>(a, grid, s);
-        }
-        return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 0>(a, grid, s);
-    }
-    if (a.scale && !a.R1 && !a.R2 && !a.Mk) return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 1>(a, grid, s);
-    if (a.Mk) return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 5>(a, grid, s);
-    return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 4>(a, grid, s);
-}
+// ---- the dispatch decision (host only) -------------------------------------------------------------------------------------------
+// One call = one or two launches.  linear_decide() below is the ONLY place that chooses; the launchers switch over what it
+// decided, and dispu_linear_plan exports the same record (so a test or a profiler can name the instantiation a call takes).
+struct LinearLaunch {
+    int skinny;            // 1: linear_skinny.hip, 0: linear_mfma_kernel
+    int n0, n1;            // output columns [n0, n1) of the call this launch produces
+    int bm, bn, bk;        // tiled: block tile and slab depth
+    int transb;
+    int edge;              // tiled: predicated loaders / scalar epilogue
+    int epi;               // tiled: 0 plain, 1 BatchNorm fold, 4 residuals, 5 ReLU-gradient mask, 6 = 0 at K >= 1024 on the 128 x 256 DMA path
+    int ng;                // skinny: unroll depth (2, 8, 16, 24)
+};
+constexpr int DISPU_LINEAR_PLAN_INTS = 21;     // include/dispu_hip.h
+struct LinearPlan {
+    int n;
+    LinearLaunch l[2];
+};
 
-// BK: slab depth of the interior, untransposed path (16 = the DMA pipeline); BKR: of the register-staged paths (transposed B, edge tiles)
-template <int BM, int BN, int WM, int WN, int BK, int BKR = BK>
-static int launch_linear(const LinearArgs& a, int batch, bool transb, hipStream_t s) {
-    dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, batch);
-    const bool aligned = ((a.ldx & 3) == 0) && ((a.ldw & 3) == 0) && ((a.sx & 3) == 0) && ((a.sw & 3) == 0) &&
-                         ((((uintptr_t)a.X) & 15) == 0) && ((((uintptr_t)a.W) & 15) == 0);
-    // (round 5: interior tiles store / fetch TN-wide vectors in the epilogue -- Y, bias and the optional epilogue operands must allow it)
-    const auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-    const bool out_aligned = ((a.ldy & 3) == 0) && ((a.sy & 3) == 0) && al16(a.Y) && (!a.bias || al16(a.bias)) &&
-                             (!a.scale || (al16(a.scale) && al16(a.shift))) &&
-                             (!a.R1 || (((a.ldr1 & 3) == 0) && ((a.sr1 & 3) == 0) && al16(a.R1))) &&
-                             (!a.R2 || (((a.ldr2 & 3) == 0) && ((a.sr2 & 3) == 0) && al16(a.R2))) &&
-                             (!a.Mk || (((a.ldm & 3) == 0) && al16(a.Mk) && a.mcols >= a.N));   // the vector epilogue loads whole TN-wide mask rows:
-                                                                                                   // a mask narrower than the product keeps the guarded per-column path
-    const bool tiles_ok = aligned && out_aligned && (a.M % BM == 0) && (a.N % BN == 0);
-    if (tiles_ok && !transb && (a.K % BK == 0)) return launch_one<BM, BN, WM, WN, BK, false, false>(a, grid, s);
-    if (tiles_ok && transb && (a.K % BKR == 0)) return launch_one<BM, BN, WM, WN, BKR, true, false>(a, grid, s);
-    if (BKR != BK && tiles_ok && !transb && (a.K % BKR == 0)) return launch_one<BM, BN, WM, WN, BKR, false, false>(a, grid, s);
-    if (transb) return launch_one<BM, BN, WM, WN, BKR, true, true>(a, grid, s);
-    return launch_one<BM, BN, WM, WN, BKR, false, true>(a, grid, s);
-}
-
-int linear_skinny_dispatch(int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb, const float* bias,
-                           int act, float* Y, long ldy, const float* R1, long ldr1, const float* Mk, long ldm, int mcols,
-                           hipStream_t st);   // linear_skinny.hip
+int linear_skinny_rule(int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb);   // linear_skinny.hip
+int linear_skinny_launch(int ng, int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb, const float* bias,
+                         int act, float* Y, long ldy, const float* R1, long ldr1, const float* Mk, long ldm, int mcols,
+                         hipStream_t st);
 
 }  // namespace dispu
 
@@ -608,7 +592,7 @@ using namespace dispu;
 
 // Block-tile choice of dispu_linear as BM*1000 + BN (128128, 64128, 128064, 64064): the largest tile that still
 // yields >= 256 workgroups (one per CU).  Exported so a profiler can name the kernel instantiation.
-static int g_tile_override = 0;     // tools/gemm_bench.py only (dispu_debug_linear_tile): force one tile for a sweep; 0 = the rule below
+static int g_tile_override = 0;     // tools/gemm_bench.py and the kernel-path tests (dispu_debug_linear_tile): force one tile; 0 = the rule below
 DISPU_EXPORT void dispu_debug_linear_tile(int code) { g_tile_override = code; }
 
 // dma: the product can take the DMA pipeline (untransposed, K % 16 == 0; alignment assumed) -- the 64 x 128 tile only pays there
@@ -633,6 +617,110 @@ DISPU_EXPORT int dispu_linear_tile(int batch, int M, int N) { return linear_tile
 // The tile the launch of THIS product takes: transposed-B products and K % 16 != 0 never use the DMA pipeline, and with 256 - 511
 // workgroups that changes the choice (64 x 64 instead of 64 x 128).  dispu_linear_tile (ABI <= 4) assumes the DMA pipeline.
 DISPU_EXPORT int dispu_linear_tile2(int batch, int M, int K, int N, int transb) { return linear_tile_rule(batch, M, N, !transb && (K % 16) == 0); }
+
+// The tiled launch of columns [0, a.N): tile, load path and epilogue.
+static LinearLaunch linear_decide_tiled(const LinearArgs& a, int batch, bool transb) {
+    LinearLaunch l{};
+    l.n0 = 0; l.n1 = a.N; l.transb = transb ? 1 : 0;
+    // BK: slab depth of the interior, untransposed path (16 = the DMA pipeline); BKR: of the register-staged paths (transposed B, edge
+    // tiles): 32, but 16 on the 128 x 256 tile
+    constexpr int BK = 16;
+    int bkr = 32;
+    switch (linear_tile_rule(batch, a.M, a.N, !transb && (a.K % 16) == 0)) {
+        case 128257: l.bm = 128; l.bn = 256; bkr = 16; break;
+        case 128128: l.bm = 128; l.bn = 128; break;
+        case 64128: l.bm = 64; l.bn = 128; break;
+        case 128064: l.bm = 128; l.bn = 64; break;
+        default: l.bm = 64; l.bn = 64; break;
+    }
+    const bool aligned = ((a.ldx & 3) == 0) && ((a.ldw & 3) == 0) && ((a.sx & 3) == 0) && ((a.sw & 3) == 0) &&
+                         ((((uintptr_t)a.X) & 15) == 0) && ((((uintptr_t)a.W) & 15) == 0);
+    // (round 5: interior tiles store / fetch TN-wide vectors in the epilogue -- Y, bias and the optional epilogue operands must allow it)
+    const auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+    const bool out_aligned = ((a.ldy & 3) == 0) && ((a.sy & 3) == 0) && al16(a.Y) && (!a.bias || al16(a.bias)) &&
+                             (!a.scale || (al16(a.scale) && al16(a.shift))) &&
+                             (!a.R1 || (((a.ldr1 & 3) == 0) && ((a.sr1 & 3) == 0) && al16(a.R1))) &&
+                             (!a.R2 || (((a.ldr2 & 3) == 0) && ((a.sr2 & 3) == 0) && al16(a.R2))) &&
+                             (!a.Mk || (((a.ldm & 3) == 0) && al16(a.Mk) && a.mcols >= a.N));   // the vector epilogue loads whole TN-wide mask rows:
+                                                                                                   // a mask narrower than the product keeps the guarded per-column path
+    const bool tiles_ok = aligned && out_aligned && (a.M % l.bm == 0) && (a.N % l.bn == 0);
+    // (an interior untransposed product at BK = BKR = 32 does not exist: K % 32 == 0 implies K % 16 == 0, the DMA pipeline)
+    if (tiles_ok && !transb && (a.K % BK == 0)) { l.bk = BK; l.edge = 0; }
+    else if (tiles_ok && transb && (a.K % bkr == 0)) { l.bk = bkr; l.edge = 0; }
+    else { l.bk = bkr; l.edge = 1; }
+    if (!a.scale && !a.R1 && !a.R2 && !a.Mk)
+        l.epi = (l.bm == 128 && l.bn == 256 && l.bk == 16 && !transb && !l.edge && a.K >= 1024) ? 6 : 0;
+    else if (a.scale && !a.R1 && !a.R2 && !a.Mk) l.epi = 1;
+    else l.epi = a.Mk ? 5 : 4;
+    return l;
+}
+
+// The whole decision for one call (the arguments of linear_impl without act and the stream).  Pointers are tested for NULL and
+// alignment only.  0 launches: an empty product.
+static int linear_decide(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw, int transb,
+                         const float* bias, const float* scale, const float* shift, int act, const float* Y, long ldy, long sy,
+                         const float* R1, long ldr1, long sr1, const float* R2, long ldr2, long sr2, const float* Mk, long ldm, int mcols,
+                         LinearPlan& plan) {
+    plan = LinearPlan{};
+    if (batch < 0 || M < 0 || K <= 0 || N <= 0 || !X || !W || !Y || act < 0 || act > 1 || ((scale == nullptr) != (shift == nullptr)))
+        return (int)hipErrorInvalidValue;
+    if (Mk && batch != 1) return (int)hipErrorInvalidValue;
+    if (batch == 0 || M == 0) return 0;
+    int nh = N;                         // columns [0, nh) still to be placed
+    if (batch == 1 && !scale && !R2) {
+        int ng = linear_skinny_rule(M, K, N, X, ldx, W, ldw, transb);   // latency-bound shapes
+        if (ng == 0) {
+            // a few columns past a multiple of 128 (N = 134: the PointShuffle conv0 gradient): the tiled kernel would spend a second,
+            // almost empty column of 128-wide edge tiles on them.  Columns are independent: the multiple of 128 goes to the tiled
+            // kernel (interior path when aligned), the tail to the skinny kernel.
+            const int tail = N % 128, n0 = N - tail;
+            if (n0 > 0 && tail > 0 && tail <= 32) {
+                const float* Wt = transb ? W + (size_t)n0 * ldw : W + n0;
+                const int ngt = linear_skinny_rule(M, K, tail, X, ldx, Wt, ldw, transb);
+                if (ngt) {
+                    LinearLaunch& t = plan.l[plan.n++];
+                    t.skinny = 1; t.n0 = n0; t.n1 = N; t.transb = transb ? 1 : 0; t.ng = ngt;
+                    nh = n0;
+                    ng = linear_skinny_rule(M, K, nh, X, ldx, W, ldw, transb);    // the head alone may be a skinny shape (128 columns, K <= 32)
+                }
+            }
+        }
+        if (ng) {
+            LinearLaunch& t = plan.l[plan.n++];
+            t.skinny = 1; t.n0 = 0; t.n1 = nh; t.transb = transb ? 1 : 0; t.ng = ng;
+            return 0;
+        }
+    }
+    LinearArgs a{M, K, nh, X, ldx, sx, W, ldw, sw, bias, const_cast<float*>(Y), ldy, sy, R1, ldr1, sr1, R2, ldr2, sr2, act, scale, shift,
+                 (Mk && mcols > 0) ? Mk : nullptr, ldm, mcols};
+    plan.l[plan.n++] = linear_decide_tiled(a, batch, transb != 0);
+    return 0;
+}
+
+// ---- launchers: switch over the decision, choose nothing -------------------------------------------------------------------------
+template <int BM, int BN, int WM, int WN, int BK, bool TRANSB, bool EDGE>
+static int launch_one(const LinearArgs& a, dim3 grid, int epi, hipStream_t s) {
+    switch (epi) {
+        case 0: return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 0>(a, grid, s);
+        case 1: return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 1>(a, grid, s);
+        case 4: return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 4>(a, grid, s);
+        case 5: return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 5>(a, grid, s);
+        case 6:
+            if constexpr (BM == 128 && BN == 256 && BK == 16 && !TRANSB && !EDGE) return launch_epi<BM, BN, WM, WN, BK, TRANSB, EDGE, 6>(a, grid, s);
+            break;
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+// BK: slab depth of the interior, untransposed path (16 = the DMA pipeline); BKR: of the register-staged paths (transposed B, edge tiles)
+template <int BM, int BN, int WM, int WN, int BK, int BKR = BK>
+static int launch_linear(const LinearArgs& a, int batch, const LinearLaunch& l, hipStream_t s) {
+    dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, batch);
+    if (!l.edge && !l.transb) return launch_one<BM, BN, WM, WN, BK, false, false>(a, grid, l.epi, s);
+    if (!l.edge) return launch_one<BM, BN, WM, WN, BKR, true, false>(a, grid, l.epi, s);
+    if (l.transb) return launch_one<BM, BN, WM, WN, BKR, true, true>(a, grid, l.epi, s);
+    return launch_one<BM, BN, WM, WN, BKR, false, true>(a, grid, l.epi, s);
+}
 
 static int linear_impl(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw, int transb,
                        const float* bias, const float* scale, const float* shift, int act, float* Y, long ldy, long sy, const float* R1,
@@ -666,37 +754,59 @@ DISPU_EXPORT int dispu_linear_bn(int batch, int M, int K, int N, const float* X,
                        nullptr, 0, 0, stream);
 }
 
+// The launches a dispu_linear / dispu_linear_bn / dispu_linear_masked call with these arguments would make, without making them: no
+// HIP call, no pointer is dereferenced (NULL-ness and alignment only), so it answers on a machine without a GPU.  include/dispu_hip.h
+// has the layout of `plan`.
+DISPU_EXPORT int dispu_linear_plan(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw,
+                                   int transb, const float* bias, const float* scale, const float* shift, int act, const float* Y, long ldy,
+                                   long sy, const float* R1, long ldr1, long sr1, const float* R2, long ldr2, long sr2, const float* Mk,
+                                   long ldm, int mcols, int* plan) {
+    if (!plan) return (int)hipErrorInvalidValue;
+    LinearPlan p;
+    const int rc = linear_decide(batch, M, K, N, X, ldx, sx, W, ldw, sw, transb, bias, scale, shift, act, Y, ldy, sy, R1, ldr1, sr1, R2,
+                                 ldr2, sr2, Mk, ldm, Mk ? mcols : 0, p);
+    for (int i = 0; i < DISPU_LINEAR_PLAN_INTS; ++i) plan[i] = 0;
+    if (rc) return rc;
+    plan[0] = p.n;
+    for (int i = 0; i < p.n; ++i) {
+        const LinearLaunch& l = p.l[i];
+        int* o = plan + 1 + 10 * i;
+        o[0] = l.skinny ? 0 : 1; o[1] = l.n0; o[2] = l.n1; o[3] = l.bm; o[4] = l.bn; o[5] = l.bk; o[6] = l.transb; o[7] = l.edge;
+        o[8] = l.epi; o[9] = l.ng;
+    }
+    return 0;
+}
+
 static int linear_impl(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw, int transb,
                        const float* bias, const float* scale, const float* shift, int act, float* Y, long ldy, long sy, const float* R1,
                        long ldr1, long sr1, const float* R2, long ldr2, long sr2, const float* Mk, long ldm, int mcols, void* stream) {
-    if (batch < 0 || M < 0 || K <= 0 || N <= 0 || !X || !W || !Y || act < 0 || act > 1 || ((scale == nullptr) != (shift == nullptr)))
-        return (int)hipErrorInvalidValue;
-    if (batch == 0 || M == 0) return 0;
+    LinearPlan plan;
+    int rc = linear_decide(batch, M, K, N, X, ldx, sx, W, ldw, sw, transb, bias, scale, shift, act, Y, ldy, sy, R1, ldr1, sr1, R2, ldr2, sr2,
+                           Mk, ldm, mcols, plan);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (batch == 1 && !scale && !R2) {
-        const int rc = linear_skinny_dispatch(M, K, N, X, ldx, W, ldw, transb, bias, act, Y, ldy, R1, ldr1, Mk, ldm, mcols, s);   // latency-bound shapes
-        if (rc >= 0) return rc;
-        // a few columns past a multiple of 128 (N = 134: the PointShuffle conv0 gradient): the tiled kernel would spend a second,
-        // almost empty column of 128-wide edge tiles on them.  Columns are independent: the multiple of 128 goes to the tiled
-        // kernel (interior path when aligned), the tail to the skinny kernel.
-        const int tail = N % 128, n0 = N - tail;
-        if (n0 > 0 && tail > 0 && tail <= 32) {
+    for (int i = 0; i < plan.n; ++i) {
+        const LinearLaunch& l = plan.l[i];
+        const int n0 = l.n0, nn = l.n1 - l.n0;
+        if (l.skinny) {
+            // columns [n0, n1) of every per-column operand; the mask's column count is relative to n0
             const float* Wt = transb ? W + (size_t)n0 * ldw : W + n0;
-            if (linear_skinny_dispatch(M, K, tail, X, ldx, Wt, ldw, transb, bias ? bias + n0 : nullptr, act, Y + n0, ldy,
-                                       R1 ? R1 + n0 : nullptr, ldr1, Mk ? Mk + n0 : nullptr, ldm, mcols - n0, s) >= 0)
-                return linear_impl(batch, M, K, n0, X, ldx, sx, W, ldw, sw, transb, bias, scale, shift, act, Y, ldy, sy, R1, ldr1, sr1,
-                                   R2, ldr2, sr2, Mk, ldm, mcols, stream);
+            rc = linear_skinny_launch(l.ng, M, K, nn, X, ldx, Wt, ldw, transb, bias ? bias + n0 : nullptr, act, Y + n0, ldy,
+                                      R1 ? R1 + n0 : nullptr, ldr1, Mk ? Mk + n0 : nullptr, ldm, mcols - n0, s);
+        } else {
+            // (tiled launches start at column 0)
+            LinearArgs a{M, K, nn, X, ldx, sx, W, ldw, sw, bias, Y, ldy, sy, R1, ldr1, sr1, R2, ldr2, sr2, act, scale, shift,
+                         (Mk && mcols > 0) ? Mk : nullptr, ldm, mcols};
+            // interior untransposed products: BK = 16 slabs through the DMA pipeline; transposed B / edge tiles: register-staged, BK = 32
+            switch (l.bm * 1000 + l.bn) {
+                case 128256: rc = launch_linear<128, 256, 2, 2, 16>(a, batch, l, s); break;
+                case 128128: rc = launch_linear<128, 128, 2, 2, 16, 32>(a, batch, l, s); break;
+                case 64128: rc = launch_linear<64, 128, 2, 2, 16, 32>(a, batch, l, s); break;
+                case 128064: rc = launch_linear<128, 64, 2, 2, 16, 32>(a, batch, l, s); break;
+                default: rc = launch_linear<64, 64, 2, 2, 16, 32>(a, batch, l, s); break;
+            }
         }
+        if (rc) return rc;
     }
-    LinearArgs a{M, K, N, X, ldx, sx, W, ldw, sw, bias, Y, ldy, sy, R1, ldr1, sr1, R2, ldr2, sr2, act, scale, shift,
-                 (Mk && mcols > 0) ? Mk : nullptr, ldm, mcols};
-    const bool tb = transb != 0;
-    switch (linear_tile_rule(batch, M, N, !tb && (K % 16) == 0)) {
-        // interior untransposed products: BK = 16 slabs through the DMA pipeline; transposed B / edge tiles: register-staged, BK = 32
-        case 128257: return launch_linear<128, 256, 2, 2, 16>(a, batch, tb, s);
-        case 128128: return launch_linear<128, 128, 2, 2, 16, 32>(a, batch, tb, s);
-        case 64128: return launch_linear<64, 128, 2, 2, 16, 32>(a, batch, tb, s);
-        case 128064: return launch_linear<128, 64, 2, 2, 16, 32>(a, batch, tb, s);
-        default: return launch_linear<64, 64, 2, 2, 16, 32>(a, batch, tb, s);
-    }
+    return 0;
 }

@@ -314,16 +314,28 @@ __global__ __launch_bounds__(256) void gemm_bf16_reduce_kernel(int M, int N, int
     }
 }
 
-// tile choice: narrow outputs (N <= 32) take 128 x 32 tiles, launches that would not fill the chip 64 x 64, the rest 128 x 128
+// tile choice (host only; gb_launch and dispu_linear_bf16_plan both ask here): narrow outputs (N <= 32) take 128 x 32 tiles, launches
+// that would not fill the chip 64 x 64, the rest 128 x 128.  As BM * 1000 + BN.
+static int gb_tile_rule(int batch, int M, int N, int splits) {
+    auto tiles = [&](int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
+    if (N <= 32) return 128032;
+    if (tiles(128, 128) * splits * batch < 512) return 64064;
+    return 128128;
+}
+
 template <bool A_KFAST, bool B_KFAST>
 static int gb_launch(const GbArgs& a, int batch, hipStream_t s) {
     auto tiles = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    if (a.N <= 32) {
-        hipLaunchKernelGGL((gemm_bf16_kernel<128, 32, 4, 1, 64, A_KFAST, B_KFAST>), dim3((unsigned)tiles(128, 32), a.splits, batch), dim3(256), 0, s, a);
-    } else if (tiles(128, 128) * a.splits * batch < 512) {
-        hipLaunchKernelGGL((gemm_bf16_kernel<64, 64, 2, 2, 64, A_KFAST, B_KFAST>), dim3((unsigned)tiles(64, 64), a.splits, batch), dim3(256), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, 2, 2, 32, A_KFAST, B_KFAST>), dim3((unsigned)tiles(128, 128), a.splits, batch), dim3(256), 0, s, a);
+    switch (gb_tile_rule(batch, a.M, a.N, a.splits)) {
+        case 128032:
+            hipLaunchKernelGGL((gemm_bf16_kernel<128, 32, 4, 1, 64, A_KFAST, B_KFAST>), dim3((unsigned)tiles(128, 32), a.splits, batch), dim3(256), 0, s, a);
+            break;
+        case 64064:
+            hipLaunchKernelGGL((gemm_bf16_kernel<64, 64, 2, 2, 64, A_KFAST, B_KFAST>), dim3((unsigned)tiles(64, 64), a.splits, batch), dim3(256), 0, s, a);
+            break;
+        default:
+            hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, 2, 2, 32, A_KFAST, B_KFAST>), dim3((unsigned)tiles(128, 128), a.splits, batch), dim3(256), 0, s, a);
+            break;
     }
     return (int)hipGetLastError();
 }
@@ -342,6 +354,13 @@ static void tn_bf16_plan(int batch, int M, int K, int N, int& splits, int& per) 
 }  // namespace dispu
 
 using namespace dispu;
+
+// The block tile (BM * 1000 + BN: 128032, 64064, 128128) the bf16 GEMMs launch for an output of M x N per batch entry in `splits`
+// contraction splits (1 for the NN / NT products).  No HIP call: answers without a GPU.
+DISPU_EXPORT int dispu_linear_bf16_plan(int batch, int M, int N, int splits) {
+    if (batch <= 0 || M <= 0 || N <= 0 || splits <= 0) return 0;
+    return gb_tile_rule(batch, M, N, splits);
+}
 
 // Same contract as dispu_linear (include/dispu_hip.h) with bf16 products: Y = R2 + R1 + act(X . W + bias).
 DISPU_EXPORT int dispu_linear_bf16(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw,

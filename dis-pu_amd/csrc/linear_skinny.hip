@@ -133,22 +133,31 @@ static void launch_skinny(const SkinnyArgs& a, bool transb, hipStream_t st) {
     else hipLaunchKernelGGL((linear_skinny_kernel<NG, false>), grid, block, 0, st, a);
 }
 
-// Returns -1 when the shape is outside this path (the caller then uses the tiled kernel).
-int linear_skinny_dispatch(int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb, const float* bias,
-                           int act, float* Y, long ldy, const float* R1, long ldr1, const float* Mk, long ldm, int mcols,
-                           hipStream_t st) {
-    if (K > 384 || K < 4 || (K & 3) || (ldx & 3) || (((uintptr_t)X) & 15)) return -1;
-    if (transb && ((ldw & 3) || (((uintptr_t)W) & 15))) return -1;
-    if ((long)M * ldx >= (1l << 29) || (long)(transb ? N : K) * ldw >= (1l << 29)) return -1;     // 32-bit byte offsets (buffer loads)
+// The decision, host only: the unroll depth NG (k groups of 16 held in registers: 2, 8, 16 or 24) this path takes for the shape,
+// or 0 when the shape is outside it (the caller then uses the tiled kernel).  Pointers are looked at for alignment only.
+int linear_skinny_rule(int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb) {
+    if (K > 384 || K < 4 || (K & 3) || (ldx & 3) || (((uintptr_t)X) & 15)) return 0;
+    if (transb && ((ldw & 3) || (((uintptr_t)W) & 15))) return 0;
+    if ((long)M * ldx >= (1l << 29) || (long)(transb ? N : K) * ldw >= (1l << 29)) return 0;     // 32-bit byte offsets (buffer loads)
     // where the tiled kernel does badly: too few 64 x 64 tiles to fill the chip (latency-bound), outputs narrower than half
     // a tile, or a contraction shorter than one K-slab (then it only moves data, mostly through predicated edge paths)
     const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-    if (!(N <= 64 && tiles64 < 256) && !(N <= 32) && !(K <= 32 && N <= 128)) return -1;
+    if (!(N <= 64 && tiles64 < 256) && !(N <= 32) && !(K <= 32 && N <= 128)) return 0;
+    return K <= 32 ? 2 : K <= 128 ? 8 : K <= 256 ? 16 : 24;
+}
+
+// One launch at the depth linear_skinny_rule returned.
+int linear_skinny_launch(int ng, int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb, const float* bias,
+                         int act, float* Y, long ldy, const float* R1, long ldr1, const float* Mk, long ldm, int mcols,
+                         hipStream_t st) {
     SkinnyArgs a{M, K, N, X, ldx, W, ldw, bias, act, Y, ldy, R1, ldr1, (Mk && mcols > 0) ? Mk : nullptr, ldm, mcols};
-    if (K <= 32) launch_skinny<2>(a, transb != 0, st);
-    else if (K <= 128) launch_skinny<8>(a, transb != 0, st);
-    else if (K <= 256) launch_skinny<16>(a, transb != 0, st);
-    else launch_skinny<24>(a, transb != 0, st);
+    switch (ng) {
+        case 2: launch_skinny<2>(a, transb != 0, st); break;
+        case 8: launch_skinny<8>(a, transb != 0, st); break;
+        case 16: launch_skinny<16>(a, transb != 0, st); break;
+        case 24: launch_skinny<24>(a, transb != 0, st); break;
+        default: return (int)hipErrorInvalidValue;
+    }
     return (int)hipGetLastError();
 }
 

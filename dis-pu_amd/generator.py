@@ -46,6 +46,20 @@ class _Opts(object):
     up_ratio = 4
 
 
+def linear_profile_name(plan, batch, M, K, N):
+    """The profile row of a dispu_linear call from its plan (_lib.linear_plan): the instantiation rocprofv3 reports,
+    "linear<BM, BN, 2, 2, BK, transb, edge, epi>[MxKxN]" or "linear_skinny<NG, transb>[MxKxN]".  A call split into a tiled head and a
+    skinny tail is named after its head."""
+    tf = lambda v: "true" if v else "false"
+    tiled = [l for l in plan if l[0] == "tiled"]
+    if tiled:
+        _, _, _, bm, bn, bk, tb, edge, epi = tiled[0]
+        return "linear<%d, %d, 2, 2, %d, %s, %s, %d>[%dx%dx%d]" % (bm, bn, bk, tf(tb), tf(edge), epi, M * batch, K, N)
+    if plan:
+        return "linear_skinny<%d, %s>[%dx%dx%d]" % (plan[-1][3], tf(plan[-1][4]), M, K, N)
+    return "linear"
+
+
 class Generator(object):
     """Generator(opts, is_training=False)(inputs[B,N,3]) -> (coarse[B,4N,3], fine[B,4N,3]).
 
@@ -207,31 +221,11 @@ class Generator(object):
         p = lambda t, off=0: _lib.C.c_void_p(t.data_ptr() + 4 * off) if t is not None else _lib.C.c_void_p(0)
         name = "linear"
         if self.profile is not None:     # "linear<BM, BN, 2, 2, BK, transb, edge, epi>[MxKxN]": the instantiation rocprofv3 reports
-            t = L.dispu_linear_tile2(batch, M, K, N, int(bool(transb)))
-            bm, bn = {128257: (128, 256), 128128: (128, 128), 64128: (64, 128), 128064: (128, 64)}.get(t, (64, 64))
-            al = lambda q, o=0: q is None or (q.data_ptr() + 4 * o) % 16 == 0
-            ok = (M % bm == 0 and N % bn == 0 and ldx % 4 == 0 and ldw % 4 == 0 and sx % 4 == 0 and sw % 4 == 0 and al(X, xoff) and al(W, woff)
-                  and ldy % 4 == 0 and sy % 4 == 0 and al(Y, yoff) and al(bias) and (R1 is None or (R1.stride(0) % 4 == 0 and al(R1)))
-                  and (R2 is None or (R2.stride(0) % 4 == 0 and al(R2))))
-            bkr = 16 if t == 128257 else 32                 # register-staged paths (transposed B, edge tiles) of the smaller tiles: BK 32
-            if ok and not transb and K % 16 == 0:
-                bk, edge = 16, False                        # the DMA pipeline
-            elif ok and K % bkr == 0:
-                bk, edge = bkr, False
-            else:
-                bk, edge = bkr, True
-            epi = 0 if (R1 is None and R2 is None) else 4       # epilogue variant: 0 bias/act, 4 with residual inputs
-            if epi == 0 and (bm, bn, bk) == (128, 256, 16) and not transb and not edge and K >= 1024:
-                epi = 6                                          # long contractions: an instantiation of their own (csrc/linear.hip)
-            name = "linear<%d, %d, 2, 2, %d, %s, %s, %d>[%dx%dx%d]" % (bm, bn, bk, "true" if transb else "false",
-                                                                      "true" if edge else "false", epi, M * batch, K, N)
-            # latency-bound shapes leave the tiled kernel (csrc/linear_skinny.hip:linear_skinny_dispatch; same conditions)
-            tiles64 = ((M + 63) // 64) * ((N + 63) // 64)
-            if (batch == 1 and R2 is None and 4 <= K <= 384 and K % 4 == 0 and ldx % 4 == 0 and (X.data_ptr() + 4 * xoff) % 16 == 0
-                    and not (transb and (ldw % 4 or (W.data_ptr() + 4 * woff) % 16))
-                    and ((N <= 64 and tiles64 < 256) or N <= 32 or (K <= 32 and N <= 128))):
-                name = "linear_skinny<%d, %s>[%dx%dx%d]" % (2 if K <= 32 else 8 if K <= 128 else 16 if K <= 256 else 24,
-                                                           "true" if transb else "false", M, K, N)
+            a = lambda t, off=0: (t.data_ptr() + 4 * off) if t is not None else None
+            plan = _lib.linear_plan(batch, M, K, N, a(X, xoff), ldx, sx, a(W, woff), ldw, sw, transb, a(bias), None, None, act, a(Y, yoff), ldy,
+                                    sy, a(R1), R1.stride(0) if R1 is not None else 0, 0, a(R2), R2.stride(0) if R2 is not None else 0, 0,
+                                    None, 0, 0)
+            name = linear_profile_name(plan, batch, M, K, N)
         self._call(name, L.dispu_linear, batch, M, K, N,
                    p(X, xoff), ldx, sx, p(W, woff), ldw, sw, transb, p(bias), act, p(Y, yoff), ldy, sy, p(R1),
                    R1.stride(0) if R1 is not None else 0, 0, p(R2), R2.stride(0) if R2 is not None else 0, 0, st)

@@ -265,6 +265,20 @@ int dispu_linear_tile(int batch, int M, int N);
 int dispu_linear_tile2(int batch, int M, int K, int N, int transb);
 /* benchmarking aid (tools/gemm_bench.py): force the block tile of every later dispu_linear call; 0 restores the rule.  Not used by the product path. */
 void dispu_debug_linear_tile(int code);
+/* The launches a dispu_linear / dispu_linear_bn / dispu_linear_masked call with these arguments would make (debug / profiling
+ * aid; the launchers run off the same decision).  Takes every argument of the three entries but the stream (scale / shift NULL for
+ * dispu_linear, Mk NULL and mcols 0 without a mask).  Pointers are tested for NULL and alignment only and never dereferenced, and
+ * no HIP call is made: it answers on a machine without a GPU.  Returns 0, or the error the call itself would return.
+ * plan[0]: number of launches (0 for an empty product, 1, or 2 when the last N % 128 <= 32 columns go to the skinny kernel).
+ * Launch i at plan[1 + 10 i ...]: kind (0 skinny kernel, 1 tiled kernel), first column, end column, then for the tiled kernel
+ * BM, BN, BK, transb, edge (1: predicated loaders), EPI (0 plain, 1 BatchNorm fold, 4 residuals, 5 mask, 6 = 0 on the long-K
+ * instantiation), 0; for the skinny kernel 0, 0, 0, transb, 0, 0, NG (k groups of 16 in registers: 2, 8, 16, 24).
+ * Launches are listed in issue order.  Honours dispu_debug_linear_tile. */
+#define DISPU_LINEAR_PLAN_INTS 21
+int dispu_linear_plan(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw,
+                      int transb, const float* bias, const float* scale, const float* shift, int act, const float* Y, long ldy,
+                      long sy, const float* R1, long ldr1, long sr1, const float* R2, long ldr2, long sr2, const float* Mk,
+                      long ldm, int mcols, int* plan);
 /* K <= 4 inputs, N in {16, 24} outputs (feature_extraction layer0, ops.py:1449-1451). */
 int dispu_linear_small_k(long rows, int K, int N, const float* X, long ldx, const float* W, const float* bias, int act,
                          float* Y, long ldy, void* stream);
@@ -533,6 +547,10 @@ int dispu_linear_masked(int batch, int M, int K, int N, const float* X, long ldx
 int dispu_linear_bf16_masked(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw,
                              int transb, const float* bias, int act, float* Y, long ldy, long sy, const float* R1, long ldr1, long sr1,
                              const float* Mk, long ldm, int mcols, void* stream);
+/* The block tile dispu_linear_bf16 / _bf16s / _bf16_masked (splits = 1) and the dispu_linear_tn_bf16* products launch for an
+ * M x N output per batch entry, as BM*1000 + BN: 128032 (N <= 32), 64064 (fewer than 512 tiles of 128 x 128 over splits and batch)
+ * or 128128; 0 for an empty product.  Debug / profiling aid like dispu_linear_plan: no HIP call. */
+int dispu_linear_bf16_plan(int batch, int M, int N, int splits);
 /* Streaming bf16-product GEMM for the step's largest dense products (Trainer(dtype="bf16"); csrc/linear_bf16_stream.hip): operands by
  * DMA into LDS, X fp32 rounded to bf16 (nearest even) in front of the matrix pipe, B supplied as Bt [N][K] bf16 (k contiguous) by
  * dispu_bf16_pack (transpose = 1 of W [K][N] for Y = X.W; transpose = 0 of W [N][K] for dX = dZ.W^T).  Same products as
