@@ -15,6 +15,9 @@ ARITH_PINNED_EXP = 2   # OR-able, approx_match only (bit-reproducible exp; parit
 MESH_BRUTE_FORCE = 8   # OR-able, point_to_mesh only (visit every face tile; A/B tests)
 MESH_TILE = 64         # faces per tile of point_to_mesh's face layout
 LINEAR_PLAN_INTS = 21  # include/dispu_hip.h: DISPU_LINEAR_PLAN_INTS
+POISSON_MAX_N = 49152       # include/dispu_hip.h: DISPU_POISSON_MAX_N
+POISSON_MAX_ROUNDS = 256    # include/dispu_hip.h: DISPU_POISSON_MAX_ROUNDS
+SORT_ROWS_MAX_K = 4096      # dispu_sort_rows_i32
 
 _vp, _i, _sz, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_long
 
@@ -193,6 +196,11 @@ SIGNATURES = {
                                       _vp, _vp]),
     "dispu_geodesic_disk_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dispu_geodesic_disk_fill": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dispu_mesh_sample": (_i, [_i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _vp, _vp, _vp, _vp]),
+    "dispu_poisson_disk_scratch_bytes": (_sz, [_i, _i]),
+    "dispu_poisson_disk_keep": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "dispu_poisson_disk_select": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "dispu_sort_rows_i32": (_i, [_i, _i, _vp, _vp]),
 }
 
 class TnReduceDesc(C.Structure):

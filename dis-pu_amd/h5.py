@@ -1,4 +1,5 @@
-"""Read-only HDF5 access for the training-patch file (the data format on the input side of the path).
+"""HDF5 access for the training-patch file (the data format on the input side of the path): whole-dataset reads (`File`)
+and, for the files tools/make_dataset.py produces, whole-dataset writes (`write`).
 
 The reference opens `PUGAN_poisson_256_poisson_1024.h5` with h5py and slices whole datasets
 (DisPU/dataset.py:52-78: `f['poisson_%d' % num][:]`).  h5py is not in this image, but the HDF5 C library it wraps is
@@ -8,6 +9,9 @@ filter the library supports (contiguous, chunked, gzip, shuffle) therefore reads
 
 Library lookup order: $DISPU_HDF5_LIB, ctypes.util.find_library('hdf5'), /opt/conda/lib, the usual system directories.
 A missing library is an error (no fallback format guessing).
+
+`write(path, {name: array})` creates a file of contiguous datasets in native byte order through the same library (H5Fcreate,
+H5Screate_simple, H5Dcreate2, H5Dwrite) for float32 / float64 / int32 / int64 / uint8 arrays; `File` reads it back.
 """
 import ctypes
 import ctypes.util
@@ -22,6 +26,7 @@ _hsize_t = ctypes.c_uint64
 _herr_t = ctypes.c_int
 
 H5F_ACC_RDONLY = 0
+H5F_ACC_TRUNC = 2
 H5P_DEFAULT = 0
 H5S_ALL = 0
 H5T_INTEGER, H5T_FLOAT = 0, 1                # H5T_class_t
@@ -65,6 +70,10 @@ def lib():
         "H5get_libversion": (_herr_t, [ctypes.POINTER(ctypes.c_uint)] * 3),
         "H5Fopen": (_hid_t, [ctypes.c_char_p, ctypes.c_uint, _hid_t]),
         "H5Fclose": (_herr_t, [_hid_t]),
+        "H5Fcreate": (_hid_t, [ctypes.c_char_p, ctypes.c_uint, _hid_t, _hid_t]),
+        "H5Screate_simple": (_hid_t, [ctypes.c_int, ctypes.POINTER(_hsize_t), ctypes.POINTER(_hsize_t)]),
+        "H5Dcreate2": (_hid_t, [_hid_t, ctypes.c_char_p, _hid_t, _hid_t, _hid_t, _hid_t, _hid_t]),
+        "H5Dwrite": (_herr_t, [_hid_t, _hid_t, _hid_t, _hid_t, _hid_t, ctypes.c_void_p]),
         "H5Dopen2": (_hid_t, [_hid_t, ctypes.c_char_p, _hid_t]),
         "H5Dclose": (_herr_t, [_hid_t]),
         "H5Dget_space": (_hid_t, [_hid_t]),
@@ -210,3 +219,43 @@ class File(object):
         finally:
             h.H5Dclose(did)
         return out
+
+
+# numpy dtype -> the library's native type id (a global of the library, valid after H5open)
+_WRITE_TYPES = {"float32": "H5T_NATIVE_FLOAT_g", "float64": "H5T_NATIVE_DOUBLE_g", "int32": "H5T_NATIVE_INT32_g",
+                "int64": "H5T_NATIVE_INT64_g", "uint8": "H5T_NATIVE_UINT8_g"}
+
+
+def write(path, datasets):
+    """Create (or replace) the HDF5 file `path` with one contiguous dataset per item of `datasets` ({name: array}), in native byte
+    order, at the root.  Arrays of float32, float64, int32, int64 or uint8 and at least one dimension; anything else raises TypeError
+    before the file is touched."""
+    h = lib()
+    arrays = []
+    for name, a in datasets.items():
+        a = np.asarray(a)
+        if a.dtype.name not in _WRITE_TYPES or not a.dtype.isnative:
+            raise TypeError("dataset %r: dtype %s is not one of %s (native byte order)" % (name, a.dtype, ", ".join(sorted(_WRITE_TYPES))))
+        if a.ndim == 0 or not name or "/" in name:
+            raise TypeError("dataset %r: need a plain name and an array of at least one dimension" % name)
+        arrays.append((name, np.ascontiguousarray(a)))
+    fid = h.H5Fcreate(os.fsencode(path), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT)
+    if fid < 0:
+        raise IOError("HDF5: cannot create %s" % path)
+    try:
+        for name, a in arrays:
+            tid = _hid_t.in_dll(h, _WRITE_TYPES[a.dtype.name]).value
+            dims = (_hsize_t * a.ndim)(*a.shape)
+            sid = _check(h.H5Screate_simple(a.ndim, dims, None), "dataspace of %r" % name)
+            try:
+                did = _check(h.H5Dcreate2(fid, name.encode(), tid, sid, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), "create %r" % name)
+                try:
+                    if a.size:
+                        _check(h.H5Dwrite(did, tid, H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(ctypes.c_void_p)), "write %r" % name)
+                finally:
+                    h.H5Dclose(did)
+            finally:
+                h.H5Sclose(sid)
+    finally:
+        if h.H5Fclose(fid) < 0:
+            raise IOError("HDF5: closing %s failed" % path)

@@ -56,8 +56,8 @@ extern "C" {
  * 5 = round 6: dispu_approx_match works inside the reference op's own temp ([b, 2(n+m)] floats; until 4 it needed
  * dispu_approx_match_scratch_bytes and had no way to refuse less); the tiled fast path is dispu_approx_match_ws with an explicit size.
  * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std) and its geodesic disks
- * (dispu_geodesic_*) and the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments):
- * additions only. */
+ * (dispu_geodesic_*), the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments) and the
+ * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -832,6 +832,45 @@ int dispu_geodesic_disk_fill(int S, int R, const long long* cand_off, const int*
 /* per-row mean and standard deviation (ddof 0) of x[b, n] over the non-NaN entries, fp64: out [b][2] (np.nanmean / np.nanstd of
  * evaluate.py:158-159,202-203 on the P2F distances; the std companion of dispu_row_mean_max). */
 int dispu_row_mean_std(int b, int n, const float* x, double* out, void* stream);
+
+/* ---- meshes -> data: surface samples, Poisson-disk selection (no reference counterpart: the reference's patches and test clouds were
+ * Poisson-disk sampled upstream with tools in neither tree; the yardstick is the sequential float64 / numpy restatement in
+ * tests/mesh_sample_oracle.py, reproduced bit for bit).  dis-pu_amd/mesh_sample.py, csrc/mesh_sample.hip, csrc/poisson_disk.hip -------- */
+/* count samples on the surface of a triangle mesh, face chosen with probability proportional to its area, uniform inside the face.
+ * verts [V,3] f32, faces [F,3] i32, cum [F+1] f64 = the normalised cumulative face areas (cum[0] = 0).  Sample i draws Philox4x32-10
+ * with counter (i lo, i hi, 0, 0xD15C5A3D) and key (seed lo, seed hi) -> w0..w3:  u = ((w0 << 21) | (w1 >> 11)) 2^-53;  face = the largest
+ * f in [0, F) with cum[f] <= u (a face of zero area is never drawn);  r1 = (w2 >> 8) 2^-24, r2 = (w3 >> 8) 2^-24, s = sqrt((double)r1),
+ * b = (1 - s, s (1 - r2), s r2);  point = (b0 v0 + b1 v1) + b2 v2 per coordinate in fp64, no contraction, rounded to fp32 once.
+ * -> points [count,3] f32, face [count] i32, bary [count,3] f64 (NULL: not written).  One thread per sample and no state: sample i does
+ * not depend on count or on the launch shape. */
+int dispu_mesh_sample(int V, int F, const float* verts, const int* faces, const double* cum, int count, unsigned long long seed,
+                      float* points, int* face, double* bary, void* stream);
+/* Greedy dart throwing over points [b,n,3] in index order: keep[i] = 1 iff no j < i has keep[j] and d2(p_i, p_j) < fl32(r r), with
+ * d2 = (dx dx + dy dy) + dz dz in fp32 (DISPU_ARITH_PLAIN) and a strict comparison; radius [b] per cloud, r <= 0 keeps everything.
+ * Computed in parallel rounds, one workgroup per cloud over a 32^3 grid (csrc/poisson_disk.hip); the result is the sequential one
+ * whatever the timing, and identical from run to run (no float atomics).  keep [b,n] u8, count [b] i32 = kept points per cloud,
+ * status [b] i32: bit 0 = the round loop hit DISPU_POISSON_MAX_ROUNDS (a dependency chain that long; the outputs are then incomplete).
+ * Coordinates must be finite.  scratch >= dispu_poisson_disk_scratch_bytes(b, n), 16-byte aligned; refused (hipErrorInvalidValue) when
+ * smaller, and for n > DISPU_POISSON_MAX_N.
+ * DISPU_POISSON_MAX_N: a cloud lives in ONE workgroup whose LDS holds the 16-bit offsets of the 32^3 cells (64 KB), one state byte per
+ * point and one selection bit per point: 128 + 65536 + n + n / 8 bytes.  The 16-bit offsets bound n below 65536; 49152 (6 x 8192: up to
+ * 6 x oversampling of an 8192-point cloud) needs 118 KB of the 160 KB a CU of this part has.  Larger clouds would need a
+ * multi-workgroup tier, which does not exist. */
+#define DISPU_POISSON_MAX_N 49152
+#define DISPU_POISSON_MAX_ROUNDS 256
+size_t dispu_poisson_disk_scratch_bytes(int b, int n);
+int dispu_poisson_disk_keep(int b, int n, const float* points, const float* radius, unsigned char* keep, int* count, void* scratch,
+                            size_t scratch_bytes, int* status, void* stream);
+/* Exactly m points per cloud: bisection of the radius on the device (lo = 0, hi = r_hi[c]; steps times mid = 0.5f (lo + hi), the keep
+ * count at mid >= m ? lo = mid : hi = mid, fp32), then idx [b,m] i32 = the first m kept indices (ascending) at r = lo,
+ * r_out [b] = lo, count_out [b] = the keep count at lo (>= m; the surplus count - m is what the resolution of `steps` leaves).  Any
+ * r_hi is legal, a poor one only costs resolution (the natural one: the hexagonal-lattice spacing sqrt(2 area / (sqrt 3 m))).
+ * One launch, no host readback.  status as above (bit 1: fewer than m indices were written, only together with bit 0).  1 <= m <= n. */
+int dispu_poisson_disk_select(int b, int n, int m, int steps, const float* points, const float* r_hi, int* idx, float* r_out,
+                              int* count_out, void* scratch, size_t scratch_bytes, int* status, void* stream);
+/* every row of idx [b,k] i32 ascending, in place (k <= 4096; one workgroup per row, bitonic network in LDS).  dispu_knn_patch returns
+ * a region's points by distance; the greedy order of the selection must be the sample order, i.e. the index order. */
+int dispu_sort_rows_i32(int b, int k, int* idx, void* stream);
 
 #ifdef __cplusplus
 }
