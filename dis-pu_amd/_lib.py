@@ -2,6 +2,7 @@
 
 There is NO CPU fallback: if the library is missing or a call fails, the op raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -121,6 +122,9 @@ SIGNATURES = {
     "dispu_linear_tn_scratch_floats": (_l, [_i, _i, _i, _i]),
     "dispu_linear_tn": (_i, [_i, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _l, _vp]),
     "dispu_ps_local_grad": (_i, [_l, _i] + [_vp] * 3 + [_l] + [_vp] * 14),
+    "dispu_linear_tn_plan": (_i, [_i, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _l, _vp]),
+    "dispu_linear_tn_bf16_plan": (_i, [_i, _i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _l, _i, _vp]),
+    "dispu_linear_tn_bf16_stream_plan": (_i, [_i, _i, _i, _vp, _l, _vp, _l, _i, _vp, _l, _i, _vp, _vp, _l, _vp]),
     "dispu_tn_defer": (_i, [_vp]),
     "dispu_tn_reduce_grouped": (_i, [_i, _vp, _vp, _vp]),
     "dispu_act_bias_grad_scratch_floats": (_l, [_l, _i]),
@@ -258,7 +262,8 @@ class Tape(object):
 
 
 _TAPE = None                     # the Tape being recorded, if any
-_NO_TAPE = ("dispu_version", "dispu_error_string", "dispu_linear_tile", "dispu_linear_tile2", "dispu_linear_plan", "dispu_linear_bf16_plan")
+_NO_TAPE = ("dispu_version", "dispu_error_string", "dispu_linear_tile", "dispu_linear_tile2", "dispu_linear_plan", "dispu_linear_bf16_plan",
+            "dispu_linear_tn_plan", "dispu_linear_tn_bf16_plan", "dispu_linear_tn_bf16_stream_plan")
 
 
 class _TapeLib(object):
@@ -333,6 +338,38 @@ def linear_plan(batch, M, K, N, X, ldx, sx, W, ldw, sw, transb, bias, scale, shi
         kind, n0, n1, bm, bn, bk, tb, edge, epi, ng = buf[1 + 10 * i:11 + 10 * i]
         out.append(("tiled", n0, n1, bm, bn, bk, tb, edge, epi) if kind else ("skinny", n0, n1, ng, tb))
     return out
+
+
+TnPlan = collections.namedtuple("TnPlan", "rc kind TK TNN edge splits rows direct reduce reduce_grid capped wpb grid_y")
+TnBf16Plan = collections.namedtuple("TnBf16Plan", "rc kind tile splits rows reduce rows_p")
+TnStreamPlan = collections.namedtuple("TnStreamPlan", "rc BN storage splits rows")
+TN_KINDS = ("none", "narrow", "tiled", "clear")
+TN_REDUCE = ("none", "scalar", "vec4")
+
+
+def linear_tn_plan(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats):
+    """dispu_linear_tn_plan: the arguments of dispu_linear_tn without the stream -> TnPlan (kind and reduce as names from TN_KINDS /
+    TN_REDUCE).  rc is the error the entry would return (the plan is then empty); nothing is raised, dereferenced or launched."""
+    buf = (_i * 12)()
+    rc = lib().dispu_linear_tn_plan(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats, buf)
+    v = list(buf)
+    return TnPlan(rc, TN_KINDS[v[0]], v[1], v[2], v[3], v[4], v[5], v[6], TN_REDUCE[v[7]], v[8], v[9], v[10], v[11])
+
+
+def linear_tn_bf16_plan(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats, storage=0):
+    """dispu_linear_tn_bf16_plan: the arguments of dispu_linear_tn_bf16s without the stream -> TnBf16Plan."""
+    buf = (_i * 6)()
+    rc = lib().dispu_linear_tn_bf16_plan(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats,
+                                         storage, buf)
+    v = list(buf)
+    return TnBf16Plan(rc, TN_KINDS[v[0]], v[1], v[2], v[3], v[4], v[5])
+
+
+def linear_tn_bf16_stream_plan(M, K, N, X, ldx, Z, ldz, storage, out, ldo, accumulate, dbias, scratch, scratch_floats):
+    """dispu_linear_tn_bf16_stream_plan: the arguments of dispu_linear_tn_bf16_stream without the stream -> TnStreamPlan."""
+    buf = (_i * 4)()
+    rc = lib().dispu_linear_tn_bf16_stream_plan(M, K, N, X, ldx, Z, ldz, storage, out, ldo, accumulate, dbias, scratch, scratch_floats, buf)
+    return TnStreamPlan(rc, *list(buf))
 
 
 def stream_ptr(device=None):

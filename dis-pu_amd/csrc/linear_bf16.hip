@@ -324,9 +324,9 @@ static int gb_tile_rule(int batch, int M, int N, int splits) {
 }
 
 template <bool A_KFAST, bool B_KFAST>
-static int gb_launch(const GbArgs& a, int batch, hipStream_t s) {
+static int gb_launch_tile(const GbArgs& a, int batch, int tile, hipStream_t s) {
     auto tiles = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    switch (gb_tile_rule(batch, a.M, a.N, a.splits)) {
+    switch (tile) {
         case 128032:
             hipLaunchKernelGGL((gemm_bf16_kernel<128, 32, 4, 1, 64, A_KFAST, B_KFAST>), dim3((unsigned)tiles(128, 32), a.splits, batch), dim3(256), 0, s, a);
             break;
@@ -338,6 +338,11 @@ static int gb_launch(const GbArgs& a, int batch, hipStream_t s) {
             break;
     }
     return (int)hipGetLastError();
+}
+
+template <bool A_KFAST, bool B_KFAST>
+static int gb_launch(const GbArgs& a, int batch, hipStream_t s) {
+    return gb_launch_tile<A_KFAST, B_KFAST>(a, batch, gb_tile_rule(batch, a.M, a.N, a.splits), s);
 }
 
 static void tn_bf16_plan(int batch, int M, int K, int N, int& splits, int& per) {
@@ -421,6 +426,44 @@ DISPU_EXPORT int dispu_linear_tn_bf16(int batch, int M, int K, int N, const floa
     return dispu_linear_tn_bf16s(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats, 0, stream);
 }
 
+// The one host decision of dispu_linear_tn_bf16 / _bf16s (dispu_linear_tn_bf16_plan exports it): refusal, no-op, the M == 0 clear, or the
+// product's block tile, its split of the rows, and whether partial tiles + gemm_bf16_reduce_kernel follow.  Dereferences nothing.
+struct TnBf16Decision {
+    int rc;
+    int kind;                            // 0 nothing to launch, 2 product, 3 M == 0 (clear out / dbias unless accumulating)
+    int tile, splits, per, reduce, rows_p;
+};
+
+static TnBf16Decision tn_bf16_decide(int batch, int M, int K, int N, const void* X, const void* Z, const float* out, const float* dbias,
+                                     const float* scratch, long scratch_floats) {
+    TnBf16Decision d{};
+    if (batch < 0 || M < 0 || K < 0 || N < 0 || !out || (dbias && batch != 1)) { d.rc = (int)hipErrorInvalidValue; return d; }
+    if (batch == 0 || K == 0 || N == 0) return d;
+    if (M == 0) { d.kind = 3; return d; }
+    if (!X || !Z) { d.rc = (int)hipErrorInvalidValue; return d; }             // (as dispu_linear_tn_bf16_stream refuses them)
+    tn_bf16_plan(batch, M, K, N, d.splits, d.per);
+    d.rows_p = dbias ? K + 1 : K;
+    if (d.splits > 1 && (!scratch || scratch_floats < (long)batch * d.splits * (long)d.rows_p * N)) {
+        d = TnBf16Decision{};
+        d.rc = (int)hipErrorInvalidValue;
+        return d;
+    }
+    d.kind = 2;
+    d.tile = gb_tile_rule(batch, K, N, d.splits);
+    d.reduce = d.splits > 1 ? 1 : 0;
+    return d;
+}
+
+DISPU_EXPORT int dispu_linear_tn_bf16_plan(int batch, int M, int K, int N, const void* X, long ldx, long sx, const void* Z, long ldz, long sz,
+                                           const float* out, long ldo, long so, int accumulate, const float* dbias, const float* scratch,
+                                           long scratch_floats, int storage, int* plan) {
+    (void)ldx; (void)sx; (void)ldz; (void)sz; (void)ldo; (void)so; (void)accumulate; (void)storage;
+    if (!plan) return (int)hipErrorInvalidValue;
+    const TnBf16Decision d = tn_bf16_decide(batch, M, K, N, X, Z, out, dbias, scratch, scratch_floats);
+    plan[0] = d.kind, plan[1] = d.tile, plan[2] = d.splits, plan[3] = d.per, plan[4] = d.reduce, plan[5] = d.rows_p;
+    return d.rc;
+}
+
 // dispu_linear_tn_bf16 with bf16-STORED operands: storage bit 0: X holds bf16 elements, bit 1: Z does (the bias gradient is then the
 // sum of the stored, i.e. rounded, values).
 DISPU_EXPORT int dispu_linear_tn_bf16s(int batch, int M, int K, int N, const void* Xv, long ldx, long sx, const void* Zv, long ldz, long sz,
@@ -432,35 +475,31 @@ DISPU_EXPORT int dispu_linear_tn_bf16s(int batch, int M, int K, int N, const voi
     dispu_tn_reduce_desc* sink = tn_take_defer();                 // dispu_tn_defer (train_gemm.hip): describe the reduction, do not launch it
     if (sink) sink->splits = 0;
     if (batch != 1) sink = nullptr;
-    if (batch < 0 || M < 0 || K < 0 || N < 0 || !out || (dbias && batch != 1)) return (int)hipErrorInvalidValue;
-    if (batch == 0 || K == 0 || N == 0) return 0;
+    const TnBf16Decision d = tn_bf16_decide(batch, M, K, N, Xv, Zv, out, dbias, scratch, scratch_floats);
+    if (d.rc != 0 || d.kind == 0) return d.rc;
     hipStream_t s = (hipStream_t)stream;
-    if (M == 0) {
+    if (d.kind == 3) {
         if (!accumulate) {
             for (int z = 0; z < batch; ++z) DISPU_TRY(hipMemset2DAsync(out + (size_t)z * so, sizeof(float) * ldo, 0, sizeof(float) * N, K, s));
             if (dbias) DISPU_TRY(hipMemsetAsync(dbias, 0, sizeof(float) * N, s));
         }
         return 0;
     }
-    int splits, per;
-    tn_bf16_plan(batch, M, K, N, splits, per);
-    if (splits == 1) {       // one workgroup per output tile walks the whole contraction; accumulate = out as its own residual
+    if (!d.reduce) {         // one workgroup per output tile walks the whole contraction; accumulate = out as its own residual
         GbArgs a{K, N, M, X, 1, ldx, sx, Z, 1, ldz, sz, out, ldo, so, nullptr, 0, accumulate ? out : nullptr, ldo, so, nullptr, 0, 0, 1,
-                 per, nullptr, dbias, accumulate, nullptr, 0, 0, xa, zb, 0};
-        return gb_launch<false, false>(a, batch, s);
+                 d.per, nullptr, dbias, accumulate, nullptr, 0, 0, xa, zb, 0};
+        return gb_launch_tile<false, false>(a, batch, d.tile, s);
     }
-    const long rows_p = dbias ? (long)K + 1 : (long)K;
-    if (!scratch || scratch_floats < (long)batch * splits * rows_p * N) return (int)hipErrorInvalidValue;
-    GbArgs a{K, N, M, X, 1, ldx, sx, Z, 1, ldz, sz, out, ldo, so, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, splits, per, scratch, dbias,
+    GbArgs a{K, N, M, X, 1, ldx, sx, Z, 1, ldz, sz, out, ldo, so, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, d.splits, d.per, scratch, dbias,
              accumulate, nullptr, 0, 0, xa, zb, 0};
-    const int rc = gb_launch<false, false>(a, batch, s);
+    const int rc = gb_launch_tile<false, false>(a, batch, d.tile, s);
     if (rc != 0) return rc;
-    const long total = rows_p * N;
+    const long total = (long)d.rows_p * N;
     if (sink) {
-        *sink = dispu_tn_reduce_desc{scratch, out, dbias, ldo, total, K, N, splits, (int)rows_p, accumulate, accumulate, 1, 0};
+        *sink = dispu_tn_reduce_desc{scratch, out, dbias, ldo, total, K, N, d.splits, d.rows_p, accumulate, accumulate, 1, 0};
         return 0;
     }
-    hipLaunchKernelGGL(gemm_bf16_reduce_kernel, dim3((unsigned)((total + 31) / 32), batch), dim3(256), 0, s, K, N, splits, dbias ? 1 : 0,
+    hipLaunchKernelGGL(gemm_bf16_reduce_kernel, dim3((unsigned)((total + 31) / 32), batch), dim3(256), 0, s, K, N, d.splits, dbias ? 1 : 0,
                        scratch, out, ldo, so, accumulate, dbias);
     return (int)hipGetLastError();
 }

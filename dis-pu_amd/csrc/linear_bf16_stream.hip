@@ -405,20 +405,51 @@ DISPU_EXPORT long dispu_linear_tn_bf16_stream_scratch_floats(int M, int K, int N
     return (long)splits * ((long)K + 1) * N;
 }
 
-DISPU_EXPORT int dispu_linear_tn_bf16_stream(int M, int K, int N, const void* X, long ldx, const void* Z, long ldz, int storage, float* out,
-                                             long ldo, int accumulate, float* dbias, float* scratch, long scratch_floats, void* stream) {
+// The one host decision of dispu_linear_tn_bf16_stream (dispu_linear_tn_bf16_stream_plan exports it).  Dereferences nothing.
+struct TnStreamDecision {
+    int rc;
+    int bn, bf16, splits, rows;          // gemm_bf16_tn_stream_kernel<bn, bf16>, row splits, rows of each
+};
+
+static TnStreamDecision tn_stream_decide(int M, int K, int N, const void* X, long ldx, const void* Z, long ldz, int storage, const float* out,
+                                         const float* scratch, long scratch_floats) {
+    TnStreamDecision d{};
     int splits;
     const bool bf = storage == 3;
-    dispu_tn_reduce_desc* sink = tn_take_defer();                 // dispu_tn_defer (train_gemm.hip): describe the reduction, do not launch it
-    if (sink) sink->splits = 0;
     if (!(storage == 0 || storage == 3) || !tn_stream_plan(M, K, N, splits) || !X || !Z || !out || !scratch ||
         scratch_floats < (long)splits * ((long)K + 1) * N || ldx < K || ldz < N || (ldx & (bf ? 7 : 3)) || (ldz & (bf ? 7 : 3)) ||
-        (((uintptr_t)X) & 15) || (((uintptr_t)Z) & 15))
-        return (int)hipErrorInvalidValue;
+        (((uintptr_t)X) & 15) || (((uintptr_t)Z) & 15)) {
+        d.rc = (int)hipErrorInvalidValue;
+        return d;
+    }
+    d.bn = (N % 256) == 0 ? 256 : 128;
+    d.bf16 = bf ? 1 : 0;
+    d.splits = splits;
+    d.rows = M / splits;
+    return d;
+}
+
+DISPU_EXPORT int dispu_linear_tn_bf16_stream_plan(int M, int K, int N, const void* X, long ldx, const void* Z, long ldz, int storage,
+                                                  const float* out, long ldo, int accumulate, const float* dbias, const float* scratch,
+                                                  long scratch_floats, int* plan) {
+    (void)ldo; (void)accumulate; (void)dbias;
+    if (!plan) return (int)hipErrorInvalidValue;
+    const TnStreamDecision d = tn_stream_decide(M, K, N, X, ldx, Z, ldz, storage, out, scratch, scratch_floats);
+    plan[0] = d.bn, plan[1] = d.bf16 ? 3 : 0, plan[2] = d.splits, plan[3] = d.rows;
+    return d.rc;
+}
+
+DISPU_EXPORT int dispu_linear_tn_bf16_stream(int M, int K, int N, const void* X, long ldx, const void* Z, long ldz, int storage, float* out,
+                                             long ldo, int accumulate, float* dbias, float* scratch, long scratch_floats, void* stream) {
+    dispu_tn_reduce_desc* sink = tn_take_defer();                 // dispu_tn_defer (train_gemm.hip): describe the reduction, do not launch it
+    if (sink) sink->splits = 0;
+    const TnStreamDecision d = tn_stream_decide(M, K, N, X, ldx, Z, ldz, storage, out, scratch, scratch_floats);
+    if (d.rc != 0) return d.rc;
+    const int splits = d.splits;
+    const bool bf = d.bf16 != 0, wide = d.bn == 256;
     hipStream_t s = (hipStream_t)stream;
-    const bool wide = (N % 256) == 0;
-    const int bn = wide ? 256 : 128, es = bf ? 2 : 4;
-    StArgs a{M / splits, K, N, X, ldx, Z, ldz, scratch, dbias ? 1 : 0};
+    const int bn = d.bn, es = bf ? 2 : 4;
+    StArgs a{d.rows, K, N, X, ldx, Z, ldz, scratch, dbias ? 1 : 0};
     const size_t lds = (size_t)SB_NST * 32 * (128 + bn) * es;
     static DevOnce attr;
     if (attr.needed()) {

@@ -376,20 +376,6 @@ __global__ __launch_bounds__(256) void tn_reduce_grouped_kernel(int count, const
     else tn_reduce_chunk<float>(d, b, reinterpret_cast<float(*)[32]>(red));
 }
 
-static void launch_tn_reduce(int batch, int K, int N, int splits, const float* part, float* out, long ldo, long so, int accumulate,
-                             float* dbias, hipStream_t s) {
-    const bool vec = (N % 4 == 0) && (ldo % 4 == 0) && (so % 4 == 0) && ((((uintptr_t)part) | ((uintptr_t)out)) & 15) == 0;
-    if (vec) {
-        const size_t chunks = ((((size_t)(K + 1) * N) / 4 + 31) / 32) * batch;
-        hipLaunchKernelGGL(tn_reduce4_kernel, dim3((unsigned)(chunks > 16384 ? 16384 : chunks)), dim3(256), 0, s, batch, K, N, splits, part, out,
-                           ldo, so, accumulate, dbias);
-    } else {
-        const size_t chunks = (((size_t)(K + 1) * N + 63) / 64) * batch;
-        hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)(chunks > 8192 ? 8192 : chunks)), dim3(512), 0, s, batch, K, N, splits, part, out, ldo,
-                           so, accumulate, dbias);
-    }
-}
-
 // ---- narrow outputs (N <= 64, K <= 256: the edge-conv layers' [96 x 24]-sized weight gradients over 10^4 .. 10^5 rows) --------
 // The tiled kernel above gives such a product ONE 128 x 64 block tile that is < 30 % full and as many workgroups as it has
 // M-splits, each paying a full LDS pipeline for a few KB of output (18 us + the reduction for 16 MB of operands).  Here a
@@ -582,65 +568,126 @@ DISPU_EXPORT long dispu_linear_tn_scratch_floats(int batch, int M, int K, int N)
     return (long)batch * splits * (K + 1) * N;
 }
 
-DISPU_EXPORT int dispu_linear_tn(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* Z, long ldz,
-                                 long sz, float* out, long ldo, long so, int accumulate, float* dbias, float* scratch,
-                                 long scratch_floats, void* stream) {
-    dispu_tn_reduce_desc* sink = tn_take_defer();                 // armed by dispu_tn_defer: describe the reduction instead of launching it
-    if (sink) sink->splits = 0;
-    if (batch != 1) sink = nullptr;                               // batched products (the unfused attention backward) reduce themselves
-    if (batch < 0 || M < 0 || K < 0 || N < 0) return (int)hipErrorInvalidValue;
-    if (batch == 0 || K == 0 || N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (M == 0) {   // nothing to add to dbias
-        if (!accumulate)
-            for (int z = 0; z < batch; ++z)
-                DISPU_TRY(hipMemset2DAsync(out + (size_t)z * so, sizeof(float) * ldo, 0, sizeof(float) * N, K, s));
-        return 0;
-    }
+// The one host decision of dispu_linear_tn: everything the entry chooses (refusal, no-op, the M == 0 clear, narrow or tiled kernel and
+// its instantiation, the split, direct store or partials + which reduction at which grid) from its arguments alone.  Pointers are
+// tested for NULL and alignment only.  dispu_linear_tn switches over this record and dispu_linear_tn_plan exports it.
+struct TnDecision {
+    int rc;                              // the error the entry returns (kind = 0 then)
+    int kind;                            // 0 nothing to launch, 1 narrow kernel, 2 tiled kernel, 3 M == 0 (clear `out` unless accumulating)
+    int tk, tnn, edge;                   // tiled: linear_tn_kernel<tk, tnn, edge>
+    int splits, rows;                    // M-splits (narrow: chunks) and rows of each
+    int direct;                          // tiled, one split, no accumulate, no dbias: the product kernel writes `out`
+    int reduce, reduce_grid, capped;     // 0 none, 1 tn_reduce_kernel, 2 tn_reduce4_kernel; its grid; 1 = grid-stride loop takes > 1 trip
+    int wpb, grid_y;                     // narrow: waves per block and grid.y
+};
+
+static void tn_decide_reduce(TnDecision& d, int batch, int K, int N, const float* part, const float* out, long ldo, long so) {
+    const bool vec = (N % 4 == 0) && (ldo % 4 == 0) && (so % 4 == 0) && ((((uintptr_t)part) | ((uintptr_t)out)) & 15) == 0;
+    const size_t chunks = vec ? ((((size_t)(K + 1) * N) / 4 + 31) / 32) * batch : (((size_t)(K + 1) * N + 63) / 64) * batch;
+    const size_t cap = vec ? 16384 : 8192;
+    d.reduce = vec ? 2 : 1;
+    d.capped = chunks > cap ? 1 : 0;
+    d.reduce_grid = (int)(chunks > cap ? cap : chunks);
+}
+
+static TnDecision tn_decide(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* Z, long ldz, long sz,
+                            const float* out, long ldo, long so, int accumulate, const float* dbias, const float* scratch,
+                            long scratch_floats) {
+    TnDecision d{};
+    if (batch < 0 || M < 0 || K < 0 || N < 0) { d.rc = (int)hipErrorInvalidValue; return d; }
+    if (batch == 0 || K == 0 || N == 0) return d;
+    if (!out || (M > 0 && (!X || !Z))) { d.rc = (int)hipErrorInvalidValue; return d; }   // (as dispu_linear_tn_bf16s / _stream refuse them)
+    if (M == 0) { d.kind = 3; return d; }
     {
         int nrows;
         const int nchunks = tn_narrow_chunks(batch, M, K, N, nrows);
         if (nchunks > 0 && (long)M * ldx < (1l << 29) && (long)M * ldz < (1l << 29) && scratch != nullptr &&
             scratch_floats >= (long)nchunks * (K + 1) * N) {
             const int KT = (K + 15) / 16, NT = (N + 15) / 16, jobs = (KT + 1) * NT;
-            const int wpb = jobs < 16 ? jobs : 16;
-            hipLaunchKernelGGL(linear_tn_narrow_kernel, dim3(nchunks, (jobs + wpb - 1) / wpb), dim3(64 * wpb), 0, s, M, K, N, nrows, KT, NT,
-                               X, ldx, Z, ldz, scratch);
-            DISPU_CHECK_LAUNCH();
-            if (sink) {
-                *sink = dispu_tn_reduce_desc{scratch, out, dbias, ldo, (long)(K + 1) * N, K, N, nchunks, K + 1, accumulate, 1, 0, 0};
-                return 0;
-            }
-            launch_tn_reduce(1, K, N, nchunks, scratch, out, ldo, so, accumulate, dbias, s);
-            DISPU_CHECK_LAUNCH();
-            return 0;
+            d.kind = 1;
+            d.splits = nchunks, d.rows = nrows;
+            d.wpb = jobs < 16 ? jobs : 16;
+            d.grid_y = (jobs + d.wpb - 1) / d.wpb;
+            tn_decide_reduce(d, 1, K, N, scratch, out, ldo, so);
+            return d;
         }
     }
-    int tk, tnn, splits, rows;
-    tn_plan(batch, M, K, N, tk, tnn, splits, rows);
+    tn_plan(batch, M, K, N, d.tk, d.tnn, d.splits, d.rows);
     // (measured and not kept: every split adding its tile to `out` with float atomics instead of partial tiles + reduction --
     // 124 vs 111 us for the 2048 x 256 gradient, 69 vs 54 us for 131072 rows x 128 x 128, a few us better only on the small ones)
-    const int direct = (splits == 1 && !accumulate && !dbias) ? 1 : 0;
-    if (!direct && (scratch == nullptr || scratch_floats < (long)batch * splits * (K + 1) * N)) return (int)hipErrorInvalidValue;
-    TnArgs a{M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, scratch, splits, rows, direct, dbias ? 1 : 0};
-    const int tiles = ((K + 64 * tk - 1) / (64 * tk)) * ((N + 64 * tnn - 1) / (64 * tnn));
-    dim3 grid(tiles, splits, batch);
-    const bool edge = !(K % (64 * tk) == 0 && N % (64 * tnn) == 0 && M % TN_SLAB == 0 && (ldx & 3) == 0 && (ldz & 3) == 0 &&
-                        (sx & 3) == 0 && (sz & 3) == 0 && (((uintptr_t)X) & 15) == 0 && (((uintptr_t)Z) & 15) == 0);
-    int rc;
-    if (tk == 1 && tnn == 1) rc = launch_tn_e<1, 1>(a, grid, edge, s);
-    else if (tk == 1 && tnn == 2) rc = launch_tn_e<1, 2>(a, grid, edge, s);
-    else if (tk == 1) rc = launch_tn_e<1, 4>(a, grid, edge, s);
-    else if (tnn == 1) rc = launch_tn_e<2, 1>(a, grid, edge, s);
-    else if (tnn == 2) rc = launch_tn_e<2, 2>(a, grid, edge, s);
-    else rc = launch_tn_e<2, 4>(a, grid, edge, s);
-    if (rc != 0) return rc;
-    if (!direct) {
+    d.direct = (d.splits == 1 && !accumulate && !dbias) ? 1 : 0;
+    if (!d.direct && (scratch == nullptr || scratch_floats < (long)batch * d.splits * (K + 1) * N)) {
+        d = TnDecision{};
+        d.rc = (int)hipErrorInvalidValue;
+        return d;
+    }
+    d.kind = 2;
+    d.edge = !(K % (64 * d.tk) == 0 && N % (64 * d.tnn) == 0 && M % TN_SLAB == 0 && (ldx & 3) == 0 && (ldz & 3) == 0 &&
+               (sx & 3) == 0 && (sz & 3) == 0 && (((uintptr_t)X) & 15) == 0 && (((uintptr_t)Z) & 15) == 0);
+    if (!d.direct) tn_decide_reduce(d, batch, K, N, scratch, out, ldo, so);
+    return d;
+}
+
+static void launch_tn_reduce(const TnDecision& d, int batch, int K, int N, const float* part, float* out, long ldo, long so, int accumulate,
+                             float* dbias, hipStream_t s) {
+    if (d.reduce == 2)
+        hipLaunchKernelGGL(tn_reduce4_kernel, dim3((unsigned)d.reduce_grid), dim3(256), 0, s, batch, K, N, d.splits, part, out, ldo, so,
+                           accumulate, dbias);
+    else
+        hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)d.reduce_grid), dim3(512), 0, s, batch, K, N, d.splits, part, out, ldo, so,
+                           accumulate, dbias);
+}
+
+DISPU_EXPORT int dispu_linear_tn_plan(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* Z, long ldz, long sz,
+                                      const float* out, long ldo, long so, int accumulate, const float* dbias, const float* scratch,
+                                      long scratch_floats, int* plan) {
+    if (!plan) return (int)hipErrorInvalidValue;
+    const TnDecision d = tn_decide(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats);
+    const int v[12] = {d.kind, d.tk, d.tnn, d.edge, d.splits, d.rows, d.direct, d.reduce, d.reduce_grid, d.capped, d.wpb, d.grid_y};
+    for (int i = 0; i < 12; ++i) plan[i] = v[i];
+    return d.rc;
+}
+
+DISPU_EXPORT int dispu_linear_tn(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* Z, long ldz,
+                                 long sz, float* out, long ldo, long so, int accumulate, float* dbias, float* scratch,
+                                 long scratch_floats, void* stream) {
+    dispu_tn_reduce_desc* sink = tn_take_defer();                 // armed by dispu_tn_defer: describe the reduction instead of launching it
+    if (sink) sink->splits = 0;
+    if (batch != 1) sink = nullptr;                               // batched products (the unfused attention backward) reduce themselves
+    const TnDecision d = tn_decide(batch, M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, accumulate, dbias, scratch, scratch_floats);
+    if (d.rc != 0 || d.kind == 0) return d.rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (d.kind == 3) {   // nothing to add to dbias
+        if (!accumulate)
+            for (int z = 0; z < batch; ++z)
+                DISPU_TRY(hipMemset2DAsync(out + (size_t)z * so, sizeof(float) * ldo, 0, sizeof(float) * N, K, s));
+        return 0;
+    }
+    if (d.kind == 1) {
+        const int KT = (K + 15) / 16, NT = (N + 15) / 16;
+        hipLaunchKernelGGL(linear_tn_narrow_kernel, dim3(d.splits, d.grid_y), dim3(64 * d.wpb), 0, s, M, K, N, d.rows, KT, NT, X, ldx, Z,
+                           ldz, scratch);
+        DISPU_CHECK_LAUNCH();
+    } else {
+        TnArgs a{M, K, N, X, ldx, sx, Z, ldz, sz, out, ldo, so, scratch, d.splits, d.rows, d.direct, dbias ? 1 : 0};
+        const int tiles = ((K + 64 * d.tk - 1) / (64 * d.tk)) * ((N + 64 * d.tnn - 1) / (64 * d.tnn));
+        dim3 grid(tiles, d.splits, batch);
+        const bool edge = d.edge != 0;
+        int rc;
+        if (d.tk == 1 && d.tnn == 1) rc = launch_tn_e<1, 1>(a, grid, edge, s);
+        else if (d.tk == 1 && d.tnn == 2) rc = launch_tn_e<1, 2>(a, grid, edge, s);
+        else if (d.tk == 1) rc = launch_tn_e<1, 4>(a, grid, edge, s);
+        else if (d.tnn == 1) rc = launch_tn_e<2, 1>(a, grid, edge, s);
+        else if (d.tnn == 2) rc = launch_tn_e<2, 2>(a, grid, edge, s);
+        else rc = launch_tn_e<2, 4>(a, grid, edge, s);
+        if (rc != 0) return rc;
+    }
+    if (d.reduce) {
         if (sink) {
-            *sink = dispu_tn_reduce_desc{scratch, out, dbias, ldo, (long)(K + 1) * N, K, N, splits, K + 1, accumulate, 1, 0, 0};
+            *sink = dispu_tn_reduce_desc{scratch, out, dbias, ldo, (long)(K + 1) * N, K, N, d.splits, K + 1, accumulate, 1, 0, 0};
             return 0;
         }
-        launch_tn_reduce(batch, K, N, splits, scratch, out, ldo, so, accumulate, dbias, s);
+        launch_tn_reduce(d, batch, K, N, scratch, out, ldo, so, accumulate, dbias, s);
         DISPU_CHECK_LAUNCH();
     }
     return 0;

@@ -455,6 +455,29 @@ long dispu_linear_tn_scratch_floats(int batch, int M, int K, int N);
 int dispu_linear_tn(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* Z, long ldz, long sz,
                     float* out, long ldo, long so, int accumulate, float* dbias, float* scratch, long scratch_floats,
                     void* stream);
+/* What a dispu_linear_tn / dispu_linear_tn_bf16(s) / dispu_linear_tn_bf16_stream call with these arguments would launch (debug / test aid
+ * like dispu_linear_plan; each launcher switches over the same host decision).  Every argument of the entry but the stream; pointers are
+ * tested for NULL and alignment only and never dereferenced, no HIP call is made.  Returns 0, or the error the entry itself would return
+ * (the plan is then all zero).  The three entries refuse a NULL `out`, and NULL X / Z when M > 0.
+ * dispu_linear_tn_plan, plan[0..11]: kind (0 nothing to launch, 1 narrow kernel, 2 tiled kernel, 3 M == 0: `out` is cleared unless
+ *   accumulating), TK, TNN, edge (tiled: block tile 64 TK x 64 TNN, predicated loaders), splits (narrow: chunks), rows per split, direct
+ *   (the product kernel writes `out` itself: one split, no accumulate, no dbias; scratch may be NULL), reduce (0 none, 1 scalar, 2 float4
+ *   kernel), the reduction's grid, capped (1: that grid is at its limit and loops), then for the narrow kernel waves per block and grid.y.
+ * dispu_linear_tn_bf16_plan (arguments of dispu_linear_tn_bf16s), plan[0..5]: kind (0, 2 product, 3 M == 0: `out` and dbias are cleared
+ *   unless accumulating), block tile (128032 / 64064 / 128128), splits, rows per split, reduce (1: partial tiles + reduction; 0: one
+ *   workgroup per tile writes `out`, scratch unused), rows of a partial (K, or K + 1 with dbias).
+ * dispu_linear_tn_bf16_stream_plan, plan[0..3]: BN (256 / 128), storage (0 / 3), splits, rows per split; always partials + reduction. */
+#define DISPU_LINEAR_TN_PLAN_INTS 12
+int dispu_linear_tn_plan(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* Z, long ldz, long sz,
+                         const float* out, long ldo, long so, int accumulate, const float* dbias, const float* scratch,
+                         long scratch_floats, int* plan);
+#define DISPU_LINEAR_TN_BF16_PLAN_INTS 6
+int dispu_linear_tn_bf16_plan(int batch, int M, int K, int N, const void* X, long ldx, long sx, const void* Z, long ldz, long sz,
+                              const float* out, long ldo, long so, int accumulate, const float* dbias, const float* scratch,
+                              long scratch_floats, int storage, int* plan);
+#define DISPU_LINEAR_TN_BF16_STREAM_PLAN_INTS 4
+int dispu_linear_tn_bf16_stream_plan(int M, int K, int N, const void* X, long ldx, const void* Z, long ldz, int storage, const float* out,
+                                     long ldo, int accumulate, const float* dbias, const float* scratch, long scratch_floats, int* plan);
 /* Deferred split reductions (ABI 5; csrc/train_gemm.hip).  The training step has ~20 weight-gradient products, each followed by its own
  * 4 - 25 us reduction launch that only Adam waits for.  dispu_tn_defer(&desc) arms a ONE-SHOT, per-thread sink: the next dispu_linear_tn /
  * dispu_linear_tn_bf16(s) / dispu_linear_tn_bf16_stream call on this thread (batch == 1) launches its product only and fills `desc` with the

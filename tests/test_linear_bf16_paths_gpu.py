@@ -11,7 +11,8 @@ The 128 x 128 tile is reached at small cost with batch 8, M = N = 1000 (8 x 8 x 
 there with 4097 x 1921 (33 x 16 tiles).
 
 The TN products (dispu_linear_tn_bf16*) are not forced into 128 x 128 here: their split plan keeps tiles x splits near 256 - 1024 on
-the 64 x 64 / 128 x 32 tiling, so they never select that tile at any K x N this model has.
+the 64 x 64 / 128 x 32 tiling, so they never select that tile at any K x N this model has.  tests/test_tn_paths_gpu.py runs them on
+every tile their plan can reach (128 x 128 included: one- and two-tile outputs over >= 130817 rows, or 512 tiles without a split).
 
 [measured] worst |got - z| / bound over all cases: 0.061 (dispu_linear_bf16, 128 x 128 tile, NN, K = 65, R1).
 """
