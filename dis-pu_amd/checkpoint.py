@@ -366,14 +366,14 @@ def save_generator_params(prefix, params, scope="generator", step=None, epoch=No
 
 
 # ------------------------------------------------------------------------ the reference's two restore sites ----
-def restore_generator(log_dir, device=None, opts=None):
+def restore_generator(log_dir, device=None, opts=None, dtype="f32"):
     """`Model.test` (DisPU/model.py:350-353: Saver().restore(sess, pre_load_checkpoint(log_dir))) -> (restore_epoch, Generator):
-    the latest checkpoint named by `<log_dir>/checkpoint`, loaded into device tensors."""
+    the latest checkpoint named by `<log_dir>/checkpoint`, loaded into device tensors.  dtype: Generator(dtype=...)."""
     from .generator import Generator
     epoch, prefix = pre_load_checkpoint(log_dir)
     if prefix is None:
         raise FileNotFoundError("no checkpoint state file under %s" % log_dir)
-    return epoch, Generator(opts=opts, params=load_generator_params(prefix), device=device)
+    return epoch, Generator(opts=opts, params=load_generator_params(prefix), device=device, dtype=dtype)
 
 
 def restore_train_state(log_dir, trainer):

@@ -17,6 +17,7 @@
 #include "common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace dispu {
 
@@ -24,6 +25,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PL_BM = 128, PL_BN = 128, PL_BK = 32, PL_K = 128, PL_NT = 256;
 constexpr int PL_LDA = PL_BM + 1, PL_LDB = PL_BN + 4;
@@ -232,13 +235,16 @@ constexpr size_t PW_LDS_BYTES = (size_t)PW_FLOATS * sizeof(float);
 // instruction count is what the MFMA waves end up waiting for (PL_STAMPS: 1450 - 2600 cycles per group at the slab barriers): with UNI
 // a group's cloud base is ONE scalar division (it was an unsigned vector division, ~25 instructions, per gathered row), every index /
 // coordinate / A-row / G-row load is a buffer load whose group offset is a scalar, and nothing is clamped.
-template <bool UNI>
+// OUT16 (dispu_ps_local_bf16): F' leaves as bf16 -- the fp32 tile values, unchanged, rounded to nearest even at the store (what a bf16
+// after_conv GEMM does to its X operand on load anyway): half the bytes of the step's largest tensor, here and in its consumer.
+template <bool UNI, bool OUT16 = false>
 __global__ __launch_bounds__(512) void ps_local_ws_kernel(long npoints, int n_per_cloud, const int* __restrict__ idx,
                                                            const float* __restrict__ xyz, const float* __restrict__ Gm, int ldg,
                                                            const float* __restrict__ Am, const float* __restrict__ W1,
                                                            const float* __restrict__ b1, const float* __restrict__ Ww,
                                                            const float* __restrict__ bw, const float* __restrict__ scale,
-                                                           const float* __restrict__ shift, float* __restrict__ out) {
+                                                           const float* __restrict__ shift,
+                                                           std::conditional_t<OUT16, unsigned short, float>* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* wres = lds;                                               // [128][PW_LDB]
     float* astg = wres + PW_WRES;                                    // [2][128][PW_LDAR]
@@ -527,7 +533,7 @@ __global__ __launch_bounds__(512) void ps_local_ws_kernel(long npoints, int n_pe
     for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) o[pt][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((unsigned)np * 8192u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((unsigned)np * (OUT16 ? 4096u : 8192u)), 0x00020000);
     int g_prev = 0;
     // tile (pt, cb) of group gp -> F'.  Round 5: the contraction runs TRANSPOSED, O^T[t][ch] = sum_s wv[s][t] * X2[s][ch] (wv^T is the A
     // operand, relu(acc + b1) -- already in the lane that holds it, see above -- the B operand; the same products in the same s order,
@@ -539,8 +545,13 @@ __global__ __launch_bounds__(512) void ps_local_ws_kernel(long npoints, int n_pe
         const int ch = wn * 64 + cb * 16 + lc;
         // a BUFFER store: an offset beyond the resource's range is dropped by the hardware, so "nothing to flush yet" (first group)
         // and "point beyond np" (ragged last group) need no branch -- a branch here ends the scheduling region
-        const unsigned off = (live && pi < np) ? ((unsigned)pi * 2048u + (unsigned)(ch * 16 + 4 * la)) * 4u : 0xFFFFFFF0u;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[pt][cb]), out_rsrc, (int)off, 0, 0);
+        const unsigned off = (live && pi < np) ? ((unsigned)pi * 2048u + (unsigned)(ch * 16 + 4 * la)) * (OUT16 ? 2u : 4u) : 0xFFFFFFF0u;
+        if constexpr (OUT16) {                                       // the lane's four t of its channel: 4 bf16 (RNE) = one 8-byte store
+            const bf16x4 h = {(__bf16)o[pt][cb][0], (__bf16)o[pt][cb][1], (__bf16)o[pt][cb][2], (__bf16)o[pt][cb][3]};
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), out_rsrc, (int)off, 0, 0);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[pt][cb]), out_rsrc, (int)off, 0, 0);
+        }
     };
     for (int g = g_first; g < ng; g += gstep, ++n) {
         const bool have_prev = n > 0;
@@ -633,6 +644,32 @@ __global__ __launch_bounds__(512) void ps_local_ws_kernel(long npoints, int n_pe
 
 using namespace dispu;
 
+// The persistent kernel over a whole call.  The F' tiles leave through a buffer resource whose byte range is a 32-bit field: launches of
+// at most 2^18 points (2 GB of fp32 F'), cut at cloud boundaries (neighbour ids are cloud-local, the kernel derives a point's cloud from
+// its index); the output base advances in elements of the stored type.
+template <bool OUT16>
+static int pw_launch(long npoints, int n_per_cloud, const int* idx, const float* xyz, const float* G, long ldg, const float* A, const float* W1,
+                     const float* b1, const float* Ww, const float* bw, const float* scale, const float* shift,
+                     std::conditional_t<OUT16, unsigned short, float>* out, hipStream_t stream) {
+    const long max_pts = 262144;
+    if (n_per_cloud > max_pts) return (int)hipErrorInvalidValue;
+    const long per = npoints <= max_pts ? npoints : (max_pts / n_per_cloud) * (long)n_per_cloud;
+    for (long p0 = 0; p0 < npoints; p0 += per) {
+        const long np = (npoints - p0 < per) ? npoints - p0 : per;
+        const long ngroups = (np + 7) / 8;
+        const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);      // one persistent workgroup per CU
+        // whole 8-point groups inside one cloud, 32-bit byte offsets for the helpers' buffer loads
+        const bool uni = (n_per_cloud % 8) == 0 && (np % 8) == 0 && np * ldg * 4 < 0x7fffffffL;
+        if (uni)
+            hipLaunchKernelGGL((ps_local_ws_kernel<true, OUT16>), dim3(grid), dim3(512), PW_LDS_BYTES, stream, np, n_per_cloud, idx + p0 * 16,
+                               xyz + p0 * 3, G + p0 * ldg, (int)ldg, A + p0 * PL_K, W1, b1, Ww, bw, scale, shift, out + p0 * 2048);
+        else
+            hipLaunchKernelGGL((ps_local_ws_kernel<false, OUT16>), dim3(grid), dim3(512), PW_LDS_BYTES, stream, np, n_per_cloud, idx + p0 * 16,
+                               xyz + p0 * 3, G + p0 * ldg, (int)ldg, A + p0 * PL_K, W1, b1, Ww, bw, scale, shift, out + p0 * 2048);
+    }
+    return 0;
+}
+
 DISPU_EXPORT int dispu_ps_local(long npoints, int n_per_cloud, int k, int c, const int* idx, const float* xyz, const float* G,
                                 long ldg, const float* A, const float* W1, const float* b1, const float* Ww, const float* bw,
                                 const float* scale, const float* shift, float* out, void* stream) {
@@ -657,24 +694,30 @@ DISPU_EXPORT int dispu_ps_local(long npoints, int n_per_cloud, int k, int c, con
         hipLaunchKernelGGL(ps_local_kernel, dim3((unsigned)((npoints + 7) / 8)), dim3(PL_NT), PL_LDS_BYTES, (hipStream_t)stream, npoints,
                            n_per_cloud, idx, xyz, G, ldg, A, W1, b1, Ww, bw, scale, shift, out);
     } else {
-        // the F' tiles leave through a buffer resource whose byte range is a 32-bit field: launches of at most 2^18 points
-        // (2 GB of F'), cut at cloud boundaries (neighbour ids are cloud-local, the kernel derives a point's cloud from its index)
-        const long max_pts = 262144;
-        if (n_per_cloud > max_pts) return (int)hipErrorInvalidValue;
-        const long per = npoints <= max_pts ? npoints : (max_pts / n_per_cloud) * (long)n_per_cloud;
-        for (long p0 = 0; p0 < npoints; p0 += per) {
-            const long np = (npoints - p0 < per) ? npoints - p0 : per;
-            const long ngroups = (np + 7) / 8;
-            const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);      // one persistent workgroup per CU
-            // whole 8-point groups inside one cloud, 32-bit byte offsets for the helpers' buffer loads
-            const bool uni = (n_per_cloud % 8) == 0 && (np % 8) == 0 && np * ldg * 4 < 0x7fffffffL;
-            if (uni)
-                hipLaunchKernelGGL(ps_local_ws_kernel<true>, dim3(grid), dim3(512), PW_LDS_BYTES, (hipStream_t)stream, np, n_per_cloud, idx + p0 * 16,
-                                   xyz + p0 * 3, G + p0 * ldg, (int)ldg, A + p0 * PL_K, W1, b1, Ww, bw, scale, shift, out + p0 * 2048);
-            else
-                hipLaunchKernelGGL(ps_local_ws_kernel<false>, dim3(grid), dim3(512), PW_LDS_BYTES, (hipStream_t)stream, np, n_per_cloud, idx + p0 * 16,
-                                   xyz + p0 * 3, G + p0 * ldg, (int)ldg, A + p0 * PL_K, W1, b1, Ww, bw, scale, shift, out + p0 * 2048);
-        }
+        const int rc = pw_launch<false>(npoints, n_per_cloud, idx, xyz, G, ldg, A, W1, b1, Ww, bw, scale, shift, out, (hipStream_t)stream);
+        if (rc) return rc;
     }
+    return (int)hipGetLastError();
+}
+
+// dispu_ps_local with F' stored as bf16 [npoints, 2048] (Generator(dtype="bf16"): after_conv then reads half the bytes).  The fp32 tile
+// values are those of dispu_ps_local, rounded to nearest even at the store; the persistent kernel only (pw_launch).
+DISPU_EXPORT int dispu_ps_local_bf16(long npoints, int n_per_cloud, int k, int c, const int* idx, const float* xyz, const float* G,
+                                     long ldg, const float* A, const float* W1, const float* b1, const float* Ww, const float* bw,
+                                     const float* scale, const float* shift, void* out, void* stream) {
+    if (npoints < 0 || n_per_cloud <= 0 || k != 16 || c != 128 || ldg < 128 || (ldg & 3) || npoints * ldg > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    if ((((uintptr_t)G) | ((uintptr_t)A) | ((uintptr_t)W1) | ((uintptr_t)out)) & 15) return (int)hipErrorInvalidValue;
+    if (npoints == 0) return 0;
+    static DevOnce attr;
+    if (attr.needed()) {
+        DISPU_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ps_local_ws_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)PW_LDS_BYTES));
+        DISPU_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ps_local_ws_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)PW_LDS_BYTES));
+        attr.done();
+    }
+    const int rc = pw_launch<true>(npoints, n_per_cloud, idx, xyz, G, ldg, A, W1, b1, Ww, bw, scale, shift, reinterpret_cast<unsigned short*>(out),
+                                   (hipStream_t)stream);
+    if (rc) return rc;
     return (int)hipGetLastError();
 }

@@ -76,7 +76,15 @@ class Generator(object):
                               # (~17 MB per 256 input points, dominated by F' [B*4N, 2048]) at ~35 GB; larger batches run in chunks
                               # of max(1, MAX_POINTS // N) patches
 
-    def __init__(self, opts=None, is_training=False, name="Generator", params=None, device=None):
+    def __init__(self, opts=None, is_training=False, name="Generator", params=None, device=None, dtype="f32"):
+        # dtype = "bf16" (inference only): ONE rounded product -- F' is stored as bf16 by the local cell (dispu_ps_local_bf16) and
+        # after_conv multiplies it with the bf16 image of its weight, fp32 accumulation; everything else is the fp32 path, so the
+        # numerics do not depend on the batch size.  Checked before the device is touched.
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("Generator dtype must be 'f32' or 'bf16', got %r" % (dtype,))
+        if dtype == "bf16" and is_training:
+            raise ValueError("Generator(dtype='bf16') is the inference mode; mixed-precision training is Trainer(dtype='bf16')")
+        self.dtype = dtype
         self.opts = opts if opts is not None else _Opts()
         self.is_training = is_training
         self.name = name
@@ -98,6 +106,7 @@ class Generator(object):
         # tolerance-checked).  Off by default; bench.py --split-bf16 reports it beside the strict-fp32 line.
         self.split_bf16 = False
         self._planes = {}
+        self._aft_bt = None          # dtype = "bf16": after_conv's weight as bf16 [256][2048] (dispu_bf16_pack), made by load_params
         self.split_up3 = True        # the N = 320 product as 256 + 64 columns (each launch reads up128 once)
         # non-local cell on a second stream next to the grouping / skip / local cell (round 4: on by default, -1 % since the head chains
         # form their own inputs -- the branch now joins right before the fine chain; rounds 1 - 3 measured it +1 %)
@@ -161,6 +170,12 @@ class Generator(object):
                                 torch.zeros(128, dtype=torch.float32, device=dev)]).contiguous()
         wsk = self.P["refine/PointShuffle/skip/weights"]
         self.w_skip_pad = torch.cat([wsk, torch.zeros((10, wsk.shape[1]), dtype=torch.float32, device=dev)], dim=0).contiguous()
+        if self.dtype == "bf16":
+            # packed once per parameter set, on the stream current here: forward (and a captured graph) holds no pack launch
+            w = self.P["refine/PointShuffle/after_conv/weights"]
+            bt = torch.empty((256, 2048), dtype=torch.bfloat16, device=dev)
+            _lib.check(_lib.lib().dispu_bf16_pack(2048, 256, _lib.ptr(w), 256, 1, _lib.ptr(bt), _lib.stream_ptr(dev)), "dispu_bf16_pack")
+            self._aft_bt = bt
 
     def _w(self, scope):
         return self.P[scope + "/weights"], self.P[scope + "/biases"]
@@ -183,7 +198,7 @@ class Generator(object):
             up256=E(rm, 256), up128=E(rm, 128), c256=E(rm, 256), c64=E(rm, 64), coarse=E(B, M, 3),
             psidx=E(rm, k, dtype=i32), up3=E(rm, 320), att=E(rm, 64), nl=E(rm, 256),
             skipin=torch.zeros((rm, 144), dtype=f32, device=dev), skip=E(rm, 256), am=E(rm, 128),
-            fp=E(rm, 2048), aft=E(rm, 256), agg=E(rm, 256),
+            fp=E(rm, 2048, dtype=torch.bfloat16 if self.dtype == "bf16" else f32), aft=E(rm, 256), agg=E(rm, 256),
             f256=E(rm, 256), f64=E(rm, 64), fine=E(B, M, 3))
         ws["kv"], ws["q"], ws["gm"] = ws["up3"][:, 0:128], ws["up3"][:, 128:192], ws["up3"][:, 192:320]   # views, row stride 320
         self._ws[key] = ws
@@ -247,6 +262,9 @@ class Generator(object):
         if not (isinstance(inputs, torch.Tensor) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 3
                 and inputs.shape[2] == 3):
             raise ValueError("Generator expects a float32 [B,N,3] tensor on a ROCm device")
+        bf16 = self.dtype == "bf16"
+        if bf16 and (self.split_bf16 or not self.fused_local):
+            raise ValueError("Generator(dtype='bf16') stores F' as bf16 in the fused local cell: it excludes split_bf16 and fused_local = False")
         inputs = inputs.contiguous()
         B, N, _ = inputs.shape
         if N <= K_NEIGH:
@@ -419,7 +437,11 @@ class Generator(object):
         self._call("ps_prep", L.dispu_ps_prep, rm, 128, ptr(coarse), ptr(w0), ptr(b0), ptr(ws["gm"]), 320, ptr(ws["am"]), 128, st)
         w1, b1 = self._w(ps + "conv1")
         ww, bw = self._w(ps + "weight_net/wconv0")
-        if self.fused_local:
+        if bf16:
+            # the fused kernel below with F' leaving as bf16 [rm, 2048] (RNE at the store)
+            self._call("ps_local_bf16", L.dispu_ps_local_bf16, rm, M, k, 128, ptr(ws["psidx"]), ptr(coarse), ptr(ws["gm"]), 320, ptr(ws["am"]),
+                       ptr(w1), ptr(b1), ptr(ww), ptr(bw), ptr(self.bn_scale), ptr(self.bn_shift), ptr(ws["fp"]), st)
+        elif self.fused_local:
             # gather_sub_relu + conv1 + weight_net + feature x weight in one kernel: only F' [rm, 2048] touches HBM
             self._call("ps_local", L.dispu_ps_local, rm, M, k, 128, ptr(ws["psidx"]), ptr(coarse), ptr(ws["gm"]), 320, ptr(ws["am"]),
                        ptr(w1), ptr(b1), ptr(ww), ptr(bw), ptr(self.bn_scale), ptr(self.bn_shift), ptr(ws["fp"]), st)
@@ -435,7 +457,21 @@ class Generator(object):
         nl_late = br and heads and self.chain_inputs      # nl is first read by the fine chain's loader
         if br and not nl_late:
             torch.cuda.current_stream(self.device).wait_event(ev_nl)
-        if self.split_bf16 and rm % 128 == 0:
+        if bf16:
+            # relu(bf16(F') . bf16(W) + b), fp32 accumulation: the streaming kernel on the pre-packed weight where its shape rules hold,
+            # else the generic bf16 kernel on the fp32 weight (rounded on load: the same products in the same order, bit-identical)
+            if rm % 128 == 0:
+                self._call("linear_bf16_stream[%dx2048x256]" % rm, L.dispu_linear_bf16_stream, rm, 2048, 256, ptr(ws["fp"]), 2048, 1,
+                           ptr(self._aft_bt), 2048, ptr(b), 1, ptr(ws["aft"]), 256, 0, 1, 0, st)
+            else:
+                self._call("linear_bf16s[%dx2048x256]" % rm, L.dispu_linear_bf16s, 1, rm, 2048, 256, ptr(ws["fp"]), 2048, 0, ptr(w), 256, 0, 0,
+                           ptr(b), 1, ptr(ws["aft"]), 256, 0, None, 0, 0, 1, st)
+            if not (heads and self.chain_inputs):
+                # (relu(.) + skip) + nl, the association of the fp32 paths, into a buffer of its own: aft stays the product
+                if "sum" not in ws:
+                    ws["sum"] = torch.empty((rm, 256), dtype=torch.float32, device=self.device)
+                self._call("add3", L.dispu_add3, rm * 256, ptr(ws["aft"]), ptr(ws["skip"]), ptr(ws["nl"]), ptr(ws["sum"]), st)
+        elif self.split_bf16 and rm % 128 == 0:
             pl = self._planes.get("after_conv")
             if pl is None:
                 pl = torch.empty((3 * 2048 * 256,), dtype=torch.bfloat16, device=self.device)
@@ -468,12 +504,12 @@ class Generator(object):
             w2, b2_ = self._w(fs + "fc_layer0")
             w3, b3_ = self._w(fs + "fc_layer1")
             w4, b4_ = self._w(fs + "fc_layer2")
-            self._call("mlp_chain[fine]", L.dispu_mlp_chain, rm, 256, 256, 256, 64, ptr(ws["aft"]), 256, ptr(w1), ptr(b1_), ptr(w2), ptr(b2_),
+            self._call("mlp_chain[fine]", L.dispu_mlp_chain, rm, 256, 256, 256, 64, ptr(ws["sum"] if bf16 else ws["aft"]), 256, ptr(w1), ptr(b1_), ptr(w2), ptr(b2_),
                        ptr(w3), ptr(b3_), ptr(w4), ptr(b4_), ptr(ws["agg"]) if self.keep_intermediates else None, 256, 1, ptr(coarse), 3,
                        ptr(fine), 3, st)
         else:
             w, b = self._w(ps + "aggregation")
-            self._linear(st, ws["aft"], 256, w, b, 1, ws["agg"], 256)
+            self._linear(st, ws["sum"] if bf16 else ws["aft"], 256, w, b, 1, ws["agg"], 256)
             # ---- fine coordinate_regressor (is_off) + residual (generator.py:76-81)
             w, b = self._w(fs + "fc_layer0")
             self._linear(st, ws["agg"], 256, w, b, 1, ws["f256"], 256)

@@ -333,6 +333,12 @@ int dispu_ps_point_matmul(long rows, int k, int c, int t_n, const float* X2, lon
 int dispu_ps_local(long npoints, int n_per_cloud, int k, int c, const int* idx, const float* xyz, const float* G, long ldg,
                    const float* A, const float* W1, const float* b1, const float* Ww, const float* bw, const float* scale,
                    const float* shift, float* out, void* stream);
+/* dispu_ps_local (ops.py:1055-1067) with F' STORED AS bf16: out is bf16 [npoints, 2048], every element the fp32 value dispu_ps_local
+ * writes rounded to nearest even -- the operand rounding of a bf16 after_conv product (ops.py:1078), done at the store, at half the
+ * bytes.  Same arguments and checks otherwise (k == 16, c == 128, 16-byte aligned G / A / W1 / out). */
+int dispu_ps_local_bf16(long npoints, int n_per_cloud, int k, int c, const int* idx, const float* xyz, const float* G, long ldg,
+                        const float* A, const float* W1, const float* b1, const float* Ww, const float* bw, const float* scale,
+                        const float* shift, void* out, void* stream);
 /* PointNonLocalCell attention fused (ops.py:326-339): O[b,m,64] = softmax(scale * Q.K^T) . V per cloud, logits never
  * written to HBM.  d must be 64, nk % 32 == 0, rows 16-byte aligned (else hipErrorInvalidValue: use the 3-kernel path). */
 int dispu_attention(int b, int m, int nk, int d, const float* Q, long ldq, const float* K, long ldk, const float* V,

@@ -64,6 +64,8 @@ def parse_args(argv=None):
     ap.add_argument("--patch_num_ratio", type=int, default=3, help="patch seeds per patch_num_point input points")
     ap.add_argument("--max-points", dest="max_points", type=int, default=1 << 20,
                     help="input points per batch of clouds (bounds device memory and keeps packed offsets below 2^31)")
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
+                    help="f32: the strict fp32 generator; bf16: after_conv as a bf16 product over F' stored as bf16 (Generator(dtype='bf16'))")
     return ap.parse_args(argv)
 
 
@@ -91,7 +93,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         sys.exit("no ROCm device")
     dev = torch.device("cuda:0")
-    epoch, gen = restore_generator(a.log_dir, device=dev)
+    epoch, gen = restore_generator(a.log_dir, device=dev, dtype=a.dtype)
     print("restored %s (epoch %d)" % (a.log_dir, epoch))
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
