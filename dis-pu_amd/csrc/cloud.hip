@@ -54,8 +54,11 @@ __global__ __launch_bounds__(256) void knn_patch_kernel(int n, int npad, int m, 
 }
 
 // normalize_point_cloud (pc_util.py:147-161) per patch: centroid = mean, p -= centroid, furthest = max |p|, p /= furthest.
-// One wave per patch (n <= 64 * 16); sums use a fixed butterfly order (numpy's pairwise order is not reproduced;
-// parity is tolerance-based, 1e-6).  off: a packed ragged batch of whole clouds (seg_ext), one wave per segment.
+// One wave per patch or per whole cloud, any n > 0 (the evaluator runs it at 8192 points and more).  Every operation is a rounded
+// float32 one in numpy's order (the sequential centroid sum below, (dx dx + dy dy) + dz dz, sqrtf, a maximum, IEEE divisions), so
+// centroid, furthest and every coordinate equal normalize_point_cloud in float32 bit for bit; tests/test_cloud_ops_gpu.py holds that.
+// n = 1 and coincident points give furthest = 0 and NaN coordinates, as numpy does.
+// off: a packed ragged batch of whole clouds (seg_ext), one wave per segment.
 __global__ __launch_bounds__(64) void normalize_patches_kernel(int n, const float* __restrict__ in, float* __restrict__ out,
                                                                float* __restrict__ centroid, float* __restrict__ furthest,
                                                                const int* __restrict__ off) {

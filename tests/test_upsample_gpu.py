@@ -16,6 +16,23 @@ def N(t):
     return t.detach().cpu().numpy()
 
 
+def merged_from_stages(pc, st):
+    """the float32 numpy denormalisation (patch, then cloud: model.py:310-311, :371-372) of the device's own fine cloud with the
+    device's own centroids and scales -- normalize_patches again on the stage inputs, which must give the stages back bit for bit."""
+    from dispu_amd import upsample as U
+    dev = st["fine"].device
+    cloud_n, c0, f0 = U.normalize_patches(torch.from_numpy(np.ascontiguousarray(pc, np.float32)[None]).to(dev))
+    assert torch.equal(cloud_n, st["cloud_n"])
+    patches = st["cloud_n"][0][st["pidx"][0].long()].contiguous()
+    pn, pc_c, pc_f = U.normalize_patches(patches)
+    assert torch.equal(pn, st["patches_n"])
+    fine = N(st["fine"])
+    pred = N(pc_c)[:, None, :] + fine * N(pc_f)[:, None, None]
+    merged = N(c0)[:, None, :] + pred.reshape(1, -1, 3) * N(f0)[:, None, None]
+    assert fine.dtype == np.float32 and merged.dtype == np.float32
+    return merged
+
+
 def test_knn_patch_large_k(dev):
     from dispu_amd import upsample as U
     rng = np.random.default_rng(0)
@@ -129,6 +146,7 @@ def test_upsample_cloud_stage_parity(dev):
     c_want, f_want = OG.generator_forward(P, N(st["patches_n"]))
     assert np.abs(N(st["fine"]) - f_want).max() <= 1e-5
     merged = N(st["merged"])
+    assert merged.shape == (1, 12 * 1024, 3) and np.array_equal(merged, merged_from_stages(pc, st))
     assert np.array_equal(N(st["sel"]), O.farthest_point_sample(4096, merged))
     assert np.array_equal(out, merged[0][N(st["sel"])[0]])
     # end to end against the independent oracle run: same point set up to float noise unless a near-tie flipped
@@ -168,7 +186,7 @@ def test_upsample_cloud_16x_stage_parity(dev):
     assert np.array_equal(N(gen._ws[(12, 1024)]["psidx"]).reshape(12, 4096, 16), tap["ps_idx"])
     assert np.abs(N(f2) - f2_want).max() <= 1e-5
     merged = N(st["merged"])
-    assert merged.shape == (1, 49152, 3)
+    assert merged.shape == (1, 49152, 3) and np.array_equal(merged, merged_from_stages(pc, st))
     assert np.array_equal(N(st["sel"]), O.farthest_point_sample(16384, merged))
     assert np.array_equal(out, merged[0][N(st["sel"])[0]])
 
