@@ -19,6 +19,8 @@ LINEAR_PLAN_INTS = 21  # include/dispu_hip.h: DISPU_LINEAR_PLAN_INTS
 POISSON_MAX_N = 49152       # include/dispu_hip.h: DISPU_POISSON_MAX_N
 POISSON_MAX_ROUNDS = 256    # include/dispu_hip.h: DISPU_POISSON_MAX_ROUNDS
 SORT_ROWS_MAX_K = 4096      # dispu_sort_rows_i32
+RADIX_TILE = 2048           # include/dispu_hip.h: DISPU_RADIX_TILE
+GRID_NONFINITE, GRID_AXIS_X, GRID_AXIS_Y, GRID_AXIS_Z, GRID_TOO_MANY_POINTS = 1, 2, 3, 4, 5   # include/dispu_hip.h: DISPU_GRID_*
 
 _vp, _i, _sz, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_long
 
@@ -206,6 +208,11 @@ SIGNATURES = {
     "dispu_poisson_disk_keep": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dispu_poisson_disk_select": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dispu_sort_rows_i32": (_i, [_i, _i, _vp, _vp]),
+    "dispu_radix_sort_scratch_bytes": (_sz, [C.c_longlong]),
+    "dispu_radix_sort_pairs": (_i, [C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_grid_subsample_scratch_bytes": (_sz, [C.c_longlong, _i, _i]),
+    "dispu_grid_subsample_plan": (_i, [C.c_longlong, _vp, C.c_float, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dispu_grid_subsample_emit": (_i, [C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
 class TnReduceDesc(C.Structure):

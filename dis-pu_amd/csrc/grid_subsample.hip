@@ -1,0 +1,598 @@
+// Grid subsampling (gfx950): every point of a cloud that falls into a cube of edge dl is replaced by the cube's barycentre, with the mean
+// feature and the most frequent label of the cube.  Replaces libs/cpp_wrappers/cpp_subsampling (grid_subsampling.cpp:5-106,
+// grid_subsampling.h:10-80, cloud.cpp:27-67), the KPConv voxel-grid subsampler, bit for bit: the yardstick is the sequential float32
+// numpy restatement in tests/grid_subsample_oracle.py, itself held to outputs recorded from the reference's own function.
+//
+// The reference adds the points of a voxel in ascending point index into an std::unordered_map.  Here the same order comes from a STABLE
+// device-wide radix sort of (voxel key, point index): equal keys keep ascending index, so a serial walk along each run of equal keys
+// adds in the reference's order.  All arithmetic is fp32 with one rounding per operation (the library is built with -ffp-contract=off,
+// divisions are the correctly rounded ones).  No float atomics anywhere: two runs give identical bytes.
+//
+//   bounds    per-workgroup min / max / non-finite partials, finished by one small workgroup          -> READBACK 1 (7 words)
+//   grid      origin, NX, NY, NZ, the key range and the pass count: on the host, in grid_params() ONLY
+//   keys      key[i] = iX + NX iY + NX NY iZ - key_min (uint64), val[i] = i (uint32)
+//   sort      LSD radix sort, 8 bits per pass, ceil(bits / 8) passes (none when the grid is one cell), ping-pong buffers; per pass:
+//               histogram   256 bins per tile of kRsTile elements in LDS (integer LDS atomics: counts are order-free)
+//               scan        exclusive scan of the digit-major table [256][tiles]
+//               scatter     stable rank inside the tile: lanes of equal digit found by ballots, ranked by lane; waves prefixed in wave
+//                           order; wave w owns the contiguous elements [w 512, (w + 1) 512) of the tile, so rank order = index order
+//   heads     head[j] = (j == 0 || key[j] != key[j-1]); an exclusive scan numbers the voxels and gives the start of every run and the
+//             voxel count m                                                                            -> READBACK 2 (m)
+//   reduce    one lane per (voxel, output column) walks its run from start to end: serial by necessity, the float order is pinned
+//   labels    per label column, the same sorter on (voxel id << 32) | (label ^ 0x80000000), then per voxel the longest run of equal
+//             keys, the first such run winning: ties go to the smallest label (signed)
+//
+// Cross-workgroup ordering is by kernel boundaries only: no kernel waits on anything another workgroup writes.  The device-wide scans
+// are the plain three-step kind (tile sums, scan of sums, apply); one building block serves the histogram table and the heads.
+// Two small host readbacks per call (dispu_grid_subsample_plan): the bounds with the non-finite flag, and m.
+#include "common.h"
+#include <math.h>
+#include <float.h>
+
+namespace dispu {
+
+constexpr int kRsThreads = 256;                      // 4 waves
+constexpr int kRsWaves = kRsThreads / kWave;
+constexpr int kRsItems = 8;                          // elements per thread
+constexpr int kRsTile = kRsThreads * kRsItems;       // 2048 = DISPU_RADIX_TILE
+constexpr int kRsWaveSpan = kWave * kRsItems;        // 512 contiguous elements per wave
+constexpr int kBoundsMaxBlocks = 1024;
+
+// ---- block helpers (256 threads) ---------------------------------------------------------------------------------------------------
+// exclusive prefix of one value per thread in thread order, and the block total; wsum: kRsWaves words of LDS, reusable on return
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o, kWave);
+        if (lane >= o) inc += t;
+    }
+    if (lane == kWave - 1) wsum[w] = inc;
+    __syncthreads();
+    uint32_t off = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < kRsWaves; ++i) {
+        const uint32_t s = wsum[i];
+        if (i < w) off += s;
+        total += s;
+    }
+    __syncthreads();
+    return off + inc - v;
+}
+
+// ---- device-wide exclusive scan of uint32 data[L], in place: reduce -> sums -> apply; chunks of kRsTile ------------------------------
+__global__ __launch_bounds__(kRsThreads) void scan_reduce_kernel(const uint32_t* __restrict__ data, size_t L, uint32_t* __restrict__ sums) {
+    __shared__ uint32_t wsum[kRsWaves];
+    const size_t base = (size_t)blockIdx.x * kRsTile + (size_t)threadIdx.x * kRsItems;
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < kRsItems; ++k)
+        if (base + k < L) s += data[base + k];
+    uint32_t total;
+    (void)block_excl_scan(s, wsum, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one workgroup: sums[nb] -> their exclusive prefixes, in place; the grand total -> *total_out (if not null)
+__global__ __launch_bounds__(kRsThreads) void scan_sums_kernel(uint32_t* __restrict__ sums, unsigned nb, uint32_t* __restrict__ total_out) {
+    __shared__ uint32_t wsum[kRsWaves];
+    const unsigned per = (nb + kRsThreads - 1) / kRsThreads;
+    const unsigned lo = min(threadIdx.x * per, nb), hi = min(lo + per, nb);
+    uint32_t s = 0;
+    for (unsigned i = lo; i < hi; ++i) s += sums[i];
+    uint32_t total;
+    uint32_t run = block_excl_scan(s, wsum, total);
+    for (unsigned i = lo; i < hi; ++i) {
+        const uint32_t v = sums[i];
+        sums[i] = run;
+        run += v;
+    }
+    if (total_out && threadIdx.x == 0) *total_out = total;
+}
+
+__global__ __launch_bounds__(kRsThreads) void scan_apply_kernel(uint32_t* __restrict__ data, size_t L, const uint32_t* __restrict__ sums) {
+    __shared__ uint32_t wsum[kRsWaves];
+    const size_t base = (size_t)blockIdx.x * kRsTile + (size_t)threadIdx.x * kRsItems;
+    uint32_t v[kRsItems];
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < kRsItems; ++k) {
+        v[k] = base + k < L ? data[base + k] : 0u;
+        s += v[k];
+    }
+    uint32_t total;
+    uint32_t run = block_excl_scan(s, wsum, total) + sums[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kRsItems; ++k) {
+        if (base + k < L) data[base + k] = run;
+        run += v[k];
+    }
+}
+
+static inline size_t scan_blocks(size_t L) { return (L + kRsTile - 1) / kRsTile; }
+
+// sums: scan_blocks(L) words
+static int exclusive_scan_u32(uint32_t* data, size_t L, uint32_t* sums, uint32_t* total_out, hipStream_t st) {
+    const unsigned nb = (unsigned)scan_blocks(L);
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kRsThreads), 0, st, data, L, sums);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kRsThreads), 0, st, sums, nb, total_out);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kRsThreads), 0, st, data, L, sums);
+    return (int)hipGetLastError();
+}
+
+// ---- radix sort ----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kRsThreads) void radix_hist_kernel(const uint64_t* __restrict__ keys, size_t n, int shift, unsigned tiles,
+                                                                uint32_t* __restrict__ table) {
+    __shared__ uint32_t hist[256];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * kRsTile;
+#pragma unroll
+    for (int k = 0; k < kRsItems; ++k) {
+        const size_t p = base + (size_t)k * kRsThreads + threadIdx.x;
+        if (p < n) atomicAdd(&hist[(unsigned)(keys[p] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    table[(size_t)threadIdx.x * tiles + blockIdx.x] = hist[threadIdx.x];
+}
+
+// table: the SCANNED digit-major table, table[d][tile] = the first output position of digit d of this tile
+__global__ __launch_bounds__(kRsThreads) void radix_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                                   size_t n, int shift, unsigned tiles, const uint32_t* __restrict__ table,
+                                                                   uint64_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
+    __shared__ uint32_t wcount[kRsWaves][256];       // per wave: elements of each digit seen so far, at the end the wave's count
+    __shared__ uint32_t wbase[kRsWaves][256];        // first output position of (wave, digit)
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+#pragma unroll
+    for (int i = 0; i < kRsWaves; ++i) wcount[i][threadIdx.x] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * kRsTile + (size_t)w * kRsWaveSpan + lane;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    volatile uint32_t* wc = wcount[w];               // this wave's row: read by all its lanes, then written by the digit leaders, in order
+    uint64_t key[kRsItems];
+    uint32_t val[kRsItems], rank[kRsItems];
+#pragma unroll
+    for (int k = 0; k < kRsItems; ++k) {
+        const size_t p = base + (size_t)k * kWave;
+        const bool valid = p < n;
+        key[k] = valid ? keys[p] : 0ull;
+        val[k] = valid ? vals[p] : 0u;
+        const unsigned d = (unsigned)(key[k] >> shift) & 255u;
+        unsigned long long peers = __ballot(valid);  // the lanes that hold an element of the same digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            peers &= bit ? bal : ~bal;
+        }
+        const uint32_t before = wc[d];
+        __builtin_amdgcn_wave_barrier();
+        rank[k] = before + (uint32_t)__popcll(peers & below);
+        if (valid && (peers & below) == 0ull) wc[d] = before + (uint32_t)__popcll(peers);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    {
+        uint32_t run = table[(size_t)threadIdx.x * tiles + blockIdx.x];
+#pragma unroll
+        for (int i = 0; i < kRsWaves; ++i) {
+            wbase[i][threadIdx.x] = run;
+            run += wcount[i][threadIdx.x];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kRsItems; ++k) {
+        const size_t p = base + (size_t)k * kWave;
+        if (p < n) {
+            const size_t dst = (size_t)wbase[w][(unsigned)(key[k] >> shift) & 255u] + rank[k];
+            if (dst < n) {                           // always true for a consistent table; keeps a wrong one from writing outside
+                keys_out[dst] = key[k];
+                vals_out[dst] = val[k];
+            }
+        }
+    }
+}
+
+static inline unsigned rs_tiles(size_t n) { return (unsigned)((n + kRsTile - 1) / kRsTile); }
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline size_t rs_table_words(size_t n) { return (size_t)256 * rs_tiles(n); }
+
+// `passes` stable 8-bit passes from (src_k, src_v), which is only read, alternating into (xk, xv), (yk, yv), (xk, xv), ...:
+// the result is in x when passes is odd and in y when it is even (passes >= 1)
+static int radix_passes(size_t n, int passes, const uint64_t* src_k, const uint32_t* src_v, uint64_t* xk, uint32_t* xv, uint64_t* yk,
+                        uint32_t* yv, uint32_t* table, uint32_t* sums, hipStream_t st) {
+    const unsigned tiles = rs_tiles(n);
+    const uint64_t* ck = src_k;
+    const uint32_t* cv = src_v;
+    for (int p = 0; p < passes; ++p) {
+        uint64_t* dk = (p & 1) ? yk : xk;
+        uint32_t* dv = (p & 1) ? yv : xv;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(tiles), dim3(kRsThreads), 0, st, ck, n, 8 * p, tiles, table);
+        const int rc = exclusive_scan_u32(table, rs_table_words(n), sums, nullptr, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(tiles), dim3(kRsThreads), 0, st, ck, cv, n, 8 * p, tiles, table, dk, dv);
+        ck = dk;
+        cv = dv;
+    }
+    return (int)hipGetLastError();
+}
+
+// scratch of the sorter alone: alternate keys, alternate payload, table, scan sums
+struct SortScratch {
+    size_t keys, vals, table, sums, total;
+};
+static SortScratch sort_scratch(size_t n) {
+    SortScratch s;
+    size_t o = 0;
+    s.keys = o;  o += align256(8 * n);
+    s.vals = o;  o += align256(4 * n);
+    s.table = o; o += align256(4 * rs_table_words(n));
+    s.sums = o;  o += align256(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
+    s.total = o;
+    return s;
+}
+
+// ---- bounds ----------------------------------------------------------------------------------------------------------------------------
+struct Bounds {
+    float mn[3], mx[3];
+    uint32_t bad;
+};
+
+__device__ __forceinline__ void bounds_block_reduce(Bounds& b, Bounds* lds) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float a = __shfl_xor(b.mn[c], o, kWave), z = __shfl_xor(b.mx[c], o, kWave);
+            b.mn[c] = a < b.mn[c] ? a : b.mn[c];
+            b.mx[c] = z > b.mx[c] ? z : b.mx[c];
+        }
+        b.bad |= __shfl_xor(b.bad, o, kWave);
+    }
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    if (lane == 0) lds[w] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < kRsWaves; ++i) {
+            for (int c = 0; c < 3; ++c) {
+                b.mn[c] = lds[i].mn[c] < b.mn[c] ? lds[i].mn[c] : b.mn[c];
+                b.mx[c] = lds[i].mx[c] > b.mx[c] ? lds[i].mx[c] : b.mx[c];
+            }
+            b.bad |= lds[i].bad;
+        }
+    }
+}
+
+// partial[blockIdx.x] = min / max / non-finite flag of the points this workgroup strides over; every workgroup sees at least one point
+__global__ __launch_bounds__(kRsThreads) void bounds_partial_kernel(const float* __restrict__ points, size_t n, Bounds* __restrict__ partial) {
+    __shared__ Bounds lds[kRsWaves];
+    Bounds b;
+    for (int c = 0; c < 3; ++c) b.mn[c] = b.mx[c] = points[c];      // the reference starts from point 0 (cloud.cpp:30,51)
+    b.bad = 0;
+    for (size_t i = (size_t)blockIdx.x * kRsThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kRsThreads) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = points[3 * i + c];
+            b.bad |= !(fabsf(v) <= FLT_MAX);
+            b.mn[c] = v < b.mn[c] ? v : b.mn[c];
+            b.mx[c] = v > b.mx[c] ? v : b.mx[c];
+        }
+    }
+    bounds_block_reduce(b, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+}
+
+__global__ __launch_bounds__(kRsThreads) void bounds_finish_kernel(const Bounds* __restrict__ partial, int blocks, Bounds* __restrict__ out) {
+    __shared__ Bounds lds[kRsWaves];
+    Bounds b = partial[0];
+    for (int i = threadIdx.x; i < blocks; i += kRsThreads) {
+        const Bounds p = partial[i];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            b.mn[c] = p.mn[c] < b.mn[c] ? p.mn[c] : b.mn[c];
+            b.mx[c] = p.mx[c] > b.mx[c] ? p.mx[c] : b.mx[c];
+        }
+        b.bad |= p.bad;
+    }
+    bounds_block_reduce(b, lds);
+    if (threadIdx.x == 0) *out = b;
+}
+
+// ---- grid parameters: the ONE place where origin, NX, NY, NZ and the key range are computed (host, fp32, one rounding per operation) ----
+struct GridParams {
+    float origin[3];
+    long long N[3];          // NX, NY, NZ
+    long long key_min;       // the smallest key a point can get (0 unless an axis has a point below the rounded origin, see below)
+    int bits, passes;
+    int status;              // 0, or DISPU_GRID_AXIS_X.. when an axis has more than 2^21 cells
+};
+
+static int bit_length_u64(unsigned long long x) {
+    int b = 0;
+    while (x) { ++b; x >>= 1; }
+    return b;
+}
+
+static inline float cell_f(float p, float o, float dl) {
+#pragma clang fp contract(off)
+    const float t = p - o;
+    return floorf(t / dl);
+}
+
+static GridParams grid_params(const Bounds& b, float dl) {
+#pragma clang fp contract(off)
+    GridParams g;
+    const float inv = 1.0f / dl;                                  // grid_subsampling.cpp:27: (1/sampleDl) in float
+    long long lo[3];
+    g.status = 0;
+    for (int c = 0; c < 3; ++c) {
+        const float s = b.mn[c] * inv;
+        g.origin[c] = floorf(s) * dl;
+        const float top = cell_f(b.mx[c], g.origin[c], dl);       // :30-32
+        const float bot = cell_f(b.mn[c], g.origin[c], dl);
+        // in float, before any conversion to an integer: at most 2^21 cells per axis keeps every key below 2^63
+        if (!(top + 1.0f <= 2097152.0f) || !(bot >= -2097152.0f)) {
+            if (!g.status) g.status = 2 + c;
+            g.N[c] = 1;
+            lo[c] = 0;
+            continue;
+        }
+        g.N[c] = (long long)top + 1;
+        // floor(min * inv) * dl is rounded twice and can land a few ulps ABOVE the minimum; such a point gets cell -1 on that axis.  The
+        // reference converts the negative float to size_t and lets the key wrap modulo 2^64, which groups exactly like signed keys do;
+        // here keys are signed, and the sorter sees key - key_min >= 0
+        lo[c] = (long long)bot;
+    }
+    g.key_min = lo[0] + g.N[0] * lo[1] + g.N[0] * g.N[1] * lo[2];
+    const long long key_max = (g.N[0] - 1) + g.N[0] * (g.N[1] - 1) + g.N[0] * g.N[1] * (g.N[2] - 1);
+    g.bits = bit_length_u64((unsigned long long)key_max - (unsigned long long)g.key_min);        // modulo 2^64: no signed overflow
+    g.passes = (g.bits + 7) / 8;
+    return g;
+}
+
+__global__ __launch_bounds__(kRsThreads) void grid_keys_kernel(const float* __restrict__ points, size_t n, float ox, float oy, float oz, float dl,
+                                                               long long NX, long long NXY, long long key_min, uint64_t* __restrict__ keys,
+                                                               uint32_t* __restrict__ vals) {
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (i >= n) return;
+    const float tx = points[3 * i + 0] - ox, ty = points[3 * i + 1] - oy, tz = points[3 * i + 2] - oz;
+    const long long ix = (long long)floorf(__fdiv_rn(tx, dl));    // :53-55, the correctly rounded division
+    const long long iy = (long long)floorf(__fdiv_rn(ty, dl));
+    const long long iz = (long long)floorf(__fdiv_rn(tz, dl));
+    keys[i] = (uint64_t)ix + (uint64_t)NX * (uint64_t)iy + (uint64_t)NXY * (uint64_t)iz - (uint64_t)key_min;   // modulo 2^64, >= 0
+    vals[i] = (uint32_t)i;
+}
+
+__global__ __launch_bounds__(kRsThreads) void iota_kernel(size_t n, uint32_t* __restrict__ vals) {
+    const size_t i = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (i < n) vals[i] = (uint32_t)i;
+}
+
+// ---- run heads ---------------------------------------------------------------------------------------------------------------------------
+// keys == nullptr: all keys are equal (the zero-pass path)
+__global__ __launch_bounds__(kRsThreads) void heads_kernel(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ head) {
+    const size_t j = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (j < n) head[j] = (j == 0 || (keys && keys[j] != keys[j - 1])) ? 1u : 0u;
+}
+
+// ex: the exclusive scan of the heads, replaced in place by the voxel id of every sorted position; start[v] = the first position of voxel
+// v, start[m] = n
+__global__ __launch_bounds__(kRsThreads) void runs_kernel(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ ex,
+                                                          uint32_t* __restrict__ start) {
+    const size_t j = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t h = (j == 0 || (keys && keys[j] != keys[j - 1])) ? 1u : 0u;
+    const uint32_t e = ex[j];                        // heads before j: e < n, and e + h <= n
+    if (h) start[e] = (uint32_t)j;
+    if (j == n - 1) start[e + h] = (uint32_t)n;
+    ex[j] = e + h - 1u;
+}
+
+// ---- reduce: one lane per (voxel, column), columns = 3 coordinates then fdim features ------------------------------------------------------
+// (positions and point indices are clamped to n: a no-op for the sorter's output, it keeps a wrong table from reading outside)
+__global__ __launch_bounds__(kRsThreads) void grid_reduce_kernel(uint32_t n, uint32_t m, int fdim, const uint32_t* __restrict__ start,
+                                                                 const uint32_t* __restrict__ perm, const float* __restrict__ points,
+                                                                 const float* __restrict__ features, float* __restrict__ out_points,
+                                                                 float* __restrict__ out_features) {
+#pragma clang fp contract(off)
+    const int cols = 3 + fdim;
+    const size_t t = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (t >= (size_t)m * cols) return;
+    const uint32_t v = (uint32_t)(t / cols);
+    const int c = (int)(t % cols);
+    const uint32_t lo = start[v], hi = min(start[v + 1], n);
+    float acc = 0.0f;                                // SampledData(): point and features start from 0
+    if (c < 3) {
+        for (uint32_t j = lo; j < hi; ++j) acc += points[3 * (size_t)min(perm[j], n - 1) + c];
+        const float r = (float)(1.0 / (double)(int)(hi - lo));     // :87: point * (1.0 / count), the reciprocal in double, then float
+        out_points[3 * (size_t)v + c] = acc * r;
+    } else {
+        for (uint32_t j = lo; j < hi; ++j) acc += features[(size_t)min(perm[j], n - 1) * fdim + (c - 3)];
+        out_features[(size_t)v * fdim + (c - 3)] = __fdiv_rn(acc, (float)(int)(hi - lo));   // :94: f / count
+    }
+}
+
+// ---- labels --------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kRsThreads) void label_keys_kernel(size_t n, const uint32_t* __restrict__ vid, const uint32_t* __restrict__ perm,
+                                                                const int* __restrict__ classes, int ldim, int col,
+                                                                uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const size_t j = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t l = (uint32_t)classes[(size_t)min(perm[j], (uint32_t)(n - 1)) * ldim + col] ^ 0x80000000u;      // unsigned order = signed order
+    keys[j] = ((uint64_t)vid[j] << 32) | l;
+    vals[j] = (uint32_t)j;
+}
+
+// keys sorted: voxel v owns [start[v], start[v+1]) again; the longest run of equal keys, the first such run (the smallest label) winning
+__global__ __launch_bounds__(kRsThreads) void label_mode_kernel(uint32_t n, uint32_t m, const uint32_t* __restrict__ start, const uint64_t* __restrict__ keys,
+                                                                int ldim, int col, int* __restrict__ out_classes) {
+    const size_t v = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (v >= m) return;
+    const uint32_t lo = min(start[v], n - 1), hi = min(start[v + 1], n);
+    uint64_t best = keys[lo], cur = best;
+    uint32_t best_n = 0, cur_n = 0;
+    for (uint32_t j = lo; j < hi; ++j) {
+        const uint64_t k = keys[j];
+        if (k != cur) { cur = k; cur_n = 0; }
+        ++cur_n;
+        if (cur_n > best_n) { best_n = cur_n; best = cur; }
+    }
+    out_classes[v * ldim + col] = (int)((uint32_t)best ^ 0x80000000u);
+}
+
+// ---- scratch of the whole operator -----------------------------------------------------------------------------------------------------------
+struct GridScratch {
+    size_t kA, kB, vA, vB, perm, vid, start, table, sums, partial, small, total;
+};
+static GridScratch grid_scratch(size_t n) {
+    GridScratch s;
+    size_t o = 0;
+    s.kA = o;      o += align256(8 * n);
+    s.kB = o;      o += align256(8 * n);
+    s.vA = o;      o += align256(4 * n);
+    s.vB = o;      o += align256(4 * n);
+    s.perm = o;    o += align256(4 * n);
+    s.vid = o;     o += align256(4 * n);
+    s.start = o;   o += align256(4 * (n + 1));
+    s.table = o;   o += align256(4 * rs_table_words(n));
+    s.sums = o;    o += align256(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
+    s.partial = o; o += align256(sizeof(Bounds) * kBoundsMaxBlocks);
+    s.small = o;   o += 256;                         // Bounds result, m
+    s.total = o;
+    return s;
+}
+
+static inline unsigned blocks_for(size_t work) { return (unsigned)((work + kRsThreads - 1) / kRsThreads); }
+
+}  // namespace dispu
+
+using namespace dispu;
+
+DISPU_EXPORT size_t dispu_radix_sort_scratch_bytes(long long n) {
+    if (n <= 0 || n >= (1ll << 31)) return 0;
+    return sort_scratch((size_t)n).total;
+}
+
+DISPU_EXPORT int dispu_radix_sort_pairs(long long n, int bits, const unsigned long long* keys_in, const unsigned int* vals_in,
+                                        unsigned long long* keys_out, unsigned int* vals_out, void* scratch, size_t scratch_bytes,
+                                        void* stream) {
+    if (n < 0 || n >= (1ll << 31) || bits < 0 || bits > 64) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!keys_in || !vals_in || !keys_out || !vals_out || keys_in == keys_out || vals_in == vals_out) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)n;
+    const int passes = (bits + 7) / 8;
+    if (passes == 0) {
+        DISPU_TRY(hipMemcpyAsync(keys_out, keys_in, 8 * N, hipMemcpyDeviceToDevice, st));
+        DISPU_TRY(hipMemcpyAsync(vals_out, vals_in, 4 * N, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    const SortScratch s = sort_scratch(N);
+    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    char* base = (char*)scratch;
+    uint64_t* ak = (uint64_t*)(base + s.keys);
+    uint32_t* av = (uint32_t*)(base + s.vals);
+    uint64_t* ok = (uint64_t*)keys_out;
+    uint32_t* ov = (uint32_t*)vals_out;
+    const bool odd = passes & 1;                     // the result lands in x for an odd pass count, in y for an even one
+    return radix_passes(N, passes, (const uint64_t*)keys_in, (const uint32_t*)vals_in, odd ? ok : ak, odd ? ov : av, odd ? ak : ok,
+                        odd ? av : ov, (uint32_t*)(base + s.table), (uint32_t*)(base + s.sums), st);
+}
+
+DISPU_EXPORT size_t dispu_grid_subsample_scratch_bytes(long long n, int fdim, int ldim) {
+    if (n <= 0 || n >= (1ll << 31) || fdim < 0 || ldim < 0) return 0;
+    return grid_scratch((size_t)n).total;            // features and labels are read in place: fdim and ldim add nothing
+}
+
+DISPU_EXPORT int dispu_grid_subsample_plan(long long n, const float* points, float dl, void* scratch, size_t scratch_bytes, int* m_out,
+                                           int* status_out, double* grid_out, void* stream) {
+    if (!m_out || !status_out) return (int)hipErrorInvalidValue;
+    *m_out = 0;
+    *status_out = 0;
+    if (n >= (1ll << 31)) { *status_out = 5; return 0; }          // DISPU_GRID_TOO_MANY_POINTS, before anything is touched
+    if (n <= 0 || !points || !(dl > 0.0f) || !(dl <= FLT_MAX)) return (int)hipErrorInvalidValue;
+    const size_t N = (size_t)n;
+    const GridScratch s = grid_scratch(N);
+    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)scratch;
+    uint64_t *kA = (uint64_t*)(base + s.kA), *kB = (uint64_t*)(base + s.kB);
+    uint32_t *vA = (uint32_t*)(base + s.vA), *vB = (uint32_t*)(base + s.vB);
+    uint32_t *perm = (uint32_t*)(base + s.perm), *vid = (uint32_t*)(base + s.vid), *start = (uint32_t*)(base + s.start);
+    uint32_t *table = (uint32_t*)(base + s.table), *sums = (uint32_t*)(base + s.sums);
+    Bounds* partial = (Bounds*)(base + s.partial);
+    Bounds* d_bounds = (Bounds*)(base + s.small);
+    uint32_t* d_m = (uint32_t*)(base + s.small + 128);
+
+    const int bblocks = (int)(blocks_for(N) < (unsigned)kBoundsMaxBlocks ? blocks_for(N) : (unsigned)kBoundsMaxBlocks);
+    hipLaunchKernelGGL(bounds_partial_kernel, dim3(bblocks), dim3(kRsThreads), 0, st, points, N, partial);
+    hipLaunchKernelGGL(bounds_finish_kernel, dim3(1), dim3(kRsThreads), 0, st, (const Bounds*)partial, bblocks, d_bounds);
+    DISPU_CHECK_LAUNCH();
+    Bounds hb;
+    DISPU_TRY(hipMemcpyAsync(&hb, d_bounds, sizeof(Bounds), hipMemcpyDeviceToHost, st));      // readback 1
+    DISPU_TRY(hipStreamSynchronize(st));
+    if (hb.bad) { *status_out = 1; return 0; }                    // DISPU_GRID_NONFINITE
+    const GridParams g = grid_params(hb, dl);
+    if (grid_out) {
+        for (int c = 0; c < 3; ++c) { grid_out[c] = g.origin[c]; grid_out[3 + c] = (double)g.N[c]; }
+        grid_out[6] = g.passes;
+        grid_out[7] = (double)g.key_min;
+    }
+    if (g.status) { *status_out = g.status; return 0; }
+
+    const uint64_t* sorted = nullptr;                // null: one cell, every key equal
+    if (g.passes == 0) {
+        hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, N, perm);
+    } else {
+        hipLaunchKernelGGL(grid_keys_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, points, N, g.origin[0], g.origin[1], g.origin[2],
+                           dl, g.N[0], g.N[0] * g.N[1], g.key_min, kA, vA);
+        const int rc = radix_passes(N, g.passes, kA, vA, kB, vB, kA, vA, table, sums, st);
+        if (rc) return rc;
+        const bool odd = g.passes & 1;
+        sorted = odd ? kB : kA;
+        DISPU_TRY(hipMemcpyAsync(perm, odd ? vB : vA, 4 * N, hipMemcpyDeviceToDevice, st));
+    }
+    hipLaunchKernelGGL(heads_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, sorted, N, vid);
+    const int rc = exclusive_scan_u32(vid, N, sums, d_m, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(runs_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, sorted, N, vid, start);
+    DISPU_CHECK_LAUNCH();
+    uint32_t hm = 0;
+    DISPU_TRY(hipMemcpyAsync(&hm, d_m, sizeof(hm), hipMemcpyDeviceToHost, st));               // readback 2
+    DISPU_TRY(hipStreamSynchronize(st));
+    *m_out = (int)hm;
+    return 0;
+}
+
+DISPU_EXPORT int dispu_grid_subsample_emit(long long n, int m, int fdim, int ldim, const float* points, const float* features,
+                                           const int* classes, void* scratch, size_t scratch_bytes, float* out_points, float* out_features,
+                                           int* out_classes, void* stream) {
+    if (n <= 0 || n >= (1ll << 31) || m <= 0 || m > n || fdim < 0 || ldim < 0 || !points || !out_points) return (int)hipErrorInvalidValue;
+    if ((fdim > 0 && (!features || !out_features)) || (ldim > 0 && (!classes || !out_classes))) return (int)hipErrorInvalidValue;
+    const size_t N = (size_t)n;
+    const GridScratch s = grid_scratch(N);
+    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)scratch;
+    uint64_t *kA = (uint64_t*)(base + s.kA), *kB = (uint64_t*)(base + s.kB);
+    uint32_t *vA = (uint32_t*)(base + s.vA), *vB = (uint32_t*)(base + s.vB);
+    const uint32_t *perm = (const uint32_t*)(base + s.perm), *vid = (const uint32_t*)(base + s.vid), *start = (const uint32_t*)(base + s.start);
+    uint32_t *table = (uint32_t*)(base + s.table), *sums = (uint32_t*)(base + s.sums);
+
+    hipLaunchKernelGGL(grid_reduce_kernel, dim3(blocks_for((size_t)m * (3 + fdim))), dim3(kRsThreads), 0, st, (uint32_t)N, (uint32_t)m, fdim, start, perm,
+                       points, features, out_points, out_features);
+    DISPU_CHECK_LAUNCH();
+    const int lpasses = (32 + bit_length_u64((unsigned long long)m - 1) + 7) / 8;
+    for (int col = 0; col < ldim; ++col) {
+        hipLaunchKernelGGL(label_keys_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, N, vid, perm, classes, ldim, col, kA, vA);
+        const int rc = radix_passes(N, lpasses, kA, vA, kB, vB, kA, vA, table, sums, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(label_mode_kernel, dim3(blocks_for((size_t)m)), dim3(kRsThreads), 0, st, (uint32_t)N, (uint32_t)m, start,
+                           (const uint64_t*)((lpasses & 1) ? kB : kA), ldim, col, out_classes);
+    }
+    return (int)hipGetLastError();
+}

@@ -901,6 +901,47 @@ int dispu_poisson_disk_select(int b, int n, int m, int steps, const float* point
  * a region's points by distance; the greedy order of the selection must be the sample order, i.e. the index order. */
 int dispu_sort_rows_i32(int b, int k, int* idx, void* stream);
 
+/* ---- grid subsampling: libs/cpp_wrappers/cpp_subsampling (compile_op.sh builds it with the other ops), the KPConv voxel-grid
+ * subsampler.  dis-pu_amd/grid_subsampling.py, csrc/grid_subsample.hip; the yardstick is the sequential float32 numpy restatement in
+ * tests/grid_subsample_oracle.py, held to outputs recorded from the reference's own function, reproduced bit for bit ------------------- */
+/* Stable LSD radix sort of n (key u64, payload u32) pairs by the low `bits` bits of the key (0 <= bits <= 64; the higher bits must be
+ * equal in all keys, or the order is the one of the low bits only), 8 bits per pass, ceil(bits / 8) passes; bits = 0 copies.  Equal
+ * keys keep their input order: the order std::unordered_map<size_t, SampledData> insertion followed by in-order accumulation has in
+ * grid_subsampling.cpp:50-77, which no sort of the reference provides (it has none).  The inputs are only read and must not alias the
+ * outputs.  scratch >= dispu_radix_sort_scratch_bytes(n), 16-byte aligned.  0 <= n < 2^31.  A tile is DISPU_RADIX_TILE elements.
+ * No kernel waits on another workgroup; integer LDS atomics only; identical bytes from run to run. */
+#define DISPU_RADIX_TILE 2048
+size_t dispu_radix_sort_scratch_bytes(long long n);
+int dispu_radix_sort_pairs(long long n, int bits, const unsigned long long* keys_in, const unsigned int* vals_in,
+                           unsigned long long* keys_out, unsigned int* vals_out, void* scratch, size_t scratch_bytes, void* stream);
+/* grid_subsampling (grid_subsampling.cpp:5-106, SampledData grid_subsampling.h:10-80, min_point / max_point cloud.cpp:27-67) in two
+ * steps over one scratch buffer of dispu_grid_subsample_scratch_bytes(n, fdim, ldim) bytes (16-byte aligned; 0 for illegal sizes).
+ * All in fp32, one rounding per operation, divisions correctly rounded:  origin = floor(min * (1.0f / dl)) * dl;  NX = floor((max.x -
+ * origin.x) / dl) + 1, NY, NZ likewise;  per point i = floor((p - origin) / dl) per axis, key = iX + NX iY + NX NY iZ (signed: the
+ * doubly rounded origin can lie a few ulps above the minimum, a point below it gets cell -1 -- the reference's size_t key wraps modulo
+ * 2^64 there, which groups the same points).  Per key: count, the sum of the points and of the features added in ascending point index
+ * from 0, one label histogram per label column.  Output row per key, rows in ASCENDING KEY ORDER (the reference: unordered_map order):
+ * point * (float)(1.0 / count), features / (float)count, per label column the most frequent label, a tie going to the SMALLEST label
+ * (signed; the reference: whichever std::max_element meets first in unordered_map order).
+ * plan: points [n,3] f32 -> *m_out = the number of occupied voxels, the sorted order left in scratch for emit.  Synchronous: it reads
+ * back the bounds with the non-finite flag, and m (two small device-to-host copies).  *status_out = 0, or a refusal (nothing further is
+ * launched, *m_out = 0): DISPU_GRID_NONFINITE a coordinate is NaN or infinite; DISPU_GRID_AXIS_X / _Y / _Z that axis has more than 2^21
+ * cells (keys must stay below 2^63; tested in float before any conversion to an integer) -- use a larger dl;
+ * DISPU_GRID_TOO_MANY_POINTS n >= 2^31.  grid_out (NULL or 8 doubles): origin x y z, NX, NY, NZ, sort passes, the smallest key.
+ * emit: with the same n, points and scratch and plan's m -> out_points [m,3] f32, out_features [m,fdim] f32 (features [n,fdim]),
+ * out_classes [m,ldim] i32 (classes [n,ldim]); fdim = 0 / ldim = 0: those pointers are not used.  Asynchronous on the stream.
+ * One lane per (voxel, column) walks its run serially (the float order is pinned): a voxel holding all n points costs n serial adds. */
+#define DISPU_GRID_NONFINITE 1
+#define DISPU_GRID_AXIS_X 2
+#define DISPU_GRID_AXIS_Y 3
+#define DISPU_GRID_AXIS_Z 4
+#define DISPU_GRID_TOO_MANY_POINTS 5
+size_t dispu_grid_subsample_scratch_bytes(long long n, int fdim, int ldim);
+int dispu_grid_subsample_plan(long long n, const float* points, float dl, void* scratch, size_t scratch_bytes, int* m_out, int* status_out,
+                              double* grid_out, void* stream);
+int dispu_grid_subsample_emit(long long n, int m, int fdim, int ldim, const float* points, const float* features, const int* classes,
+                              void* scratch, size_t scratch_bytes, float* out_points, float* out_features, int* out_classes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,214 @@
+"""GPU tests of dispu_amd.grid_subsampling.compute (csrc/grid_subsample.hip) against the sequential float32 numpy restatement
+(tests/grid_subsample_oracle.py): points, features, classes and the row order, bit for bit.
+
+One oracle run per (n, grid) with 5 feature and 2 label columns serves every (fdim, ldim): columns are summed and counted independently,
+so the oracle of a column subset is the subset of the oracle's columns."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import grid_subsample_oracle as O  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+TILE = 2048
+SIZES = (1, 2, TILE - 1, TILE, TILE + 1, 20000)
+# the cloud spans [-1.5, 2.5]^3 ("one": shifted to [0.5, 4.5]^3 so that a single cell holds it)
+GRIDS = {"one": f32(1000.0),       # one voxel for the whole cloud: the zero-pass path and one serial run of n points
+         "dense": f32(1.0),        # 64 voxels: ~300 points per voxel at n = 20000
+         "fine": f32(0.05)}        # 80^3 = 512000 cells in range > 2^16: three passes
+COLUMNS = ((0, 0), (1, 0), (3, 1), (5, 2), (0, 2))
+LABELS = np.array([-2 ** 31, -3, 0, 2, 2 ** 31 - 1], np.int32)
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def make_cloud(n, grid):
+    """points with negative coordinates, a fifth of them exactly on voxel faces of this grid, a tenth duplicated; features of mixed
+    magnitude (the order of the adds shows); labels from five values including the int32 extremes, duplicates labelled differently"""
+    dl = GRIDS[grid]
+    rng = np.random.default_rng(n * 7 + len(grid))
+    p = (rng.random((n, 3)) * 4 - 1.5).astype(f32)
+    k = n // 5
+    p[:k] = (np.round(p[:k] / dl) * dl).astype(f32) if grid != "one" else np.round(p[:k]).astype(f32)
+    d = n // 10
+    p[k:k + d] = p[rng.integers(0, n, d)]
+    if grid == "one":
+        p = np.clip(p + f32(2.0), f32(0.5), f32(4.5))
+    f = (rng.standard_normal((n, 5)) * np.array([1, 1e-3, 1e3, 1, 30], f32)).astype(f32)
+    c = LABELS[rng.integers(0, 5, (n, 2))]
+    return np.ascontiguousarray(p), np.ascontiguousarray(f), np.ascontiguousarray(c), dl
+
+
+_CASES = {}
+
+
+def case(n, grid):
+    if (n, grid) not in _CASES:
+        p, f, c, dl = make_cloud(n, grid)
+        _CASES[(n, grid)] = (p, f, c, dl) + O.compute(p, f, c, dl)
+    return _CASES[(n, grid)]
+
+
+def compute(*a, **k):
+    import dispu_amd  # noqa: F401
+    from dispu_amd import grid_subsampling as G
+    return G.compute(*a, **k)
+
+
+def test_the_cases_cover_what_they_claim():
+    p, f, c, dl, op, of, oc = case(20000, "one")
+    assert O.grid(p, dl)[1] == [1, 1, 1] and len(op) == 1
+    p, f, c, dl, op, of, oc = case(20000, "dense")
+    assert len(op) <= 125 and 20000 / len(op) > 150
+    p, f, c, dl, op, of, oc = case(20000, "fine")
+    N = O.grid(p, dl)[1]
+    assert N[0] * N[1] * N[2] > 1 << 16 and N[0] * N[1] * N[2] <= 1 << 24
+    k = O.keys(p, dl)
+    assert (np.bincount(np.unique(k, return_inverse=True)[1]) > 1).any()          # duplicates share voxels even on the fine grid
+    assert p.min() < 0
+
+
+@pytest.mark.parametrize("fdim, ldim", COLUMNS)
+@pytest.mark.parametrize("grid", sorted(GRIDS))
+@pytest.mark.parametrize("n", SIZES)
+def test_compute_matches_the_oracle_bit_for_bit(dev, n, grid, fdim, ldim):
+    p, f, c, dl, op, of, oc = case(n, grid)
+    kw = {}
+    if fdim:
+        kw["features"] = np.ascontiguousarray(f[:, :fdim])
+    if ldim:
+        kw["classes"] = np.ascontiguousarray(c[:, :ldim])
+    out = compute(p, sampleDl=dl, **kw)
+    out = list(out) if isinstance(out, tuple) else [out]
+    assert len(out) == 1 + (fdim > 0) + (ldim > 0)
+    assert same_bits(out[0], op), "points (or the row order)"
+    if fdim:
+        assert same_bits(out[1], of[:, :fdim]), "features"
+    if ldim:
+        assert same_bits(out[-1], oc[:, :ldim]), "classes"
+
+
+def test_one_dimensional_classes_and_empty_feature_columns(dev):
+    p, f, c, dl, op, of, oc = case(TILE + 1, "dense")
+    pts, feats, cls = compute(p, features=f[:, :0], classes=np.ascontiguousarray(c[:, 0]), sampleDl=dl)
+    assert same_bits(pts, op) and feats.shape == (len(op), 0) and same_bits(cls, oc[:, :1])
+    assert same_bits(compute(p, sampleDl=dl, method="voxelcenters"), op)           # the wrapper computes barycentres for both names
+
+
+def test_forced_label_ties_and_negative_labels(dev):
+    p = np.zeros((8, 3), f32) + f32(0.25)
+    p[4:] += f32(1.0)
+    c = np.array([[5, -7], [-1, -7], [5, 3], [-1, 3], [2 ** 31 - 1, 0], [-2 ** 31, 0], [9, 1], [9, 2]], np.int32)
+    pts, cls = compute(p, classes=c, sampleDl=1.0)
+    assert cls.tolist() == [[-1, -7], [9, 0]]
+    assert same_bits(cls, O.compute(p, None, c, 1.0)[2])
+
+
+def test_numpy_and_tensor_entries_give_the_same_bytes_twice(dev):
+    import torch
+    p, f, c, dl, op, of, oc = case(20000, "fine")
+    a = compute(p, f, c, sampleDl=dl)
+    tp, tf, tc = (torch.from_numpy(x).to(dev) for x in (p, f, c))
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):                                                 # the tensor entry works on the current stream
+        b = compute(tp, tf, tc, sampleDl=float(dl))
+    side.synchronize()
+    b2 = compute(tp, tf, tc, sampleDl=float(dl))
+    assert all(isinstance(x, torch.Tensor) and x.device == tp.device for x in b)
+    assert b[0].dtype == torch.float32 and b[1].dtype == torch.float32 and b[2].dtype == torch.int32
+    for x, y, z, o in zip(a, b, b2, (op, of, oc)):
+        assert same_bits(x, o) and same_bits(y.cpu().numpy(), o) and same_bits(z.cpu().numpy(), o)
+
+
+@pytest.mark.parametrize("name", ("unit", "faces", "fine", "below_origin"))
+def test_golden_clouds_of_the_reference(dev, golden_dir, name):
+    g = np.load(os.path.join(golden_dir, "grid_subsample_ref.npz"))
+    pts, feats, cls = compute(g[name + "_points"], g[name + "_features"], g[name + "_classes"], sampleDl=g[name + "_dl"])
+    assert same_bits(pts, g[name + "_out_points"])
+    assert same_bits(feats, g[name + "_out_features"])
+    assert same_bits(cls, g[name + "_out_classes"])
+
+
+def test_grid_parameters_are_the_oracles(dev):
+    import torch
+    from dispu_amd import _lib
+    L = _lib.lib()
+    for n, grid in ((20000, "fine"), (TILE - 1, "dense"), (20000, "one")):       # passes: 3, 1, 0
+        p, f, c, dl, op, of, oc = case(n, grid)
+        tp = torch.from_numpy(p).to(dev)
+        nbytes = L.dispu_grid_subsample_scratch_bytes(n, 0, 0)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        m, status, info = C.c_int(0), C.c_int(0), (C.c_double * 8)()
+        _lib.check(L.dispu_grid_subsample_plan(n, _lib.ptr(tp), float(dl), _lib.ptr(scratch), nbytes, C.byref(m), C.byref(status), info,
+                                               _lib.stream_ptr(dev)), "plan")
+        origin, N = O.grid(p, dl)
+        assert status.value == 0 and m.value == len(op)
+        assert [f32(info[i]) for i in range(3)] == origin.tolist() and [int(info[3 + i]) for i in range(3)] == N
+        lo = [int(np.floor(f32(f32(p[:, a].min() - origin[a]) / dl))) for a in range(3)]      # 0, or -1 below a doubly rounded origin
+        key_min = lo[0] + N[0] * lo[1] + N[0] * N[1] * lo[2]
+        key_max = N[0] * N[1] * N[2] - 1
+        assert int(info[7]) == key_min <= O.keys(p, dl).min() and int(info[6]) == ((key_max - key_min).bit_length() + 7) // 8
+
+
+def test_refusals_leave_the_device_usable(dev):
+    p, f, c, dl, op, of, oc = case(TILE + 1, "dense")
+    for bad in (np.nan, np.inf, -np.inf):
+        q = p.copy()
+        q[TILE, 1] = bad
+        with pytest.raises(ValueError, match="NaN or infinite"):
+            compute(q, f, c, sampleDl=dl)
+    q = p.copy()
+    q[:, 1] *= f32(0.25)
+    q[:, 2] *= f32(0.25)                                  # x spans 4 / 1e-6 = 4e6 > 2^21 cells, y and z 1e6
+    with pytest.raises(ValueError, match=r"the x axis .* 2\^21 cells .* larger sampleDl"):
+        compute(q, sampleDl=1e-6)
+    with pytest.raises(ValueError, match=r"the z axis .* larger sampleDl"):
+        compute(np.ascontiguousarray(q[:, ::-1]), sampleDl=1e-6)
+    with pytest.raises(ValueError, match=r"axis .* larger sampleDl"):
+        compute(p, sampleDl=1e-30)
+    out = compute(p, f, c, sampleDl=dl)
+    assert same_bits(out[0], op) and same_bits(out[1], of) and same_bits(out[2], oc)
+
+
+def test_upsample_tool_with_grid_size_end_to_end(dev, tmp_path):
+    """tools/upsample.py --grid_size on an uneven .xyz scan with a restored checkpoint: the output is the upsampled SUBSAMPLED cloud,
+    final_ratio x its count, and the printed line shows both counts"""
+    import subprocess
+    ROOT = os.path.dirname(HERE)
+    sys.path.insert(0, ROOT)
+    import dispu_amd  # noqa: F401
+    from dispu_amd import checkpoint as CK, upsample as U
+    from oracle import generator as OG
+    log_dir, data = tmp_path / "log", tmp_path / "data"
+    (data / "test").mkdir(parents=True)
+    log_dir.mkdir()
+    CK.save_generator_params(str(log_dir / "model"), OG.init_params(seed=6, bias_scale=0.05), step=3)
+    rng = np.random.default_rng(3)
+    v = rng.standard_normal((6000, 3))
+    v[:4000, 2] = np.abs(v[:4000, 2]) * 4                  # two thirds of the scan crowd around one pole
+    v = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(f32)
+    np.savetxt(str(data / "test" / "scan.xyz"), v, fmt="%.6f")
+    pts = np.loadtxt(str(data / "test" / "scan.xyz"), ndmin=2).astype(f32)
+    sub = compute(pts, sampleDl=0.15)
+    assert 256 <= len(sub) < 3000
+    _, gen = CK.restore_generator(str(log_dir), device=dev)
+    want = str(tmp_path / "want.xyz")
+    np.savetxt(want, U.upsample_cloud(gen, sub), fmt="%.6f")
+    cmd = [sys.executable, os.path.join(ROOT, "tools", "upsample.py"), "--log_dir", str(log_dir), "--data_dir", str(data), "--grid_size", "0.15"]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    text = r.stdout.decode(errors="replace")
+    assert r.returncode == 0, text
+    got = data / "test" / "output" / "scan_X4.xyz"
+    assert open(str(got), "rb").read() == open(want, "rb").read()
+    assert np.loadtxt(str(got)).shape == (4 * len(sub), 3)
+    assert "6000 -> %d (grid 0.15) -> %d points" % (len(sub), 4 * len(sub)) in text

@@ -6,9 +6,14 @@ np.savetxt(fmt='%.6f') into --out_folder (default <data_dir>/test/output) -- the
 Clouds go through dis-pu_amd/upsample.py:upsample_ragged in groups of at most --max-points input points (a larger cloud is a group of
 its own), so clouds of different sizes share launches; the outputs do not depend on the grouping.  Each output has final_ratio * n
 points for its own n (the reference takes n from the first globbed file for all of them, model.py:356-359).  .xyz only: rows of
->= 3 numbers, read like pc_util.load (np.loadtxt, first three columns)."""
+>= 3 numbers, read like pc_util.load (np.loadtxt, first three columns).
+
+--grid_size G (off by default) first thins every cloud on the GPU to one barycentre per cube of edge G (dis-pu_amd/grid_subsampling.py,
+the reference's cpp_subsampling): FPS seeds and 256-NN patches only mean "a patch of surface" at a roughly even density, which a raw
+scan does not have.  The output then has final_ratio times the SUBSAMPLED count."""
 import argparse
 import glob
+import math
 import os
 import sys
 import time
@@ -53,6 +58,13 @@ def group_by_budget(sizes, max_points):
     return groups
 
 
+def positive_float(text):
+    v = float(text)
+    if not (math.isfinite(v) and v > 0.0):
+        raise argparse.ArgumentTypeError("must be a finite number > 0, got %s" % text)
+    return v
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Upsample point clouds with a trained generator (the reference's --phase test).")
     ap.add_argument("--log_dir", default="log", help="checkpoint directory (its `checkpoint` file names the latest model)")
@@ -66,6 +78,9 @@ def parse_args(argv=None):
                     help="input points per batch of clouds (bounds device memory and keeps packed offsets below 2^31)")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32: the strict fp32 generator; bf16: after_conv as a bf16 product over F' stored as bf16 (Generator(dtype='bf16'))")
+    ap.add_argument("--grid_size", type=positive_float, default=None,
+                    help="off by default; G: grid-subsample every input cloud on the GPU first, one barycentre per cube of edge G "
+                         "(for dense, uneven scans); the output has final_ratio x the subsampled count")
     return ap.parse_args(argv)
 
 
@@ -97,6 +112,14 @@ def main(argv=None):
     print("restored %s (epoch %d)" % (a.log_dir, epoch))
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
+    raw = [c.shape[0] for c in clouds]
+    if a.grid_size is not None:
+        from dispu_amd import grid_subsampling
+        for i, c in enumerate(clouds):
+            try:
+                clouds[i] = grid_subsampling.compute(c, sampleDl=a.grid_size)
+            except ValueError as e:
+                sys.exit("%s: %s" % (paths[i], e))
     for group in group_by_budget([c.shape[0] for c in clouds], a.max_points):
         try:
             preds = upsample_ragged(gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
@@ -105,7 +128,10 @@ def main(argv=None):
         for i, pred in zip(group, preds):
             out = os.path.join(out_dir, output_name(paths[i], a.final_ratio))
             save_xyz(out, pred)
-            print("%s: %d -> %d points, %s" % (paths[i], clouds[i].shape[0], pred.shape[0], out))
+            if a.grid_size is None:
+                print("%s: %d -> %d points, %s" % (paths[i], clouds[i].shape[0], pred.shape[0], out))
+            else:
+                print("%s: %d -> %d (grid %g) -> %d points, %s" % (paths[i], raw[i], clouds[i].shape[0], a.grid_size, pred.shape[0], out))
     print("%d clouds in %.2f s" % (len(paths), time.time() - t0))
 
 
