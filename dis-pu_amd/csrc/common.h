@@ -72,6 +72,17 @@ __device__ __forceinline__ SegExt seg_ext(const int* __restrict__ off, const int
 // indices (the tie rule is arithmetic), so the choice only sets the speed.
 __host__ __device__ __forceinline__ int fps_family(int n, int m) { return n > 24576 ? 2 : (n > 4096 && m >= 64) ? 1 : 0; }
 
+// dispu_fps_segments_auto adds family 3, the cell-skipping kernels of fps_cells.hip, for the segments above 24576 points that
+// fps_cells_rule names: THE rule for when the cell path beats the streaming kernel (dispu_fps_cells_wanted returns it), read off
+// profiles/fps_large_bench.json (tools/fps_large_bench.py).  The pre-pass costs a fixed 0.1 - 0.2 ms and the first rounds reach every
+// cell, so a short sampling does not repay it: at n = 30000 the cell path loses at m = 32 (0.245 against 0.184 ms), wins at m = 64
+// by no more than its own spread (0.323 - 0.343 against 0.365 - 0.368 ms) and clearly from m = 128 (0.45 against 0.74 ms); at n = 122880 it loses at m = 16 (0.40 against 0.36 ms) and
+// wins from m = 32, clearly from m = 64 (0.62 against 1.41 ms).  Between the two measured sizes the stricter bound holds.
+__host__ __device__ __forceinline__ bool fps_cells_rule(int n, int m) { return n > 24576 && m >= (n >= 122880 ? 64 : 128); }
+__host__ __device__ __forceinline__ int fps_family4(int n, int m, bool with_cells) {
+    return (with_cells && fps_cells_rule(n, m)) ? 3 : fps_family(n, m);
+}
+
 template <bool FMA>
 __device__ __forceinline__ float sqdist3(float dx, float dy, float dz) {
     if constexpr (FMA) {

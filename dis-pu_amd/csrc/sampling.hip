@@ -168,7 +168,7 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, const float
     constexpr int BS = 1024, W = BS / kWave;
     __shared__ uint64_t slot[2][W];
     const SegExt e = seg_ext(off, moff, blockIdx.x, n, m);
-    if (off && fps_family(e.n, e.m) != fam) return;
+    if (off && fps_family4(e.n, e.m, fam & 4) != (fam & 3)) return;   // fam | 4 (dispu_fps_segments_auto): family 3 goes to fps_cells.hip
     n = e.n;
     m = e.m;
     const float* __restrict__ p = xyz + e.base * 3;
@@ -376,8 +376,8 @@ DISPU_EXPORT int dispu_fps(int b, int n, int m, const float* inp, float* temp, i
 namespace dispu {
 
 struct FpsSide {
-    hipStream_t st[2];
-    hipEvent_t fork, join[2];
+    hipStream_t st[3];
+    hipEvent_t fork, join[3];
 };
 static int fps_side(FpsSide** out) {
     static std::mutex mu;
@@ -390,7 +390,7 @@ static int fps_side(FpsSide** out) {
     if (!made[d]) {
         FpsSide& f = side[d];
         DISPU_TRY(hipEventCreateWithFlags(&f.fork, hipEventDisableTiming));
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 3; ++i) {
             DISPU_TRY(hipStreamCreateWithFlags(&f.st[i], hipStreamNonBlocking));
             DISPU_TRY(hipEventCreateWithFlags(&f.join[i], hipEventDisableTiming));
         }
@@ -401,41 +401,39 @@ static int fps_side(FpsSide** out) {
 }
 
 // -> 0 and the largest segment of every family (0: none), or hipErrorInvalidValue for offsets that are not a ragged batch
-static int fps_segment_families(int C, const int* off_host, const int* moff_host, int nmax[3]) {
-    nmax[0] = nmax[1] = nmax[2] = 0;
+static int fps_segment_families(int C, const int* off_host, const int* moff_host, int nmax[4], bool with_cells = false) {
+    nmax[0] = nmax[1] = nmax[2] = nmax[3] = 0;
     if (!off_host || !moff_host || off_host[0] != 0 || moff_host[0] != 0) return (int)hipErrorInvalidValue;
     for (int c = 0; c < C; ++c) {
         const int n = off_host[c + 1] - off_host[c], m = moff_host[c + 1] - moff_host[c];
         if (off_host[c + 1] <= off_host[c] || moff_host[c + 1] <= moff_host[c]) return (int)hipErrorInvalidValue;
-        const int f = fps_family(n, m);
+        const int f = fps_family4(n, m, with_cells);
         if (n > nmax[f]) nmax[f] = n;
     }
     return 0;
 }
 
-}  // namespace dispu
+// csrc/fps_cells.hip: the cell-skipping kernels over the segments of family 3 (mode 1) or over all of them (mode 0)
+size_t fps_cells_scratch(int C, const int* off_host, const int* moff_host, int cell, int mode);
+int fps_cells_run(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* scratch,
+                  size_t scratch_bytes, int* out, int* status, int arith, int cell, int mode, hipStream_t st);
 
-DISPU_EXPORT size_t dispu_fps_segments_scratch_bytes(int C, const int* off_host, const int* moff_host) {
-    int nmax[3];
-    if (C <= 0 || fps_segment_families(C, off_host, moff_host, nmax) != 0) return 0;
-    return (nmax[1] || nmax[2]) ? (size_t)off_host[C] * sizeof(float) : 0;
-}
+static inline size_t fps_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-DISPU_EXPORT int dispu_fps_segments(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp,
-                                    void* temp, size_t temp_bytes, int* out, int arith, void* stream) {
-    if (C < 0) return (int)hipErrorInvalidValue;
-    if (C == 0) return 0;
-    int nmax[3];
-    if (!off || !moff || !inp || !out || fps_segment_families(C, off_host, moff_host, nmax) != 0) return (int)hipErrorInvalidValue;
-    if ((nmax[1] || nmax[2]) && (!temp || temp_bytes < (size_t)off_host[C] * sizeof(float))) return (int)hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    // one launch (sequence) per family, sized for its largest segment: the kernels' results do not depend on their tier
+// One launch (sequence) per family, sized for its largest segment: the kernels' results do not depend on their tier.  The first
+// family runs on the caller's stream, the others on side streams.  cells: family 3 exists (dispu_fps_segments_auto) and takes
+// [cscratch, cscratch + cbytes) and status.
+static int fps_segments_run(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp,
+                            void* temp, const int nmax[4], bool cells, void* cscratch, size_t cbytes, int* status, int* out, int arith,
+                            hipStream_t s) {
     auto run = [&](int f, hipStream_t st) -> int {
+        if (f == 3) return fps_cells_run(C, off, moff, off_host, moff_host, inp, cscratch, cbytes, out, status, arith, 0, 1, st);
         if (f == 1) return fps_wave_launch(C, nmax[1], 0, inp, reinterpret_cast<int*>(temp), out, arith, st, off, moff);
-        return fps_dense(C, nmax[f], 0, inp, reinterpret_cast<float*>(temp), out, arith, st, off, moff, f);
+        return fps_dense(C, nmax[f], 0, inp, reinterpret_cast<float*>(temp), out, arith, st, off, moff,
+                         (cells && f == 2) ? (f | 4) : f);      // only the streaming kernel shares its size range with family 3
     };
-    int fams[3], nf = 0;
-    for (int f = 0; f < 3; ++f)
+    int fams[4], nf = 0;
+    for (int f = 0; f < 4; ++f)
         if (nmax[f]) fams[nf++] = f;
     if (nf == 1) return run(fams[0], s);
     FpsSide* side = nullptr;
@@ -453,6 +451,49 @@ DISPU_EXPORT int dispu_fps_segments(int C, const int* off, const int* moff, cons
     if (r == 0) r = rm;
     for (int i = 1; i < nf; ++i) DISPU_TRY(hipStreamWaitEvent(s, side->join[i - 1], 0));
     return r;
+}
+
+}  // namespace dispu
+
+DISPU_EXPORT size_t dispu_fps_segments_scratch_bytes(int C, const int* off_host, const int* moff_host) {
+    int nmax[4];
+    if (C <= 0 || fps_segment_families(C, off_host, moff_host, nmax) != 0) return 0;
+    return (nmax[1] || nmax[2]) ? (size_t)off_host[C] * sizeof(float) : 0;
+}
+
+DISPU_EXPORT int dispu_fps_segments(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp,
+                                    void* temp, size_t temp_bytes, int* out, int arith, void* stream) {
+    if (C < 0) return (int)hipErrorInvalidValue;
+    if (C == 0) return 0;
+    int nmax[4];
+    if (!off || !moff || !inp || !out || fps_segment_families(C, off_host, moff_host, nmax) != 0) return (int)hipErrorInvalidValue;
+    if ((nmax[1] || nmax[2]) && (!temp || temp_bytes < (size_t)off_host[C] * sizeof(float))) return (int)hipErrorInvalidValue;
+    return fps_segments_run(C, off, moff, off_host, moff_host, inp, temp, nmax, false, nullptr, 0, nullptr, out, arith, (hipStream_t)stream);
+}
+
+// dispu_fps_segments with family 3: scratch = [4 * sum n_c for families 1 and 2, if any | the cell kernels' scratch, if any]
+DISPU_EXPORT size_t dispu_fps_segments_auto_scratch_bytes(int C, const int* off_host, const int* moff_host) {
+    int nmax[4];
+    if (C <= 0 || fps_segment_families(C, off_host, moff_host, nmax, true) != 0) return 0;
+    const size_t a = (nmax[1] || nmax[2]) ? fps_align256((size_t)off_host[C] * sizeof(float)) : 0;
+    if (!nmax[3]) return a;
+    const size_t b = fps_cells_scratch(C, off_host, moff_host, 0, 1);
+    return b ? a + b : 0;                             // 0: a family-3 segment the cell kernels refuse (above 2^24 points)
+}
+
+DISPU_EXPORT int dispu_fps_segments_auto(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp,
+                                         void* temp, size_t temp_bytes, int* out, int* status, int arith, void* stream) {
+    if (C < 0) return (int)hipErrorInvalidValue;
+    if (C == 0) return 0;
+    int nmax[4];
+    if (!off || !moff || !inp || !out || fps_segment_families(C, off_host, moff_host, nmax, true) != 0) return (int)hipErrorInvalidValue;
+    const size_t a = (nmax[1] || nmax[2]) ? fps_align256((size_t)off_host[C] * sizeof(float)) : 0;
+    const size_t b = nmax[3] ? fps_cells_scratch(C, off_host, moff_host, 0, 1) : 0;
+    if (nmax[3] && (!b || !status)) return (int)hipErrorInvalidValue;
+    if ((a || b) && (!temp || temp_bytes < a + b || ((uintptr_t)temp & 15))) return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    if (status) DISPU_TRY(hipMemsetAsync(status, 0, sizeof(int) * (size_t)C, s));
+    return fps_segments_run(C, off, moff, off_host, moff_host, inp, temp, nmax, true, (char*)temp + a, b, status, out, arith, s);
 }
 
 // probsampleLauncher(b,n,m,inp_p,inp_r,temp,out)  tf_sampling.cpp:65,83-89: temp [b, n] receives the cumulative sums.

@@ -6,16 +6,95 @@ from . import _lib
 from ._util import f32, i32, req
 
 
-def farthest_point_sample(npoint, inp, arith=_lib.ARITH_CONTRACT):
+FPS_PATHS = ("auto", "cells", "stream")
+
+
+def _check_path(path):
+    req(path in FPS_PATHS, "path must be one of %s, got %r" % (", ".join(repr(p) for p in FPS_PATHS), path))
+    return path
+
+
+def _host_ptr(a):
+    return _lib.C.c_void_p(a.ctypes.data)
+
+
+def fps_ragged(inp, off, moff, arith=_lib.ARITH_CONTRACT, path="auto", cell=0):
+    """farthest_point_sample per segment of a packed batch: inp [sum n_c, 3] (device), off / moff host offsets of the points and of the
+    samples -> idx [sum m_c] int32, local to each segment; every path returns the same indices.  path: "stream" = dispu_fps_segments
+    (above 24576 points the streaming kernel), "cells" = the cell-skipping kernels of csrc/fps_cells.hip for EVERY segment (cell: forced
+    cell size, 0 = automatic), "auto" = dispu_fps_segments_auto.  A segment the cell kernels refuse for a non-finite coordinate
+    (status != 0) is sampled again through dispu_fps_segments, so such input behaves as on the "stream" path."""
+    import numpy as np
+    _check_path(path)
+    off, moff = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(moff, np.int32)
+    req(off.ndim == 1 and off.shape == moff.shape and len(off) >= 1, "off and moff must be [C + 1] offsets")
+    C = len(off) - 1
+    inp = inp.contiguous()
+    dev = inp.device
+    out = torch.empty((int(moff[-1]),), dtype=torch.int32, device=dev)
+    if C == 0:
+        return out
+    L = _lib.lib()
+    d_off, d_moff = torch.from_numpy(off).to(dev), torch.from_numpy(moff).to(dev)
+    st = _lib.stream_ptr(dev)
+
+    def stream_call(o, mo, d_o, d_mo, x, res):
+        nbytes = L.dispu_fps_segments_scratch_bytes(len(o) - 1, _host_ptr(o), _host_ptr(mo))
+        temp = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev) if nbytes else None
+        _lib.check(L.dispu_fps_segments(len(o) - 1, _lib.ptr(d_o), _lib.ptr(d_mo), _host_ptr(o), _host_ptr(mo), _lib.ptr(x), _lib.ptr(temp),
+                                        nbytes, _lib.ptr(res), int(arith), st), "dispu_fps_segments")
+
+    if path == "stream":
+        stream_call(off, moff, d_off, d_moff, inp, out)
+        return out
+    n_c, m_c = np.diff(off), np.diff(moff)
+    if path == "cells":
+        nbytes = L.dispu_fps_cells_scratch_bytes(C, _host_ptr(off), _host_ptr(moff), int(cell))
+        req(nbytes > 0, "dispu_fps_cells refuses these segments (illegal offsets or cell size, or a segment above 2^24 points)")
+        uses_cells = True
+    else:
+        req(int(cell) == 0, "a forced cell size needs path='cells'")
+        uses_cells = any(L.dispu_fps_cells_wanted(int(n), int(m)) for n, m in zip(n_c, m_c) if n > 24576)
+        nbytes = L.dispu_fps_segments_auto_scratch_bytes(C, _host_ptr(off), _host_ptr(moff))
+        if uses_cells and nbytes == 0:           # a segment above 2^24 points: only the streaming kernel takes it
+            stream_call(off, moff, d_off, d_moff, inp, out)
+            return out
+    temp = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+    status = torch.zeros((C,), dtype=torch.int32, device=dev) if uses_cells else None
+    if path == "cells":
+        _lib.check(L.dispu_fps_cells(C, _lib.ptr(d_off), _lib.ptr(d_moff), _host_ptr(off), _host_ptr(moff), _lib.ptr(inp), _lib.ptr(temp),
+                                     nbytes, _lib.ptr(out), _lib.ptr(status), int(arith), int(cell), st), "dispu_fps_cells")
+    else:
+        _lib.check(L.dispu_fps_segments_auto(C, _lib.ptr(d_off), _lib.ptr(d_moff), _host_ptr(off), _host_ptr(moff), _lib.ptr(inp),
+                                             _lib.ptr(temp), nbytes, _lib.ptr(out), _lib.ptr(status), int(arith), st),
+                   "dispu_fps_segments_auto")
+    if uses_cells:
+        for c in np.nonzero(status.cpu().numpy())[0]:          # non-finite segments: the existing entry, one segment at a time
+            o1, m1 = np.array([0, n_c[c]], np.int32), np.array([0, m_c[c]], np.int32)
+            stream_call(o1, m1, torch.from_numpy(o1).to(dev), torch.from_numpy(m1).to(dev), inp[int(off[c]):int(off[c + 1])],
+                        out[int(moff[c]):int(moff[c + 1])])
+    return out
+
+
+def farthest_point_sample(npoint, inp, arith=_lib.ARITH_CONTRACT, path="auto"):
     """(npoint:int, inp[b,n,3] f32) -> idx[b,npoint] i32.   tf_sampling.py:48-56; no gradient (:57).
-    idx[:,0] == 0; ties follow the reference kernel's rule (tf_sampling_g.cu:146,158)."""
+    idx[:,0] == 0; ties follow the reference kernel's rule (tf_sampling_g.cu:146,158).
+    path: "stream" = dispu_fps_ws; "cells" = the cell-skipping kernels for large clouds (csrc/fps_cells.hip) whatever the shape;
+    "auto" = the batch as a ragged batch with trivial offsets through dispu_fps_segments_auto where dispu_fps_cells_wanted(n, npoint)
+    says the cell kernels are faster, dispu_fps_ws (which that entry would pick itself) otherwise.  All paths return the same indices."""
+    _check_path(path)
     inp = f32(inp, "inp")
     req(int(npoint) > 0, "FarthestPointSample expects positive npoint")
     req(inp.dim() == 3 and inp.shape[2] == 3, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
     b, n, _ = inp.shape
     req(n > 0, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
-    out = torch.empty((b, int(npoint)), dtype=torch.int32, device=inp.device)
     L = _lib.lib()
+    if b > 0 and (path == "cells" or (path == "auto" and n > 24576 and L.dispu_fps_cells_wanted(n, int(npoint)))):
+        req(b * n < 2 ** 31 and b * int(npoint) < 2 ** 31, "the batch does not fit int32 offsets")
+        import numpy as np
+        off, moff = np.arange(b + 1, dtype=np.int64) * n, np.arange(b + 1, dtype=np.int64) * int(npoint)
+        return fps_ragged(inp.reshape(-1, 3), off, moff, arith, path).reshape(b, int(npoint))
+    out = torch.empty((b, int(npoint)), dtype=torch.int32, device=inp.device)
     nbytes = L.dispu_fps_scratch_bytes(b, n, int(npoint))
     temp = torch.empty((nbytes // 4,), dtype=torch.float32, device=inp.device) if nbytes else None
     _lib.check(L.dispu_fps_ws(b, n, int(npoint), _lib.ptr(inp), _lib.ptr(temp), nbytes, _lib.ptr(out), int(arith),

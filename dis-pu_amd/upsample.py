@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .tf_sampling import farthest_point_sample, gather_point
+from .tf_sampling import farthest_point_sample, fps_ragged, gather_point
 
 
 def knn_patch(cloud, queries, k):
@@ -100,19 +100,12 @@ def _dev(a, device):
     return torch.from_numpy(a).to(device)
 
 
-def fps_segments(inp, off, moff, arith=_lib.ARITH_CONTRACT):
+def fps_segments(inp, off, moff, arith=_lib.ARITH_CONTRACT, path="auto", cell=0):
     """farthest_point_sample per segment: inp [sum n_c, 3] (device), off / moff host offsets of the points and of the samples ->
-    idx [sum m_c] int32, local to each segment.  Segment c equals farthest_point_sample(m_c, cloud_c) bit for bit."""
-    off, moff = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(moff, np.int32)
-    C = len(off) - 1
-    out = torch.empty((int(moff[-1]),), dtype=torch.int32, device=inp.device)
-    L = _lib.lib()
-    nbytes = L.dispu_fps_segments_scratch_bytes(C, _host_ptr(off), _host_ptr(moff))
-    temp = torch.empty((nbytes // 4,), dtype=torch.float32, device=inp.device) if nbytes else None
-    d_off, d_moff = _dev(off, inp.device), _dev(moff, inp.device)
-    _lib.check(L.dispu_fps_segments(C, _lib.ptr(d_off), _lib.ptr(d_moff), _host_ptr(off), _host_ptr(moff), _lib.ptr(inp.contiguous()),
-                                    _lib.ptr(temp), nbytes, _lib.ptr(out), int(arith), _lib.stream_ptr(inp.device)), "dispu_fps_segments")
-    return out
+    idx [sum m_c] int32, local to each segment.  Segment c equals farthest_point_sample(m_c, cloud_c) bit for bit.
+    path: "auto" (dispu_fps_segments_auto: the cell-skipping kernels where they are faster), "cells" (those kernels for every segment,
+    cell = a forced cell size) or "stream" (dispu_fps_segments); the indices do not depend on it (tf_sampling.fps_ragged)."""
+    return fps_ragged(inp, off, moff, arith, path, cell)
 
 
 def knn_patch_segments(cloud, off, queries, qoff, k):

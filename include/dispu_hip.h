@@ -57,7 +57,8 @@ extern "C" {
  * dispu_approx_match_scratch_bytes and had no way to refuse less); the tiled fast path is dispu_approx_match_ws with an explicit size.
  * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std) and its geodesic disks
  * (dispu_geodesic_*), the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments) and the
- * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32): additions only. */
+ * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32), and the large-cloud sampling (dispu_fps_cells*,
+ * dispu_fps_segments_auto*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -93,6 +94,32 @@ int dispu_fps_ws(int b, int n, int m, const float* inp, float* temp, size_t temp
 size_t dispu_fps_segments_scratch_bytes(int C, const int* off_host, const int* moff_host);
 int dispu_fps_segments(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* temp,
                        size_t temp_bytes, int* out, int arith, void* stream);
+/* The same sampling (tf_sampling.cpp:94,118; kernel tf_sampling_g.cu:105-170) for LARGE clouds, csrc/fps_cells.hip: the cloud stays in
+ * global memory, a device-wide pre-pass (bounding boxes, Morton keys, one dispu_radix_sort_pairs over the batch, cells of S consecutive
+ * sorted positions with their boxes) lets every round skip the cells whose box is farther from the new sample than their largest
+ * running distance.  The indices are those of dispu_fps_ws and dispu_fps_segments bit for bit, in both arithmetic flavours: skipped
+ * updates are no-ops, ties are decided by the original index (k mod 512, then k).
+ * dispu_fps_cells takes a ragged batch described as in dispu_fps_segments and serves EVERY segment with these kernels, for any
+ * n_c >= 1 and m_c >= 1 (m_c > n_c included) up to n_c = 2^24; the offsets need C <= 65535.  cell: 0 = the cell size the dispatch
+ * picks (64 up to 262144 points, doubling above: at most 4096 cells per segment), or a power of two in 64 .. 4096 to force that size
+ * on every segment for which it is not smaller than the automatic one (tests visit every size at small n).  status [C] (device):
+ * 0, or 1 for a segment that holds a non-finite coordinate, for which NO index is written.  scratch: 16-byte aligned,
+ * scratch_bytes >= dispu_fps_cells_scratch_bytes(C, off_host, moff_host, cell) (0 for illegal offsets, cell sizes or segments above
+ * 2^24 points); a scratch that is NULL or too small is refused (hipErrorInvalidValue) untouched.
+ * dispu_fps_cells_wanted(n, m): 1 where the cell kernels beat the streaming kernel (measured: profiles/fps_large_bench.json), never
+ * for n <= 24576. */
+size_t dispu_fps_cells_scratch_bytes(int C, const int* off_host, const int* moff_host, int cell);
+int dispu_fps_cells(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* scratch,
+                    size_t scratch_bytes, int* out, int* status, int arith, int cell, void* stream);
+int dispu_fps_cells_wanted(int n, int m);
+/* dispu_fps_segments (tf_sampling.cpp:94,118; tf_sampling_g.cu:105-170 per segment) with a fourth family: segments with n_c > 24576 for
+ * which dispu_fps_cells_wanted(n_c, m_c) says yes go through the cell kernels, all others through the launchers of dispu_fps_segments,
+ * concurrently on side streams.  Same arguments and results; in addition status [C] (device; may be NULL when no segment is wanted by
+ * the cell kernels) is 0, or 1 for a cell-kernel segment with a non-finite coordinate, whose indices are then NOT written: sample
+ * it again with dispu_fps_segments.  temp: 16-byte aligned, temp_bytes >= dispu_fps_segments_auto_scratch_bytes(C, off_host, moff_host). */
+size_t dispu_fps_segments_auto_scratch_bytes(int C, const int* off_host, const int* moff_host);
+int dispu_fps_segments_auto(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* temp,
+                            size_t temp_bytes, int* out, int* status, int arith, void* stream);
 
 /* probsampleLauncher(b,n,m,inp_p,inp_r,temp,out)   tf_sampling.cpp:65,83-89; kernels tf_sampling_g.cu:7-104 (cumulative sums
  * of the weights inp_p[b,n] into temp[b,n], then out[b,m] = the first position whose cumulative weight is >= inp_r * total).
