@@ -39,6 +39,8 @@ SIGNATURES = {
     "dispu_fps_cells_scratch_bytes": (_sz, [_i, _vp, _vp, _i]),
     "dispu_fps_cells": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _vp]),
     "dispu_fps_cells_wanted": (_i, [_i, _i]),
+    "dispu_pca_normals_scratch_bytes": (_sz, [_i, _vp, _i]),
+    "dispu_pca_normals_segments": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_fps_segments_auto_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_fps_segments_auto": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "dispu_prob_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -56,8 +56,12 @@ __host__ __device__ __forceinline__ int fpc_cell_size(int n, int cell) {
 }
 // first cell of segment c in the cell table: every segment has at most n_c / 64 + 1 cells
 __device__ __forceinline__ size_t fpc_cell_base(size_t base, int c) { return base / kFpcMinCell + (size_t)c; }
-// mode 0: every segment; 1: the segments dispu_fps_segments_auto sends here (family 3)
-__host__ __device__ __forceinline__ bool fpc_served(int n, int m, int mode) { return mode == 0 || fps_cells_rule(n, m); }
+// mode 0: every segment; 1: the segments dispu_fps_segments_auto sends here (family 3); 2: every segment, in cells of exactly
+// kFpcMinCell points whatever its size (the pre-pass alone, for normals.hip: one query per lane of a wave)
+__host__ __device__ __forceinline__ bool fpc_served(int n, int m, int mode) { return mode != 1 || fps_cells_rule(n, m); }
+__host__ __device__ __forceinline__ int fpc_cell_size_mode(int n, int cell, int mode) {
+    return mode == 2 ? kFpcMinCell : fpc_cell_size(n, cell);
+}
 
 __device__ __forceinline__ uint32_t fpc_tiekey(int k) {       // same key as sampling.hip:fps_tiekey
     return 0xFFFFFFFFu - ((((uint32_t)k & 511u) << 22) | ((uint32_t)k >> 9));
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(kFpcPre) void fpc_cells_kernel(const float* __restr
     const int c = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
     const SegExt e = seg_ext(off, moff, c, 0, 0);
     if (!fpc_served(e.n, e.m, mode) || segb[(size_t)c * 8 + 6]) return;
-    const int S = fpc_cell_size(e.n, cell), K = (e.n + S - 1) / S;
+    const int S = fpc_cell_size_mode(e.n, cell, mode), K = (e.n + S - 1) / S;
     const int cb = blockIdx.x * (kFpcPre / kWave) + tid / kWave;
     if (cb >= K) return;
     const int pb = cb * S, cnt = min(S, e.n - pb);
@@ -320,7 +324,7 @@ static int fpc_plan(int C, const int* off_host, const int* moff_host, int cell, 
         if (n > *nall) *nall = n;
         if (!fpc_served(n, m, mode)) continue;
         if (n > kFpcMaxN) return (int)hipErrorInvalidValue;
-        const int S = fpc_cell_size(n, cell), K = (n + S - 1) / S;
+        const int S = fpc_cell_size_mode(n, cell, mode), K = (n + S - 1) / S;
         if (n > *nserved) *nserved = n;
         if (K > *kmax) *kmax = K;
     }
@@ -334,17 +338,10 @@ size_t fps_cells_scratch(int C, const int* off_host, const int* moff_host, int c
     return fpc_scratch((size_t)off_host[C], C).total;
 }
 
-int fps_cells_run(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* scratch,
-                  size_t scratch_bytes, int* out, int* status, int arith, int cell, int mode, hipStream_t st) {
-    int nall, nserved, kmax;
-    const int rc = fpc_plan(C, off_host, moff_host, cell, mode, &nall, &nserved, &kmax);
-    if (rc != 0) return rc;
-    if (!nserved) return 0;
-    if (!off || !moff || !inp || !out || !status) return (int)hipErrorInvalidValue;
-    const size_t N = (size_t)off_host[C];
-    const FpcScratch s = fpc_scratch(N, C);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
-    char* base = (char*)scratch;
+// The pre-pass alone: bounds, keys, sort, cells.  scratch as fpc_scratch(off_host[C], C) lays it out; afterwards spt (over the two key
+// buffers), td (over the input values), tab and segb hold what the kernels above describe.  nall / nserved / kmax from fpc_plan.
+static int fpc_prepass(int C, const int* off, const int* moff, const float* inp, char* base, const FpcScratch& s, size_t N, int nall,
+                       int nserved, int kmax, int cell, int mode, hipStream_t st) {
     unsigned long long* kin = (unsigned long long*)(base + s.kin);
     unsigned long long* kout = (unsigned long long*)(base + s.kout);
     uint32_t* vin = (uint32_t*)(base + s.vin);
@@ -366,6 +363,51 @@ int fps_cells_run(int C, const int* off, const int* moff, const int* off_host, c
     hipLaunchKernelGGL(fpc_cells_kernel, dim3((kmax + wpb - 1) / wpb, C), dim3(kFpcPre), 0, st, inp, off, moff, segb, vout, spt, td, tab, cell,
                        mode);
     DISPU_CHECK_LAUNCH();
+    return 0;
+}
+
+// The pre-pass for another kernel family (normals.hip): every segment of the packed batch in cells of exactly 64 sorted points (cell j
+// of segment c: sorted positions off[c] + 64 j ...).  -> spt [N] (x, y, z, local index as bits) in sorted order, tab [.][8] the cells'
+// boxes (lo x3, hi x3, -, -; segment c's first row is off[c] / 64 + c), segb [C][8] (word 6: the non-finite flag; such a segment has no
+// cells), kmax the largest cell count of a segment.  The scratch is refused, untouched, when NULL, misaligned or too small.
+size_t fps_cells_prepass_scratch(int C, const int* off_host) {
+    int nall, nserved, kmax;
+    if (fpc_plan(C, off_host, off_host, 0, 2, &nall, &nserved, &kmax) != 0) return 0;
+    return fpc_scratch((size_t)off_host[C], C).total;
+}
+int fps_cells_prepass(int C, const int* off, const int* off_host, const float* inp, void* scratch, size_t scratch_bytes,
+                      const float4** spt, const float** tab, const uint32_t** segb, int* kmax, hipStream_t st) {
+    int nall, nserved;
+    const int rc = fpc_plan(C, off_host, off_host, 0, 2, &nall, &nserved, kmax);
+    if (rc != 0) return rc;
+    if (!off || !inp) return (int)hipErrorInvalidValue;
+    const size_t N = (size_t)off_host[C];
+    const FpcScratch s = fpc_scratch(N, C);
+    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    char* base = (char*)scratch;
+    *spt = (const float4*)(base + s.kin);
+    *tab = (const float*)(base + s.tab);
+    *segb = (const uint32_t*)(base + s.segb);
+    return fpc_prepass(C, off, off, inp, base, s, N, nall, nserved, *kmax, 0, 2, st);
+}
+
+int fps_cells_run(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* scratch,
+                  size_t scratch_bytes, int* out, int* status, int arith, int cell, int mode, hipStream_t st) {
+    int nall, nserved, kmax;
+    const int rc = fpc_plan(C, off_host, moff_host, cell, mode, &nall, &nserved, &kmax);
+    if (rc != 0) return rc;
+    if (!nserved) return 0;
+    if (!off || !moff || !inp || !out || !status) return (int)hipErrorInvalidValue;
+    const size_t N = (size_t)off_host[C];
+    const FpcScratch s = fpc_scratch(N, C);
+    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    char* base = (char*)scratch;
+    const uint32_t* segb = (const uint32_t*)(base + s.segb);
+    const float* tab = (const float*)(base + s.tab);
+    const float4* spt = (const float4*)(base + s.kin);
+    float* td = (float*)(base + s.vin);
+    const int rp = fpc_prepass(C, off, moff, inp, base, s, N, nall, nserved, kmax, cell, mode, st);
+    if (rp != 0) return rp;
     const size_t lds = (size_t)8 * 4 * kFpcThreads * ((kmax + kFpcThreads - 1) / kFpcThreads);
     static DevOnce attr;
     if (attr.needed()) {

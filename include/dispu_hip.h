@@ -58,7 +58,7 @@ extern "C" {
  * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std) and its geodesic disks
  * (dispu_geodesic_*), the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments) and the
  * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32), and the large-cloud sampling (dispu_fps_cells*,
- * dispu_fps_segments_auto*): additions only. */
+ * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -968,6 +968,29 @@ int dispu_grid_subsample_plan(long long n, const float* points, float dl, void* 
                               double* grid_out, void* stream);
 int dispu_grid_subsample_emit(long long n, int m, int fdim, int ldim, const float* points, const float* features, const int* classes,
                               void* scratch, size_t scratch_bytes, float* out_points, float* out_features, int* out_classes, void* stream);
+
+/* ---- oriented normals of whole clouds, csrc/normals.hip, dis-pu_amd/normals.py.  The reference has no counterpart: it reads and writes
+ * bare x y z.  The neighbourhood rule is pc_util.py:83-92's k-NN made deterministic, the rule of dispu_knn_patch_segments: the
+ * k' = min(k, n_c) points of the query's own segment with the smallest (d2, local index), d2 = ((dx*dx + dy*dy) + dz*dz) in fp32
+ * (DISPU_ARITH_PLAIN), the point itself and duplicates included.  The yardstick is tests/normals_oracle.py. -------------------------- */
+/* cloud [sum n_c, 3] packs C <= 65535 clouds of 1 <= n_c <= 2^24 points, off [C+1] device offsets, off_host the same on the host (never
+ * read on the device); 4 <= k <= 32.  The pre-pass of dispu_fps_cells (Morton cells of 64 sorted points with boxes) makes the exact
+ * search nearly linear: one wave per cell, a cell is visited only if its box-to-box lower bound does not exceed the wave's largest
+ * k-th distance.  With q_j = p_j - p_i over the neighbourhood, mu = sum q_j / k', Cov = sum q_j q_j^T / k' - mu mu^T in double,
+ * eigenvalues l0 <= l1 <= l2 (cyclic Jacobi in double):  normal [sum n_c, 3] = a unit eigenvector of l0 as fp32;  variation
+ * [sum n_c] (or NULL) = fp32(max(l0, 0) / (l0 + l1 + l2));  k' < 3 or l2 = 0: normal (0, 0, 0), variation -1.
+ * Sign: orient_mode 0: the component of largest magnitude is positive (ties: the lowest axis);  1: orient [sum n_c, 3], one direction
+ * per point, the normal is flipped where the dot product is negative, a dot product of exactly 0 keeps the mode-0 sign;  2: orient
+ * [C, 3], one viewpoint per segment, direction = viewpoint - p.  orient may be NULL for mode 0.
+ * idx_out [sum n_c, k] (or NULL): the neighbours' local indices in ascending (d2, index) order, rows with k' < k padded with -1.
+ * status [C] (device): 0, or 1 for a segment that holds a NaN or an infinite coordinate, for which NO output is written.
+ * scratch: 16-byte aligned, scratch_bytes >= dispu_pca_normals_scratch_bytes(C, off_host, k) (0 for an illegal C, k, offsets or a
+ * segment above 2^24 points); the library never allocates, and a refusal (hipErrorInvalidValue: k outside 4 .. 32, illegal offsets,
+ * a scratch that is NULL or too small) touches no output.  Identical bytes from run to run. */
+size_t dispu_pca_normals_scratch_bytes(int C, const int* off_host, int k);
+int dispu_pca_normals_segments(int C, const int* off, const int* off_host, int k, const float* cloud, int orient_mode, const float* orient,
+                               float* normal, float* variation, int* idx_out, int* status, void* scratch, size_t scratch_bytes,
+                               void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,13 @@ points for its own n (the reference takes n from the first globbed file for all 
 
 --grid_size G (off by default) first thins every cloud on the GPU to one barycentre per cube of edge G (dis-pu_amd/grid_subsampling.py,
 the reference's cpp_subsampling): FPS seeds and 256-NN patches only mean "a patch of surface" at a roughly even density, which a raw
-scan does not have.  The output then has final_ratio times the SUBSAMPLED count."""
+scan does not have.  The output then has final_ratio times the SUBSAMPLED count.
+
+--normals pca (off by default) adds a unit normal to every output point, six columns x y z nx ny nz: the PCA of its --normals_k exact
+nearest neighbours in the output cloud (dis-pu_amd/normals.py; the reference has no counterpart).  --orient picks the sign: none (the
+largest component positive), centroid (outwards), viewpoint (towards --viewpoint X Y Z) or input (in agreement with the normal of the
+nearest input point: every input file then needs six columns; with --grid_size the input normals are averaged per cube and
+renormalised, and a cube whose normals cancel orients nothing)."""
 import argparse
 import glob
 import math
@@ -41,6 +47,20 @@ def load_xyz(path):
     if pts.shape[1] < 3:
         raise ValueError("%s: expected at least three columns, got %d" % (path, pts.shape[1]))
     return np.ascontiguousarray(pts[:, :3])
+
+
+def load_xyz_normals(path):
+    """(points [n, 3], normals [n, 3]) float32 of an .xyz file with rows x y z nx ny nz [...]; ValueError naming a file with fewer than
+    six columns."""
+    rows = np.loadtxt(path, ndmin=2).astype(np.float32)
+    if rows.shape[1] < 6:
+        raise ValueError("%s: --orient input needs six columns x y z nx ny nz, got %d" % (path, rows.shape[1]))
+    return np.ascontiguousarray(rows[:, :3]), np.ascontiguousarray(rows[:, 3:6])
+
+
+def save_xyz_normals(path, points, normals):
+    """rows x y z nx ny nz at %.6f"""
+    np.savetxt(path, np.concatenate([np.asarray(points, np.float32), np.asarray(normals, np.float32)], axis=1), fmt="%.6f")
 
 
 def group_by_budget(sizes, max_points):
@@ -81,7 +101,23 @@ def parse_args(argv=None):
     ap.add_argument("--grid_size", type=positive_float, default=None,
                     help="off by default; G: grid-subsample every input cloud on the GPU first, one barycentre per cube of edge G "
                          "(for dense, uneven scans); the output has final_ratio x the subsampled count")
-    return ap.parse_args(argv)
+    ap.add_argument("--normals", choices=("none", "pca"), default="none",
+                    help="pca: write six columns x y z nx ny nz, the normal from the PCA of the --normals_k nearest output points")
+    ap.add_argument("--normals_k", type=int, default=16, help="neighbourhood size of --normals pca, 4 .. 32")
+    ap.add_argument("--orient", choices=("none", "centroid", "viewpoint", "input"), default="none",
+                    help="sign of the normals: none (largest component positive), centroid (outwards), viewpoint (towards --viewpoint), "
+                         "input (as the nearest input point's normal; the inputs need six columns)")
+    ap.add_argument("--viewpoint", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None, help="the viewpoint of --orient viewpoint")
+    a = ap.parse_args(argv)
+    if a.normals == "none" and (a.orient != "none" or a.viewpoint is not None):
+        ap.error("--orient and --viewpoint need --normals pca")
+    if not 4 <= a.normals_k <= 32:
+        ap.error("--normals_k must be in 4 .. 32, got %d" % a.normals_k)
+    if (a.orient == "viewpoint") != (a.viewpoint is not None):
+        ap.error("--orient viewpoint and --viewpoint X Y Z go together")
+    if a.viewpoint is not None and not all(math.isfinite(v) for v in a.viewpoint):
+        ap.error("--viewpoint must be finite")
+    return a
 
 
 def main(argv=None):
@@ -97,7 +133,14 @@ def main(argv=None):
         refuse_unsupported(paths)
     except ValueError as e:
         sys.exit(str(e))
-    clouds = [load_xyz(p) for p in paths]
+    in_normals = None
+    if a.orient == "input":
+        try:
+            clouds, in_normals = (list(t) for t in zip(*[load_xyz_normals(p) for p in paths]))
+        except ValueError as e:
+            sys.exit(str(e))
+    else:
+        clouds = [load_xyz(p) for p in paths]
 
     sys.path.insert(0, ROOT)
     import torch
@@ -117,7 +160,14 @@ def main(argv=None):
         from dispu_amd import grid_subsampling
         for i, c in enumerate(clouds):
             try:
-                clouds[i] = grid_subsampling.compute(c, sampleDl=a.grid_size)
+                if in_normals is None:
+                    clouds[i] = grid_subsampling.compute(c, sampleDl=a.grid_size)
+                else:                                    # the normals ride through as features: the mean per cube, renormalised below
+                    pts, nrm = grid_subsampling.compute(torch.from_numpy(c).to(dev), features=torch.from_numpy(in_normals[i]).to(dev),
+                                                        sampleDl=a.grid_size)
+                    length = nrm.norm(dim=1, keepdim=True)
+                    in_normals[i] = torch.where(length > 0, nrm / length, torch.zeros_like(nrm))      # a zero mean stays zero
+                    clouds[i] = pts.cpu().numpy()
             except ValueError as e:
                 sys.exit("%s: %s" % (paths[i], e))
     for group in group_by_budget([c.shape[0] for c in clouds], a.max_points):
@@ -125,9 +175,27 @@ def main(argv=None):
             preds = upsample_ragged(gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
         except ValueError as e:
             sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
-        for i, pred in zip(group, preds):
+        if a.normals == "pca":
+            from dispu_amd.normals import estimate_normals
+            dpred = [torch.from_numpy(p).to(dev) for p in preds]
+            orient = None
+            if a.orient == "centroid":
+                orient = ("centroid",)
+            elif a.orient == "viewpoint":
+                orient = ("viewpoint", a.viewpoint)
+            elif a.orient == "input":
+                orient = ("reference", [torch.from_numpy(clouds[i]).to(dev) for i in group],
+                          [torch.as_tensor(in_normals[i], device=dev).contiguous() for i in group])
+            try:
+                normals = [t.cpu().numpy() for t in estimate_normals(dpred, k=a.normals_k, orient=orient)]
+            except ValueError as e:
+                sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
+        for j, (i, pred) in enumerate(zip(group, preds)):
             out = os.path.join(out_dir, output_name(paths[i], a.final_ratio))
-            save_xyz(out, pred)
+            if a.normals == "pca":
+                save_xyz_normals(out, pred, normals[j])
+            else:
+                save_xyz(out, pred)
             if a.grid_size is None:
                 print("%s: %d -> %d points, %s" % (paths[i], clouds[i].shape[0], pred.shape[0], out))
             else:
