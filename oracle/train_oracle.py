@@ -226,10 +226,11 @@ def pu_loss(coarse, fine, gt, radius, epoch=0, repulsion_w=1.0, use_repulse=True
     return total, {"dis_coarse_cd": cd_c, "dis_fine_cd": cd_f, "repulsion_loss": rep}
 
 
-def loss_and_grads(P, inputs, gt, radius, epoch=0, is_training=True, act_grads=None):
+def loss_and_grads(P, inputs, gt, radius, epoch=0, is_training=True, act_grads=None, fwd_taps=None):
     """-> (loss float, terms, {name: grad ndarray float64}, bn_state, (coarse, fine) float64 ndarrays).
     `act_grads` (a dict) additionally receives d loss / d activation for the dense blocks' outputs dc1..dc4,
-    coarse, fine and the PointShuffle2 output fine_feat (row-wise checks of the backward, see tests)."""
+    coarse, fine and the PointShuffle2 output fine_feat (row-wise checks of the backward, see tests).
+    `fwd_taps` (a dict) receives the forward VALUES generator_forward taps: feat480, up128, fine_feat."""
     Pt = to_torch(P)
     idx = neighbour_indices(P, inputs)
     bn_state, tap = {}, {}
@@ -246,6 +247,8 @@ def loss_and_grads(P, inputs, gt, radius, epoch=0, is_training=True, act_grads=N
     if act_grads is not None:
         for k in watch:
             act_grads[k] = tap[k].grad.numpy()
+    if fwd_taps is not None:
+        fwd_taps.update((k, tap[k].detach().numpy()) for k in ("feat480", "up128", "fine_feat"))
     return (float(total.detach()), {k: float(v.detach()) for k, v in terms.items()}, gd,
             {k: v.numpy() for k, v in bn_state.items()}, (coarse.detach().numpy(), fine.detach().numpy()))
 
