@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libdispu_hip.so")
+PUBLIC_HEADER = os.path.join(os.path.dirname(HERE), "include", "dispu_hip.h")   # csrc/common.h includes it
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
@@ -21,11 +22,11 @@ def _sources():
 
 
 def _headers():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [PUBLIC_HEADER]
 
 
 def source_hash():
-    """sha1 over the kernel sources (csrc/*.hip, csrc/*.h, this file's flags): names the build a profile was taken from -- the GPU box
+    """sha1 over the kernel sources (csrc/*.hip, csrc/*.h, include/dispu_hip.h, this file's flags): names the build a profile was taken from -- the GPU box
     has no .git, so counter summaries are stamped with this and bench.py checks it against the tree it runs from."""
     import hashlib
     h = hashlib.sha1(" ".join(FLAGS).encode())
@@ -65,7 +66,7 @@ def build(force=False, verbose=False):
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         objs = list(ex.map(_compile, srcs))
     if _stale(LIB, objs):
-        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB + ".tmp"],
+        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined"] + objs + ["-o", LIB + ".tmp"],
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n%s" % r.stdout.decode(errors="replace"))

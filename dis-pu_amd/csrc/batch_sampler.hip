@@ -23,9 +23,6 @@
 #include "augment_point.h"
 #include "philox.h"
 
-#define DISPU_SAMPLER_MAX_ROUNDS 4096   /* both mirror include/dispu_hip.h (which shares a struct with common.h and cannot be included */
-#define DISPU_SAMPLER_MAX_G 8192        /* here); tests/test_train_phase.py holds the two files to the same values */
-
 namespace dispu {
 
 constexpr int kSamplerThreads = 256;

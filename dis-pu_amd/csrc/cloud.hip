@@ -3,6 +3,7 @@
 // In the reference these run on the host (sklearn NearestNeighbors, numpy) once per patch with batch size 1;
 // here they are batched device kernels so the whole cloud goes through ONE generator launch.
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 
@@ -103,12 +104,6 @@ __global__ void denormalize_patches_kernel(long total, int m, const float* __res
 }  // namespace dispu
 
 using namespace dispu;
-
-namespace dispu {
-int knn_general_launch(int mode, int b, int n, int m, int c, int k, long ldp, long ldq, const float* points, const float* queries,
-                       float* dist, int* idx, int neg, hipStream_t st, const int* off = nullptr, const int* qoff = nullptr,
-                       int seg_nmin = 0);
-}
 
 DISPU_EXPORT int dispu_knn_patch(int b, int n, int m, int k, const float* cloud, const float* queries, int* idx, void* stream) {
     if (b < 0 || n <= 0 || m < 0 || k <= 0 || k > n) return (int)hipErrorInvalidValue;

@@ -6,14 +6,9 @@
 #include <stdint.h>
 #include <atomic>
 
-#define DISPU_EXPORT extern "C" __attribute__((visibility("default")))
+#include "../../include/dispu_hip.h"   // the public C-ABI: every exported definition is checked against its prototype
 
-// Arithmetic flavour flags shared with include/dispu_hip.h
-#define DISPU_ARITH_PLAIN 0     // ((dx*dx + dy*dy) + dz*dz): the reference's CPU functions
-#define DISPU_ARITH_CONTRACT 1  // fmaf(dz,dz, fmaf(dx,dx, dy*dy)): nvcc-contracted GPU kernels
-#define DISPU_ARITH_PINNED_EXP 2  // OR-able: approx_match uses the bit-reproducible exp (parity mode)
-#define DISPU_KNN_LANE_PER_QUERY 4  // OR-able, dispu_knn_xyz: force the lane-per-query kernel (A/B tests)
-#define DISPU_MESH_BRUTE_FORCE 8    // OR-able, dispu_point_to_mesh: visit every face tile (A/B tests)
+#define DISPU_EXPORT extern "C" __attribute__((visibility("default")))
 
 #define DISPU_CHECK_LAUNCH()                         \
     do {                                             \
@@ -27,22 +22,15 @@
         if (e__ != hipSuccess) return (int)e__;      \
     } while (0)
 
-// A split reduction a TN (weight-gradient) product leaves undone when the caller asked for that (dispu_tn_defer, include/dispu_hip.h):
-// out[k][n] (+)= sum_s part[s][k][n], row K of the partials (rows_p == K + 1) -> dbias[n].  Mirrors dispu_tn_reduce_desc.
-struct dispu_tn_reduce_desc {
-    const float* part; float* out; float* dbias;
-    long ldo, stride;                       // row stride of out; floats between consecutive partials
-    int K, N, splits, rows_p;
-    int accumulate, bias_accumulate, assoc, reserved;   // assoc 0: the fp32 kernels' order (tn_reduce_kernel), 1: the bf16 kernels'
-};
+// dispu_tn_reduce_desc (include/dispu_hip.h): the split reduction a TN (weight-gradient) product leaves undone under dispu_tn_defer
 static_assert(sizeof(dispu_tn_reduce_desc) == 72, "descriptor layout is part of the C-ABI");
 
 namespace dispu {
 
 constexpr int kWave = 64;
 
-// the one-shot sink dispu_tn_defer arms for the NEXT TN product on this thread (train_gemm.hip); taking it disarms it
-dispu_tn_reduce_desc* tn_take_defer();
+// byte offsets inside a caller's scratch buffer advance in steps of 256
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // "done once per DEVICE" flag for hipFuncSetAttribute (function attributes are per device: a process that drives several
 // GPUs must opt every one of them in to > 64 KB of dynamic LDS).  Two threads racing through the first call both set the

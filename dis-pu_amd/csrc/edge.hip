@@ -682,10 +682,6 @@ DISPU_EXPORT int dispu_edge_dense_conv(int npoints, int n_per_cloud, int C, cons
     return (int)hipGetLastError();
 }
 
-DISPU_EXPORT int dispu_linear(int batch, int M, int K, int N, const float* X, long ldx, long sx, const float* W, long ldw, long sw, int transb,
-                              const float* bias, int act, float* Y, long ldy, long sy, const float* R1, long ldr1, long sr1, const float* R2,
-                              long ldr2, long sr2, void* stream);     // linear.hip
-
 // One dense block of feature_extraction_GCN (Common/ops.py:1437-1486) in one launch: knn_point_2(k + 1, F, F) (tf_util.py:618-651) ->
 // get_edge_feature over neighbours ioff .. ioff + 15 (ops.py:1856-1877) -> dense_conv (:1897-1915).  Same results, bit for bit, as
 // dispu_knn_feat_strided followed by dispu_edge_dense_conv.  Clouds of up to 256 points (n_per_cloud even, >= ksel); idx_out (nullable):

@@ -20,6 +20,8 @@
 // (32, 4097, 1024) 1.22 -> 0.75 ms.  tools/micro/fps_wave_prof.hip splits a round (2900 cycles at n = 24576): dense update of
 // the busiest wave 1330, its arg-max 575, slot + barrier 120, cross-wave winner 460 - 1100 (16 waves, oldest first).
 #include "common.h"
+#include "fps_keys.h"
+#include "internal.h"
 
 #include <cstdlib>
 
@@ -33,38 +35,10 @@
 
 namespace dispu {
 
-__device__ __forceinline__ uint32_t fpsw_tiekey(int k) {      // same key as sampling.hip:fps_tiekey
-    return 0xFFFFFFFFu - ((((uint32_t)k & 511u) << 22) | ((uint32_t)k >> 9));
-}
 __device__ __forceinline__ uint32_t fpsw_order(int k) {       // ascending = the reference's tie priority
     return (((uint32_t)k & 511u) << 22) | (uint32_t)k;
 }
 
-// Running distances are >= 0 (or -1 = "no point"): as unsigned keys (bits + 1, 0 for "no point") they order like the floats, and
-// an unsigned max folds into ONE v_max_u32_dpp per step (a float max costs a DPP move plus two canonicalising v_max per step).
-__device__ __forceinline__ uint32_t fpsw_dkey(float d) { return d >= 0.f ? __float_as_uint(d) + 1u : 0u; }
-__device__ __forceinline__ float fpsw_dkey_value(uint32_t k) { return k ? __uint_as_float(k - 1u) : -1.0f; }
-template <int CTRL, int RM = 0xF>
-__device__ __forceinline__ uint32_t fpsw_umax_step(uint32_t v) {
-    const uint32_t o = dpp_u32<CTRL, RM>(0u, v);
-    return v > o ? v : o;
-}
-__device__ __forceinline__ uint32_t fpsw_wave_max_u32(uint32_t v) {
-    v = fpsw_umax_step<DPP_ROW_SHR1>(v);
-    v = fpsw_umax_step<DPP_ROW_SHR2>(v);
-    v = fpsw_umax_step<DPP_ROW_SHR4>(v);
-    v = fpsw_umax_step<DPP_ROW_SHR8>(v);
-    v = fpsw_umax_step<DPP_ROW_BCAST15, 0xA>(v);
-    v = fpsw_umax_step<DPP_ROW_BCAST31, 0xC>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t fpsw_row0_max_u32(uint32_t v) {   // max over lanes 0..15 (row 0), wave-uniform result
-    v = fpsw_umax_step<DPP_ROW_SHR1>(v);
-    v = fpsw_umax_step<DPP_ROW_SHR2>(v);
-    v = fpsw_umax_step<DPP_ROW_SHR4>(v);
-    v = fpsw_umax_step<DPP_ROW_SHR8>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 15);
-}
 __device__ __forceinline__ float fpsw_all_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -249,14 +223,14 @@ __global__ __launch_bounds__(FW_BS) void fps_wave_kernel(int n, int m, const flo
                 bd = gt ? t : bd; bi = gt ? i : bi;
             }
             FPSW_TICK(2)
-            const uint32_t ub = fpsw_dkey(bd);
-            const uint32_t um = fpsw_wave_max_u32(ub);
+            const uint32_t ub = fps_dkey(bd);
+            const uint32_t um = fps_wave_max_u32(ub);
             unsigned long long tm = __ballot(ub == um);
             int wl = (int)__builtin_ctzll(tm);
             if (tm & (tm - 1)) {                          // several lanes share the maximum: the reference's tie rule decides
                 const bool in = ub == um;
-                const uint32_t key = in ? fpsw_tiekey(perm_l[wbase + bi * 64 + lane]) : 0u;
-                const uint32_t mk = fpsw_wave_max_u32(key);
+                const uint32_t key = in ? fps_tiekey(perm_l[wbase + bi * 64 + lane]) : 0u;
+                const uint32_t mk = fps_wave_max_u32(key);
                 wl = (int)__builtin_ctzll(__ballot(in && key == mk));
             }
             const int sbi = __builtin_amdgcn_readlane(bi, wl);   // scalar slot of the winner: a scalar branch picks its registers
@@ -270,7 +244,7 @@ __global__ __launch_bounds__(FW_BS) void fps_wave_kernel(int n, int m, const flo
                 default: break;
             }
             if (PL > 0 && sbi >= PR) { const float* c = xl + (size_t)(sbi - PR) * 3 * FW_BS + tid; cx = c[0]; cy = c[FW_BS]; cz = c[2 * FW_BS]; }
-            wtd = fpsw_dkey_value(um);
+            wtd = fps_dkey_value(um);
             rk = um;
             rpos = wbase + sbi * 64 + wl;
             rx = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cx), wl));
@@ -296,13 +270,13 @@ __global__ __launch_bounds__(FW_BS) void fps_wave_kernel(int n, int m, const flo
                 const float4 a = *reinterpret_cast<const float4*>(s);
                 sk = __float_as_uint(a.x); spos = __float_as_int(a.y); sx = a.z; sy = a.w; sz = s[4];
             }
-            const uint32_t gm = fpsw_row0_max_u32(sk);  // > 0: some wave holds points
+            const uint32_t gm = fps_row0_max_u32<16>(sk);  // > 0: some wave holds points
             unsigned long long tm = __ballot(sk == gm);
             int gl = (int)__builtin_ctzll(tm);
             if (tm & (tm - 1)) {
                 const bool in = sk == gm;
-                const uint32_t key = in ? fpsw_tiekey(perm_l[spos]) : 0u;
-                const uint32_t mk = fpsw_wave_max_u32(key);
+                const uint32_t key = in ? fps_tiekey(perm_l[spos]) : 0u;
+                const uint32_t mk = fps_wave_max_u32(key);
                 gl = (int)__builtin_ctzll(__ballot(in && key == mk));
             }
             x1 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sx), gl));
@@ -424,8 +398,8 @@ __global__ __launch_bounds__(FW_BS) void fps_wave4_kernel(int n, int m, const fl
                 bs = gt ? g * PG + gbi[g] : bs;
                 bd = gt ? gbd[g] : bd;
             }
-            const uint32_t ub = fpsw_dkey(bd);
-            const uint32_t um = fpsw_wave_max_u32(ub);
+            const uint32_t ub = fps_dkey(bd);
+            const uint32_t um = fps_wave_max_u32(ub);
             const unsigned long long tm = __ballot(ub == um);
             int wl = (int)__builtin_ctzll(tm);
             int sbi = __builtin_amdgcn_readlane(bs, wl);
@@ -434,10 +408,10 @@ __global__ __launch_bounds__(FW_BS) void fps_wave4_kernel(int n, int m, const fl
                 uint32_t bk = 0u;
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
-                    const bool in = fpsw_dkey(gbd[g]) == um;
+                    const bool in = fps_dkey(gbd[g]) == um;
                     const int pos = wbase + (g * PG + gbi[g]) * 64 + lane;
-                    const uint32_t key = in ? fpsw_tiekey(pm[min(pos, n - 1)]) : 0u;
-                    const uint32_t mk = fpsw_wave_max_u32(key);
+                    const uint32_t key = in ? fps_tiekey(pm[min(pos, n - 1)]) : 0u;
+                    const uint32_t mk = fps_wave_max_u32(key);
                     if (mk > bk) {                        // wave-uniform
                         bk = mk;
                         wl = (int)__builtin_ctzll(__ballot(in && key == mk));
@@ -455,7 +429,7 @@ __global__ __launch_bounds__(FW_BS) void fps_wave4_kernel(int n, int m, const fl
                 default: break;
             }
             if (PL > 0 && sbi >= PR) { const float* c = xl + (size_t)(sbi - PR) * 3 * FW_BS + tid; cx = c[0]; cy = c[FW_BS]; cz = c[2 * FW_BS]; }
-            wtd = fpsw_dkey_value(um);
+            wtd = fps_dkey_value(um);
             rk = um;
             rpos = wbase + sbi * 64 + wl;
             rx = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cx), wl));
@@ -481,13 +455,13 @@ __global__ __launch_bounds__(FW_BS) void fps_wave4_kernel(int n, int m, const fl
                 const float4 a = *reinterpret_cast<const float4*>(s);
                 sk = __float_as_uint(a.x); spos = __float_as_int(a.y); sx = a.z; sy = a.w; sz = s[4];
             }
-            const uint32_t gm = fpsw_row0_max_u32(sk);
+            const uint32_t gm = fps_row0_max_u32<16>(sk);
             const unsigned long long tm = __ballot(sk == gm);
             int gl = (int)__builtin_ctzll(tm);
             if (tm & (tm - 1)) {
                 const bool in = sk == gm;
-                const uint32_t key = in ? fpsw_tiekey(pm[min(spos, n - 1)]) : 0u;
-                const uint32_t mk = fpsw_wave_max_u32(key);
+                const uint32_t key = in ? fps_tiekey(pm[min(spos, n - 1)]) : 0u;
+                const uint32_t mk = fps_wave_max_u32(key);
                 gl = (int)__builtin_ctzll(__ballot(in && key == mk));
             }
             x1 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(sx), gl));

@@ -24,10 +24,9 @@
 // scratch.  An arena or hash that overflows sets the seed's status and its distances are not written: the caller reruns the seed
 // with a larger arena (dis-pu_amd/mesh.py), nothing is truncated.
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
-int disk_scan_launch(long long M, long long* offsets, hipStream_t st);   // mesh_eval.hip
-
 constexpr int GEO_BS = 256;
 constexpr int GEO_TCH = 1024;            // targets per evaluation pass (LDS)
 constexpr int GEO_HMIN = 512, GEO_HMAX = 4096;

@@ -11,229 +11,23 @@
 //   bounds    per-workgroup min / max / non-finite partials, finished by one small workgroup          -> READBACK 1 (7 words)
 //   grid      origin, NX, NY, NZ, the key range and the pass count: on the host, in grid_params() ONLY
 //   keys      key[i] = iX + NX iY + NX NY iZ - key_min (uint64), val[i] = i (uint32)
-//   sort      LSD radix sort, 8 bits per pass, ceil(bits / 8) passes (none when the grid is one cell), ping-pong buffers; per pass:
-//               histogram   256 bins per tile of kRsTile elements in LDS (integer LDS atomics: counts are order-free)
-//               scan        exclusive scan of the digit-major table [256][tiles]
-//               scatter     stable rank inside the tile: lanes of equal digit found by ballots, ranked by lane; waves prefixed in wave
-//                           order; wave w owns the contiguous elements [w 512, (w + 1) 512) of the tile, so rank order = index order
+//   sort      the stable LSD radix sort of radix_sort.hip, ceil(bits / 8) passes (none when the grid is one cell)
 //   heads     head[j] = (j == 0 || key[j] != key[j-1]); an exclusive scan numbers the voxels and gives the start of every run and the
 //             voxel count m                                                                            -> READBACK 2 (m)
 //   reduce    one lane per (voxel, output column) walks its run from start to end: serial by necessity, the float order is pinned
 //   labels    per label column, the same sorter on (voxel id << 32) | (label ^ 0x80000000), then per voxel the longest run of equal
 //             keys, the first such run winning: ties go to the smallest label (signed)
 //
-// Cross-workgroup ordering is by kernel boundaries only: no kernel waits on anything another workgroup writes.  The device-wide scans
-// are the plain three-step kind (tile sums, scan of sums, apply); one building block serves the histogram table and the heads.
+// Cross-workgroup ordering is by kernel boundaries only: no kernel waits on anything another workgroup writes.  The sorter and the
+// device-wide scan (histogram table there, the heads here) are those of radix_sort.hip.
 // Two small host readbacks per call (dispu_grid_subsample_plan): the bounds with the non-finite flag, and m.
-#include "common.h"
+#include "internal.h"
 #include <math.h>
 #include <float.h>
 
 namespace dispu {
 
-constexpr int kRsThreads = 256;                      // 4 waves
-constexpr int kRsWaves = kRsThreads / kWave;
-constexpr int kRsItems = 8;                          // elements per thread
-constexpr int kRsTile = kRsThreads * kRsItems;       // 2048 = DISPU_RADIX_TILE
-constexpr int kRsWaveSpan = kWave * kRsItems;        // 512 contiguous elements per wave
 constexpr int kBoundsMaxBlocks = 1024;
-
-// ---- block helpers (256 threads) ---------------------------------------------------------------------------------------------------
-// exclusive prefix of one value per thread in thread order, and the block total; wsum: kRsWaves words of LDS, reusable on return
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += t;
-    }
-    if (lane == kWave - 1) wsum[w] = inc;
-    __syncthreads();
-    uint32_t off = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kRsWaves; ++i) {
-        const uint32_t s = wsum[i];
-        if (i < w) off += s;
-        total += s;
-    }
-    __syncthreads();
-    return off + inc - v;
-}
-
-// ---- device-wide exclusive scan of uint32 data[L], in place: reduce -> sums -> apply; chunks of kRsTile ------------------------------
-__global__ __launch_bounds__(kRsThreads) void scan_reduce_kernel(const uint32_t* __restrict__ data, size_t L, uint32_t* __restrict__ sums) {
-    __shared__ uint32_t wsum[kRsWaves];
-    const size_t base = (size_t)blockIdx.x * kRsTile + (size_t)threadIdx.x * kRsItems;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kRsItems; ++k)
-        if (base + k < L) s += data[base + k];
-    uint32_t total;
-    (void)block_excl_scan(s, wsum, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[nb] -> their exclusive prefixes, in place; the grand total -> *total_out (if not null)
-__global__ __launch_bounds__(kRsThreads) void scan_sums_kernel(uint32_t* __restrict__ sums, unsigned nb, uint32_t* __restrict__ total_out) {
-    __shared__ uint32_t wsum[kRsWaves];
-    const unsigned per = (nb + kRsThreads - 1) / kRsThreads;
-    const unsigned lo = min(threadIdx.x * per, nb), hi = min(lo + per, nb);
-    uint32_t s = 0;
-    for (unsigned i = lo; i < hi; ++i) s += sums[i];
-    uint32_t total;
-    uint32_t run = block_excl_scan(s, wsum, total);
-    for (unsigned i = lo; i < hi; ++i) {
-        const uint32_t v = sums[i];
-        sums[i] = run;
-        run += v;
-    }
-    if (total_out && threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(kRsThreads) void scan_apply_kernel(uint32_t* __restrict__ data, size_t L, const uint32_t* __restrict__ sums) {
-    __shared__ uint32_t wsum[kRsWaves];
-    const size_t base = (size_t)blockIdx.x * kRsTile + (size_t)threadIdx.x * kRsItems;
-    uint32_t v[kRsItems];
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kRsItems; ++k) {
-        v[k] = base + k < L ? data[base + k] : 0u;
-        s += v[k];
-    }
-    uint32_t total;
-    uint32_t run = block_excl_scan(s, wsum, total) + sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kRsItems; ++k) {
-        if (base + k < L) data[base + k] = run;
-        run += v[k];
-    }
-}
-
-static inline size_t scan_blocks(size_t L) { return (L + kRsTile - 1) / kRsTile; }
-
-// sums: scan_blocks(L) words
-static int exclusive_scan_u32(uint32_t* data, size_t L, uint32_t* sums, uint32_t* total_out, hipStream_t st) {
-    const unsigned nb = (unsigned)scan_blocks(L);
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kRsThreads), 0, st, data, L, sums);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kRsThreads), 0, st, sums, nb, total_out);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kRsThreads), 0, st, data, L, sums);
-    return (int)hipGetLastError();
-}
-
-// ---- radix sort ----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kRsThreads) void radix_hist_kernel(const uint64_t* __restrict__ keys, size_t n, int shift, unsigned tiles,
-                                                                uint32_t* __restrict__ table) {
-    __shared__ uint32_t hist[256];
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * kRsTile;
-#pragma unroll
-    for (int k = 0; k < kRsItems; ++k) {
-        const size_t p = base + (size_t)k * kRsThreads + threadIdx.x;
-        if (p < n) atomicAdd(&hist[(unsigned)(keys[p] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    table[(size_t)threadIdx.x * tiles + blockIdx.x] = hist[threadIdx.x];
-}
-
-// table: the SCANNED digit-major table, table[d][tile] = the first output position of digit d of this tile
-__global__ __launch_bounds__(kRsThreads) void radix_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                                   size_t n, int shift, unsigned tiles, const uint32_t* __restrict__ table,
-                                                                   uint64_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
-    __shared__ uint32_t wcount[kRsWaves][256];       // per wave: elements of each digit seen so far, at the end the wave's count
-    __shared__ uint32_t wbase[kRsWaves][256];        // first output position of (wave, digit)
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-#pragma unroll
-    for (int i = 0; i < kRsWaves; ++i) wcount[i][threadIdx.x] = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * kRsTile + (size_t)w * kRsWaveSpan + lane;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    volatile uint32_t* wc = wcount[w];               // this wave's row: read by all its lanes, then written by the digit leaders, in order
-    uint64_t key[kRsItems];
-    uint32_t val[kRsItems], rank[kRsItems];
-#pragma unroll
-    for (int k = 0; k < kRsItems; ++k) {
-        const size_t p = base + (size_t)k * kWave;
-        const bool valid = p < n;
-        key[k] = valid ? keys[p] : 0ull;
-        val[k] = valid ? vals[p] : 0u;
-        const unsigned d = (unsigned)(key[k] >> shift) & 255u;
-        unsigned long long peers = __ballot(valid);  // the lanes that hold an element of the same digit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long bal = __ballot(bit);
-            peers &= bit ? bal : ~bal;
-        }
-        const uint32_t before = wc[d];
-        __builtin_amdgcn_wave_barrier();
-        rank[k] = before + (uint32_t)__popcll(peers & below);
-        if (valid && (peers & below) == 0ull) wc[d] = before + (uint32_t)__popcll(peers);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    {
-        uint32_t run = table[(size_t)threadIdx.x * tiles + blockIdx.x];
-#pragma unroll
-        for (int i = 0; i < kRsWaves; ++i) {
-            wbase[i][threadIdx.x] = run;
-            run += wcount[i][threadIdx.x];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kRsItems; ++k) {
-        const size_t p = base + (size_t)k * kWave;
-        if (p < n) {
-            const size_t dst = (size_t)wbase[w][(unsigned)(key[k] >> shift) & 255u] + rank[k];
-            if (dst < n) {                           // always true for a consistent table; keeps a wrong one from writing outside
-                keys_out[dst] = key[k];
-                vals_out[dst] = val[k];
-            }
-        }
-    }
-}
-
-static inline unsigned rs_tiles(size_t n) { return (unsigned)((n + kRsTile - 1) / kRsTile); }
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline size_t rs_table_words(size_t n) { return (size_t)256 * rs_tiles(n); }
-
-// `passes` stable 8-bit passes from (src_k, src_v), which is only read, alternating into (xk, xv), (yk, yv), (xk, xv), ...:
-// the result is in x when passes is odd and in y when it is even (passes >= 1)
-static int radix_passes(size_t n, int passes, const uint64_t* src_k, const uint32_t* src_v, uint64_t* xk, uint32_t* xv, uint64_t* yk,
-                        uint32_t* yv, uint32_t* table, uint32_t* sums, hipStream_t st) {
-    const unsigned tiles = rs_tiles(n);
-    const uint64_t* ck = src_k;
-    const uint32_t* cv = src_v;
-    for (int p = 0; p < passes; ++p) {
-        uint64_t* dk = (p & 1) ? yk : xk;
-        uint32_t* dv = (p & 1) ? yv : xv;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(tiles), dim3(kRsThreads), 0, st, ck, n, 8 * p, tiles, table);
-        const int rc = exclusive_scan_u32(table, rs_table_words(n), sums, nullptr, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(tiles), dim3(kRsThreads), 0, st, ck, cv, n, 8 * p, tiles, table, dk, dv);
-        ck = dk;
-        cv = dv;
-    }
-    return (int)hipGetLastError();
-}
-
-// scratch of the sorter alone: alternate keys, alternate payload, table, scan sums
-struct SortScratch {
-    size_t keys, vals, table, sums, total;
-};
-static SortScratch sort_scratch(size_t n) {
-    SortScratch s;
-    size_t o = 0;
-    s.keys = o;  o += align256(8 * n);
-    s.vals = o;  o += align256(4 * n);
-    s.table = o; o += align256(4 * rs_table_words(n));
-    s.sums = o;  o += align256(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
-    s.total = o;
-    return s;
-}
 
 // ---- bounds ----------------------------------------------------------------------------------------------------------------------------
 struct Bounds {
@@ -335,7 +129,7 @@ static GridParams grid_params(const Bounds& b, float dl) {
         const float bot = cell_f(b.mn[c], g.origin[c], dl);
         // in float, before any conversion to an integer: at most 2^21 cells per axis keeps every key below 2^63
         if (!(top + 1.0f <= 2097152.0f) || !(bot >= -2097152.0f)) {
-            if (!g.status) g.status = 2 + c;
+            if (!g.status) g.status = DISPU_GRID_AXIS_X + c;
             g.N[c] = 1;
             lo[c] = 0;
             continue;
@@ -472,37 +266,6 @@ static inline unsigned blocks_for(size_t work) { return (unsigned)((work + kRsTh
 
 using namespace dispu;
 
-DISPU_EXPORT size_t dispu_radix_sort_scratch_bytes(long long n) {
-    if (n <= 0 || n >= (1ll << 31)) return 0;
-    return sort_scratch((size_t)n).total;
-}
-
-DISPU_EXPORT int dispu_radix_sort_pairs(long long n, int bits, const unsigned long long* keys_in, const unsigned int* vals_in,
-                                        unsigned long long* keys_out, unsigned int* vals_out, void* scratch, size_t scratch_bytes,
-                                        void* stream) {
-    if (n < 0 || n >= (1ll << 31) || bits < 0 || bits > 64) return (int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!keys_in || !vals_in || !keys_out || !vals_out || keys_in == keys_out || vals_in == vals_out) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t N = (size_t)n;
-    const int passes = (bits + 7) / 8;
-    if (passes == 0) {
-        DISPU_TRY(hipMemcpyAsync(keys_out, keys_in, 8 * N, hipMemcpyDeviceToDevice, st));
-        DISPU_TRY(hipMemcpyAsync(vals_out, vals_in, 4 * N, hipMemcpyDeviceToDevice, st));
-        return 0;
-    }
-    const SortScratch s = sort_scratch(N);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
-    char* base = (char*)scratch;
-    uint64_t* ak = (uint64_t*)(base + s.keys);
-    uint32_t* av = (uint32_t*)(base + s.vals);
-    uint64_t* ok = (uint64_t*)keys_out;
-    uint32_t* ov = (uint32_t*)vals_out;
-    const bool odd = passes & 1;                     // the result lands in x for an odd pass count, in y for an even one
-    return radix_passes(N, passes, (const uint64_t*)keys_in, (const uint32_t*)vals_in, odd ? ok : ak, odd ? ov : av, odd ? ak : ok,
-                        odd ? av : ov, (uint32_t*)(base + s.table), (uint32_t*)(base + s.sums), st);
-}
-
 DISPU_EXPORT size_t dispu_grid_subsample_scratch_bytes(long long n, int fdim, int ldim) {
     if (n <= 0 || n >= (1ll << 31) || fdim < 0 || ldim < 0) return 0;
     return grid_scratch((size_t)n).total;            // features and labels are read in place: fdim and ldim add nothing
@@ -513,7 +276,7 @@ DISPU_EXPORT int dispu_grid_subsample_plan(long long n, const float* points, flo
     if (!m_out || !status_out) return (int)hipErrorInvalidValue;
     *m_out = 0;
     *status_out = 0;
-    if (n >= (1ll << 31)) { *status_out = 5; return 0; }          // DISPU_GRID_TOO_MANY_POINTS, before anything is touched
+    if (n >= (1ll << 31)) { *status_out = DISPU_GRID_TOO_MANY_POINTS; return 0; }   // before anything is touched
     if (n <= 0 || !points || !(dl > 0.0f) || !(dl <= FLT_MAX)) return (int)hipErrorInvalidValue;
     const size_t N = (size_t)n;
     const GridScratch s = grid_scratch(N);
@@ -535,7 +298,7 @@ DISPU_EXPORT int dispu_grid_subsample_plan(long long n, const float* points, flo
     Bounds hb;
     DISPU_TRY(hipMemcpyAsync(&hb, d_bounds, sizeof(Bounds), hipMemcpyDeviceToHost, st));      // readback 1
     DISPU_TRY(hipStreamSynchronize(st));
-    if (hb.bad) { *status_out = 1; return 0; }                    // DISPU_GRID_NONFINITE
+    if (hb.bad) { *status_out = DISPU_GRID_NONFINITE; return 0; }
     const GridParams g = grid_params(hb, dl);
     if (grid_out) {
         for (int c = 0; c < 3; ++c) { grid_out[c] = g.origin[c]; grid_out[3 + c] = (double)g.N[c]; }

@@ -10,6 +10,7 @@
 // loop as soon as all of its lanes are full (cnt == nsample).
 #include "ball_mask.h"
 #include "common.h"
+#include "internal.h"
 
 #include <cstdlib>
 

@@ -13,6 +13,7 @@
 // KNNResultSet order for candidates presented in index order.  The insertion is branch-free
 // inside the lane (v_med3_f32 per slot) and skipped for the whole wave when no lane accepts.
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 
@@ -212,25 +213,6 @@ static int launch_feat(int b, int n, int m, int c, int k, int ldp, int ldq, cons
     if (c <= 128) return launch_feat_k<128, GEMM_FORM, NEG>(b, n, m, c, k, ldp, ldq, p, q, dist, idx, st);
     return (int)hipErrorInvalidValue;
 }
-
-// wave-per-query fast paths (knn_wave.hip); return -1 when the shape is outside their range
-int knn_xyz_wave_dispatch(int b, int n, int m, int k, const float* s, const float* q, int* idx, float* dist, int arith,
-                          hipStream_t st);
-int knn_feat_wave_dispatch(int b, int n, int m, int c, int k, int ldp, int ldq, const float* p, const float* q, float* dist,
-                           int* idx, hipStream_t st, long pstride = 0);
-size_t knn_feat_chunked_scratch(int b, int n, int m, int c, int k);
-int knn_feat_chunked_dispatch(int b, int n, int m, int c, int k, int ldp, int ldq, const float* p, const float* q, float* dist, int* idx,
-                              void* scratch, size_t scratch_bytes, hipStream_t st);
-
-// 1024 < n <= 8192, k <= 32 (knn_wave.hip): per-chunk wave kernel + merge; needs caller scratch
-size_t knn_xyz_chunked_scratch(int b, int n, int m, int k);
-int knn_xyz_lds_dispatch(int b, int n, int m, int k, const float* s, const float* q, int* idx, float* dist, int arith, hipStream_t st);
-int knn_xyz_chunked_dispatch(int b, int n, int m, int k, const float* s, const float* q, int* idx, float* dist, void* scratch,
-                             size_t scratch_bytes, int arith, hipStream_t st);
-// general path (knn_general.hip): any k <= 4096, c <= 4096, any n; mode 0/1 xyz plain/contract, 2 knn_point, 3 knn_point_2
-int knn_general_launch(int mode, int b, int n, int m, int c, int k, long ldp, long ldq, const float* points, const float* queries,
-                       float* dist, int* idx, int neg, hipStream_t st, const int* off = nullptr, const int* qoff = nullptr,
-                       int seg_nmin = 0);
 
 }  // namespace dispu
 

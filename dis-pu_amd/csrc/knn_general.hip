@@ -11,6 +11,7 @@
 // arithmetic of the fast paths (xyz: sqdist3 PLAIN / CONTRACT; knn_point: sum((p - q)^2) left to right, every op rounded;
 // knn_point_2: (rq - 2 q.p) + rp with ascending-channel fmaf chains), so both paths agree bit for bit where they overlap.
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 

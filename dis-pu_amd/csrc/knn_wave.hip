@@ -12,6 +12,7 @@
 // Feature space: the cloud's features are staged once per workgroup in LDS, channel-quad major
 // ([C/4][n] float4 -> conflict-free ds_read_b128), dots are the same ascending-channel fmaf chains.
 #include "common.h"
+#include "internal.h"
 #include "knn_select.h"
 
 #include <cstdlib>
@@ -405,7 +406,7 @@ static int launch_xyz_wave(int b, int n, int m, int k, const float* s, const flo
 
 template <int R, int CP>
 static int launch_feat_wave(int b, int n, int m, int c, int k, int ldp, int ldq, const float* p, const float* q, float* dist,
-                            int* idx, hipStream_t st, long pstride = 0) {
+                            int* idx, hipStream_t st, long pstride) {
     if (pstride == 0) pstride = (long)n * ldp;
     const int qpb = 16;         // 2 queries per wave; the cloud's features are re-staged per workgroup (L2-resident)
     dim3 grid((m + qpb - 1) / qpb, b);
@@ -645,7 +646,7 @@ static int feat_wave_r(int b, int n, int m, int c, int k, int ldp, int ldq, cons
 int knn_feat_big_dispatch(int b, int n, int m, int c, int k, int ldp, int ldq, const float* p, const float* q, float* dist, int* idx,
                           hipStream_t st);
 int knn_feat_wave_dispatch(int b, int n, int m, int c, int k, int ldp, int ldq, const float* p, const float* q, float* dist,
-                           int* idx, hipStream_t st, long pstride = 0) {
+                           int* idx, hipStream_t st, long pstride) {
     if (n > 512 && pstride == 0) return knn_feat_big_dispatch(b, n, m, c, k, ldp, ldq, p, q, dist, idx, st);
     if (n > 512 || c > 64 || k > 64) return -1;
     const int cp = (c + 3) & ~3;

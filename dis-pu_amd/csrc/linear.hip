@@ -16,6 +16,7 @@
 //   there is ONE barrier per K-tile and no load/store-only phase.  Interior tiles take a predicate-free path.
 //   Epilogue fuses bias, BatchNorm scale/shift, ReLU and two residual adds.
 #include "common.h"
+#include "internal.h"
 
 #include <type_traits>
 
@@ -575,16 +576,10 @@ struct LinearLaunch {
     int epi;               // tiled: 0 plain, 1 BatchNorm fold, 4 residuals, 5 ReLU-gradient mask, 6 = 0 at K >= 1024 on the 128 x 256 DMA path
     int ng;                // skinny: unroll depth (2, 8, 16, 24)
 };
-constexpr int DISPU_LINEAR_PLAN_INTS = 21;     // include/dispu_hip.h
 struct LinearPlan {
     int n;
     LinearLaunch l[2];
 };
-
-int linear_skinny_rule(int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb);   // linear_skinny.hip
-int linear_skinny_launch(int ng, int M, int K, int N, const float* X, long ldx, const float* W, long ldw, int transb, const float* bias,
-                         int act, float* Y, long ldy, const float* R1, long ldr1, const float* Mk, long ldm, int mcols,
-                         hipStream_t st);
 
 }  // namespace dispu
 

@@ -17,6 +17,7 @@
 // TN splits the long contraction (m = rows of the batch) over workgroups; partial tiles go to caller scratch and are added
 // in split order by gemm_bf16_reduce_kernel (deterministic, no float atomics).
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 

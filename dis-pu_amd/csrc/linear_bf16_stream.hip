@@ -18,6 +18,7 @@
 // Shapes outside M % 128 == 0, K % 32 == 0, N % 128 == 0 (16-byte aligned rows) return hipErrorInvalidValue: the caller keeps
 // dispu_linear_bf16 for them.
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 

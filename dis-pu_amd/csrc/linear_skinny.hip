@@ -10,6 +10,7 @@
 // a 4 x 4 transpose between the four 16-lane rows and the float4 components, done with gfx950's
 // v_permlane32_swap / v_permlane16_swap (4 instructions per float4, no LDS).
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 

@@ -14,10 +14,12 @@
 // Uniformity: one workgroup per disk, the nearest OTHER member by a tiled all-pairs scan through LDS (any disk size), fp64 terms
 // reduced in a fixed order, then one wave per radius sums the kept disks in ascending seed order.
 #include "common.h"
+#include "internal.h"
 
 namespace dispu {
 
-constexpr int P2M_TILE = 64;        // faces per tile == lanes per wave (include/dispu_hip.h: DISPU_MESH_TILE)
+constexpr int P2M_TILE = 64;        // faces per tile == lanes per wave
+static_assert(P2M_TILE == DISPU_MESH_TILE, "the tile the public header documents");
 constexpr int P2M_WAVES = 4;
 
 // Closest point on triangle (a, b, c) to p by Voronoi regions (vertex, edge, face; C. Ericson, Real-Time Collision Detection,

@@ -4,7 +4,7 @@
 // (d2, original local index), d2 = ((dx*dx + dy*dy) + dz*dz) in fp32 without contraction, the query itself and duplicates included --
 // the rule of dispu_knn_patch_segments, so the two agree bit for bit.
 //
-//   pre-pass   the one of fps_cells.hip (fps_cells_prepass): segment boxes and non-finite flags, Morton keys with the segment id on top,
+//   pre-pass   morton_cells.hip (fps_cells_prepass):: segment boxes and non-finite flags, Morton keys with the segment id on top,
 //              one stable dispu_radix_sort_pairs, cells of 64 consecutive sorted positions with their boxes
 //   search     one wave per cell, one query per lane; every lane keeps its k best keys (d2 bits << 32 | local index) sorted in
 //              registers.  The wave visits its own cell, then the cells at growing Morton offset (c - 1, c + 1, c - 2, ...) until it
@@ -27,16 +27,13 @@
 //
 // No [n, k] tensor reaches memory unless idx_out is asked for.  Every value is written with ordinary stores; no atomics of its own;
 // ordering between the pre-pass and the search by kernel boundaries only; identical bytes from run to run.
-#include "common.h"
+#include "morton_cells.h"
 
 namespace dispu {
 
-size_t fps_cells_prepass_scratch(int C, const int* off_host);
-int fps_cells_prepass(int C, const int* off, const int* off_host, const float* inp, void* scratch, size_t scratch_bytes,
-                      const float4** spt, const float** tab, const uint32_t** segb, int* kmax, hipStream_t st);
-
 constexpr int kNrmThreads = 256, kNrmWaves = kNrmThreads / kWave, kNrmCell = 64;
 constexpr uint64_t kNrmNone = ~0ull;
+static_assert(kNrmCell == kFpcMinCell && kNrmCell == kWave, "kCellsFixed64: one query per lane, the cell table indexed as the pre-pass wrote it");
 
 template <int KMAX>
 struct NrmBest {

@@ -25,9 +25,6 @@
 // No float atomics; integer atomics only where the order cannot matter.
 #include "common.h"
 
-#define DISPU_POISSON_MAX_N 49152      /* both mirror include/dispu_hip.h (which shares a struct with common.h and cannot be included */
-#define DISPU_POISSON_MAX_ROUNDS 256   /* here); tests/test_mesh_sample.py holds the two files to the same values */
-
 namespace dispu {
 
 constexpr int PD_BS = 1024;

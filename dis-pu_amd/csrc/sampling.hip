@@ -12,39 +12,16 @@
 //   key = float_bits(d) << 32 | (0xFFFFFFFF - ((k & 511) << 22 | k >> 9))
 // whose unsigned maximum is exactly that winner, independent of this kernel's thread layout.
 #include "common.h"
+#include "fps_keys.h"
+#include "internal.h"
 
 #include <mutex>
 
 namespace dispu {
 
-__device__ __forceinline__ uint32_t fps_tiekey(int k) {
-    return 0xFFFFFFFFu - ((((uint32_t)k & 511u) << 22) | ((uint32_t)k >> 9));
-}
-__device__ __forceinline__ int fps_key_to_index(uint64_t key) {
-    const uint32_t t = 0xFFFFFFFFu - (uint32_t)key;
-    return (int)(((t & 0x3FFFFFu) << 9) | (t >> 22));
-}
-
-// Wave arg-max of (distance, tie key) on 32-bit DPP steps (round 4).  The 64-bit key needs two DPP moves, a 64-bit compare and two
-// selects per step (wave_max_u64: ~45 dependent-ish instructions per round); running distances are >= 0 (or -1 = "no point"), so
-// their bit patterns + 1 order like unsigned integers and fold with ONE v_max_u32_dpp per step.  Two such reductions - the
-// largest distance, then the largest tie key among the lanes that hold it (tie keys are unique, 0 elsewhere) - give the same
-// (distance, key) pair, wave-uniform, in 12 single-instruction steps and two v_readlane.
-__device__ __forceinline__ uint32_t fps_dkey(float d) { return d >= 0.f ? __float_as_uint(d) + 1u : 0u; }
-template <int CTRL, int RM = 0xF>
-__device__ __forceinline__ uint32_t fps_umax_step(uint32_t v) {
-    const uint32_t o = dpp_u32<CTRL, RM>(0u, v);
-    return v > o ? v : o;
-}
-__device__ __forceinline__ uint32_t fps_wave_max_u32(uint32_t v) {
-    v = fps_umax_step<DPP_ROW_SHR1>(v);
-    v = fps_umax_step<DPP_ROW_SHR2>(v);
-    v = fps_umax_step<DPP_ROW_SHR4>(v);
-    v = fps_umax_step<DPP_ROW_SHR8>(v);
-    v = fps_umax_step<DPP_ROW_BCAST15, 0xA>(v);
-    v = fps_umax_step<DPP_ROW_BCAST31, 0xC>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
+// Wave arg-max of (distance, tie key) on the 32-bit DPP steps of fps_keys.h.  Two such reductions - the largest distance, then the
+// largest tie key among the lanes that hold it (tie keys are unique, 0 elsewhere) - give the same (distance, key) pair as a 64-bit
+// key maximum, wave-uniform, in 12 single-instruction steps and two v_readlane.
 // -> the wave's best as the 64-bit key of fps_tiekey's scheme (distance bits << 32 | tie key), 0 when the wave holds no point
 __device__ __forceinline__ uint64_t fps_wave_best(float bd, int k) {
     const uint32_t dk = fps_dkey(bd);
@@ -58,20 +35,12 @@ __device__ __forceinline__ uint64_t fps_wave_best(float bd, int k) {
 // W 64-bit compare/select triples in every lane), then the same two-stage 32-bit reduction over DPP row 0.
 template <int W>
 __device__ __forceinline__ uint64_t fps_slots_best(const uint64_t* slots, int lane) {
-    static_assert(W <= 16, "one DPP row");
     const uint64_t v = (lane < W) ? slots[lane] : 0ull;
-    auto row0_max = [](uint32_t x) -> uint32_t {
-        x = fps_umax_step<DPP_ROW_SHR1>(x);
-        if (W > 2) x = fps_umax_step<DPP_ROW_SHR2>(x);
-        if (W > 4) x = fps_umax_step<DPP_ROW_SHR4>(x);
-        if (W > 8) x = fps_umax_step<DPP_ROW_SHR8>(x);
-        return (uint32_t)__builtin_amdgcn_readlane((int)x, W - 1 < 15 ? (W <= 2 ? 1 : W <= 4 ? 3 : W <= 8 ? 7 : 15) : 15);
-    };
     // distance bits are compared as (bits + 1) with 0 = empty slot, exactly as inside the waves
     const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
     const uint32_t dk = v ? hi + 1u : 0u;
-    const uint32_t dmax = row0_max(dk);
-    const uint32_t tmax = row0_max(dk == dmax ? lo : 0u);
+    const uint32_t dmax = fps_row0_max_u32<W>(dk);
+    const uint32_t tmax = fps_row0_max_u32<W>(dk == dmax ? lo : 0u);
     return dmax ? (((uint64_t)(dmax - 1u) << 32) | tmax) : 0ull;
 }
 
@@ -209,11 +178,6 @@ static int launch_fps_reg(int b, int n, int m, const float* xyz, int* out, int a
     return (int)hipGetLastError();
 }
 
-// out[i,j,:] = inp[i, idx[i,j], :]   (c == 3, like the reference kernel tf_sampling_g.cu:172-181): gather_xyz_kernel of
-// csrc/grouping.hip (12-byte loads per lane, LDS-staged float4 stores).
-int launch_gather_rows(size_t rows, int n, int c, size_t rows_per_cloud, const float* points, const int* idx, float* out,
-                       hipStream_t st);
-
 // inp_g[i, idx[i,j], :] += out_g[i,j,:]  on a zero-filled buffer (tf_sampling_g.cu:183-192, tf_sampling.cpp:174)
 __global__ void gather_point_grad_kernel(int n, int m, size_t total, const float* __restrict__ out_g,
                                          const int* __restrict__ idx, float* __restrict__ inp_g) {
@@ -226,13 +190,6 @@ __global__ void gather_point_grad_kernel(int n, int m, size_t total, const float
         unsafeAtomicAdd(dst + 2, src[2]);
     }
 }
-
-// csrc/fps_wave.hip: exact sampling with wave-level skipping for 4096 < n <= 24576 (scratch = the sorted permutation)
-bool fps_wave_wants_scratch(int n, int m);
-int fps_wave_dispatch(int b, int n, int m, const float* xyz, void* temp, int* out, int arith, hipStream_t s);
-int fps_wave_launch(int b, int n, int m, const float* xyz, int* perm, int* out, int arith, hipStream_t s, const int* off, const int* moff);
-
-static bool fps_dense_only() { return false; }     // (the region-skipping kernels of csrc/fps_wave.hip whenever scratch is given)
 
 // the dense (scratch-free for n <= 24576) kernels.  off / moff: a ragged batch of b segments of at most n points each, of which
 // the kernel serves those of family `fam`.
@@ -336,7 +293,7 @@ __global__ void prob_search_kernel(int n, int m, int base, const float* __restri
 using namespace dispu;
 
 DISPU_EXPORT size_t dispu_fps_scratch_bytes(int b, int n, int m) {
-    if (n > 24576 || (fps_wave_wants_scratch(n, m) && !fps_dense_only())) return (size_t)b * n * sizeof(float);
+    if (n > 24576 || fps_wave_wants_scratch(n, m)) return (size_t)b * n * sizeof(float);
     return 0;
 }
 
@@ -348,7 +305,7 @@ DISPU_EXPORT int dispu_fps_ws(int b, int n, int m, const float* inp, float* temp
     hipStream_t s = (hipStream_t)stream;
     const size_t need = (size_t)b * n * sizeof(float);
     if (!temp) temp_bytes = 0;
-    if (n > 4096 && n <= 24576 && !fps_dense_only() && temp_bytes >= need) {   // region skipping needs the b*n-int permutation
+    if (n > 4096 && n <= 24576 && temp_bytes >= need) {   // region skipping needs the b*n-int permutation
         const int r = fps_wave_dispatch(b, n, m, inp, temp, out, arith, s);
         if (r >= 0) return r;
     }
@@ -413,13 +370,6 @@ static int fps_segment_families(int C, const int* off_host, const int* moff_host
     return 0;
 }
 
-// csrc/fps_cells.hip: the cell-skipping kernels over the segments of family 3 (mode 1) or over all of them (mode 0)
-size_t fps_cells_scratch(int C, const int* off_host, const int* moff_host, int cell, int mode);
-int fps_cells_run(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* scratch,
-                  size_t scratch_bytes, int* out, int* status, int arith, int cell, int mode, hipStream_t st);
-
-static inline size_t fps_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // One launch (sequence) per family, sized for its largest segment: the kernels' results do not depend on their tier.  The first
 // family runs on the caller's stream, the others on side streams.  cells: family 3 exists (dispu_fps_segments_auto) and takes
 // [cscratch, cscratch + cbytes) and status.
@@ -427,7 +377,7 @@ static int fps_segments_run(int C, const int* off, const int* moff, const int* o
                             void* temp, const int nmax[4], bool cells, void* cscratch, size_t cbytes, int* status, int* out, int arith,
                             hipStream_t s) {
     auto run = [&](int f, hipStream_t st) -> int {
-        if (f == 3) return fps_cells_run(C, off, moff, off_host, moff_host, inp, cscratch, cbytes, out, status, arith, 0, 1, st);
+        if (f == 3) return fps_cells_run(C, off, moff, off_host, moff_host, inp, cscratch, cbytes, out, status, arith, 0, kCellsAuto, st);
         if (f == 1) return fps_wave_launch(C, nmax[1], 0, inp, reinterpret_cast<int*>(temp), out, arith, st, off, moff);
         return fps_dense(C, nmax[f], 0, inp, reinterpret_cast<float*>(temp), out, arith, st, off, moff,
                          (cells && f == 2) ? (f | 4) : f);      // only the streaming kernel shares its size range with family 3
@@ -475,9 +425,9 @@ DISPU_EXPORT int dispu_fps_segments(int C, const int* off, const int* moff, cons
 DISPU_EXPORT size_t dispu_fps_segments_auto_scratch_bytes(int C, const int* off_host, const int* moff_host) {
     int nmax[4];
     if (C <= 0 || fps_segment_families(C, off_host, moff_host, nmax, true) != 0) return 0;
-    const size_t a = (nmax[1] || nmax[2]) ? fps_align256((size_t)off_host[C] * sizeof(float)) : 0;
+    const size_t a = (nmax[1] || nmax[2]) ? align256((size_t)off_host[C] * sizeof(float)) : 0;
     if (!nmax[3]) return a;
-    const size_t b = fps_cells_scratch(C, off_host, moff_host, 0, 1);
+    const size_t b = fps_cells_scratch(C, off_host, moff_host, 0, kCellsAuto);
     return b ? a + b : 0;                             // 0: a family-3 segment the cell kernels refuse (above 2^24 points)
 }
 
@@ -487,8 +437,8 @@ DISPU_EXPORT int dispu_fps_segments_auto(int C, const int* off, const int* moff,
     if (C == 0) return 0;
     int nmax[4];
     if (!off || !moff || !inp || !out || fps_segment_families(C, off_host, moff_host, nmax, true) != 0) return (int)hipErrorInvalidValue;
-    const size_t a = (nmax[1] || nmax[2]) ? fps_align256((size_t)off_host[C] * sizeof(float)) : 0;
-    const size_t b = nmax[3] ? fps_cells_scratch(C, off_host, moff_host, 0, 1) : 0;
+    const size_t a = (nmax[1] || nmax[2]) ? align256((size_t)off_host[C] * sizeof(float)) : 0;
+    const size_t b = nmax[3] ? fps_cells_scratch(C, off_host, moff_host, 0, kCellsAuto) : 0;
     if (nmax[3] && (!b || !status)) return (int)hipErrorInvalidValue;
     if ((a || b) && (!temp || temp_bytes < a + b || ((uintptr_t)temp & 15))) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;

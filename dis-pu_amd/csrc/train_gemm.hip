@@ -11,6 +11,7 @@
 // = a row pair of X, B operand = the same row pair of Z: neither needs a transpose).  Splits write partial tiles to
 // a scratch buffer and a second kernel sums them in split order, so the result is deterministic (no float atomics).
 #include "common.h"
+#include "internal.h"
 
 #include <cstdio>
 #include <cstdlib>

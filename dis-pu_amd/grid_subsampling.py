@@ -5,7 +5,7 @@ dense, uneven scan to an even spacing before patches are taken from it.
 
 compute() mirrors the wrapper's signature.  The outputs are the reference's bit for bit, with the two things it leaves to
 std::unordered_map defined (include/dispu_hip.h: dispu_grid_subsample_plan): rows come in ascending key order, and a tie between label
-counts goes to the smallest label.  Kernels: csrc/grid_subsample.hip; the yardstick is tests/grid_subsample_oracle.py.
+counts goes to the smallest label.  Kernels: csrc/grid_subsample.hip, csrc/radix_sort.hip; the yardstick is tests/grid_subsample_oracle.py.
 A single cloud per call; packed batches of clouds are out of scope."""
 import ctypes as C
 import math

@@ -94,7 +94,7 @@ int dispu_fps_ws(int b, int n, int m, const float* inp, float* temp, size_t temp
 size_t dispu_fps_segments_scratch_bytes(int C, const int* off_host, const int* moff_host);
 int dispu_fps_segments(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, const float* inp, void* temp,
                        size_t temp_bytes, int* out, int arith, void* stream);
-/* The same sampling (tf_sampling.cpp:94,118; kernel tf_sampling_g.cu:105-170) for LARGE clouds, csrc/fps_cells.hip: the cloud stays in
+/* The same sampling (tf_sampling.cpp:94,118; kernel tf_sampling_g.cu:105-170) for LARGE clouds, csrc/fps_cells.hip (pre-pass: csrc/morton_cells.hip): the cloud stays in
  * global memory, a device-wide pre-pass (bounding boxes, Morton keys, one dispu_radix_sort_pairs over the batch, cells of S consecutive
  * sorted positions with their boxes) lets every round skip the cells whose box is farther from the new sample than their largest
  * running distance.  The indices are those of dispu_fps_ws and dispu_fps_segments bit for bit, in both arithmetic flavours: skipped
@@ -929,7 +929,7 @@ int dispu_poisson_disk_select(int b, int n, int m, int steps, const float* point
 int dispu_sort_rows_i32(int b, int k, int* idx, void* stream);
 
 /* ---- grid subsampling: libs/cpp_wrappers/cpp_subsampling (compile_op.sh builds it with the other ops), the KPConv voxel-grid
- * subsampler.  dis-pu_amd/grid_subsampling.py, csrc/grid_subsample.hip; the yardstick is the sequential float32 numpy restatement in
+ * subsampler.  dis-pu_amd/grid_subsampling.py, csrc/grid_subsample.hip, csrc/radix_sort.hip; the yardstick is the sequential float32 numpy restatement in
  * tests/grid_subsample_oracle.py, held to outputs recorded from the reference's own function, reproduced bit for bit ------------------- */
 /* Stable LSD radix sort of n (key u64, payload u32) pairs by the low `bits` bits of the key (0 <= bits <= 64; the higher bits must be
  * equal in all keys, or the order is the one of the low bits only), 8 bits per pass, ceil(bits / 8) passes; bits = 0 copies.  Equal

@@ -1,4 +1,4 @@
-"""GPU test of the device-wide stable radix sort alone (dispu_radix_sort_pairs, csrc/grid_subsample.hip) against
+"""GPU test of the device-wide stable radix sort alone (dispu_radix_sort_pairs, csrc/radix_sort.hip) against
 np.argsort(kind="stable"): keys and payload exact.  Sizes around the tile and the one-workgroup scan, every pass count the bits give
 (0 extra bits in a pass, a pass of one bit, all eight passes), and key sets where stability decides every position."""
 import numpy as np

@@ -203,11 +203,15 @@ def test_loop_restore_advances_an_epoch_counting_fetcher(tmp_path):
 
 
 def test_sampler_limits_agree_between_header_and_kernel():
-    """DISPU_SAMPLER_MAX_ROUNDS / DISPU_SAMPLER_MAX_G are written in the public header and in the kernel source."""
+    """DISPU_SAMPLER_MAX_ROUNDS / DISPU_SAMPLER_MAX_G are written in the public header only: the kernel source uses them under these
+    names and holds no value of its own (it compiles against the header through csrc/common.h)."""
     pat = re.compile(r"^#define (DISPU_SAMPLER_MAX_\w+) (\d+)", re.M)
     hdr = dict(pat.findall(open(os.path.join(ROOT, "include", "dispu_hip.h")).read()))
-    src = dict(pat.findall(open(os.path.join(ROOT, "dis-pu_amd", "csrc", "batch_sampler.hip")).read()))
-    assert hdr == src and set(hdr) == {"DISPU_SAMPLER_MAX_ROUNDS", "DISPU_SAMPLER_MAX_G"}
+    src = open(os.path.join(ROOT, "dis-pu_amd", "csrc", "batch_sampler.hip")).read()
+    common = open(os.path.join(ROOT, "dis-pu_amd", "csrc", "common.h")).read()
+    assert set(hdr) == {"DISPU_SAMPLER_MAX_ROUNDS", "DISPU_SAMPLER_MAX_G"} and all(int(v) > 0 for v in hdr.values())
+    assert not pat.findall(src) and not pat.findall(common) and 'include/dispu_hip.h"' in common
+    assert all(re.search(r"\b%s\b" % name, src) for name in hdr)
 
 
 def test_loop_step_function_choice(tmp_path):

@@ -31,7 +31,7 @@
 
 namespace dispu {
 
-__device__ __forceinline__ uint32_t fpsb_tiekey(int k) {      // same key as sampling.hip:fps_tiekey
+__device__ __forceinline__ uint32_t fpsb_tiekey(int k) {      // same key as csrc/fps_keys.h:fps_tiekey
     return 0xFFFFFFFFu - ((((uint32_t)k & 511u) << 22) | ((uint32_t)k >> 9));
 }
 __device__ __forceinline__ int fpsb_key_to_index(uint32_t tk) {

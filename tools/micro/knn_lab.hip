@@ -3,7 +3,6 @@
 #include "../../dis-pu_amd/csrc/knn_wave.hip"
 #include <cstdio>
 #include <vector>
-namespace dispu { int knn_xyz_wave_dispatch(int, int, int, int, const float*, const float*, int*, float*, int, hipStream_t); int knn_feat_wave_dispatch(int, int, int, int, int, int, int, const float*, const float*, float*, int*, hipStream_t); }
 int main() {
     const int b = 32, n = 256, c = 48, k = 17;
     std::vector<float> hf((size_t)b * n * c);
