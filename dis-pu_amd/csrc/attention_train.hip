@@ -26,7 +26,7 @@ namespace dispu {
 typedef float fa_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int FT_D = 64, FT_T = 32, FT_P = FT_D + 1;          // tile rows, padded pitch (conflict-free column reads)
-constexpr float FT_LOG2E = 1.4426950408889634f;
+constexpr float FT_LOG2E = 1.4426950408889634f, FT_LN2 = 0.6931471805599453f;
 
 __device__ __forceinline__ int ft_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }   // accumulator register -> tile row
 
@@ -70,15 +70,19 @@ struct FtLoader {
             pb[it] = *reinterpret_cast<const float4*>(B + (size_t)row * ldb + c4 * 4);
         }
     }
-    // stage layout: slot-major, per slot [A tile | B tile | EXTRA floats]
-    template <int SLOT_STRIDE>
-    __device__ __forceinline__ void store(float* st, int tid) const {
+    // stage layout: slot-major, per slot [A tile | B tile | EXTRA floats].  SCALE_A: the A tile is stored times `amul`.
+    template <int SLOT_STRIDE, bool SCALE_A = false>
+    __device__ __forceinline__ void store(float* st, int tid, float amul = 1.0f) const {
 #pragma unroll
         for (int it = 0; it < F; ++it) {
             const int e = tid + it * 256, row = e >> 4, c4 = e & 15;
             float* base = st + (row >> 5) * SLOT_STRIDE;
             float* a = base + (row & 31) * FT_P + c4 * 4;
-            a[0] = pa[it].x; a[1] = pa[it].y; a[2] = pa[it].z; a[3] = pa[it].w;
+            if constexpr (SCALE_A) {
+                a[0] = pa[it].x * amul; a[1] = pa[it].y * amul; a[2] = pa[it].z * amul; a[3] = pa[it].w * amul;
+            } else {
+                a[0] = pa[it].x; a[1] = pa[it].y; a[2] = pa[it].z; a[3] = pa[it].w;
+            }
             if constexpr (PADB) {
                 float* b = base + FT_T * FT_P + (row & 31) * FT_P + c4 * 4;
                 b[0] = pb[it].x; b[1] = pb[it].y; b[2] = pb[it].z; b[3] = pb[it].w;
@@ -370,6 +374,12 @@ __global__ __launch_bounds__(512) void fa_train_bwd_dq_kernel(int m, int nk, con
 // A workgroup owns keys (columns) and streams the cloud's Q|dO tiles (+ lse2, D of the tile's 32 queries):
 //   S[q][k] = Q.K^T (log2 domain), dP[q][k] = dO.V^T, P = 2^(S - lse2[q]), dS = P o (dP - D[q]),
 //   dV^T[d][k] += dO^T[d][q] P[q][k],   dK^T[d][k] += Q^T[d][q] dS[q][k].
+// S must be the FORWARD's S, because lse2 was formed from that one: the products are (Q[q][d] * scale2) * K[k][d] in the same d order
+// as there (Q scaled, K raw), not Q[q][d] * (K[k][d] * scale2).  The two differ by eps32 |S| in absolute terms, which P = 2^(S - lse2)
+// turns into a relative error of every probability of a row that the row's lse2 does not share: with max |S| = 280 dK and dV were up
+// to 5 times further from float64 than dQ (tests/test_attention_train_gpu.py, test_ill_conditioned_inputs).  So the LOADER waves store
+// the Q tile times scale2 (nothing is added to the MFMA waves' loop), and dK^T, accumulated over that tile, leaves the kernel times
+// scale / scale2 = ln 2.
 template <bool SPLIT>
 __global__ __launch_bounds__(512) void fa_train_bwd_dkv_kernel(int m, int nk, const float* __restrict__ Q, long ldq,
                                                                const float* __restrict__ K, long ldk, const float* __restrict__ V,
@@ -390,6 +400,7 @@ __global__ __launch_bounds__(512) void fa_train_bwd_dkv_kernel(int m, int nk, co
     const int ntile = m / FT_T, nstage = (ntile + TS - 1) / TS;
     const int li = lane & 31, kh = lane >> 5;
     const size_t krow = (size_t)cloud * nk + kblk * FtShape<SPLIT>::COLS + (SPLIT ? 0 : (wave & 3) * 32) + li;
+    const float scale2 = scale * FT_LOG2E;
     fa_f32x16 kacc[2], vacc[2];
 
     if (wave >= 4) {
@@ -406,14 +417,14 @@ __global__ __launch_bounds__(512) void fa_train_bwd_dkv_kernel(int m, int nk, co
         auto store_stat = [&](float* st) { if (sslot < TS) st[sslot * SLOT + Ld::TILE + sj] = st_l; };
         ld.load(qb, ldq, gb, lddo, 0, m, tid);
         load_stat(0);
-        ld.template store<SLOT>(lds, tid);
+        ld.template store<SLOT, true>(lds, tid, scale2);
         store_stat(lds);
         if (nstage > 1) { ld.load(qb, ldq, gb, lddo, TS * FT_T, m, tid); load_stat(TS * FT_T); }
         __syncthreads();
         for (int t = 0; t < nstage; ++t) {
             if (t + 1 < nstage) {
                 float* st = lds + ((t + 1) & 1) * STAGE;
-                ld.template store<SLOT>(st, tid);
+                ld.template store<SLOT, true>(st, tid, scale2);
                 store_stat(st);
                 if (t + 2 < nstage) { ld.load(qb, ldq, gb, lddo, (t + 2) * TS * FT_T, m, tid); load_stat((t + 2) * TS * FT_T); }
             }
@@ -422,14 +433,13 @@ __global__ __launch_bounds__(512) void fa_train_bwd_dkv_kernel(int m, int nk, co
     } else {
         const float* __restrict__ kp = K + krow * ldk;
         const float* __restrict__ vp = V + krow * ldv;
-        const float scale2 = scale * FT_LOG2E;
         float kf[32], vf[32];
 #pragma unroll
         for (int s4 = 0; s4 < 16; ++s4) {
             const float4 a = *reinterpret_cast<const float4*>(kp + s4 * 4);
             const float4 b = *reinterpret_cast<const float4*>(vp + s4 * 4);
-            kf[2 * s4] = (kh ? a.y : a.x) * scale2;
-            kf[2 * s4 + 1] = (kh ? a.w : a.z) * scale2;
+            kf[2 * s4] = kh ? a.y : a.x;
+            kf[2 * s4 + 1] = kh ? a.w : a.z;
             vf[2 * s4] = kh ? b.y : b.x;
             vf[2 * s4 + 1] = kh ? b.w : b.z;
         }
@@ -488,13 +498,13 @@ __global__ __launch_bounds__(512) void fa_train_bwd_dkv_kernel(int m, int nk, co
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float4 a, b;
-                a.x = kacc[c][4 * g + 0] * scale; a.y = kacc[c][4 * g + 1] * scale; a.z = kacc[c][4 * g + 2] * scale; a.w = kacc[c][4 * g + 3] * scale;
+                a.x = kacc[c][4 * g + 0] * FT_LN2; a.y = kacc[c][4 * g + 1] * FT_LN2; a.z = kacc[c][4 * g + 2] * FT_LN2; a.w = kacc[c][4 * g + 3] * FT_LN2;
                 b.x = vacc[c][4 * g + 0]; b.y = vacc[c][4 * g + 1]; b.z = vacc[c][4 * g + 2]; b.w = vacc[c][4 * g + 3];
                 *reinterpret_cast<float4*>(dkp + c * 32 + 8 * g + 4 * kh) = a;
                 *reinterpret_cast<float4*>(dvp + c * 32 + 8 * g + 4 * kh) = b;
             }
     } else {
-        ft_split_reduce_store(lds, kacc, wave, lane, scale, nullptr, dkp);
+        ft_split_reduce_store(lds, kacc, wave, lane, FT_LN2, nullptr, dkp);
         ft_split_reduce_store(lds, vacc, wave, lane, 1.0f, nullptr, dvp);
     }
 }
