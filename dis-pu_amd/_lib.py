@@ -41,6 +41,13 @@ SIGNATURES = {
     "dispu_fps_cells_wanted": (_i, [_i, _i]),
     "dispu_pca_normals_scratch_bytes": (_sz, [_i, _vp, _i]),
     "dispu_pca_normals_segments": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_knn_mean_dist_scratch_bytes": (_sz, [_i, _vp, _i]),
+    "dispu_knn_mean_dist_segments": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_radius_count_scratch_bytes": (_sz, [_i, _vp]),
+    "dispu_radius_count_segments": (_i, [_i, _vp, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_outlier_threshold_segments": (_i, [_i, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "dispu_compact_scratch_bytes": (_sz, [_i, _vp]),
+    "dispu_compact_segments": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_fps_segments_auto_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_fps_segments_auto": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "dispu_prob_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

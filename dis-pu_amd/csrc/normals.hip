@@ -6,7 +6,7 @@
 //
 //   pre-pass   morton_cells.hip (fps_cells_prepass):: segment boxes and non-finite flags, Morton keys with the segment id on top,
 //              one stable dispu_radix_sort_pairs, cells of 64 consecutive sorted positions with their boxes
-//   search     one wave per cell, one query per lane; every lane keeps its k best keys (d2 bits << 32 | local index) sorted in
+//   search     (knn_cells.h, knn_cells_search.h) one wave per cell, one query per lane; every lane keeps its k best keys (d2 bits << 32 | local index) sorted in
 //              registers.  The wave visits its own cell, then the cells at growing Morton offset (c - 1, c + 1, c - 2, ...) until it
 //              has seen k' points (every lane sees every point of a visited cell, so all lanes then hold k' candidates), then walks
 //              the segment's box table, 64 boxes per step (one per lane), and visits a cell only if its lower bound does not exceed
@@ -27,34 +27,9 @@
 //
 // No [n, k] tensor reaches memory unless idx_out is asked for.  Every value is written with ordinary stores; no atomics of its own;
 // ordering between the pre-pass and the search by kernel boundaries only; identical bytes from run to run.
-#include "morton_cells.h"
+#include "knn_cells.h"
 
 namespace dispu {
-
-constexpr int kNrmThreads = 256, kNrmWaves = kNrmThreads / kWave, kNrmCell = 64;
-constexpr uint64_t kNrmNone = ~0ull;
-static_assert(kNrmCell == kFpcMinCell && kNrmCell == kWave, "kCellsFixed64: one query per lane, the cell table indexed as the pre-pass wrote it");
-
-template <int KMAX>
-struct NrmBest {
-    uint64_t b[KMAX];
-    uint64_t thr;                                                     // b[k - 1]: the lane's current k-th key
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j) b[j] = kNrmNone;
-        thr = kNrmNone;
-    }
-    __device__ __forceinline__ void push(uint64_t key, int k) {
-        if (key < thr) {
-#pragma unroll
-            for (int j = KMAX - 1; j > 0; --j) b[j] = key < b[j - 1] ? b[j - 1] : (key < b[j] ? key : b[j]);
-            b[0] = key < b[0] ? key : b[0];
-#pragma unroll
-            for (int j = 0; j < KMAX; ++j)
-                if (j == k - 1) thr = b[j];
-        }
-    }
-};
 
 // one Jacobi rotation that zeroes a_pq of a symmetric 3x3 matrix; r is the third index: arp, arq its other two off-diagonals
 __device__ __forceinline__ void nrm_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
@@ -97,57 +72,8 @@ __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* _
     const bool valid = lane < qcnt;
     const float4 q = sp[cb * kNrmCell + (valid ? lane : 0)];                    // idle lanes repeat query 0 and store nothing
     const int kp = min(k, n);
-    const float4 qlo4 = *reinterpret_cast<const float4*>(gt + (size_t)cb * 8);
-    const float4 qhi4 = *reinterpret_cast<const float4*>(gt + (size_t)cb * 8 + 4);
-    const float qlx = qlo4.x, qly = qlo4.y, qlz = qlo4.z, qhx = qlo4.w, qhy = qhi4.x, qhz = qhi4.y;
 
-    NrmBest<KMAX> best;
-    best.init();
-    auto visit = [&](int j) {                                                   // j wave-uniform: all 64 queries against cell j
-        const int cnt = min(kNrmCell, n - j * kNrmCell);
-        const float4 p = sp[j * kNrmCell + min(lane, cnt - 1)];
-        for (int i = 0; i < cnt; ++i) {
-            const float px = __shfl(p.x, i, kWave), py = __shfl(p.y, i, kWave), pz = __shfl(p.z, i, kWave);
-            const uint32_t pi = (uint32_t)__shfl(__float_as_int(p.w), i, kWave);
-            const float d = sqdist3<false>(px - q.x, py - q.y, pz - q.z);
-            best.push(((uint64_t)__float_as_uint(d) << 32) | pi, k);
-        }
-    };
-    visit(cb);
-    int seen = qcnt, vlo = cb, vhi = cb;
-    for (int d = 1; seen < kp; ++d) {                                           // kp <= n: ends at the latest with every cell visited
-        if (cb - d >= 0) { visit(cb - d); seen += kNrmCell; vlo = cb - d; }     // only the last cell of a segment is short, and it
-        if (cb + d < K) { visit(cb + d); seen += min(kNrmCell, n - (cb + d) * kNrmCell); vhi = cb + d; }   // is never at cb - d
-    }
-    uint32_t wk = (uint32_t)(wave_max_u64(best.thr) >> 32);                     // bits of the wave's largest k-th distance
-    for (int j0 = 0; j0 < K; j0 += kWave) {
-        const int j = j0 + lane;
-        uint32_t lbb = 0xFFFFFFFFu;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        const bool open = j < K && (j < vlo || j > vhi);
-        if (open) {
-            a = *reinterpret_cast<const float4*>(gt + (size_t)j * 8);
-            b = *reinterpret_cast<const float4*>(gt + (size_t)j * 8 + 4);
-            const float ex = fmaxf(fmaxf(a.x - qhx, qlx - a.w), 0.f);
-            const float ey = fmaxf(fmaxf(a.y - qhy, qly - b.x), 0.f);
-            const float ez = fmaxf(fmaxf(a.z - qhz, qlz - b.y), 0.f);
-            lbb = __float_as_uint(sqdist3<false>(ex, ey, ez));
-        }
-        unsigned long long reach = __ballot(open && lbb <= wk);
-        while (reach) {
-            const int bl = (int)__builtin_ctzll(reach);
-            reach &= reach - 1;
-            const uint32_t lb1 = (uint32_t)__shfl((int)lbb, bl, kWave);
-            if (lb1 > wk) continue;                                             // the k-th distance shrank since the ballot
-            // the same bound per lane, the query point as its own box: a cell no lane can gain from is not visited either
-            const float ex = fmaxf(fmaxf(__shfl(a.x, bl, kWave) - q.x, q.x - __shfl(a.w, bl, kWave)), 0.f);
-            const float ey = fmaxf(fmaxf(__shfl(a.y, bl, kWave) - q.y, q.y - __shfl(b.x, bl, kWave)), 0.f);
-            const float ez = fmaxf(fmaxf(__shfl(a.z, bl, kWave) - q.z, q.z - __shfl(b.y, bl, kWave)), 0.f);
-            if (!__any(__float_as_uint(sqdist3<false>(ex, ey, ez)) <= (uint32_t)(best.thr >> 32))) continue;
-            visit(j0 + bl);
-            wk = (uint32_t)(wave_max_u64(best.thr) >> 32);
-        }
-    }
+#include "knn_cells_search.h"  // the search, as text: defines `best`
     if (!valid) return;
 
     const int qi = __float_as_int(q.w);

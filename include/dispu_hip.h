@@ -58,7 +58,8 @@ extern "C" {
  * Still 5 with the evaluator's mesh metrics (dispu_point_to_mesh, dispu_disk_*, dispu_row_mean_std) and its geodesic disks
  * (dispu_geodesic_*), the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments) and the
  * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32), and the large-cloud sampling (dispu_fps_cells*,
- * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*): additions only. */
+ * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*), and the outlier filters (dispu_knn_mean_dist_*,
+ * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -991,6 +992,44 @@ size_t dispu_pca_normals_scratch_bytes(int C, const int* off_host, int k);
 int dispu_pca_normals_segments(int C, const int* off, const int* off_host, int k, const float* cloud, int orient_mode, const float* orient,
                                float* normal, float* variation, int* idx_out, int* status, void* scratch, size_t scratch_bytes,
                                void* stream);
+
+/* ---- outlier removal for whole clouds, csrc/outliers.hip, dis-pu_amd/outliers.py: the statistical and the radius filter.  The reference
+ * has no counterpart.  Batches as for dispu_pca_normals_segments: cloud [sum n_c, 3] packs C <= 65535 clouds of 1 <= n_c <= 2^24 points,
+ * off [C+1] on the device, off_host the same on the host; d2 = ((dx*dx + dy*dy) + dz*dz) in fp32 (DISPU_ARITH_PLAIN); neighbourhoods
+ * never cross segments.  status [C] (device): 0, or 1 for a segment that holds a NaN or an infinite coordinate, for which nothing else
+ * is written.  Every scratch is 16-byte aligned and at least its *_scratch_bytes (0 for illegal arguments); the library never
+ * allocates; a refusal (hipErrorInvalidValue) touches no output.  Ordinary stores, no float atomics, identical bytes from run to run.
+ * The yardstick is tests/outliers_oracle.py.  Additions only: dispu_version() stays 5. ------------------------------------------------- */
+/* The mean distance of every point to its k nearest other points, 1 <= k <= 31.  For point i of a segment of n points take the
+ * k' = min(k + 1, n) smallest keys (d2, local index), the point itself included (the rule of dispu_pca_normals_segments at k + 1);
+ * s = sum_j sqrt((double)d2_j), added in ascending rank in double;  mean_dist [sum n_c] = (float)(s / max(k' - 1, 1)).  The point's own
+ * entry adds 0; where k + 1 duplicates of lower index push it out every term is 0 anyway.  Equal d2 give equal terms: no dependence on
+ * tie order.  n = 1 gives 0.  sqrt and / are IEEE double: the value can be reproduced bit for bit.  The search is the cell-pruned exact
+ * k-NN of the normals (csrc/knn_cells.h); no [n, k] tensor reaches memory. */
+size_t dispu_knn_mean_dist_scratch_bytes(int C, const int* off_host, int k);
+int dispu_knn_mean_dist_segments(int C, const int* off, const int* off_host, int k, const float* cloud, float* mean_dist, int* status,
+                                 void* scratch, size_t scratch_bytes, void* stream);
+/* count [sum n_c] = min(cap, #{ j != i in the segment : d2_ij <= r2 }), r2 = radius * radius rounded once in fp32, the boundary
+ * inclusive; radius finite and > 0, cap >= 1 (INT_MAX: exact counts).  Duplicates of a point count as its neighbours.  One wave per
+ * Morton cell; a cell is skipped when its box-to-box (or, for every lane, point-to-box) lower bound exceeds r2, and the walk ends once
+ * every query of the wave has reached cap. */
+size_t dispu_radius_count_scratch_bytes(int C, const int* off_host);
+int dispu_radius_count_segments(int C, const int* off, const int* off_host, float radius, int cap, const float* cloud, int* count,
+                                int* status, void* scratch, size_t scratch_bytes, void* stream);
+/* stats [C, 3] doubles = (mu, sigma, mu + ratio * sigma) of the stored fp32 mean_dist values of each segment, in double:
+ * mu = sum d / n,  sigma = sqrt(sum (d - mu)^2 / max(n - 1, 1)), two passes, in a summation order that depends on n alone.
+ * status [C]: as dispu_knn_mean_dist_segments wrote it; a flagged segment is skipped (its stats row is not written).  ratio finite. */
+int dispu_outlier_threshold_segments(int C, const int* off, const int* off_host, const float* mean_dist, const int* status, double ratio,
+                                     double* stats, void* stream);
+/* Stable compaction.  The keep flag of point i of segment c (global row g) by rule:  0: ((const int*)src)[g] != 0;  1:
+ * (double)((const float*)src)[g] <= stats[c][2] (src = mean_dist);  2: ((const int*)src)[g] >= min_neighbors (src = count).  status
+ * (or NULL): a segment with status[c] != 0 keeps nothing.  out_points [kept, 3] (or NULL) the kept points in input order, out_index
+ * [kept] int32 their local indices, ascending per segment, new_off [C+1] the offsets of the kept segments (new_off[C] = kept; read it
+ * back to know how many rows were written; outputs must hold sum n_c rows).  stats is read by rule 1 only, min_neighbors by rule 2. */
+size_t dispu_compact_scratch_bytes(int C, const int* off_host);
+int dispu_compact_segments(int C, const int* off, const int* off_host, const float* cloud, int rule, const void* src, const double* stats,
+                           int min_neighbors, const int* status, float* out_points, int* out_index, int* new_off, void* scratch,
+                           size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

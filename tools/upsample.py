@@ -16,7 +16,13 @@ scan does not have.  The output then has final_ratio times the SUBSAMPLED count.
 nearest neighbours in the output cloud (dis-pu_amd/normals.py; the reference has no counterpart).  --orient picks the sign: none (the
 largest component positive), centroid (outwards), viewpoint (towards --viewpoint X Y Z) or input (in agreement with the normal of the
 nearest input point: every input file then needs six columns; with --grid_size the input normals are averaged per cube and
-renormalised, and a cube whose normals cancel orients nothing)."""
+renormalised, and a cube whose normals cancel orients nothing).
+
+--clean_input / --clean_output statistical|radius (both off by default) drop stray points on the GPU (dis-pu_amd/outliers.py; the
+reference has no counterpart): statistical removes the points whose mean distance to their --outliers_k nearest neighbours exceeds the
+cloud's mean + --outliers_std standard deviations of it, radius those with fewer than --outliers_min other points within
+--outliers_radius.  Input cleaning runs first of all (before --grid_size; with --orient input the input normals follow the kept
+points): one stray point shrinks its whole normalised patch.  Output cleaning runs on the upsampled cloud, before --normals."""
 import argparse
 import glob
 import math
@@ -108,7 +114,23 @@ def parse_args(argv=None):
                     help="sign of the normals: none (largest component positive), centroid (outwards), viewpoint (towards --viewpoint), "
                          "input (as the nearest input point's normal; the inputs need six columns)")
     ap.add_argument("--viewpoint", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None, help="the viewpoint of --orient viewpoint")
+    ap.add_argument("--clean_input", choices=("none", "statistical", "radius"), default="none",
+                    help="drop outliers from every input cloud first of all (before --grid_size)")
+    ap.add_argument("--clean_output", choices=("none", "statistical", "radius"), default="none",
+                    help="drop outliers from every upsampled cloud (before --normals)")
+    ap.add_argument("--outliers_k", type=int, default=16, help="statistical: neighbours per point, 1 .. 31")
+    ap.add_argument("--outliers_std", type=float, default=2.0, help="statistical: keep up to mean + this many standard deviations")
+    ap.add_argument("--outliers_radius", type=positive_float, default=None, help="radius: the search radius (needed by `radius`)")
+    ap.add_argument("--outliers_min", type=int, default=2, help="radius: keep points with at least this many others within the radius")
     a = ap.parse_args(argv)
+    if "radius" in (a.clean_input, a.clean_output) and a.outliers_radius is None:
+        ap.error("--clean_input / --clean_output radius need --outliers_radius R")
+    if not 1 <= a.outliers_k <= 31:
+        ap.error("--outliers_k must be in 1 .. 31, got %d" % a.outliers_k)
+    if not math.isfinite(a.outliers_std):
+        ap.error("--outliers_std must be finite")
+    if a.outliers_min < 1:
+        ap.error("--outliers_min must be >= 1, got %d" % a.outliers_min)
     if a.normals == "none" and (a.orient != "none" or a.viewpoint is not None):
         ap.error("--orient and --viewpoint need --normals pca")
     if not 4 <= a.normals_k <= 32:
@@ -118,6 +140,22 @@ def parse_args(argv=None):
     if a.viewpoint is not None and not all(math.isfinite(v) for v in a.viewpoint):
         ap.error("--viewpoint must be finite")
     return a
+
+
+def remove_outliers(kind, arrays, a, dev):
+    """the --clean_* step on a list of numpy clouds, in groups of at most --max-points -> (kept clouds, kept indices), numpy"""
+    import torch
+    from dispu_amd import outliers
+    kept, index = [], []
+    for group in group_by_budget([c.shape[0] for c in arrays], a.max_points):
+        d = [torch.from_numpy(np.ascontiguousarray(arrays[i], np.float32)).to(dev) for i in group]
+        if kind == "statistical":
+            pts, idx = outliers.remove_statistical_outliers(d, k=a.outliers_k, std_ratio=a.outliers_std, return_index=True)
+        else:
+            pts, idx = outliers.remove_radius_outliers(d, a.outliers_radius, min_neighbors=a.outliers_min, return_index=True)
+        kept += [t.cpu().numpy() for t in pts]
+        index += [t.cpu().numpy() for t in idx]
+    return kept, index
 
 
 def main(argv=None):
@@ -156,6 +194,20 @@ def main(argv=None):
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
     raw = [c.shape[0] for c in clouds]
+    removed_in, removed_out = [0] * len(clouds), [0] * len(clouds)
+    if a.clean_input != "none":
+        try:
+            kept, index = remove_outliers(a.clean_input, clouds, a, dev)
+        except ValueError as e:
+            sys.exit("--clean_input: %s" % e)
+        for i, (k, ix) in enumerate(zip(kept, index)):
+            if k.shape[0] < a.patch_num_point:
+                sys.exit("%s: --clean_input %s leaves %d of %d points, fewer than --patch_num_point %d"
+                         % (paths[i], a.clean_input, k.shape[0], raw[i], a.patch_num_point))
+            removed_in[i] = raw[i] - k.shape[0]
+            clouds[i] = k
+            if in_normals is not None:
+                in_normals[i] = np.ascontiguousarray(in_normals[i][ix])
     if a.grid_size is not None:
         from dispu_amd import grid_subsampling
         for i, c in enumerate(clouds):
@@ -175,6 +227,14 @@ def main(argv=None):
             preds = upsample_ragged(gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
         except ValueError as e:
             sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
+        if a.clean_output != "none":
+            try:
+                cleaned, _ = remove_outliers(a.clean_output, preds, a, dev)
+            except ValueError as e:
+                sys.exit("%s: --clean_output: %s" % (", ".join(paths[i] for i in group), e))
+            for i, before, after in zip(group, preds, cleaned):
+                removed_out[i] = before.shape[0] - after.shape[0]
+            preds = cleaned
         if a.normals == "pca":
             from dispu_amd.normals import estimate_normals
             dpred = [torch.from_numpy(p).to(dev) for p in preds]
@@ -196,10 +256,14 @@ def main(argv=None):
                 save_xyz_normals(out, pred, normals[j])
             else:
                 save_xyz(out, pred)
+            gone = ""
+            if a.clean_input != "none" or a.clean_output != "none":
+                gone = ", outliers removed: %d input, %d output" % (removed_in[i], removed_out[i])
             if a.grid_size is None:
-                print("%s: %d -> %d points, %s" % (paths[i], clouds[i].shape[0], pred.shape[0], out))
+                print("%s: %d -> %d points, %s%s" % (paths[i], clouds[i].shape[0], pred.shape[0], out, gone))
             else:
-                print("%s: %d -> %d (grid %g) -> %d points, %s" % (paths[i], raw[i], clouds[i].shape[0], a.grid_size, pred.shape[0], out))
+                print("%s: %d -> %d (grid %g) -> %d points, %s%s" % (paths[i], raw[i], clouds[i].shape[0], a.grid_size, pred.shape[0], out,
+                                                                   gone))
     print("%d clouds in %.2f s" % (len(paths), time.time() - t0))
 
 
