@@ -14,6 +14,7 @@ What is different from the reference's execution (not its results):
     16x fewer FLOPs; reassociated -> tolerance-checked).
 Everything up to and including `coarse` is bit-identical to oracle/generator.py (fp32 MFMA == fmaf chain).
 """
+import collections
 import contextlib
 import math
 
@@ -39,6 +40,14 @@ def gen_grid(up_ratio):
     gy = np.linspace(-0.2, 0.2, num_y, dtype=np.float32)
     x, y = np.meshgrid(gx, gy)
     return np.stack([x, y], -1).reshape(-1, 2).astype(np.float32)
+
+
+def _off(t, o):
+    """the address of t's element o (t is float32 or int32: 4-byte elements)"""
+    return _lib.C.c_void_p(t.data_ptr() + 4 * o)
+
+
+Path = collections.namedtuple("Path", "stem heads in_chain attention local after add3 nl_late")
 
 
 class _Opts(object):
@@ -107,21 +116,16 @@ class Generator(object):
         self.split_bf16 = False
         self._planes = {}
         self._aft_bt = None          # dtype = "bf16": after_conv's weight as bf16 [256][2048] (dispu_bf16_pack), made by load_params
-        self.split_up3 = True        # the N = 320 product as 256 + 64 columns (each launch reads up128 once)
         # non-local cell on a second stream next to the grouping / skip / local cell (round 4: on by default, -1 % since the head chains
         # form their own inputs -- the branch now joins right before the fine chain; rounds 1 - 3 measured it +1 %)
         self.branches = True           # False: everything on the launch stream (profiling passes: every kernel alone on the device)
         self._aux = None
-        self.fused_residual = True
         self.fused_heads = True      # one launch per head chain
         self.keep_intermediates = False   # fused heads: also write the aggregation output (tests compare it)
         # round 4: the head chains form their own input tiles (csrc/mlp_chain.hip XMODE): duplicate_up's rows from the per-source-point
         # product (no dup_grid launch, no [B*4N, 256] tensor) and relu(after_conv) + skip + non-local in the fine chain's loader (the
         # residual reads leave the after_conv GEMM's epilogue).  False = the producer kernels of rounds 1 - 3 (bit-identical results; A/B tests)
         self.chain_inputs = True
-        # one launch per dense block (neighbour search + edge features + dense_conv, csrc/edge.hip KNN variant) for clouds of <= 256
-        # points; False = the dispu_knn_feat_strided -> dispu_edge_dense_conv pair (A/B tests; larger clouds always take the pair)
-        self.fused_stem = True
         # forward() computes into a reusable per-(B, N) workspace.  By default the two results are returned as fresh
         # tensors (like sess.run in the reference); return_views = True hands out the workspace buffers themselves
         # (no copies -- bench.py / hipGraph capture), which the NEXT call with the same (B, N) overwrites.
@@ -204,14 +208,12 @@ class Generator(object):
         self._ws[key] = ws
         return ws
 
-    def _pair_buffers(self, B, N):
-        """[B*M*16, .] pair tensors of the UNFUSED local cell (A/B testing only; the default path never allocates them)."""
-        key = ("pair", B, N)
-        if key not in self._ws:
-            rows = B * N * self.up_ratio * K_NEIGH
-            E = lambda c: torch.empty((rows, c), dtype=torch.float32, device=self.device)
-            self._ws[key] = (E(128), E(128), E(16))
-        return self._ws[key]
+    def _extra(self, store, key, shape, dtype=torch.float32):
+        """store[key], a buffer that only some paths need: allocated when such a path first runs (again if a launch needs a larger one)"""
+        t = store.get(key)
+        if t is None or t.numel() < math.prod(shape):
+            t = store[key] = torch.empty(shape, dtype=dtype, device=self.device)
+        return t
 
     # ------------------------------------------------------------------------------------------- launch ----
     def _call(self, name, fn, *args):
@@ -228,22 +230,19 @@ class Generator(object):
     def _linear(self, st, X, K, W, bias, act, Y, N, M=None, ldx=None, ldw=None, ldy=None, batch=1, sx=0, sw=0, sy=0,
                 transb=0, R1=None, R2=None, xoff=0, woff=0, yoff=0):
         """Y[:, yoff:yoff+N] = R2 + R1 + act(X[:, xoff:xoff+K] . W + bias) via dispu_linear (element offsets in floats)."""
-        L = _lib.lib()
         M = X.shape[0] if M is None else M
         ldx = X.stride(0) if ldx is None else ldx
         ldw = W.stride(0) if ldw is None else ldw
         ldy = Y.stride(0) if ldy is None else ldy
-        p = lambda t, off=0: _lib.C.c_void_p(t.data_ptr() + 4 * off) if t is not None else _lib.C.c_void_p(0)
+        x, w, b, y, r1, r2 = _off(X, xoff), _off(W, woff), _lib.ptr(bias), _off(Y, yoff), _lib.ptr(R1), _lib.ptr(R2)
+        ldr1 = R1.stride(0) if R1 is not None else 0
+        ldr2 = R2.stride(0) if R2 is not None else 0
         name = "linear"
         if self.profile is not None:     # "linear<BM, BN, 2, 2, BK, transb, edge, epi>[MxKxN]": the instantiation rocprofv3 reports
-            a = lambda t, off=0: (t.data_ptr() + 4 * off) if t is not None else None
-            plan = _lib.linear_plan(batch, M, K, N, a(X, xoff), ldx, sx, a(W, woff), ldw, sw, transb, a(bias), None, None, act, a(Y, yoff), ldy,
-                                    sy, a(R1), R1.stride(0) if R1 is not None else 0, 0, a(R2), R2.stride(0) if R2 is not None else 0, 0,
+            plan = _lib.linear_plan(batch, M, K, N, x, ldx, sx, w, ldw, sw, transb, b, None, None, act, y, ldy, sy, r1, ldr1, 0, r2, ldr2, 0,
                                     None, 0, 0)
             name = linear_profile_name(plan, batch, M, K, N)
-        self._call(name, L.dispu_linear, batch, M, K, N,
-                   p(X, xoff), ldx, sx, p(W, woff), ldw, sw, transb, p(bias), act, p(Y, yoff), ldy, sy, p(R1),
-                   R1.stride(0) if R1 is not None else 0, 0, p(R2), R2.stride(0) if R2 is not None else 0, 0, st)
+        self._call(name, _lib.lib().dispu_linear, batch, M, K, N, x, ldx, sx, w, ldw, sw, transb, b, act, y, ldy, sy, r1, ldr1, 0, r2, ldr2, 0, st)
 
     def __call__(self, inputs):
         return self.forward(inputs)
@@ -252,6 +251,36 @@ class Generator(object):
     def trainer(self):
         """the Trainer behind a Generator(is_training=True): loss_backward / backward / adam / train_step (train.py)."""
         return self._trainer
+
+    def path(self, B, N):
+        """What a forward over B patches of N points launches, decided once from the switches and the shape (M = 4N points per upsampled
+        patch, rm = B * M rows).  No device access, and nothing is kept: the switches may change between two calls.
+          stem       one launch per dense block (search + edge features + dense_conv, csrc/edge.hip KNN variant: even clouds of at most
+                     256 points), else the dispu_knn_feat_strided_ws -> dispu_edge_dense_conv pair
+          heads      one launch per head chain (whole 128-row tiles);  in_chain: the chains also form their own input tiles
+          attention  "project" | "flash" (on chip: M % 32 == 0) | "gemm" (GEMM -> softmax -> GEMM through a score buffer)
+          local      "bf16" | "fused" | "pair" (the four-kernel chain through [rm * 16, .] pair tensors)
+          after      after_conv: "bf16_stream" | "bf16s" | "x3" (split_bf16) | "plain" | "residual" (+ skip + nl in the GEMM's epilogue)
+          add3       (aft + skip) + nl by dispu_add3 into ws["sum"], which the fine head then reads instead of ws["aft"]
+          nl_late    the non-local branch joins in front of the fine chain (its loader is nl's first reader), not of after_conv"""
+        bf16 = self.dtype == "bf16"
+        if bf16 and (self.split_bf16 or not self.fused_local):
+            raise ValueError("Generator(dtype='bf16') stores F' as bf16 in the fused local cell: it excludes split_bf16 and fused_local = False")
+        M = N * self.up_ratio
+        tiles = B * M % 128 == 0
+        heads = bool(self.fused_heads and tiles)
+        in_chain = bool(heads and self.chain_inputs)
+        on_chip = self.fused_attention and M % 32 == 0
+        if bf16:
+            after = "bf16_stream" if tiles else "bf16s"
+        elif self.split_bf16 and tiles:
+            after = "x3"
+        else:
+            after = "plain" if in_chain else "residual"
+        return Path(stem=N <= 256 and N % 2 == 0, heads=heads, in_chain=in_chain,
+                    attention="project" if on_chip and self.fused_project else "flash" if on_chip else "gemm",
+                    local="bf16" if bf16 else "fused" if self.fused_local else "pair", after=after,
+                    add3=bf16 and not in_chain, nl_late=bool(self.branches and in_chain))
 
     def forward(self, inputs):
         if not self.P:
@@ -262,261 +291,231 @@ class Generator(object):
         if not (isinstance(inputs, torch.Tensor) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 3
                 and inputs.shape[2] == 3):
             raise ValueError("Generator expects a float32 [B,N,3] tensor on a ROCm device")
-        bf16 = self.dtype == "bf16"
-        if bf16 and (self.split_bf16 or not self.fused_local):
-            raise ValueError("Generator(dtype='bf16') stores F' as bf16 in the fused local cell: it excludes split_bf16 and fused_local = False")
         inputs = inputs.contiguous()
         B, N, _ = inputs.shape
         if N <= K_NEIGH:
             raise ValueError("Generator needs patches of at least %d points (the dense blocks take the k + 1 = %d nearest "
                              "neighbours of every point), got N = %d" % (K_NEIGH + 1, K_NEIGH + 1, N))
-        M = N * self.up_ratio
         chunk = max(1, self.MAX_POINTS // N)                    # patches per launch sequence
         if B > chunk:                                           # patches are independent: run the batch in chunks
             if self.return_views:
                 raise ValueError("return_views needs B <= %d at N = %d (one workspace)" % (chunk, N))
             outs = [self.forward(inputs[lo:lo + chunk]) for lo in range(0, B, chunk)]
             return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
-        rn, rm, k = B * N, B * M, K_NEIGH
+        path = self.path(B, N)
+        M = N * self.up_ratio
+        fine = self.fine_out
+        if fine is not None and not (isinstance(fine, torch.Tensor) and fine.device == inputs.device and fine.dtype == torch.float32
+                                     and tuple(fine.shape) == (B, M, 3) and fine.is_contiguous()):
+            raise ValueError("fine_out must be a contiguous float32 [%d, %d, 3] tensor on %s" % (B, M, inputs.device))
         ws = self._workspace(B, N)
-        L = _lib.lib()
+        coarse, fine = ws["coarse"], ws["fine"] if fine is None else fine
         st = _lib.stream_ptr(inputs.device)
-        ptr = _lib.ptr
-        off = lambda t, o: _lib.C.c_void_p(t.data_ptr() + 4 * o)
-        feat = ws["feat"]
-        fe = "generator/feature_extraction_coarse/"
+        self._features(ws, path, inputs, st)
+        self._coarse_head(ws, path, B, N, st)
+        ev_up3, ev_nl = self._non_local(ws, path, B, N, st)     # what its stream records once up3 / nl are written (None: it ran on st)
+        self._knn_skip(ws, B, M, st)
+        self._join(ev_up3)
+        self._local(ws, path, B, N, st)
+        self._join(None if path.nl_late else ev_nl)
+        self._after_conv(ws, path, B * M, st)
+        self._join(ev_nl if path.nl_late else None)             # nl is first read by the fine chain's loader
+        self._fine_head(ws, path, B * M, fine, st)
+        return (coarse, fine) if self.return_views else (coarse.clone(), fine.clone())
 
-        # ---- feature_extraction_GCN (ops.py:1437-1486): features accumulate right-to-left inside feat[:, 0:480]
+    def _join(self, event):
+        if event is not None:
+            torch.cuda.current_stream(self.device).wait_event(event)
+
+    def _chain(self, first, head):
+        """the eight weight / bias pointers of a head chain: the conv `first`, then fc_layer0 .. fc_layer2 of the regressor `head`"""
+        return [_lib.ptr(t) for scope in (first, head + "fc_layer0", head + "fc_layer1", head + "fc_layer2") for t in self._w(scope)]
+
+    def _features(self, ws, path, inputs, st):
+        """feature_extraction_GCN (ops.py:1437-1486): features accumulate right-to-left inside feat[:, 0:480]"""
+        L, ptr = _lib.lib(), _lib.ptr
+        B, N, _ = inputs.shape
+        rn, k1, feat = B * N, K_NEIGH + 1, ws["feat"]
+        fe = "generator/feature_extraction_coarse/"
         wl0, bl0 = self._w(fe + "layer0")
-        stem = self.fused_stem and N <= 256 and N % 2 == 0 and N > k
-        if not stem:       # (fused stem: the first block's launch evaluates layer0 while it stages its cloud)
-            self._call("layer0", L.dispu_linear_small_k, rn, 3, 24, ptr(inputs), 3, ptr(wl0), ptr(bl0), 0, off(feat, 456), 480, st)
+        if not path.stem:  # (stem: the first block's launch evaluates layer0 while it stages its cloud)
+            self._call("layer0", L.dispu_linear_small_k, rn, 3, 24, ptr(inputs), 3, ptr(wl0), ptr(bl0), 0, _off(feat, 456), 480, st)
         col = 456          # left edge of the features produced so far
-        prep_done = False  # the previous block's launch already ran this block's bottleneck conv (fused stem)
         for d in range(1, DENSE_BLOCKS + 1):
-            pbuf = ws["prep"] if d % 2 == 0 else ws["prep_b"]        # block d reads pbuf while its launch writes the other one
+            pbuf, nxt = (ws["prep"], ws["prep_b"]) if d % 2 == 0 else (ws["prep_b"], ws["prep"])   # block d reads pbuf while its launch writes nxt
             if d == 1:
                 F, ldf, foff, C = feat, 480, 456, 24
             else:
-                if not prep_done:
+                if not path.stem:                                    # (stem: the previous block's launch already ran this bottleneck conv)
                     w, b = self._w(fe + "layer%d_prep" % d)
                     self._linear(st, feat, 480 - col, w, b, 1, pbuf, 48, xoff=col)
                 F, ldf, foff, C = pbuf, 48, 0, 48
-            w0, b0 = self._w(fe + "layer%d/l0" % d)
-            w1, b1 = self._w(fe + "layer%d/l1" % d)
-            w2, b2 = self._w(fe + "layer%d/l2" % d)
+            convs = [ptr(t) for l in range(3) for t in self._w(fe + "layer%d/l%d" % (d, l))]
             width = 3 * GROWTH + C
             col -= width
-            if stem:
+            if path.stem:
                 # + the next block's bottleneck conv over [this block's outputs | the 480 - (col + width) older columns] for d < 4
-                nxt = ws["prep_b"] if d % 2 == 0 else ws["prep"]
-                wp, bp = self._w(fe + "layer%d_prep" % (d + 1)) if d < DENSE_BLOCKS else (None, None)
-                self._call("stem_block", L.dispu_stem_block, rn, N, C, off(F, foff), ldf, k + 1, 1, ptr(w0), ptr(b0), ptr(w1), ptr(b1), ptr(w2),
-                           ptr(b2), off(feat, col), 480, ptr(ws["kidx"]) if self.keep_intermediates else None,
-                           ptr(wp) if d < DENSE_BLOCKS else None, ptr(bp) if d < DENSE_BLOCKS else None, 480 - col - width,
-                           ptr(nxt) if d < DENSE_BLOCKS else None, 48, ptr(inputs) if d == 1 else None, ptr(wl0) if d == 1 else None,
-                           ptr(bl0) if d == 1 else None, off(feat, 456) if d == 1 else None, 480, st)
-                prep_done = d < DENSE_BLOCKS
+                last = d == DENSE_BLOCKS
+                wp, bp = (None, None) if last else self._w(fe + "layer%d_prep" % (d + 1))
+                layer0 = (ptr(inputs), ptr(wl0), ptr(bl0), _off(feat, 456)) if d == 1 else (None, None, None, None)
+                self._call("stem_block", L.dispu_stem_block, rn, N, C, _off(F, foff), ldf, k1, 1, *convs, _off(feat, col), 480,
+                           ptr(ws["kidx"]) if self.keep_intermediates else None, ptr(wp), ptr(bp), 480 - col - width,
+                           None if last else ptr(nxt), 48, *layer0, 480, st)
                 continue
-            prep_done = False
-            nbf = L.dispu_knn_feat_scratch_bytes(B, N, N, C, k + 1)   # > 0 for 512 < N <= 4096 (second pass of 16x): chunked search
-            if nbf and (ws.get("knnf_scratch") is None or ws["knnf_scratch"].numel() < nbf):
-                ws["knnf_scratch"] = torch.empty((nbf,), dtype=torch.uint8, device=self.device)
-            self._call("knn_feat", L.dispu_knn_feat_strided_ws, B, N, N, C, k + 1, off(F, foff), ldf, off(F, foff), ldf, None, ptr(ws["kidx"]),
-                       ptr(ws["knnf_scratch"]) if nbf else None, nbf, st)
-            self._call("edge_dense_conv", L.dispu_edge_dense_conv, rn, N, C, off(F, foff), ldf, ptr(ws["kidx"]), k + 1, 1, ptr(w0), ptr(b0), ptr(w1),
-                                        ptr(b1), ptr(w2), ptr(b2), off(feat, col), 480, st)
+            nbf = L.dispu_knn_feat_scratch_bytes(B, N, N, C, k1)      # > 0 for 512 < N <= 4096 (second pass of 16x): chunked search
+            scratch = ptr(self._extra(ws, "knnf_scratch", (nbf,), torch.uint8)) if nbf else None
+            self._call("knn_feat", L.dispu_knn_feat_strided_ws, B, N, N, C, k1, _off(F, foff), ldf, _off(F, foff), ldf, None, ptr(ws["kidx"]),
+                       scratch, nbf, st)
+            self._call("edge_dense_conv", L.dispu_edge_dense_conv, rn, N, C, _off(F, foff), ldf, ptr(ws["kidx"]), k1, 1, *convs,
+                       _off(feat, col), 480, st)
         assert col == 0
 
-        # ---- duplicate_up (ops.py:1152-1199) + coarse coordinate_regressor (:1089-1110)
+    def _coarse_head(self, ws, path, B, N, st):
+        """duplicate_up (ops.py:1152-1199) + coarse coordinate_regressor (:1089-1110); up128 (PointShuffle2's input) is written on the way"""
+        L, ptr = _lib.lib(), _lib.ptr
+        rm = B * N * self.up_ratio
         _, b1 = self._w("generator/upshuffle_0/conv1")
-        self._linear(st, feat, 480, self.w_up_feat, None, 0, ws["h256"], 256)
-        cs = "generator/coarse_coordinate_regressor/"
-        coarse = ws["coarse"]
-        heads = self.fused_heads and rm % 128 == 0
-        in_chain = heads and self.chain_inputs
-        fine = ws["fine"]
-        if self.fine_out is not None:
-            fine = self.fine_out
-            if not (isinstance(fine, torch.Tensor) and fine.device == inputs.device and fine.dtype == torch.float32
-                    and tuple(fine.shape) == (B, M, 3) and fine.is_contiguous()):
-                raise ValueError("fine_out must be a contiguous float32 [%d, %d, 3] tensor on %s" % (B, M, inputs.device))
-        if not in_chain:
-            self._call("dup_grid", L.dispu_dup_grid, B, N, 256, self.up_ratio, ptr(ws["h256"]), 256, ptr(self.w_up_grid), ptr(b1), ptr(self.grid),
-                       ptr(ws["up256"]), 256, st)
-        if in_chain:
-            w1, b1_ = self._w("generator/upshuffle_0/conv2")
-            w2, b2_ = self._w(cs + "fc_layer0")
-            w3, b3_ = self._w(cs + "fc_layer1")
-            w4, b4_ = self._w(cs + "fc_layer2")
+        conv2, cs = "generator/upshuffle_0/conv2", "generator/coarse_coordinate_regressor/"
+        self._linear(st, ws["feat"], 480, self.w_up_feat, None, 0, ws["h256"], 256)
+        if path.in_chain:          # duplicate_up's rows formed from the per-source-point product in the chain's loader
             self._call("mlp_chain[coarse]", L.dispu_mlp_chain_dup, B, N, self.up_ratio, 256, 128, 256, 64, ptr(ws["h256"]), 256, ptr(self.w_up_grid),
-                       ptr(b1), ptr(self.grid), ptr(w1), ptr(b1_), ptr(w2), ptr(b2_), ptr(w3), ptr(b3_), ptr(w4), ptr(b4_), ptr(ws["up128"]), 128,
-                       0, None, 0, ptr(coarse), 3, st)
-        elif heads:
-            # conv2 -> fc_layer0 -> fc_layer1 -> fc_layer2 in one launch; up128 (needed by PointShuffle2) is written on the way
-            w1, b1_ = self._w("generator/upshuffle_0/conv2")
-            w2, b2_ = self._w(cs + "fc_layer0")
-            w3, b3_ = self._w(cs + "fc_layer1")
-            w4, b4_ = self._w(cs + "fc_layer2")
-            self._call("mlp_chain[coarse]", L.dispu_mlp_chain, rm, 256, 128, 256, 64, ptr(ws["up256"]), 256, ptr(w1), ptr(b1_), ptr(w2), ptr(b2_),
-                       ptr(w3), ptr(b3_), ptr(w4), ptr(b4_), ptr(ws["up128"]), 128, 0, None, 0, ptr(coarse), 3, st)
+                       ptr(b1), ptr(self.grid), *self._chain(conv2, cs), ptr(ws["up128"]), 128, 0, None, 0, ptr(ws["coarse"]), 3, st)
+            return
+        self._call("dup_grid", L.dispu_dup_grid, B, N, 256, self.up_ratio, ptr(ws["h256"]), 256, ptr(self.w_up_grid), ptr(b1), ptr(self.grid),
+                   ptr(ws["up256"]), 256, st)
+        if path.heads:             # conv2 -> fc_layer0 -> fc_layer1 -> fc_layer2 in one launch
+            self._call("mlp_chain[coarse]", L.dispu_mlp_chain, rm, 256, 128, 256, 64, ptr(ws["up256"]), 256, *self._chain(conv2, cs),
+                       ptr(ws["up128"]), 128, 0, None, 0, ptr(ws["coarse"]), 3, st)
         else:
-            w, b = self._w("generator/upshuffle_0/conv2")
+            w, b = self._w(conv2)
             self._linear(st, ws["up256"], 256, w, b, 1, ws["up128"], 128)
             w, b = self._w(cs + "fc_layer0")
             self._linear(st, ws["up128"], 128, w, b, 1, ws["c256"], 256)
             w, b = self._w(cs + "fc_layer1")
             self._linear(st, ws["c256"], 256, w, b, 1, ws["c64"], 64)
             w, b = self._w(cs + "fc_layer2")
-            self._call("coarse", L.dispu_linear_small_n, rm, 64, 3, ptr(ws["c64"]), 64, ptr(w), ptr(b), 0, None, 0, ptr(coarse), 3, st)
+            self._call("coarse", L.dispu_linear_small_n, rm, 64, 3, ptr(ws["c64"]), 64, ptr(w), ptr(b), 0, None, 0, ptr(ws["coarse"]), 3, st)
 
-        # ---- PointShuffle2 (ops.py:1012-1087)
-        ps = "refine/PointShuffle/"
-        up128 = ws["up128"]
-        # The non-local cell reads up128 only.  With self.branches it runs on a second stream next to the grouping / skip / local
-        # cell (fork here; the local cell waits for up3 = conv0's feature part, after_conv for nl): the small launches of one side
-        # fill the CUs the other leaves idle.  Captured into the same hipGraph as two parallel branches.
-        br = self.branches
+    def _non_local(self, ws, path, B, N, st):
+        """PointNonLocalCell (ops.py:302-346) and conv0's feature part.  Both read up128 only: with self.branches they run on a second
+        stream next to the grouping / skip / local cell (the small launches of one side fill the CUs the other leaves idle; captured into
+        the same hipGraph as two parallel branches).  Returns the events recorded there once up3 and nl are written, else (None, None)."""
+        L, ptr = _lib.lib(), _lib.ptr
+        M, q, kv, sb = N * self.up_ratio, ws["q"], ws["kv"], st
+        br, aux, ev_up3, ev_nl = self.branches, None, None, None
         if br:
             if self._aux is None:
                 self._aux = (torch.cuda.Stream(device=self.device), torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event())
             aux, ev_fork, ev_up3, ev_nl = self._aux
             ev_fork.record(torch.cuda.current_stream(self.device))
             aux.wait_event(ev_fork)
+            sb = _lib.C.c_void_p(aux.cuda_stream)
         with (torch.cuda.stream(aux) if br else contextlib.nullcontext()):
-            sb = _lib.C.c_void_p(aux.cuda_stream) if br else st
-            # PointNonLocalCell (ops.py:302-346)
-            if self.split_up3:
-                # N = 320 as 256 + 64 columns: each launch reads up128 ONCE (128 x 256 / 128 x 64 tiles); one launch with 128 x 64
-                # tiles re-read it five times (128 MB of counter traffic against 59 MB algorithmic in round 1)
-                self._linear(sb, up128, 128, self.w_up3, self.b_up3, 0, ws["up3"], 256)
-                self._linear(sb, up128, 128, self.w_up3, self.b_up3[256:], 0, ws["up3"], 64, woff=256, yoff=256)
-            else:
-                self._linear(sb, up128, 128, self.w_up3, self.b_up3, 0, ws["up3"], 320)  # K|V, Q and conv0's feature part at once
+            # K|V, Q and conv0's feature part, N = 320 as 256 + 64 columns: each launch reads up128 once (128 x 256 / 128 x 64 tiles)
+            self._linear(sb, ws["up128"], 128, self.w_up3, self.b_up3, 0, ws["up3"], 256)
+            self._linear(sb, ws["up128"], 128, self.w_up3, self.b_up3[256:], 0, ws["up3"], 64, woff=256, yoff=256)
             if br:
                 ev_up3.record(aux)
-            w_bp, b_bp = self._w(ps + "PointShuffle/conv_back_project")
-            projected = False
-            if self.fused_attention and M % 32 == 0 and self.fused_project:
+            w_bp, b_bp = self._w("refine/PointShuffle/PointShuffle/conv_back_project")
+            if path.attention == "project":
                 # softmax(Q.K^T / 8).V.W_bp on chip: neither the [B, M, M] logits nor the [B*M, 64] attention output reach HBM
-                self._call("attention_project", L.dispu_attention_project, B, M, M, 64, ptr(ws["q"]), 320, ptr(ws["kv"]), 320,
-                           off(ws["kv"], 64), 320, 0.125, ptr(w_bp), ptr(b_bp), 256, ptr(ws["nl"]), 256, sb)
-                projected = True
-            elif self.fused_attention and M % 32 == 0:
+                self._call("attention_project", L.dispu_attention_project, B, M, M, 64, ptr(q), 320, ptr(kv), 320, _off(kv, 64), 320, 0.125,
+                           ptr(w_bp), ptr(b_bp), 256, ptr(ws["nl"]), 256, sb)
+            elif path.attention == "flash":
                 # softmax(Q.K^T / 8).V on chip (flash style): the [B, M, M] logits never exist in HBM
-                self._call("attention", L.dispu_attention, B, M, M, 64, ptr(ws["q"]), 320, ptr(ws["kv"]), 320, off(ws["kv"], 64), 320,
-                           0.125, ptr(ws["att"]), 64, sb)
+                self._call("attention", L.dispu_attention, B, M, M, 64, ptr(q), 320, ptr(kv), 320, _off(kv, 64), 320, 0.125, ptr(ws["att"]), 64, sb)
             else:
-                key = ("scores", B, N)
-                if key not in self._ws:
-                    self._ws[key] = torch.empty((B, M, M), dtype=torch.float32, device=self.device)
-                s = self._ws[key]
-                self._linear(sb, ws["q"], 64, ws["kv"], None, 0, s, M, M=M, ldx=320, ldw=320, ldy=M, batch=B, sx=M * 320,
-                             sw=M * 320, sy=M * M, transb=1)
-                self._call("softmax", L.dispu_softmax_rows, rm, M, 0.125, ptr(s), M, sb)
-                self._linear(sb, s, M, ws["kv"], None, 0, ws["att"], 64, M=M, ldx=M, ldw=320, ldy=64, batch=B, sx=M * M,
-                             sw=M * 320, sy=M * 64, woff=64)
-            if not projected:
+                s = self._extra(self._ws, ("scores", B, N), (B, M, M))
+                self._linear(sb, q, 64, kv, None, 0, s, M, M=M, ldx=320, ldw=320, ldy=M, batch=B, sx=M * 320, sw=M * 320, sy=M * M, transb=1)
+                self._call("softmax", L.dispu_softmax_rows, B * M, M, 0.125, ptr(s), M, sb)
+                self._linear(sb, s, M, kv, None, 0, ws["att"], 64, M=M, ldx=M, ldw=320, ldy=64, batch=B, sx=M * M, sw=M * 320, sy=M * 64, woff=64)
+            if path.attention != "project":
                 self._linear(sb, ws["att"], 64, w_bp, b_bp, 1, ws["nl"], 256)
             if br:
                 ev_nl.record(aux)
+        return ev_up3, ev_nl
+
+    def _knn_skip(self, ws, B, M, st):
+        """PointShuffle2 (ops.py:1012-1087): the k nearest coarse points of every coarse point, and the skip connection"""
+        L, ptr = _lib.lib(), _lib.ptr
+        rm, k, coarse = B * M, K_NEIGH, ws["coarse"]
         nb = L.dispu_knn_xyz_scratch_bytes(B, M, M, k)             # > 0 for M > 1024 (second pass of 16x upsampling): chunked search
-        if nb and ws.get("knn_scratch") is None:
-            ws["knn_scratch"] = torch.empty((nb,), dtype=torch.uint8, device=self.device)
-        self._call("knn_xyz", L.dispu_knn_xyz_ws, B, M, M, k, ptr(coarse), ptr(coarse), ptr(ws["psidx"]), None,
-                   ptr(ws["knn_scratch"]) if nb else None, nb, _lib.ARITH_PLAIN, st)
-        # skip connection
-        self._call("skip_max", L.dispu_ps_skip_max, rm, M, k, 128, ptr(ws["psidx"]), ptr(coarse), ptr(up128), 128, ptr(ws["skipin"]), 144, st)
-        _, b = self._w(ps + "skip")
+        scratch = ptr(self._extra(ws, "knn_scratch", (nb,), torch.uint8)) if nb else None
+        self._call("knn_xyz", L.dispu_knn_xyz_ws, B, M, M, k, ptr(coarse), ptr(coarse), ptr(ws["psidx"]), None, scratch, nb, _lib.ARITH_PLAIN, st)
+        self._call("skip_max", L.dispu_ps_skip_max, rm, M, k, 128, ptr(ws["psidx"]), ptr(coarse), ptr(ws["up128"]), 128, ptr(ws["skipin"]), 144, st)
+        _, b = self._w("refine/PointShuffle/skip")
         # K padded 134 -> 144 with zero columns / zero weight rows (exact) so the GEMM takes its predicate-free path
         self._linear(st, ws["skipin"], 144, self.w_skip_pad, b, 1, ws["skip"], 256)
-        # local cell: conv0 per source point, conv1 per pair
-        if br:
-            torch.cuda.current_stream(self.device).wait_event(ev_up3)
+
+    def _local(self, ws, path, B, N, st):
+        """PointShuffle2's local cell: conv0 per source point, conv1 per pair -> F' [rm, 2048]"""
+        L, ptr = _lib.lib(), _lib.ptr
+        M, k, ps = N * self.up_ratio, K_NEIGH, "refine/PointShuffle/"
+        rm, coarse, psidx, gm, am = B * M, ws["coarse"], ws["psidx"], ws["gm"], ws["am"]
         w0, b0 = self._w(ps + "conv0")
-        self._call("ps_prep", L.dispu_ps_prep, rm, 128, ptr(coarse), ptr(w0), ptr(b0), ptr(ws["gm"]), 320, ptr(ws["am"]), 128, st)
+        self._call("ps_prep", L.dispu_ps_prep, rm, 128, ptr(coarse), ptr(w0), ptr(b0), ptr(gm), 320, ptr(am), 128, st)
         w1, b1 = self._w(ps + "conv1")
-        ww, bw = self._w(ps + "weight_net/wconv0")
-        if bf16:
-            # the fused kernel below with F' leaving as bf16 [rm, 2048] (RNE at the store)
-            self._call("ps_local_bf16", L.dispu_ps_local_bf16, rm, M, k, 128, ptr(ws["psidx"]), ptr(coarse), ptr(ws["gm"]), 320, ptr(ws["am"]),
-                       ptr(w1), ptr(b1), ptr(ww), ptr(bw), ptr(self.bn_scale), ptr(self.bn_shift), ptr(ws["fp"]), st)
-        elif self.fused_local:
-            # gather_sub_relu + conv1 + weight_net + feature x weight in one kernel: only F' [rm, 2048] touches HBM
-            self._call("ps_local", L.dispu_ps_local, rm, M, k, 128, ptr(ws["psidx"]), ptr(coarse), ptr(ws["gm"]), 320, ptr(ws["am"]),
-                       ptr(w1), ptr(b1), ptr(ww), ptr(bw), ptr(self.bn_scale), ptr(self.bn_shift), ptr(ws["fp"]), st)
-        else:
-            x1, x2, wv = self._pair_buffers(B, N)
-            self._call("gather_sub_relu", L.dispu_ps_gather_sub_relu, rm, M, k, 128, ptr(ws["psidx"]), ptr(ws["gm"]), 320,
-                       ptr(ws["am"]), 128, ptr(x1), 128, st)
-            self._linear(st, x1, 128, w1, b1, 1, x2, 128)
-            self._call("weight_net", L.dispu_ps_weight_net, rm, M, k, 16, ptr(ws["psidx"]), ptr(coarse), ptr(ww), ptr(bw),
-                       ptr(self.bn_scale), ptr(self.bn_shift), ptr(wv), st)
-            self._call("point_matmul", L.dispu_ps_point_matmul, rm, k, 128, 16, ptr(x2), 128, ptr(wv), ptr(ws["fp"]), 2048, st)
-        w, b = self._w(ps + "after_conv")
-        nl_late = br and heads and self.chain_inputs      # nl is first read by the fine chain's loader
-        if br and not nl_late:
-            torch.cuda.current_stream(self.device).wait_event(ev_nl)
-        if bf16:
-            # relu(bf16(F') . bf16(W) + b), fp32 accumulation: the streaming kernel on the pre-packed weight where its shape rules hold,
-            # else the generic bf16 kernel on the fp32 weight (rounded on load: the same products in the same order, bit-identical)
-            if rm % 128 == 0:
-                self._call("linear_bf16_stream[%dx2048x256]" % rm, L.dispu_linear_bf16_stream, rm, 2048, 256, ptr(ws["fp"]), 2048, 1,
-                           ptr(self._aft_bt), 2048, ptr(b), 1, ptr(ws["aft"]), 256, 0, 1, 0, st)
-            else:
-                self._call("linear_bf16s[%dx2048x256]" % rm, L.dispu_linear_bf16s, 1, rm, 2048, 256, ptr(ws["fp"]), 2048, 0, ptr(w), 256, 0, 0,
-                           ptr(b), 1, ptr(ws["aft"]), 256, 0, None, 0, 0, 1, st)
-            if not (heads and self.chain_inputs):
-                # (relu(.) + skip) + nl, the association of the fp32 paths, into a buffer of its own: aft stays the product
-                if "sum" not in ws:
-                    ws["sum"] = torch.empty((rm, 256), dtype=torch.float32, device=self.device)
-                self._call("add3", L.dispu_add3, rm * 256, ptr(ws["aft"]), ptr(ws["skip"]), ptr(ws["nl"]), ptr(ws["sum"]), st)
-        elif self.split_bf16 and rm % 128 == 0:
+        wnet = [ptr(t) for t in self._w(ps + "weight_net/wconv0") + (self.bn_scale, self.bn_shift)]
+        if path.local != "pair":
+            # gather_sub_relu + conv1 + weight_net + feature x weight in one kernel: only F' touches HBM ("bf16": as bf16, RNE at the store)
+            name, fn = ("ps_local_bf16", L.dispu_ps_local_bf16) if path.local == "bf16" else ("ps_local", L.dispu_ps_local)
+            self._call(name, fn, rm, M, k, 128, ptr(psidx), ptr(coarse), ptr(gm), 320, ptr(am), ptr(w1), ptr(b1), *wnet, ptr(ws["fp"]), st)
+            return
+        rows = rm * k              # the [rm * 16, .] pair tensors (A/B tests only: the default path never allocates them)
+        flat = self._extra(self._ws, ("pair", B, N), (rows * 272,))
+        x1, x2, wv = (t.view(rows, -1) for t in flat.split([rows * 128, rows * 128, rows * 16]))
+        self._call("gather_sub_relu", L.dispu_ps_gather_sub_relu, rm, M, k, 128, ptr(psidx), ptr(gm), 320, ptr(am), 128, ptr(x1), 128, st)
+        self._linear(st, x1, 128, w1, b1, 1, x2, 128)
+        self._call("weight_net", L.dispu_ps_weight_net, rm, M, k, 16, ptr(psidx), ptr(coarse), *wnet, ptr(wv), st)
+        self._call("point_matmul", L.dispu_ps_point_matmul, rm, k, 128, 16, ptr(x2), 128, ptr(wv), ptr(ws["fp"]), 2048, st)
+
+    def _after_conv(self, ws, path, rm, st):
+        """aft = relu(F' . W + b), and where the fine chain does not form its own input, (aft + skip) + nl in that association"""
+        L, ptr = _lib.lib(), _lib.ptr
+        w, b = self._w("refine/PointShuffle/after_conv")
+        fp, aft = ws["fp"], ws["aft"]
+        if path.after == "bf16_stream":
+            # bf16(F') . bf16(W), fp32 accumulation: the streaming kernel on the pre-packed weight where its shape rules hold ...
+            self._call("linear_bf16_stream[%dx2048x256]" % rm, L.dispu_linear_bf16_stream, rm, 2048, 256, ptr(fp), 2048, 1,
+                       ptr(self._aft_bt), 2048, ptr(b), 1, ptr(aft), 256, 0, 1, 0, st)
+        elif path.after == "bf16s":
+            # ... else the generic bf16 kernel on the fp32 weight (rounded on load: the same products in the same order, bit-identical)
+            self._call("linear_bf16s[%dx2048x256]" % rm, L.dispu_linear_bf16s, 1, rm, 2048, 256, ptr(fp), 2048, 0, ptr(w), 256, 0, 0,
+                       ptr(b), 1, ptr(aft), 256, 0, None, 0, 0, 1, st)
+        elif path.after == "x3":
             pl = self._planes.get("after_conv")
             if pl is None:
                 pl = torch.empty((3 * 2048 * 256,), dtype=torch.bfloat16, device=self.device)
                 _lib.check(L.dispu_bf16x3_split_weights(2048, 256, ptr(w), 256, ptr(pl), st), "dispu_bf16x3_split_weights")
                 self._planes["after_conv"] = pl
-            in_chain = heads and self.chain_inputs            # + skip + nl then happen in the fine chain's loader
-            self._call("linear_bf16x3[%dx2048x256]" % rm, L.dispu_linear_bf16x3, rm, 2048, 256, ptr(ws["fp"]), 2048, ptr(pl), ptr(b), 1,
-                       ptr(ws["aft"]), 256, None if in_chain else ptr(ws["skip"]), 256, None if in_chain else ptr(ws["nl"]), 256, st)
-        elif heads and self.chain_inputs:
-            self._linear(st, ws["fp"], 2048, w, b, 1, ws["aft"], 256)          # relu(after_conv) alone; + skip + nl in the fine chain's loader
-        elif self.fused_residual:
-            self._linear(st, ws["fp"], 2048, w, b, 1, ws["aft"], 256, R1=ws["skip"], R2=ws["nl"])
-        else:
-            # same arithmetic order ((act(.) + skip) + nl) in a separate streaming kernel
-            self._linear(st, ws["fp"], 2048, w, b, 1, ws["aft"], 256)
-            self._call("add3", L.dispu_add3, rm * 256, ptr(ws["aft"]), ptr(ws["skip"]), ptr(ws["nl"]), ptr(ws["aft"]), st)
-        fs = "refine/fine_coordinate_regressor/"
-        if nl_late:
-            torch.cuda.current_stream(self.device).wait_event(ev_nl)
-        if heads and self.chain_inputs:
-            w1, b1_ = self._w(ps + "aggregation")
-            w2, b2_ = self._w(fs + "fc_layer0")
-            w3, b3_ = self._w(fs + "fc_layer1")
-            w4, b4_ = self._w(fs + "fc_layer2")
-            self._call("mlp_chain[fine]", L.dispu_mlp_chain_sum3, rm, 256, 256, 256, 64, ptr(ws["aft"]), ptr(ws["skip"]), ptr(ws["nl"]), 256,
-                       ptr(w1), ptr(b1_), ptr(w2), ptr(b2_), ptr(w3), ptr(b3_), ptr(w4), ptr(b4_),
-                       ptr(ws["agg"]) if self.keep_intermediates else None, 256, 1, ptr(coarse), 3, ptr(fine), 3, st)
-        elif heads:
-            w1, b1_ = self._w(ps + "aggregation")
-            w2, b2_ = self._w(fs + "fc_layer0")
-            w3, b3_ = self._w(fs + "fc_layer1")
-            w4, b4_ = self._w(fs + "fc_layer2")
-            self._call("mlp_chain[fine]", L.dispu_mlp_chain, rm, 256, 256, 256, 64, ptr(ws["sum"] if bf16 else ws["aft"]), 256, ptr(w1), ptr(b1_), ptr(w2), ptr(b2_),
-                       ptr(w3), ptr(b3_), ptr(w4), ptr(b4_), ptr(ws["agg"]) if self.keep_intermediates else None, 256, 1, ptr(coarse), 3,
-                       ptr(fine), 3, st)
-        else:
-            w, b = self._w(ps + "aggregation")
-            self._linear(st, ws["sum"] if bf16 else ws["aft"], 256, w, b, 1, ws["agg"], 256)
-            # ---- fine coordinate_regressor (is_off) + residual (generator.py:76-81)
-            w, b = self._w(fs + "fc_layer0")
-            self._linear(st, ws["agg"], 256, w, b, 1, ws["f256"], 256)
-            w, b = self._w(fs + "fc_layer1")
-            self._linear(st, ws["f256"], 256, w, b, 1, ws["f64"], 64)
-            w, b = self._w(fs + "fc_layer2")
-            self._call("fine", L.dispu_linear_small_n, rm, 64, 3, ptr(ws["f64"]), 64, ptr(w), ptr(b), 1, ptr(coarse), 3, ptr(fine), 3, st)
-        if self.return_views:
-            return coarse, fine
-        return coarse.clone(), fine.clone()
+            skip, nl = (None, None) if path.in_chain else (ptr(ws["skip"]), ptr(ws["nl"]))
+            self._call("linear_bf16x3[%dx2048x256]" % rm, L.dispu_linear_bf16x3, rm, 2048, 256, ptr(fp), 2048, ptr(pl), ptr(b), 1,
+                       ptr(aft), 256, skip, 256, nl, 256, st)
+        else:                      # + skip + nl in the GEMM's epilogue ("residual") or in the fine chain's loader ("plain")
+            r1, r2 = (None, None) if path.after == "plain" else (ws["skip"], ws["nl"])
+            self._linear(st, fp, 2048, w, b, 1, aft, 256, R1=r1, R2=r2)
+        if path.add3:              # into a buffer of its own: aft stays the product
+            total = self._extra(ws, "sum", (rm, 256))
+            self._call("add3", L.dispu_add3, rm * 256, ptr(aft), ptr(ws["skip"]), ptr(ws["nl"]), ptr(total), st)
+
+    def _fine_head(self, ws, path, rm, fine, st):
+        """aggregation + fine coordinate_regressor (is_off) + residual on coarse (generator.py:76-81)"""
+        L, ptr = _lib.lib(), _lib.ptr
+        agg, fs = "refine/PointShuffle/aggregation", "refine/fine_coordinate_regressor/"
+        x, coarse = ws["sum"] if path.add3 else ws["aft"], ws["coarse"]
+        if path.heads:
+            tail = (ptr(ws["agg"]) if self.keep_intermediates else None, 256, 1, ptr(coarse), 3, ptr(fine), 3, st)
+            if path.in_chain:      # relu(after_conv) + skip + nl in the chain's loader
+                self._call("mlp_chain[fine]", L.dispu_mlp_chain_sum3, rm, 256, 256, 256, 64, ptr(x), ptr(ws["skip"]), ptr(ws["nl"]), 256,
+                           *self._chain(agg, fs), *tail)
+            else:
+                self._call("mlp_chain[fine]", L.dispu_mlp_chain, rm, 256, 256, 256, 64, ptr(x), 256, *self._chain(agg, fs), *tail)
+            return
+        w, b = self._w(agg)
+        self._linear(st, x, 256, w, b, 1, ws["agg"], 256)
+        w, b = self._w(fs + "fc_layer0")
+        self._linear(st, ws["agg"], 256, w, b, 1, ws["f256"], 256)
+        w, b = self._w(fs + "fc_layer1")
+        self._linear(st, ws["f256"], 256, w, b, 1, ws["f64"], 64)
+        w, b = self._w(fs + "fc_layer2")
+        self._call("fine", L.dispu_linear_small_n, rm, 64, 3, ptr(ws["f64"]), 64, ptr(w), ptr(b), 1, ptr(coarse), 3, ptr(fine), 3, st)

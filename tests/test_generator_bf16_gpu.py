@@ -235,6 +235,10 @@ def test_profile_labels(dev):
         names = [p[0] for p in gen.profile]
         assert "ps_local_bf16" in names and label in names and "ps_local" not in names
         assert ("add3" in names) == (B * n * 4 % 128 != 0)
+        from test_generator_gpu import _labels_follow_path
+        path = gen.path(B, n)
+        assert (path.local, path.after, path.add3) == ("bf16", {256: "bf16_stream", 250: "bf16s"}[n], n == 250)
+        _labels_follow_path(names, path)
 
 
 def test_b32_hipgraph_replay_equals_eager(b32, dev):

@@ -518,6 +518,38 @@ def test_one_instance_serves_several_patch_sizes(dev):
     assert ("scores", 2, 250) in gen._ws and ("scores", 2, 256) not in gen._ws
 
 
+def _labels_follow_path(names, path):
+    """the profile labels of one forward against Generator.path's decision for it"""
+    blocks = (names.count("stem_block"), names.count("knn_feat"), names.count("edge_dense_conv"))
+    assert blocks == ((4, 0, 0) if path.stem else (0, 4, 4)), blocks
+    assert ("dup_grid" in names) == (not path.in_chain)
+    attention = {"project": "attention_project", "flash": "attention", "gemm": "softmax"}
+    assert [n for n in names if n in attention.values()] == [attention[path.attention]]
+    assert ("mlp_chain[fine]" in names) == path.heads
+    assert ("add3" in names) == path.add3
+
+
+@pytest.mark.parametrize("chain_inputs", [True, False])
+@pytest.mark.parametrize("B,n", [(1, 256), (2, 250), (1, 288)])      # the smallest shapes on either side of every shape rule
+def test_launches_follow_path(dev, B, n, chain_inputs):
+    """What Generator.path decides is what one forward launches: the dense blocks' form, dup_grid, the attention kernel, the fine
+    head chain, and no add3 in f32 mode."""
+    from dispu_amd import synth
+    from dispu_amd.generator import Generator
+    gen = Generator(params=OG.init_params(seed=9), device=dev)
+    gen.chain_inputs = chain_inputs
+    gen.profile = []
+    gen(torch.from_numpy(synth.patches(B, n, seed=23)).to(dev))
+    torch.cuda.synchronize()
+    names = [p[0] for p in gen.profile]
+    path = gen.path(B, n)
+    assert (path.stem, path.heads, path.attention) == {(1, 256): (True, True, "project"), (2, 250): (True, False, "gemm"),
+                                                       (1, 288): (False, True, "project")}[(B, n)]
+    assert path.in_chain == (path.heads and chain_inputs)
+    _labels_follow_path(names, path)
+    assert "ps_local" in names and "add3" not in names
+
+
 @pytest.mark.parametrize("n", [16, 1])
 def test_patches_of_at_most_k_points_are_refused(dev, n):
     """The dense blocks take k + 1 = 17 neighbours per point: smaller patches are refused before anything is allocated or launched."""
