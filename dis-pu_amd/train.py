@@ -15,11 +15,13 @@ Execution differences from the reference (not results):
   * duplicate_up's 482-wide conv is evaluated per source point (as in inference) and differentiated in that form.
 Training-mode forward values equal the inference path's except for BatchNorm (batch statistics here).
 """
+import collections
 import contextlib
 import ctypes
 import math
 import os
 from collections import OrderedDict
+from functools import partial
 
 import numpy as np
 import torch
@@ -32,6 +34,24 @@ from .schedule import StepSchedule
 BN_DECAY = 0.95      # DisPU/generator.py:39 bn_decay
 BN = "refine/PointShuffle/weight_net/wconv0/bn/"
 BN_CH = 16            # its channels (the weight net's 3 -> 16 conv, Common/ops.py:181-191)
+FE, UP, CS = "generator/feature_extraction_coarse/", "generator/upshuffle_0/", "generator/coarse_coordinate_regressor/"      # scopes
+PS, FS = "refine/PointShuffle/", "refine/fine_coordinate_regressor/"
+
+Path = collections.namedtuple("Path", "stem after_split defer_side attention local_bwd split_skip")      # see Trainer.path
+
+
+def _dense_blocks():
+    """(d, C, col, in_col, width) of every dense block: C input channels, its 3 * GROWTH + C output columns feat[:, col:in_col] --
+    the features accumulate right-to-left inside feat[:, 0:480], so block d reads feat[:, in_col:480] (through its prep conv)"""
+    rows, col = [], 456
+    for d, C in enumerate([24] + [48] * (DENSE_BLOCKS - 1), 1):
+        rows.append((d, C, col - 3 * GROWTH - C, col, 3 * GROWTH + C))
+        col = rows[-1][2]
+    assert col == 0
+    return tuple(rows)
+
+
+BLOCKS = _dense_blocks()
 
 
 class TrainOpts(_Opts):
@@ -68,6 +88,19 @@ def _p(t, off=0):
     return _lib.C.c_void_p(t.data_ptr() + t.element_size() * off) if t is not None else _lib.C.c_void_p(0)
 
 
+class _Step(object):
+    """What forward() leaves for loss_backward(), _recompute_pair_tensors() and backward(): the shape, the input, the workspace, the path
+    (Trainer.path) and the two flags of the current forward."""
+    __slots__ = ("B", "N", "M", "rn", "rm", "x", "ws", "path", "coarse", "dcoarse", "dfine", "fresh", "stash_ready")
+
+    def __init__(self, B, N, up, x, ws, path):
+        self.B, self.N, self.M, self.rn, self.rm = B, N, N * up, B * N, B * N * up
+        self.x, self.ws, self.path = x, ws, path
+        self.coarse, self.dcoarse, self.dfine = (ws[k].view(self.rm, 3) for k in ("coarse", "dcoarse", "dfine"))    # as row matrices
+        self.fresh = True                 # until the first backward(): the atomics accumulators (dprep, dup128s) are zero-filled for exactly ONE
+        self.stash_ready = False          # the pair tensors of the local cell's backward are in place (_recompute_pair_tensors)
+
+
 def _sched_attr(name):                                   # a Trainer switch that lives on its StepSchedule
     return property(lambda self: getattr(self.sched, name), lambda self, v: setattr(self.sched, name, v))
 
@@ -99,8 +132,7 @@ class Trainer(object):
         self._ws = {}
         self._scratch = {}                    # per stream: scratch of the split reductions / column sums
         self._bn_scratch = None
-        self._stash_ready = False
-        self._fresh = False                   # True between forward() and the first backward() on it (see backward)
+        self._step = None                     # the current forward's record (_Step)
         self._tapes = {}
         self._packs = {}                      # bf16 images of the weights for the streaming kernel (_stream)
         self._ar = None                       # parallel.BucketedAllReduce over flat_g (data parallel only, see _reducer)
@@ -441,6 +473,54 @@ class Trainer(object):
         self._tn(1, M, K, N, X, xoff, X.stride(0), 0, dY, dyoff, dY.stride(0), 0, dW, woff, dW.stride(0), 0, 1, dbias=db, side=side, after=ev,
                  wgrad=True)
 
+    # ------------------------------------------------------------------------------------------------- path ----
+    def path(self, B, N):
+        """What a step over B patches of N points launches, decided once from the switches and the shape (M = 4N points per upsampled
+        patch, rm = B * M rows).  No device access, and nothing is kept here: forward() keeps its result for the other passes.
+          stem          one launch per dense block (dispu_stem_block's shape rule: even clouds of at most 256 points), else layer0,
+                        then k-NN + edge_dense_conv + a prep product per block
+          after_split   K-chunks of after_conv's split contraction (4 or 8, see _fwd_after_conv); 0: one product through _lin
+          defer_side    side work is submitted behind the chain's kernels (up to 16 patches of 256, see StepSchedule)
+          attention     "flash" (csrc/attention_train.hip) | "gemm" (through a materialised [B, M, M] probability tensor)
+          local_bwd     "pair" (five launches through the pair tensors) | "fused" (one recomputing launch, fp32 pair-tensor storage only)
+          split_skip    the skip branch's d(up128) in a buffer of its own, summed in the coarse chain (next to overlap_dw's branches)
+        Shape limits of the fused training kernels are refused here instead of as a bare hipErrorInvalidValue mid-step:
+        dispu_mlp_chain_stash / dispu_mlp_chain_grad tile 64 rows; dispu_knn_invert sorts one cloud's graph in LDS."""
+        M = N * self.up_ratio
+        rm = B * M
+        req(N > K_NEIGH, "a patch needs more than %d points (k-NN graph of the dense blocks), got N = %d" % (K_NEIGH, N))
+        req(rm % 64 == 0, "the fused head chains work on 64-row tiles: B * %d * N must be a multiple of 64, got B = %d, N = %d "
+                          "(pad the batch)" % (self.up_ratio, B, N))
+        req(M <= 4096, "the local cell's backward inverts a cloud's k-NN graph in LDS: %d * N <= 4096, got N = %d" % (self.up_ratio, N))
+        req(M % 32 == 0, "the non-local cell's attention kernels work on 32-point tiles: %d * N must be a multiple of 32, got N = %d"
+                         % (self.up_ratio, N))
+        # after_conv's split: fp32 products only (its input hp is stored as fp32 in both dtypes; bf16 products have their own tiles)
+        split = rm <= 16384 and rm % 128 == 0 and not self._use_bf16(1, rm, 2048, 256)
+        # the fused local backward needs fp32 pair tensors (dtype "f32"); its other two conditions always hold here: whole 8-point groups
+        # (rm * 16 % 64 == 0 follows from rm % 64 == 0) and conv1's W^T copy (128 x 128 passes load_params' rule)
+        return Path(stem=N <= 256 and N % 2 == 0, after_split=(4 if rm >= 8192 else 8) if split else 0, defer_side=rm <= 16 * 1024,
+                    attention="flash" if self.flash_attn else "gemm", local_bwd="fused" if self.fused_local_bwd and not self.bf16 else "pair",
+                    split_skip=bool(self.overlap_dw))
+
+    def _w(self, scope, D=None):
+        """weights and biases of a scope as pointers: the parameters', or those of D = self.G / self.PT"""
+        D = self.P if D is None else D
+        return _p(D[scope + "/weights"]), _p(D[scope + "/biases"])
+
+    def _dense_w(self, d, D=None):
+        """the six weight / bias pointers of dense block d (l0, l1, l2)"""
+        sc = FE + "layer%d/l" % d
+        return self._w(sc + "0", D) + self._w(sc + "1", D) + self._w(sc + "2", D)
+
+    def _chain(self, first, head):
+        """the eight weight / bias pointers of a head chain: the conv `first`, then fc_layer0 .. fc_layer2 of the regressor `head`"""
+        return self._w(first) + self._w(head + "fc_layer0") + self._w(head + "fc_layer1") + self._w(head + "fc_layer2")
+
+    def _chain_T(self, first, head):
+        """what a head chain's backward multiplies by, last layer first: fc_layer2's weights, then the W^T copies of fc_layer1, fc_layer0, `first`"""
+        P, PT = self.P, self.PT
+        return _p(P[head + "fc_layer2/weights"]), _p(PT[head + "fc_layer1/weights"]), _p(PT[head + "fc_layer0/weights"]), _p(PT[first + "/weights"])
+
     # ----------------------------------------------------------------------------------------------- forward ----
     def forward(self, inputs):
         """training-mode forward (BatchNorm batch statistics, moving averages updated); keeps every activation."""
@@ -449,172 +529,158 @@ class Trainer(object):
             raise ValueError("Trainer expects a float32 [B,N,3] tensor on a ROCm device")
         x = inputs.contiguous()
         B, N, _ = x.shape
-        M, k = N * self.up_ratio, K_NEIGH
-        rn, rm = B * N, B * M
-        # shape limits of the fused training kernels, refused here instead of as a bare hipErrorInvalidValue mid-step:
-        # dispu_mlp_chain_stash / dispu_mlp_chain_grad tile 64 rows; dispu_knn_invert sorts one cloud's graph in LDS
-        req(N > K_NEIGH, "a patch needs more than %d points (k-NN graph of the dense blocks), got N = %d" % (K_NEIGH, N))
-        req(rm % 64 == 0, "the fused head chains work on 64-row tiles: B * %d * N must be a multiple of 64, got B = %d, N = %d "
-                          "(pad the batch)" % (self.up_ratio, B, N))
-        req(M <= 4096, "the local cell's backward inverts a cloud's k-NN graph in LDS: %d * N <= 4096, got N = %d" % (self.up_ratio, N))
-        req(M % 32 == 0, "the non-local cell's attention kernels work on 32-point tiles: %d * N must be a multiple of 32, got N = %d"
-                         % (self.up_ratio, N))
-        ws = self._workspace(B, N)
-        L = _lib.tape_lib()
-        self.sched.st = _lib.stream_ptr(x.device)
-        self.defer_side = rm <= 16 * 1024                # see __init__
-        self._shape = (B, N)
-        self._x = x
-        P = self.P
-        feat = ws["feat"]
-        fe = "generator/feature_extraction_coarse/"
-        stem = N <= 256 and N % 2 == 0      # one launch per dense block (dispu_stem_block's shape rule)
-        if not stem:       # (fused stem: the first block's launch evaluates layer0 while it stages its cloud)
-            _lib.check(L.dispu_linear_small_k(rn, 3, 24, _p(x), 3, _p(P[fe + "layer0/weights"]), _p(P[fe + "layer0/biases"]), 0,
-                                              _p(feat, 456), 480, self.st), "layer0")
-        col = 456
-        self._blocks = []
-        prep_done = False                      # the previous block's launch already ran this block's bottleneck conv (fused stem)
-        for d in range(1, DENSE_BLOCKS + 1):
-            if d == 1:
-                F, foff, C = feat, 456, 24
-            else:
-                if not prep_done:
-                    self._lin(feat, col, 480 - col, fe + "layer%d_prep" % d, 1, ws["prep"][d], 0, 48)
-                F, foff, C = ws["prep"][d], 0, 48
-            ldf = F.stride(0)
-            kidx = ws["kidx"][d]
-            sc = fe + "layer%d" % d
-            width = 3 * GROWTH + C
-            in_col = col
-            col -= width
-            if stem:
-                # search + edge features + dense_conv in one launch (csrc/edge.hip, KNN variant); the neighbour table stays for the backward pass
-                _lib.check(L.dispu_stem_block(rn, N, C, _p(F, foff), ldf, k + 1, 1, _p(P[sc + "/l0/weights"]), _p(P[sc + "/l0/biases"]),
-                                              _p(P[sc + "/l1/weights"]), _p(P[sc + "/l1/biases"]), _p(P[sc + "/l2/weights"]),
-                                              _p(P[sc + "/l2/biases"]), _p(feat, col), 480, _p(kidx),
-                                              _p(P[fe + "layer%d_prep/weights" % (d + 1)]) if d < DENSE_BLOCKS else None,
-                                              _p(P[fe + "layer%d_prep/biases" % (d + 1)]) if d < DENSE_BLOCKS else None, 480 - in_col,
-                                              _p(ws["prep"][d + 1]) if d < DENSE_BLOCKS else None, 48, _p(x) if d == 1 else None,
-                                              _p(P[fe + "layer0/weights"]) if d == 1 else None, _p(P[fe + "layer0/biases"]) if d == 1 else None,
-                                              _p(feat, 456) if d == 1 else None, 480, self.st), "stem_block")
-            else:
-                _lib.check(L.dispu_knn_feat_strided(B, N, N, C, k + 1, _p(F, foff), ldf, _p(F, foff), ldf, None, _p(kidx), self.st), "knn_feat")
-                # the inference kernel (csrc/edge.hip): edge features, three chained convs and the max in one launch; nothing is kept
-                # for the backward pass, which recomputes the block on chip (csrc/edge_bwd.hip)
-                _lib.check(L.dispu_edge_dense_conv(rn, N, C, _p(F, foff), ldf, _p(kidx), k + 1, 1, _p(P[sc + "/l0/weights"]),
-                                                   _p(P[sc + "/l0/biases"]), _p(P[sc + "/l1/weights"]), _p(P[sc + "/l1/biases"]),
-                                                   _p(P[sc + "/l2/weights"]), _p(P[sc + "/l2/biases"]), _p(feat, col), 480, self.st),
-                           "edge_dense_conv")
-            prep_done = stem and d < DENSE_BLOCKS
-            self._blocks.append((d, C, col, in_col, width))
-        assert col == 0
-
-        # duplicate_up (per source point) + coarse regressor
-        w1 = P["generator/upshuffle_0/conv1/weights"]
-        self._lin(feat, 0, 480, None, 0, ws["h256"], 0, 256, bias=False, W=w1)
-        _lib.check(L.dispu_dup_grid(B, N, 256, self.up_ratio, _p(ws["h256"]), 256, _p(w1, 480 * 256),
-                                    _p(P["generator/upshuffle_0/conv1/biases"]), _p(self.grid), _p(ws["up256"]), 256, self.st), "dup_grid")
-        # conv2 -> fc_layer0 -> fc_layer1 -> fc_layer2 in ONE launch (csrc/mlp_chain.hip), every intermediate stashed for the backward
-        cs = "generator/coarse_coordinate_regressor/"
-        coarse = ws["coarse"].view(rm, 3)
-        c2 = "generator/upshuffle_0/conv2"
-        _lib.check(L.dispu_mlp_chain_stash(rm, 256, 128, 256, 64, _p(ws["up256"]), 256, _p(P[c2 + "/weights"]), _p(P[c2 + "/biases"]),
-                                           _p(P[cs + "fc_layer0/weights"]), _p(P[cs + "fc_layer0/biases"]),
-                                           _p(P[cs + "fc_layer1/weights"]), _p(P[cs + "fc_layer1/biases"]),
-                                           _p(P[cs + "fc_layer2/weights"]), _p(P[cs + "fc_layer2/biases"]),
-                                           _p(ws["up128"]), 128, _p(ws["c256"]), 256, _p(ws["c64"]), 64, None, 0, 0, None, 0,
-                                           _p(coarse), 3, self.st), "mlp_chain[coarse]")
-        ps = "refine/PointShuffle/"
-        up128 = ws["up128"]
+        path = self.path(B, N)
+        sched = self.sched
+        sched.st = _lib.stream_ptr(x.device)
+        self.defer_side = path.defer_side                # see __init__
+        s = self._step = _Step(B, N, self.up_ratio, x, self._workspace(B, N), path)
+        self._fwd_features(s)
+        self._fwd_coarse(s)
         # The k-NN graph of the coarse cloud heads the step's critical path (knn -> BatchNorm statistics -> fused local cell ->
         # after_conv -> fine head): its two launches are queued BEFORE the ~8 launches of the non-local branch, which has slack
         # (round 4: queued after them, the graph waited ~70 us for the host to get there -- tools/trace_timeline.py)
-        ww, bw = P[ps + "weight_net/wconv0/weights"], P[ps + "weight_net/wconv0/biases"]
-        nb = L.dispu_ps_wnet_scratch_bytes(rm)
+        nb = _lib.tape_lib().dispu_ps_wnet_scratch_bytes(s.rm)
         if self._bn_scratch is None or self._bn_scratch.numel() * 8 < nb:
             self._bn_scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=self.device)
-        with self.sched.branch(2):
-            _lib.check(L.dispu_knn_xyz(B, M, M, k, _p(coarse), _p(coarse), _p(ws["psidx"]), None, _lib.ARITH_PLAIN, self.st), "knn_xyz")
-            _lib.check(L.dispu_ps_wnet_bn_stats(rm, M, k, 16, _p(ws["psidx"]), _p(coarse), _p(ww), _p(bw), _p(P[BN + "gamma"]), _p(P[BN + "beta"]),
-                                                BN_EPS, BN_DECAY, _p(ws["bn_stats"]), _p(ws["bn_scale"]), _p(ws["bn_shift"]),
-                                                _p(self.moving_mean), _p(self.moving_var), _p(self._bn_scratch), self._bn_scratch.numel() * 8,
-                                                self.st), "ps_wnet_bn_stats")
+        with sched.branch(2):
+            self._fwd_graph(s)
         # PointShuffle2 (ops.py:1012-1087) in the inference path's form: no [B, M, 16, 134] grouped tensor.  The k-NN graph and the
         # weight net's BatchNorm statistics (from the neighbour offsets) on a branch, next to the per-point halves of conv0
         # (G = up128.Wf + xyz.(Wc + Wr) + b0, A = xyz.Wc; h0 = relu(G[j] - A[i])) that need neither
-        w0 = P[ps + "conv0/weights"]
-        self._lin(up128, 0, 128, None, 0, ws["gm"], 0, 128, bias=False, W=w0, woff=6 * 128)
-        _lib.check(L.dispu_ps_prep(rm, 128, _p(coarse), _p(w0), _p(P[ps + "conv0/biases"]), _p(ws["gm"]), 128, _p(ws["am"]), 128, self.st), "ps_prep")
+        self._fwd_conv0(s)
         # non-local cell (its attention kept for the backward as O + one log-sum-exp per query).  It reads up128 only: a branch next to
         # the grouping, the skip and the local cell; merged before add3.  Its ~8 launches are SUBMITTED after the local cell and
         # after_conv below (the chain), but ordered after this point of the stream.
-        S = ws["S"]
-
-        def nl_branch():
-            self._lin(up128, 0, 128, ps + "PointShuffle/conv_kv", 0, ws["kv"], 0, 128)
-            self._lin(up128, 0, 128, ps + "PointShuffle/conv_query", 0, ws["q"], 0, 64)
-            if self.flash_attn:
-                # softmax(Q.K^T / 8).V on chip; what the backward needs is att and ONE float per query (csrc/attention_train.hip)
-                _lib.check(L.dispu_attention_fwd_lse(B, M, M, 64, _p(ws["q"]), 64, _p(ws["kv"]), 128, _p(ws["kv"], 64), 128, 0.125,
-                                                     _p(ws["att"]), 64, _p(ws["lse"]), self.st), "attention_fwd_lse")
-            else:
-                _lib.check(self._dl(B, M, 64, M, _p(ws["q"]), 64, M * 64, _p(ws["kv"]), 128, M * 128, 1, None, 0, _p(S), M, M * M,
-                                          None, 0, 0, None, 0, 0, self.st), "scores")
-                _lib.check(L.dispu_softmax_rows(rm, M, 0.125, _p(S), M, self.st), "softmax")
-                _lib.check(self._dl(B, M, M, 64, _p(S), M, M * M, _p(ws["kv"], 64), 128, M * 128, 0, None, 0, _p(ws["att"]), 64,
-                                          M * 64, None, 0, 0, None, 0, 0, self.st), "att.V")
-            self._lin(ws["att"], 0, 64, ps + "PointShuffle/conv_back_project", 1, ws["nl"], 0, 256)
-            # what the backward needs and nothing in the forward touches (zeroed accumulators, the W^T copies: ~45 us of kernels),
-            # behind the branch's own kernels
-            self._backward_prep(ws)
-
-        self.sched.defer_branch(0, nl_branch)
-        self.sched.merge(2)
-
+        sched.defer_branch(0, partial(self._fwd_nonlocal, s))
+        sched.merge(2)
         # skip (a second branch next to the local cell): gather-max straight from xyz / up128, then 134 -> 256
-        def skip_branch():
-            _lib.check(L.dispu_ps_skip_max(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(up128), 128, _p(ws["gmax"]), 144, self.st), "skip_max")
-            self._lin(ws["gmax"], 0, 134, ps + "skip", 1, ws["skip"], 0, 256)
+        sched.defer_branch(1, partial(self._fwd_skip, s))
+        self._fwd_local(s)
+        self._fwd_after_conv(s)
+        sched.merge(0)
+        sched.merge(1)
+        self._fwd_fine(s)
+        return s.ws["coarse"], s.ws["fine"]
 
-        self.sched.defer_branch(1, skip_branch)
+    def _fwd_features(self, s):
+        # feature extraction: layer0 and the four dense blocks, accumulating right-to-left inside feat[:, 0:480]
+        L, ws, x, stem = _lib.tape_lib(), s.ws, s.x, s.path.stem
+        B, N, rn, k1 = s.B, s.N, s.rn, K_NEIGH + 1
+        feat = ws["feat"]
+        l0 = self._w(FE + "layer0")
+        if not stem:       # (fused stem: the first block's launch evaluates layer0 while it stages its cloud)
+            _lib.check(L.dispu_linear_small_k(rn, 3, 24, _p(x), 3, *l0, 0, _p(feat, 456), 480, self.st), "layer0")
+        for d, C, col, in_col, width in BLOCKS:
+            if d == 1:
+                F, foff = feat, 456
+            else:
+                if not stem:                   # (fused stem: the previous block's launch already ran this block's bottleneck conv)
+                    self._lin(feat, in_col, 480 - in_col, FE + "layer%d_prep" % d, 1, ws["prep"][d], 0, 48)
+                F, foff = ws["prep"][d], 0
+            ldf, kidx = F.stride(0), ws["kidx"][d]
+            if stem:
+                # search + edge features + dense_conv in one launch (csrc/edge.hip, KNN variant); the neighbour table stays for the backward pass
+                last, first = d == DENSE_BLOCKS, d == 1
+                prep = (None, None) if last else self._w(FE + "layer%d_prep" % (d + 1))
+                _lib.check(L.dispu_stem_block(rn, N, C, _p(F, foff), ldf, k1, 1, *self._dense_w(d), _p(feat, col), 480, _p(kidx), *prep,
+                                              480 - in_col, None if last else _p(ws["prep"][d + 1]), 48, _p(x) if first else None,
+                                              *(l0 if first else (None, None)), _p(feat, 456) if first else None, 480, self.st), "stem_block")
+            else:
+                _lib.check(L.dispu_knn_feat_strided(B, N, N, C, k1, _p(F, foff), ldf, _p(F, foff), ldf, None, _p(kidx), self.st), "knn_feat")
+                # the inference kernel (csrc/edge.hip): edge features, three chained convs and the max in one launch; nothing is kept
+                # for the backward pass, which recomputes the block on chip (csrc/edge_bwd.hip)
+                _lib.check(L.dispu_edge_dense_conv(rn, N, C, _p(F, foff), ldf, _p(kidx), k1, 1, *self._dense_w(d), _p(feat, col), 480, self.st),
+                           "edge_dense_conv")
+
+    def _fwd_coarse(self, s):
+        # duplicate_up (per source point) + coarse regressor
+        L, ws = _lib.tape_lib(), s.ws
+        w1 = self.P[UP + "conv1/weights"]
+        self._lin(ws["feat"], 0, 480, None, 0, ws["h256"], 0, 256, bias=False, W=w1)
+        _lib.check(L.dispu_dup_grid(s.B, s.N, 256, self.up_ratio, _p(ws["h256"]), 256, _p(w1, 480 * 256), _p(self.P[UP + "conv1/biases"]),
+                                    _p(self.grid), _p(ws["up256"]), 256, self.st), "dup_grid")
+        # conv2 -> fc_layer0 -> fc_layer1 -> fc_layer2 in ONE launch (csrc/mlp_chain.hip), every intermediate stashed for the backward
+        _lib.check(L.dispu_mlp_chain_stash(s.rm, 256, 128, 256, 64, _p(ws["up256"]), 256, *self._chain(UP + "conv2", CS),
+                                           _p(ws["up128"]), 128, _p(ws["c256"]), 256, _p(ws["c64"]), 64, None, 0, 0, None, 0,
+                                           _p(s.coarse), 3, self.st), "mlp_chain[coarse]")
+
+    def _fwd_graph(self, s):
+        # the k-NN graph of the coarse cloud and the weight net's BatchNorm statistics (from the neighbour offsets)
+        L, ws, P, M, k = _lib.tape_lib(), s.ws, self.P, s.M, K_NEIGH
+        _lib.check(L.dispu_knn_xyz(s.B, M, M, k, _p(s.coarse), _p(s.coarse), _p(ws["psidx"]), None, _lib.ARITH_PLAIN, self.st), "knn_xyz")
+        _lib.check(L.dispu_ps_wnet_bn_stats(s.rm, M, k, 16, _p(ws["psidx"]), _p(s.coarse), *self._w(PS + "weight_net/wconv0"),
+                                            _p(P[BN + "gamma"]), _p(P[BN + "beta"]), BN_EPS, BN_DECAY, _p(ws["bn_stats"]), _p(ws["bn_scale"]),
+                                            _p(ws["bn_shift"]), _p(self.moving_mean), _p(self.moving_var), _p(self._bn_scratch),
+                                            self._bn_scratch.numel() * 8, self.st), "ps_wnet_bn_stats")
+
+    def _fwd_conv0(self, s):
+        # the per-point halves of the local cell's conv0: G = up128.Wf + xyz.(Wc + Wr) + b0, A = xyz.Wc
+        ws, w0 = s.ws, self.P[PS + "conv0/weights"]
+        self._lin(ws["up128"], 0, 128, None, 0, ws["gm"], 0, 128, bias=False, W=w0, woff=6 * 128)
+        _lib.check(_lib.tape_lib().dispu_ps_prep(s.rm, 128, _p(s.coarse), _p(w0), _p(self.P[PS + "conv0/biases"]), _p(ws["gm"]), 128,
+                                                 _p(ws["am"]), 128, self.st), "ps_prep")
+
+    def _fwd_nonlocal(self, s):
+        L, ws, B, M = _lib.tape_lib(), s.ws, s.B, s.M
+        up128, kv, q, att = ws["up128"], ws["kv"], ws["q"], ws["att"]
+        self._lin(up128, 0, 128, PS + "PointShuffle/conv_kv", 0, kv, 0, 128)
+        self._lin(up128, 0, 128, PS + "PointShuffle/conv_query", 0, q, 0, 64)
+        if s.path.attention == "flash":
+            # softmax(Q.K^T / 8).V on chip; what the backward needs is att and ONE float per query (csrc/attention_train.hip)
+            _lib.check(L.dispu_attention_fwd_lse(B, M, M, 64, _p(q), 64, _p(kv), 128, _p(kv, 64), 128, 0.125, _p(att), 64, _p(ws["lse"]),
+                                                 self.st), "attention_fwd_lse")
+        else:
+            S = ws["S"]
+            _lib.check(self._dl(B, M, 64, M, _p(q), 64, M * 64, _p(kv), 128, M * 128, 1, None, 0, _p(S), M, M * M,
+                                None, 0, 0, None, 0, 0, self.st), "scores")
+            _lib.check(L.dispu_softmax_rows(s.rm, M, 0.125, _p(S), M, self.st), "softmax")
+            _lib.check(self._dl(B, M, M, 64, _p(S), M, M * M, _p(kv, 64), 128, M * 128, 0, None, 0, _p(att), 64,
+                                M * 64, None, 0, 0, None, 0, 0, self.st), "att.V")
+        self._lin(att, 0, 64, PS + "PointShuffle/conv_back_project", 1, ws["nl"], 0, 256)
+        # what the backward needs and nothing in the forward touches (zeroed accumulators, the W^T copies: ~45 us of kernels),
+        # behind the branch's own kernels
+        self._backward_prep(ws)
+
+    def _fwd_skip(self, s):
+        ws = s.ws
+        _lib.check(_lib.tape_lib().dispu_ps_skip_max(s.rm, s.M, K_NEIGH, 128, _p(ws["psidx"]), _p(s.coarse), _p(ws["up128"]), 128,
+                                                     _p(ws["gmax"]), 144, self.st), "skip_max")
+        self._lin(ws["gmax"], 0, 134, PS + "skip", 1, ws["skip"], 0, 256)
+
+    def _fwd_local(self, s):
         # the fused cell (conv1, weight_net with the folded BatchNorm, feature x weight)
-        _lib.check(L.dispu_ps_local(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(ws["gm"]), 128, _p(ws["am"]),
-                                    _p(P[ps + "conv1/weights"]), _p(P[ps + "conv1/biases"]), _p(ww), _p(bw), _p(ws["bn_scale"]),
-                                    _p(ws["bn_shift"]), _p(ws["hp"]), self.st), "ps_local")
+        ws = s.ws
+        _lib.check(_lib.tape_lib().dispu_ps_local(s.rm, s.M, K_NEIGH, 128, _p(ws["psidx"]), _p(s.coarse), _p(ws["gm"]), 128, _p(ws["am"]),
+                                                  *self._w(PS + "conv1"), *self._w(PS + "weight_net/wconv0"), _p(ws["bn_scale"]),
+                                                  _p(ws["bn_shift"]), _p(ws["hp"]), self.st), "ps_local")
+
+    def _fwd_after_conv(self, s):
         # after_conv, [rows x 2048] x [2048 x 256].  At <= 16 patches the rows give 32 - 128 tiles of 128 x 256 -- a fraction of the chip --
         # and the tile rule falls back to 512 L2-bound 64 x 64 tiles (139 us in the 8-patch step for a 55 us product): the contraction is
         # split into K-chunks run as one batched launch that fills the chip with 128 x 256 tiles, a second launch adds the chunks in
         # order, then bias and ReLU (reassociated; `fine` is tolerance-checked).  fp32 products only (bf16 products have their own tiles)
-        nsp = 4 if rm >= 8192 else 8
-        if rm <= 16384 and rm % 128 == 0 and ws["hp"].dtype == torch.float32 and not self._use_bf16(1, rm, 2048, 256):
-            if ws.get("aft_parts") is None or ws["aft_parts"].numel() < nsp * rm * 256:
-                ws["aft_parts"] = torch.empty((nsp * rm, 256), dtype=torch.float32, device=self.device)
-            wa, ba = P[ps + "after_conv/weights"], P[ps + "after_conv/biases"]
-            kc = 2048 // nsp
-            _lib.check(L.dispu_linear(nsp, rm, kc, 256, _p(ws["hp"]), 2048, kc, _p(wa), 256, kc * 256, 0, None, 0, _p(ws["aft_parts"]), 256, rm * 256,
-                                      None, 0, 0, None, 0, 0, self.st), "dispu_linear[split-K]")
-            _lib.check(L.dispu_linear_splitk_finish(rm, 256, nsp, _p(ws["aft_parts"]), rm * 256, _p(ba), 1, _p(ws["aft"]), 256, self.st),
-                       "dispu_linear_splitk_finish")
-        else:
-            self._lin(ws["hp"], 0, 2048, ps + "after_conv", 1, ws["aft"], 0, 256)
-        self.sched.merge(0)
-        self.sched.merge(1)
+        L, ws, rm, nsp = _lib.tape_lib(), s.ws, s.rm, s.path.after_split
+        if not nsp:
+            self._lin(ws["hp"], 0, 2048, PS + "after_conv", 1, ws["aft"], 0, 256)
+            return
+        if ws.get("aft_parts") is None or ws["aft_parts"].numel() < nsp * rm * 256:
+            ws["aft_parts"] = torch.empty((nsp * rm, 256), dtype=torch.float32, device=self.device)
+        wa, ba = self._w(PS + "after_conv")
+        kc = 2048 // nsp
+        _lib.check(L.dispu_linear(nsp, rm, kc, 256, _p(ws["hp"]), 2048, kc, wa, 256, kc * 256, 0, None, 0, _p(ws["aft_parts"]), 256, rm * 256,
+                                  None, 0, 0, None, 0, 0, self.st), "dispu_linear[split-K]")
+        _lib.check(L.dispu_linear_splitk_finish(rm, 256, nsp, _p(ws["aft_parts"]), rm * 256, ba, 1, _p(ws["aft"]), 256, self.st),
+                   "dispu_linear_splitk_finish")
+
+    def _fwd_fine(self, s):
+        L, ws, rm = _lib.tape_lib(), s.ws, s.rm
         _lib.check(L.dispu_add3(rm * 256, _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), _p(ws["sum"]), self.st), "add3")
         # aggregation -> fine regressor (fc_layer0, fc_layer1, fc_layer2) -> coarse + sigmoid(.) - 0.5 in one launch
-        fs = "refine/fine_coordinate_regressor/"
-        ag = ps + "aggregation"
-        _lib.check(L.dispu_mlp_chain_stash(rm, 256, 256, 256, 64, _p(ws["sum"]), 256, _p(P[ag + "/weights"]), _p(P[ag + "/biases"]),
-                                           _p(P[fs + "fc_layer0/weights"]), _p(P[fs + "fc_layer0/biases"]),
-                                           _p(P[fs + "fc_layer1/weights"]), _p(P[fs + "fc_layer1/biases"]),
-                                           _p(P[fs + "fc_layer2/weights"]), _p(P[fs + "fc_layer2/biases"]),
-                                           _p(ws["agg"]), 256, _p(ws["f256"]), 256, _p(ws["f64"]), 64, _p(ws["z"]), 3, 1, _p(coarse), 3,
+        _lib.check(L.dispu_mlp_chain_stash(rm, 256, 256, 256, 64, _p(ws["sum"]), 256, *self._chain(PS + "aggregation", FS),
+                                           _p(ws["agg"]), 256, _p(ws["f256"]), 256, _p(ws["f64"]), 64, _p(ws["z"]), 3, 1, _p(s.coarse), 3,
                                            _p(ws["fine"]), 3, self.st), "mlp_chain[fine]")
-        self._stash_ready = False
-        self._fresh = True               # the atomics accumulators (dprep, dup128s) were zero-filled for exactly ONE backward()
-        return ws["coarse"], ws["fine"]
 
-    def _recompute_pair_tensors(self):
+    def _recompute_pair_tensors(self, s):
         """h0 = relu(G[j] - A[i]), h1 = relu(h0.W1 + b1), wv = relu(BN(offsets.Ww + bw)) [B*M*16, .] and the inverted k-NN graph: what
         the local cell's backward reads.  The forward kernel (csrc/ps_local.hip) keeps them on chip; they are rebuilt here, on an
         auxiliary stream next to the loss and the fine head's backward.  dtype "f32": the same fmaf chains as the forward kernel,
@@ -623,19 +689,12 @@ class Trainer(object):
         bf16 rebuild, i.e. they can differ from the forward's at pre-activations within bf16 rounding of zero; that is part of the
         mixed-precision approximation and sits inside the tolerances of tests/test_train_bf16_gpu.py (loss terms 2 %, gradient cosine
         >= 0.97), not a separate error source."""
-        if self._stash_ready:
+        if s.stash_ready:
             return
-        L = _lib.tape_lib()
-        B, N = self._shape
-        M, k = N * self.up_ratio, K_NEIGH
-        rm = B * M
-        ws = self._workspace(B, N)
-        P = self.P
-        ps = "refine/PointShuffle/"
-        coarse = ws["coarse"].view(rm, 3)
-        fused = self._fused_local_bwd_ok(ws)
+        L, ws, rm, M, k = _lib.tape_lib(), s.ws, s.rm, s.M, K_NEIGH
+        fused = s.path.local_bwd == "fused"
         if not fused:
-            _lib.check(L.dispu_knn_invert(B, M, k, _p(ws["psidx"]), _p(ws["inv_off"]), _p(ws["inv"]), self.st), "knn_invert")
+            _lib.check(L.dispu_knn_invert(s.B, M, k, _p(ws["psidx"]), _p(ws["inv_off"]), _p(ws["inv"]), self.st), "knn_invert")
         if ws["h0"].dtype == torch.bfloat16:
             _lib.check(L.dispu_ps_gather_sub_relu_bf16(rm, M, k, 128, _p(ws["psidx"]), _p(ws["gm"]), 128, _p(ws["am"]), 128, _p(ws["h0"]), 128,
                                                        self.st), "gather_sub_relu_bf16")
@@ -643,23 +702,17 @@ class Trainer(object):
             _lib.check(L.dispu_ps_gather_sub_relu(rm, M, k, 128, _p(ws["psidx"]), _p(ws["gm"]), 128, _p(ws["am"]), 128, _p(ws["h0"]), 128, self.st),
                        "gather_sub_relu")
         if not fused:                                    # (fused backward: only h0 is needed in HBM -- the dW1 = h0^T . dz1 product reads it)
-            self._lin(ws["h0"], 0, 128, ps + "conv1", 1, ws["h1"], 0, 128)
-            _lib.check(L.dispu_ps_weight_net(rm, M, k, 16, _p(ws["psidx"]), _p(coarse), _p(P[ps + "weight_net/wconv0/weights"]),
-                                             _p(P[ps + "weight_net/wconv0/biases"]), _p(ws["bn_scale"]), _p(ws["bn_shift"]), _p(ws["wv"]), self.st),
-                       "weight_net")
-        self._stash_ready = True
-
-    def _fused_local_bwd_ok(self, ws):
-        """the one-launch backward of the local cell: fp32 pair-tensor storage, whole 8-point groups, transposed weight copies at hand."""
-        return (self.fused_local_bwd and ws["h0"].dtype == torch.float32 and ws["h0"].shape[0] % 64 == 0
-                and ("refine/PointShuffle/conv1/weights" in self.PT))
+            self._lin(ws["h0"], 0, 128, PS + "conv1", 1, ws["h1"], 0, 128)
+            _lib.check(L.dispu_ps_weight_net(rm, M, k, 16, _p(ws["psidx"]), _p(s.coarse), *self._w(PS + "weight_net/wconv0"),
+                                             _p(ws["bn_scale"]), _p(ws["bn_shift"]), _p(ws["wv"]), self.st), "weight_net")
+        s.stash_ready = True
 
     # -------------------------------------------------------------------------------------------------- loss ----
     def _chamfer(self, pred, gt, radius, coef, dpred, slot):
         """one Chamfer term (loss_utils.py:45-64 with nn_distance(gt, pred)): its un-scaled value into loss_vals[slot] and
         d(coef * CD)/d pred into dpred -- three launches (nn_distance, value, gradient) + one memset."""
         L = _lib.tape_lib()
-        full = self._workspace(*self._shape)
+        full = self._step.ws
         ws = full["cd"][slot]
         B, n_gt, n_pred = gt.shape[0], gt.shape[1], pred.shape[1]
         _lib.check(L.dispu_nn_distance(B, n_gt, _p(gt), n_pred, _p(pred), _p(ws["d_gt"]), _p(ws["i_gt"]), _p(ws["d_pred"]),
@@ -717,79 +770,85 @@ class Trainer(object):
 
     def loss_backward(self, gt, radius):
         """pu_loss of model.py:75-87 at the current epoch; fills dcoarse / dfine with its gradient."""
-        L = _lib.tape_lib()
-        B, N = self._shape
-        M = N * self.up_ratio
-        ws = self._workspace(B, N)
-        gt, radius = self._check_targets(gt, radius, B, M)
+        s, sched = self._step, self.sched
+        B, N, ws = s.B, s.N, s.ws
+        gt, radius = self._check_targets(gt, radius, B, s.M)
         wf = weight_fine(self.epoch)
-        uniform = bool(getattr(self.opts, "use_uniform", False))
-        if uniform:
-            tab = self._uniform_workspace(ws, B, N)             # refuses a patch size the term cannot take, before any launch
-        emd = bool(getattr(self.opts, "use_emd", False))
+        repulse, uniform, emd = bool(self.opts.use_repulse), bool(getattr(self.opts, "use_uniform", False)), bool(getattr(self.opts, "use_emd", False))
+        tab = self._uniform_workspace(ws, B, N) if uniform else None     # refuses a patch size the term cannot take, before any launch
         if emd:
             self._emd_workspace(ws, B, N)
-            emd_w = float(self.opts.emd_w)
         # side work is submitted behind the fine term's launches (the chain): the pair tensors of the local cell's backward (needed much
         # later) and the coarse term
-        self.sched.defer_branch(2, self._recompute_pair_tensors)    # off the chain: needed by the local cell's backward only
-        with self.sched.branch(0):                                   # the coarse term next to the fine term and the repulsion term
+        sched.defer_branch(2, partial(self._recompute_pair_tensors, s))    # off the chain: needed by the local cell's backward only
+        with sched.branch(0):                                        # the coarse term next to the fine term and the repulsion term
             self._chamfer(ws["coarse"], gt, radius, 1000.0, ws["dcoarse"], 0)
         # fine term: nn_distance, then value + gradient (which zero-fills dfine); the repulsion term's ball query runs next to it and
         # adds its gradient once the Chamfer gradient is in place
         # the uniform term's seeds (farthest point sampling of the fine cloud) run on the same branch; its fused value + gradient launch
         # follows the Chamfer gradient like the repulsion gradient does
-        rep = None
-        fine = ws["fine"]
-        if self.opts.use_repulse or uniform:
-            with self.sched.branch(1):
-                if self.opts.use_repulse:
-                    _lib.check(L.dispu_query_ball(B, M, M, _p(ws["r07"]), 20, _p(fine), _p(fine), _p(ws["ball"]), _p(ws["ball_cnt"]),
-                                                  _lib.ARITH_CONTRACT, self.st), "query_ball")   # as loss_utils.get_repulsion_loss
-                if uniform:
-                    _lib.check(L.dispu_fps_ws(B, M, tab.npoint, _p(fine), _p(ws["ufps_tmp"]), ws["ufps_bytes"], _p(ws["useeds"]),
-                                              _lib.ARITH_CONTRACT, self.st), "fps")              # as loss_utils.get_uniform_loss
+        if repulse or uniform:
+            with sched.branch(1):
+                self._loss_queries(s, repulse, tab)
         # the EMD term's auction (21 launches, reads fine and gt only) runs on a branch of its own next to the Chamfer launches: ordered
         # after THIS point of the stream, submitted behind the fine term's launches (the chain); its fused cost + gradient launch follows
         # the Chamfer gradient on the chain (which zero-fills dfine), like the two terms above
-        ev_emd = self.sched.fork_point() if (emd and self.overlap_dw) else None
+        ev_emd = sched.fork_point() if (emd and self.overlap_dw) else None
         self._chamfer(ws["fine"], gt, radius, 1000.0 * wf, ws["dfine"], 1)
         if emd:
-            with self.sched.branch(3, ev_emd):
-                _lib.check(L.dispu_approx_match_levels_ws(B, M, M, _p(fine), _p(gt), _p(ws["emd_temp"]), ws["emd_temp_bytes"],
-                                                          _lib.ARITH_CONTRACT, self.st), "approx_match_levels_ws")   # as loss_utils.earth_mover
-        if self.opts.use_repulse or uniform:
-            self.sched.merge(1)
-        if self.opts.use_repulse:
+            with sched.branch(3, ev_emd):
+                _lib.check(_lib.tape_lib().dispu_approx_match_levels_ws(B, s.M, s.M, _p(ws["fine"]), _p(gt), _p(ws["emd_temp"]), ws["emd_temp_bytes"],
+                                                                        _lib.ARITH_CONTRACT, self.st), "approx_match_levels_ws")   # as loss_utils.earth_mover
+        if repulse or uniform:
+            sched.merge(1)
+        self._loss_ball_terms(s, repulse, tab)
+        if emd:
+            sched.merge(3)
+            _lib.check(_lib.tape_lib().dispu_emd_loss_grad(B, s.M, s.M, _p(ws["fine"]), _p(gt), _p(ws["emd_temp"]), _p(radius),
+                                                           float(self.opts.emd_w) * wf / s.rm, _p(ws["emd_cost"]), _p(ws["dfine"]), _p(ws["emd_scratch"]),
+                                                           ws["emd_scratch_bytes"], _lib.ARITH_CONTRACT, self.st), "emd_loss_grad")
+        sched.merge(0)
+        self._loss_finalize(s, wf, repulse, tab, emd, radius)
+        terms = self._terms(ws["loss_vals"], wf, uniform, emd)
+        sched.flush(prio=0)                                          # the recompute branch: submitted behind the loss's own launches
+        return terms
+
+    def _loss_queries(self, s, repulse, tab):
+        """what the repulsion and uniform terms need of the fine cloud before their gradients: the ball query, the seeds"""
+        L, ws, B, M, fine = _lib.tape_lib(), s.ws, s.B, s.M, s.ws["fine"]
+        if repulse:
+            _lib.check(L.dispu_query_ball(B, M, M, _p(ws["r07"]), 20, _p(fine), _p(fine), _p(ws["ball"]), _p(ws["ball_cnt"]),
+                                          _lib.ARITH_CONTRACT, self.st), "query_ball")   # as loss_utils.get_repulsion_loss
+        if tab is not None:
+            _lib.check(L.dispu_fps_ws(B, M, tab.npoint, _p(fine), _p(ws["ufps_tmp"]), ws["ufps_bytes"], _p(ws["useeds"]),
+                                      _lib.ARITH_CONTRACT, self.st), "fps")              # as loss_utils.get_uniform_loss
+
+    def _loss_ball_terms(self, s, repulse, tab):
+        """value and gradient of the repulsion and uniform terms, added to dfine behind the fine Chamfer gradient"""
+        L, ws, B, M, fine = _lib.tape_lib(), s.ws, s.B, s.M, s.ws["fine"]
+        if repulse:
             _lib.check(L.dispu_repulsion_loss_grad(B * M, M, 20, 0.001, self.opts.repulsion_w / (B * M * 4.0), _p(fine), _p(ws["ball"]),
                                                    _p(ws["rep"]), _p(ws["dfine"]), self.st), "repulsion_loss_grad")
-            rep = ws["rep"]
-        if uniform:
+        if tab is not None:
             _lib.check(L.dispu_uniform_loss_grad(B, M, tab.npoint, tab.nlevels, ctypes.addressof(tab.ns), ctypes.addressof(tab.levels), _p(fine),
                                                  _p(ws["useeds"]), _p(ws["upart"]), _p(ws["dfine"]), None, None, _lib.ARITH_CONTRACT, self.st),
                        "uniform_loss_grad")
+
+    def _loss_finalize(self, s, wf, repulse, tab, emd, radius):
+        """the terms' partial values -> loss_vals[2:] (pu_loss and its weighted terms) in one launch"""
+        L, ws, B, M, uniform = _lib.tape_lib(), s.ws, s.B, s.M, tab is not None
+        out, rep = ws["loss_vals"], _p(ws["rep"]) if repulse else None
         if emd:
-            self.sched.merge(3)
-            _lib.check(L.dispu_emd_loss_grad(B, M, M, _p(fine), _p(gt), _p(ws["emd_temp"]), _p(radius), emd_w * wf / (B * M), _p(ws["emd_cost"]),
-                                             _p(ws["dfine"]), _p(ws["emd_scratch"]), ws["emd_scratch_bytes"], _lib.ARITH_CONTRACT, self.st),
-                       "emd_loss_grad")
-        self.sched.merge(0)
-        out = ws["loss_vals"]
-        if emd:
-            _lib.check(L.dispu_pu_loss_finalize_e(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
+            _lib.check(L.dispu_pu_loss_finalize_e(_p(out), rep, B * M, wf, float(self.opts.repulsion_w),
                                                   _p(ws["upart"]) if uniform else None, tab.nlevels if uniform else 0,
                                                   B * tab.npoint if uniform else 0, float(self.opts.uniform_w) if uniform else 0.0,
-                                                  _p(ws["emd_cost"]), _p(radius), B, M, emd_w, _p(out, 2), self.st), "pu_loss_finalize_e")
+                                                  _p(ws["emd_cost"]), _p(radius), B, M, float(self.opts.emd_w), _p(out, 2), self.st), "pu_loss_finalize_e")
         elif uniform:
-            _lib.check(L.dispu_pu_loss_finalize_u(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
+            _lib.check(L.dispu_pu_loss_finalize_u(_p(out), rep, B * M, wf, float(self.opts.repulsion_w),
                                                   _p(ws["upart"]), tab.nlevels, B * tab.npoint, float(self.opts.uniform_w), _p(out, 2), self.st),
                        "pu_loss_finalize_u")
         else:
-            _lib.check(L.dispu_pu_loss_finalize(_p(out), _p(rep) if rep is not None else None, B * M, wf, float(self.opts.repulsion_w),
-                                                _p(out, 2), self.st), "pu_loss_finalize")
-        terms = self._terms(out, wf, uniform, emd)
-        self.sched.flush(prio=0)                                     # the recompute branch: submitted behind the loss's own launches
-        return terms
+            _lib.check(L.dispu_pu_loss_finalize(_p(out), rep, B * M, wf, float(self.opts.repulsion_w), _p(out, 2), self.st), "pu_loss_finalize")
 
     @staticmethod
     def _terms(out, wf, uniform=False, emd=False):
@@ -806,199 +865,224 @@ class Trainer(object):
         """gradients of pu_loss w.r.t. every trainable variable, accumulated into the flat gradient buffer.
         ReLU gradients never run as separate passes: the kernel that produces a layer's dY applies that layer's mask (the fused head
         chains, the gathers, _act_bias_grad), so every dY arriving at _lin_bwd is already the pre-activation gradient dZ."""
-        L = _lib.tape_lib()
-        B, N = self._shape
-        M, k = N * self.up_ratio, K_NEIGH
-        rn, rm = B * N, B * M
-        ws = self._workspace(B, N)
-        P, G = self.P, self.G
-        coarse = ws["coarse"].view(rm, 3)
-        dcoarse, dfine = ws["dcoarse"].view(rm, 3), ws["dfine"].view(rm, 3)
-        ps = "refine/PointShuffle/"
-        fs = "refine/fine_coordinate_regressor/"
-        if not self._fresh:
+        s = self._step
+        if not s.fresh:
             # a second backward() on the same forward (new targets / loss weights): the atomics accumulators still hold the previous,
             # already masked gradients -- clear them again, on this stream, before anything accumulates
-            self._zero(ws["zeroed"])
-        self._fresh = False
-        if not self._stash_ready:                       # backward() without loss_backward(): rebuild the pair tensors here
+            self._zero(s.ws["zeroed"])
+        s.fresh = False
+        if not s.stash_ready:                           # backward() without loss_backward(): rebuild the pair tensors here
             with self.sched.branch(2):
-                self._recompute_pair_tensors()
+                self._recompute_pair_tensors(s)
+        self._backward_refine(s)
+        self._bucket_point(0)                            # data parallel: every refine/* gradient is queued -> its all-reduce starts
+        self._backward_generator(s)
+        self.sched.join()                     # every dW is in the flat gradient buffer from here on (all-reduce, Adam)
 
-        # fine = coarse + sigmoid(z) - 0.5
-        _lib.check(L.dispu_sigmoid_offset_grad(rm * 3, _p(ws["z"]), _p(dfine), _p(ws["dz"]), _p(dcoarse), self.st), "sigmoid_grad")
-        ag = ps + "aggregation"
-        # fc_layer2 -> fc_layer1 -> fc_layer0 -> aggregation backward and the three branch masks of
-        # sum = relu(after) + relu(skip) + relu(nl) in ONE launch (csrc/mlp_chain_bwd.hip); the four dW products follow on the side streams
-        PT = self.PT
-        _lib.check(L.dispu_mlp_chain_grad(rm, 256, 256, 256, _p(ws["dz"]), 3, _p(P[fs + "fc_layer2/weights"]),
-                                          _p(PT[fs + "fc_layer1/weights"]), _p(PT[fs + "fc_layer0/weights"]), _p(PT[ag + "/weights"]),
-                                          _p(ws["f64"]), 64, _p(ws["f256"]), 256, _p(ws["agg"]), 256, None, 0, None, 0,
-                                          _p(ws["df64"]), 64, _p(ws["df256"]), 256, _p(ws["dagg"]), 256,
-                                          _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), 256, _p(ws["daft"]), _p(ws["dskip"]), _p(ws["dnl"]), 256,
-                                          self.st), "mlp_chain_grad[fine]")
-        grp = self.sched.fork_group()
-        self._lin_bwd(ws["f64"], 0, 64, fs + "fc_layer2", 3, ws["dz"], 0, after=grp)
-        self._lin_bwd(ws["f256"], 0, 256, fs + "fc_layer1", 64, ws["df64"], 0, after=grp)
-        self._lin_bwd(ws["agg"], 0, 256, fs + "fc_layer0", 256, ws["df256"], 0, after=grp)
-        self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0, after=grp)
-
+    def _backward_refine(self, s):
+        """fine head, then the local cell on the chain with the non-local cell, the skip and the weight net as branches next to it"""
+        ws, sched = s.ws, self.sched
+        self._bwd_fine(s)
         # local cell first: the host needs ~0.1 ms to queue the two branches below, the chain must not sit idle meanwhile; the
         # branches themselves only need the head chain's dskip / dnl, so they are ordered after THIS point of the stream, not after the
         # product
-        ev_br = self.sched.fork_point() if self.overlap_dw else None
-        self._lin_bwd(ws["hp"], 0, 2048, ps + "after_conv", 256, ws["daft"], 0, ws["dhp"])
+        ev_br = sched.fork_point() if self.overlap_dw else None
+        self._lin_bwd(ws["hp"], 0, 2048, PS + "after_conv", 256, ws["daft"], 0, ws["dhp"])
         # non-local cell: reads dnl, writes datt / dS / dkv / dq / dup128 -- nothing the local cell or the skip branch touches, so
         # it runs as a branch next to them; merged before anything else accumulates into dup128
-        dup128 = ws["dup128"]
-        def nl_backward():
-            self._lin_bwd(ws["att"], 0, 64, ps + "PointShuffle/conv_back_project", 256, ws["dnl"], 0, ws["datt"])
-            S, dS, kv, dkv, q = ws["S"], ws["dS"], ws["kv"], ws["dkv"], ws["q"]
-            if self.flash_attn:
-                # dQ, dK, dV with the probabilities recomputed tile by tile from Q, K and the forward's log-sum-exp: two launches
-                _lib.check(L.dispu_attention_bwd(B, M, M, 64, _p(q), 64, _p(kv), 128, _p(kv, 64), 128, 0.125, _p(ws["att"]), 64,
-                                                 _p(ws["lse"]), _p(ws["datt"]), 64, _p(ws["dq"]), 64, _p(dkv), 128, _p(dkv, 64), 128,
-                                                 _p(ws["dvec"]), self.st), "attention_bwd")
-            else:
-                # dP = dO . V^T
-                _lib.check(self._dl(B, M, 64, M, _p(ws["datt"]), 64, M * 64, _p(kv, 64), 128, M * 128, 1, None, 0, _p(dS), M, M * M,
-                                          None, 0, 0, None, 0, 0, self.st), "dP")
-                # dV = P^T . dO  -> dkv[:, 64:128]
-                self._tn(B, M, M, 64, S, 0, M, M * M, ws["datt"], 0, 64, M * 64, dkv, 64, 128, M * 128, 0)
-                _lib.check(L.dispu_softmax_rows_grad(rm, M, 0.125, _p(S), M, _p(dS), M, self.st), "softmax_grad")
-                # dQ = dS . K
-                _lib.check(self._dl(B, M, M, 64, _p(dS), M, M * M, _p(kv), 128, M * 128, 0, None, 0, _p(ws["dq"]), 64, M * 64,
-                                          None, 0, 0, None, 0, 0, self.st), "dQ")
-                # dK = dS^T . Q -> dkv[:, 0:64]
-                self._tn(B, M, M, 64, dS, 0, M, M * M, q, 0, 64, M * 64, dkv, 0, 128, M * 128, 0)
-            self._lin_bwd(ws["up128"], 0, 128, ps + "PointShuffle/conv_kv", 128, dkv, 0, dup128)
-            self._lin_bwd(ws["up128"], 0, 128, ps + "PointShuffle/conv_query", 64, ws["dq"], 0, dup128, 0, acc_dx=True)
-        self.sched.defer_branch(0, nl_backward, ev_br)
+        sched.defer_branch(0, partial(self._bwd_nonlocal, s), ev_br)
         # skip branch (a second branch): 134 -> 256 backward; its max gradient is scattered after the merges below
-        split_skip = self.overlap_dw      # the skip branch's d(up128) in its own buffer, summed in the coarse chain
-        def skip_backward():
-            self._lin_bwd(ws["gmax"], 0, 134, ps + "skip", 256, ws["dskip"], 0, ws["dgmax"])
-            if split_skip:
-                _lib.check(L.dispu_ps_skip_max_grad(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(ws["up128"]), 128, _p(ws["gmax"]), 144,
-                                                    _p(ws["dgmax"]), 136, _p(dcoarse), _p(ws["dup128s"]), 128, 1, self.st), "ps_skip_max_grad")
-        self.sched.defer_branch(1, skip_backward, ev_br)
+        sched.defer_branch(1, partial(self._bwd_skip, s), ev_br)
         # after_conv's dX (0.1 - 0.15 ms on the GPU) is queued: submit the two branches the chain will wait for behind it; the weight
         # gradients stay deferred until the chain's next three kernels are queued too
-        self.sched.flush(prio=0)
-        self.sched.merge(2)                                   # h0 / h1 / wv / the inverted graph are in place
-        fused_lb = self._fused_local_bwd_ok(ws)
-        if fused_lb:
-            # one launch: dwv, dz1 (for the side-stream dW1), dG (atomics into the zeroed buffer) and -dA; h1 / dz0 / wv stay on chip
-            self._zero(ws["dG"])
-            _lib.check(L.dispu_ps_local_grad(rm, M, _p(ws["psidx"]), _p(coarse), _p(ws["gm"]), 128, _p(ws["am"]), _p(P[ps + "conv1/weights"]),
-                                             _p(P[ps + "conv1/biases"]), _p(self.PT[ps + "conv1/weights"]), _p(P[ps + "weight_net/wconv0/weights"]),
-                                             _p(P[ps + "weight_net/wconv0/biases"]), _p(ws["bn_scale"]), _p(ws["bn_shift"]), _p(ws["dhp"]),
-                                             _p(ws["dz1"]), _p(ws["dwv"]), _p(ws["dG"]), _p(ws["dAneg"]), self.st), "ps_local_grad")
-        else:
-            _lib.check(L.dispu_ps_point_matmul_grad_relu_s(rm, k, 128, 16, _p(ws["h1"]), 128, _p(ws["wv"]), _p(ws["dhp"]), 2048, _p(ws["dz1"]),
-                                                           128, _p(ws["dwv"]), 1 if ws["h1"].dtype == torch.bfloat16 else 0, self.st),
-                       "point_matmul_grad")
+        sched.flush(prio=0)
+        sched.merge(2)                                        # h0 / h1 / wv / the inverted graph are in place
+        self._bwd_local_product(s)
         # the weight net's backward (dwv -> BatchNorm -> 3 -> 16 conv -> atomics into dcoarse) next to the conv1 / conv0 gradients
-        def wnet_backward():
-            ww, bw = P[ps + "weight_net/wconv0/weights"], P[ps + "weight_net/wconv0/biases"]
-            _lib.check(L.dispu_ps_wnet_grad(rm, M, k, 16, _p(ws["psidx"]), _p(coarse), _p(ww), _p(bw), _p(ws["bn_stats"]), _p(ws["bn_scale"]),
-                                            _p(ws["bn_shift"]), _p(P[BN + "gamma"]), _p(ws["dwv"]), _p(G[ps + "weight_net/wconv0/weights"]),
-                                            _p(G[ps + "weight_net/wconv0/biases"]), _p(G[BN + "gamma"]), _p(G[BN + "beta"]), _p(dcoarse),
-                                            _p(ws["bn_sums"]), _p(self._bn_scratch), self._bn_scratch.numel() * 8, self.st), "ps_wnet_grad")
-        self.sched.defer_branch(2, wnet_backward)
-        if fused_lb:
-            self._lin_bwd(ws["h0"], 0, 128, ps + "conv1", 128, ws["dz1"], 0, None)            # dW1, db1 only: the dX product ran inside the fused launch
-        else:
-            self._lin_bwd(ws["h0"], 0, 128, ps + "conv1", 128, ws["dz1"], 0, ws["dz0"])      # dz0 holds dh0: conv0's relu' rides in the gather
-            # conv0 in its per-source-point form: dh0 * (G[j] - A[i] > 0) -> dG (gather through the inverted graph), -dA; then [B*M, 128] products
-            _lib.check(L.dispu_ps_conv0_gather_grad_s(rm, M, k, 128, _p(ws["psidx"]), _p(ws["inv_off"]), _p(ws["inv"]), _p(ws["dz0"]), 128,
-                                                      1 if ws["dz0"].dtype == torch.bfloat16 else 0, _p(ws["gm"]), 128, _p(ws["am"]), 128,
-                                                      _p(ws["dG"]), 128, _p(ws["dAneg"]), 128, self.st), "conv0_gather_grad")
+        sched.defer_branch(2, partial(self._bwd_weight_net, s))
+        self._bwd_local_convs(s)
         # the main queue now holds after_conv's dX, the feature x weight gradient, conv1's dX and the gather (~0.35 ms of kernels at 8
         # patches): time to submit the side work that piled up behind them (five weight gradients, the non-local and skip branches)
-        self.sched.flush()
-        w0, dw0 = P[ps + "conv0/weights"], G[ps + "conv0/weights"]
-        self.sched.merge(0)                                   # dup128 holds the non-local cell's part from here on
-        self._lin_bwd(ws["up128"], 0, 128, None, 128, ws["dG"], 0, dup128, 0, acc_dx=True, W=w0, dW=dw0, woff=6 * 128, bias=False,
-                      db=G[ps + "conv0/biases"])
-        _lib.check(L.dispu_ps_prep_grad(rm, 128, _p(coarse), _p(w0), _p(ws["dG"]), 128, _p(ws["dAneg"]), 128, _p(dcoarse), _p(dw0), self.st),
-                   "ps_prep_grad")
-        self.sched.merge(1)
-        if not split_skip:
-            _lib.check(L.dispu_ps_skip_max_grad(rm, M, k, 128, _p(ws["psidx"]), _p(coarse), _p(ws["up128"]), 128, _p(ws["gmax"]), 144,
-                                                _p(ws["dgmax"]), 136, _p(dcoarse), _p(dup128), 128, 1, self.st), "ps_skip_max_grad")
-        self.sched.merge(2)                                   # the weight net's share of dcoarse
+        sched.flush()
+        sched.merge(0)                                        # dup128 holds the non-local cell's part from here on
+        self._bwd_conv0(s)
+        sched.merge(1)
+        if not s.path.split_skip:
+            self._skip_max_grad(s, ws["dup128"])
+        sched.merge(2)                                        # the weight net's share of dcoarse
         # the refine branch's weight-gradient products submitted so far (after_conv's 2048 x 256 with its ~100 MB of partials among them)
-        # get their grouped reduction HERE, in the shadow of the coarse chain's backward; whatever is left at _join() is small.  (All of
-        # them at _join(): 35 us of reductions between the last product and Adam.)
-        self.sched.flush_reductions()
-        self._bucket_point(0)                            # data parallel: every refine/* gradient is queued -> its all-reduce starts
+        # get their grouped reduction HERE, in the shadow of the coarse chain's backward; whatever is left at join() is small.  (All of
+        # them at join(): 35 us of reductions between the last product and Adam.)
+        sched.flush_reductions()
 
-        # coarse regressor
-        cs = "generator/coarse_coordinate_regressor/"
-        c2 = "generator/upshuffle_0/conv2"
-        # fc_layer2 -> fc_layer1 -> fc_layer0 (+ everything already accumulated in dup128, then conv2's relu') -> conv2 (duplicate_up's
-        # relu') in one launch
-        _lib.check(L.dispu_mlp_chain_grad(rm, 256, 128, 256, _p(dcoarse), 3, _p(P[cs + "fc_layer2/weights"]),
-                                          _p(PT[cs + "fc_layer1/weights"]), _p(PT[cs + "fc_layer0/weights"]), _p(PT[c2 + "/weights"]),
-                                          _p(ws["c64"]), 64, _p(ws["c256"]), 256, _p(ws["up128"]), 128, _p(dup128), 128,
-                                          _p(ws["dup128s"]) if split_skip else None, 128, _p(ws["dc64"]), 64, _p(ws["dc256"]), 256, _p(dup128), 128,
-                                          _p(ws["up256"]), None, None, 256, _p(ws["dup256"]), None, None, 256, self.st),
-                   "mlp_chain_grad[coarse]")
-        # the chain goes on first (d(up256) summed over the four copies -> the 480-wide product below); the head's four weight
-        # gradients are queued on the side streams after it
-        _lib.check(L.dispu_dup_sum_grad(B, N, 256, self.up_ratio, _p(ws["dup256"]), 256, _p(ws["dh256"]), 256, self.st), "dup_sum_grad")
-        w1, dw1 = P["generator/upshuffle_0/conv1/weights"], G["generator/upshuffle_0/conv1/weights"]
-        grp = self.sched.fork_group()
-        self._lin_bwd(ws["c64"], 0, 64, cs + "fc_layer2", 3, dcoarse, 0, after=grp)
-        self._lin_bwd(ws["c256"], 0, 256, cs + "fc_layer1", 64, ws["dc64"], 0, after=grp)
-        self._lin_bwd(ws["up128"], 0, 128, cs + "fc_layer0", 256, ws["dc256"], 0, after=grp)
-        self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0, after=grp)
-        self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
-                 dbias=G["generator/upshuffle_0/conv1/biases"], side=True, after=grp, wgrad=True)   # read by Adam only: off the chain like every other dW
-        feat, dfeat = ws["feat"], ws["dfeat"]
-        self._lin_bwd(feat, 0, 480, None, 256, ws["dh256"], 0, dfeat, 0, bias=False, W=w1, dW=dw1)
-
-        # dense blocks, last to first (every block has its own dE / dprep: the dW products on the second stream read them while
-        # the chain moves on, no join inside the loop)
-        fe = "generator/feature_extraction_coarse/"
-        for (d, C, col, in_col, width) in reversed(self._blocks):
-            sc = fe + "layer%d" % d
-            if d == 1:
-                dF, dfoff, F, foff = dfeat, 456, feat, 456
-            else:
-                dF, dfoff, F, foff = ws["dprep"][d], 0, ws["prep"][d], 0         # zero-filled in forward(), off the chain
-            # the block's backward on the chain; its weight-gradient partials (a scratch buffer per block) are summed on a side stream
-            need = L.dispu_edge_dense_conv_grad_scratch_floats(rn, C)
-            scr = self._scratch_floats(need, "edge%d" % d)
-            _lib.check(L.dispu_edge_dense_conv_grad_partials(rn, N, C, _p(F, foff), F.stride(0), _p(ws["kidx"][d]), k + 1, 1,
-                                                             _p(P[sc + "/l0/weights"]), _p(P[sc + "/l0/biases"]), _p(P[sc + "/l1/weights"]),
-                                                             _p(P[sc + "/l1/biases"]), _p(P[sc + "/l2/weights"]), _p(P[sc + "/l2/biases"]),
-                                                             _p(dfeat, col), 480, _p(dF, dfoff), dF.stride(0), _p(scr), scr.numel(), self.st),
-                       "edge_dense_conv_grad_partials")
+    def _backward_generator(self, s):
+        # coarse head and duplicate_up, then the dense blocks, last to first (every block has its own dE / dprep: the dW products on
+        # the second stream read them while the chain moves on, no join inside the loop)
+        sched = self.sched
+        self._bwd_coarse(s)
+        for blk in reversed(BLOCKS):
+            scr = self._bwd_block_partials(s, blk)
             # the block's recomputing backward kernel (40 - 80 us) is queued: submit some of the side work deferred so far behind it
             # (the coarse head's weight gradients, the previous blocks' reductions and prep gradients) -- a few launches per block,
             # as many as the kernel's duration hides
-            tail = d == 1 and self.overlap_dw
-            self.sched.flush(n=None if tail else 5)
-            def reduce_partials(sc=sc, scr=scr, C=C, ev=(self.sched.fork_point() if (self.overlap_dw and not tail) else None)):
-                st_r = self.sched.side_stream(ev)[0] if ev is not None else self.st
-                _lib.check(L.dispu_edge_dense_conv_grad_reduce(rn, C, _p(scr), scr.numel(), _p(G[sc + "/l0/weights"]), _p(G[sc + "/l0/biases"]),
-                                                               _p(G[sc + "/l1/weights"]), _p(G[sc + "/l1/biases"]), _p(G[sc + "/l2/weights"]),
-                                                               _p(G[sc + "/l2/biases"]), st_r), "edge_dense_conv_grad_reduce")
+            tail = blk[0] == 1 and self.overlap_dw
+            sched.flush(n=None if tail else 5)
+            reduce_partials = partial(self._bwd_block_reduce, s, blk, scr, sched.fork_point() if (self.overlap_dw and not tail) else None)
             if tail:
                 # the last block of the backward: everything deferred so far is on the side streams by now; this block's own
                 # reduction (and layer0's weight gradient below) follow their producer on the chain's stream -- Adam waits for
                 # them either way, and a hop to a side stream and back costs more than the two launches take
                 reduce_partials()
             else:
-                self.sched.defer(reduce_partials)
-            if d > 1:
-                self._act_bias_grad(rn, 48, dF, 0, ws["prep"][d], 0, 1, dF, 0, None)        # prep = relu(.): its mask (dF came from atomics)
-                self._lin_bwd(feat, in_col, 480 - in_col, fe + "layer%d_prep" % d, 48, dF, 0, dfeat, in_col, acc_dx=True)
+                sched.defer(reduce_partials)
+            self._bwd_block_prep(s, blk)
         # layer0 (no activation, input has no gradient)
-        self._lin_bwd(self._x.view(rn, 3), 0, 3, fe + "layer0", 24, dfeat, 456, None, side=False)
-        self.sched.join()                     # every dW is in the flat gradient buffer from here on (all-reduce, Adam)
+        self._lin_bwd(s.x.view(s.rn, 3), 0, 3, FE + "layer0", 24, s.ws["dfeat"], 456, None, side=False)
+
+    def _bwd_fine(self, s):
+        L, ws, rm = _lib.tape_lib(), s.ws, s.rm
+        # fine = coarse + sigmoid(z) - 0.5
+        _lib.check(L.dispu_sigmoid_offset_grad(rm * 3, _p(ws["z"]), _p(s.dfine), _p(ws["dz"]), _p(s.dcoarse), self.st), "sigmoid_grad")
+        ag = PS + "aggregation"
+        # fc_layer2 -> fc_layer1 -> fc_layer0 -> aggregation backward and the three branch masks of
+        # sum = relu(after) + relu(skip) + relu(nl) in ONE launch (csrc/mlp_chain_bwd.hip); the four dW products follow on the side streams
+        _lib.check(L.dispu_mlp_chain_grad(rm, 256, 256, 256, _p(ws["dz"]), 3, *self._chain_T(ag, FS),
+                                          _p(ws["f64"]), 64, _p(ws["f256"]), 256, _p(ws["agg"]), 256, None, 0, None, 0,
+                                          _p(ws["df64"]), 64, _p(ws["df256"]), 256, _p(ws["dagg"]), 256,
+                                          _p(ws["aft"]), _p(ws["skip"]), _p(ws["nl"]), 256, _p(ws["daft"]), _p(ws["dskip"]), _p(ws["dnl"]), 256,
+                                          self.st), "mlp_chain_grad[fine]")
+        grp = self.sched.fork_group()
+        self._lin_bwd(ws["f64"], 0, 64, FS + "fc_layer2", 3, ws["dz"], 0, after=grp)
+        self._lin_bwd(ws["f256"], 0, 256, FS + "fc_layer1", 64, ws["df64"], 0, after=grp)
+        self._lin_bwd(ws["agg"], 0, 256, FS + "fc_layer0", 256, ws["df256"], 0, after=grp)
+        self._lin_bwd(ws["sum"], 0, 256, ag, 256, ws["dagg"], 0, after=grp)
+
+    def _bwd_nonlocal(self, s):
+        L, ws, B, M = _lib.tape_lib(), s.ws, s.B, s.M
+        dup128 = ws["dup128"]
+        self._lin_bwd(ws["att"], 0, 64, PS + "PointShuffle/conv_back_project", 256, ws["dnl"], 0, ws["datt"])
+        S, dS, kv, dkv, q = ws["S"], ws["dS"], ws["kv"], ws["dkv"], ws["q"]
+        if s.path.attention == "flash":
+            # dQ, dK, dV with the probabilities recomputed tile by tile from Q, K and the forward's log-sum-exp: two launches
+            _lib.check(L.dispu_attention_bwd(B, M, M, 64, _p(q), 64, _p(kv), 128, _p(kv, 64), 128, 0.125, _p(ws["att"]), 64,
+                                             _p(ws["lse"]), _p(ws["datt"]), 64, _p(ws["dq"]), 64, _p(dkv), 128, _p(dkv, 64), 128,
+                                             _p(ws["dvec"]), self.st), "attention_bwd")
+        else:
+            # dP = dO . V^T
+            _lib.check(self._dl(B, M, 64, M, _p(ws["datt"]), 64, M * 64, _p(kv, 64), 128, M * 128, 1, None, 0, _p(dS), M, M * M,
+                                None, 0, 0, None, 0, 0, self.st), "dP")
+            # dV = P^T . dO  -> dkv[:, 64:128]
+            self._tn(B, M, M, 64, S, 0, M, M * M, ws["datt"], 0, 64, M * 64, dkv, 64, 128, M * 128, 0)
+            _lib.check(L.dispu_softmax_rows_grad(s.rm, M, 0.125, _p(S), M, _p(dS), M, self.st), "softmax_grad")
+            # dQ = dS . K
+            _lib.check(self._dl(B, M, M, 64, _p(dS), M, M * M, _p(kv), 128, M * 128, 0, None, 0, _p(ws["dq"]), 64, M * 64,
+                                None, 0, 0, None, 0, 0, self.st), "dQ")
+            # dK = dS^T . Q -> dkv[:, 0:64]
+            self._tn(B, M, M, 64, dS, 0, M, M * M, q, 0, 64, M * 64, dkv, 0, 128, M * 128, 0)
+        self._lin_bwd(ws["up128"], 0, 128, PS + "PointShuffle/conv_kv", 128, dkv, 0, dup128)
+        self._lin_bwd(ws["up128"], 0, 128, PS + "PointShuffle/conv_query", 64, ws["dq"], 0, dup128, 0, acc_dx=True)
+
+    def _bwd_skip(self, s):
+        ws = s.ws
+        self._lin_bwd(ws["gmax"], 0, 134, PS + "skip", 256, ws["dskip"], 0, ws["dgmax"])
+        if s.path.split_skip:                            # the skip branch's d(up128) in its own buffer, summed in the coarse chain
+            self._skip_max_grad(s, ws["dup128s"])
+
+    def _skip_max_grad(self, s, dup128):
+        ws = s.ws
+        _lib.check(_lib.tape_lib().dispu_ps_skip_max_grad(s.rm, s.M, K_NEIGH, 128, _p(ws["psidx"]), _p(s.coarse), _p(ws["up128"]), 128,
+                                                          _p(ws["gmax"]), 144, _p(ws["dgmax"]), 136, _p(s.dcoarse), _p(dup128), 128, 1, self.st),
+                   "ps_skip_max_grad")
+
+    def _bwd_local_product(self, s):
+        """the feature x weight product's gradient: dwv and dz1 -- with conv1's dX and conv0's gather in the same launch on the fused path"""
+        L, ws, rm = _lib.tape_lib(), s.ws, s.rm
+        if s.path.local_bwd == "fused":
+            # one launch: dwv, dz1 (for the side-stream dW1), dG (atomics into the zeroed buffer) and -dA; h1 / dz0 / wv stay on chip
+            self._zero(ws["dG"])
+            _lib.check(L.dispu_ps_local_grad(rm, s.M, _p(ws["psidx"]), _p(s.coarse), _p(ws["gm"]), 128, _p(ws["am"]), *self._w(PS + "conv1"),
+                                             _p(self.PT[PS + "conv1/weights"]), *self._w(PS + "weight_net/wconv0"), _p(ws["bn_scale"]),
+                                             _p(ws["bn_shift"]), _p(ws["dhp"]), _p(ws["dz1"]), _p(ws["dwv"]), _p(ws["dG"]), _p(ws["dAneg"]), self.st),
+                       "ps_local_grad")
+        else:
+            _lib.check(L.dispu_ps_point_matmul_grad_relu_s(rm, K_NEIGH, 128, 16, _p(ws["h1"]), 128, _p(ws["wv"]), _p(ws["dhp"]), 2048, _p(ws["dz1"]),
+                                                           128, _p(ws["dwv"]), 1 if ws["h1"].dtype == torch.bfloat16 else 0, self.st),
+                       "point_matmul_grad")
+
+    def _bwd_weight_net(self, s):
+        ws, P, G = s.ws, self.P, self.G
+        wn = PS + "weight_net/wconv0"
+        _lib.check(_lib.tape_lib().dispu_ps_wnet_grad(s.rm, s.M, K_NEIGH, 16, _p(ws["psidx"]), _p(s.coarse), *self._w(wn), _p(ws["bn_stats"]),
+                                                      _p(ws["bn_scale"]), _p(ws["bn_shift"]), _p(P[BN + "gamma"]), _p(ws["dwv"]), *self._w(wn, G),
+                                                      _p(G[BN + "gamma"]), _p(G[BN + "beta"]), _p(s.dcoarse), _p(ws["bn_sums"]),
+                                                      _p(self._bn_scratch), self._bn_scratch.numel() * 8, self.st), "ps_wnet_grad")
+
+    def _bwd_local_convs(self, s):
+        ws = s.ws
+        if s.path.local_bwd == "fused":
+            self._lin_bwd(ws["h0"], 0, 128, PS + "conv1", 128, ws["dz1"], 0, None)            # dW1, db1 only: the dX product ran inside the fused launch
+            return
+        self._lin_bwd(ws["h0"], 0, 128, PS + "conv1", 128, ws["dz1"], 0, ws["dz0"])      # dz0 holds dh0: conv0's relu' rides in the gather
+        # conv0 in its per-source-point form: dh0 * (G[j] - A[i] > 0) -> dG (gather through the inverted graph), -dA; then [B*M, 128] products
+        _lib.check(_lib.tape_lib().dispu_ps_conv0_gather_grad_s(s.rm, s.M, K_NEIGH, 128, _p(ws["psidx"]), _p(ws["inv_off"]), _p(ws["inv"]),
+                                                                _p(ws["dz0"]), 128, 1 if ws["dz0"].dtype == torch.bfloat16 else 0, _p(ws["gm"]), 128,
+                                                                _p(ws["am"]), 128, _p(ws["dG"]), 128, _p(ws["dAneg"]), 128, self.st),
+                   "conv0_gather_grad")
+
+    def _bwd_conv0(self, s):
+        ws, G = s.ws, self.G
+        w0, dw0 = self.P[PS + "conv0/weights"], G[PS + "conv0/weights"]
+        self._lin_bwd(ws["up128"], 0, 128, None, 128, ws["dG"], 0, ws["dup128"], 0, acc_dx=True, W=w0, dW=dw0, woff=6 * 128, bias=False,
+                      db=G[PS + "conv0/biases"])
+        _lib.check(_lib.tape_lib().dispu_ps_prep_grad(s.rm, 128, _p(s.coarse), _p(w0), _p(ws["dG"]), 128, _p(ws["dAneg"]), 128, _p(s.dcoarse),
+                                                      _p(dw0), self.st), "ps_prep_grad")
+
+    def _bwd_coarse(self, s):
+        # coarse regressor and duplicate_up
+        L, ws, G, rm = _lib.tape_lib(), s.ws, self.G, s.rm
+        c2, dup128, dcoarse = UP + "conv2", ws["dup128"], s.dcoarse
+        # fc_layer2 -> fc_layer1 -> fc_layer0 (+ everything already accumulated in dup128, then conv2's relu') -> conv2 (duplicate_up's
+        # relu') in one launch
+        _lib.check(L.dispu_mlp_chain_grad(rm, 256, 128, 256, _p(dcoarse), 3, *self._chain_T(c2, CS),
+                                          _p(ws["c64"]), 64, _p(ws["c256"]), 256, _p(ws["up128"]), 128, _p(dup128), 128,
+                                          _p(ws["dup128s"]) if s.path.split_skip else None, 128, _p(ws["dc64"]), 64, _p(ws["dc256"]), 256, _p(dup128), 128,
+                                          _p(ws["up256"]), None, None, 256, _p(ws["dup256"]), None, None, 256, self.st),
+                   "mlp_chain_grad[coarse]")
+        # the chain goes on first (d(up256) summed over the four copies -> the 480-wide product below); the head's four weight
+        # gradients are queued on the side streams after it
+        _lib.check(L.dispu_dup_sum_grad(s.B, s.N, 256, self.up_ratio, _p(ws["dup256"]), 256, _p(ws["dh256"]), 256, self.st), "dup_sum_grad")
+        w1, dw1 = self.P[UP + "conv1/weights"], G[UP + "conv1/weights"]
+        grp = self.sched.fork_group()
+        self._lin_bwd(ws["c64"], 0, 64, CS + "fc_layer2", 3, dcoarse, 0, after=grp)
+        self._lin_bwd(ws["c256"], 0, 256, CS + "fc_layer1", 64, ws["dc64"], 0, after=grp)
+        self._lin_bwd(ws["up128"], 0, 128, CS + "fc_layer0", 256, ws["dc256"], 0, after=grp)
+        self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0, after=grp)
+        self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
+                 dbias=G[UP + "conv1/biases"], side=True, after=grp, wgrad=True)   # read by Adam only: off the chain like every other dW
+        self._lin_bwd(ws["feat"], 0, 480, None, 256, ws["dh256"], 0, ws["dfeat"], 0, bias=False, W=w1, dW=dw1)
+
+    def _bwd_block_partials(self, s, blk):
+        # the block's backward on the chain; its weight-gradient partials (a scratch buffer per block) are summed on a side stream
+        d, C, col, _, _ = blk
+        L, ws, rn = _lib.tape_lib(), s.ws, s.rn
+        F, dF, off = (ws["feat"], ws["dfeat"], 456) if d == 1 else (ws["prep"][d], ws["dprep"][d], 0)      # (dprep: zero-filled in forward(), off the chain)
+        scr = self._scratch_floats(L.dispu_edge_dense_conv_grad_scratch_floats(rn, C), "edge%d" % d)
+        _lib.check(L.dispu_edge_dense_conv_grad_partials(rn, s.N, C, _p(F, off), F.stride(0), _p(ws["kidx"][d]), K_NEIGH + 1, 1, *self._dense_w(d),
+                                                         _p(ws["dfeat"], col), 480, _p(dF, off), dF.stride(0), _p(scr), scr.numel(), self.st),
+                   "edge_dense_conv_grad_partials")
+        return scr
+
+    def _bwd_block_reduce(self, s, blk, scr, ev):
+        st_r = self.sched.side_stream(ev)[0] if ev is not None else self.st
+        _lib.check(_lib.tape_lib().dispu_edge_dense_conv_grad_reduce(s.rn, blk[1], _p(scr), scr.numel(), *self._dense_w(blk[0], self.G), st_r),
+                   "edge_dense_conv_grad_reduce")
+
+    def _bwd_block_prep(self, s, blk):
+        d, _, _, in_col, _ = blk
+        if d > 1:
+            F, dF = s.ws["prep"][d], s.ws["dprep"][d]
+            self._act_bias_grad(s.rn, 48, dF, 0, F, 0, 1, dF, 0, None)        # prep = relu(.): its mask (dF came from atomics)
+            self._lin_bwd(s.ws["feat"], in_col, 480 - in_col, FE + "layer%d_prep" % d, 48, dF, 0, s.ws["dfeat"], in_col, acc_dx=True)
 
     # -------------------------------------------------------------------------------------------------- step ----
     def _backward_prep(self, ws):

@@ -327,7 +327,7 @@ def test_loss_decreases(dev):
 
 @pytest.mark.parametrize("dtype,B", [("f32", 4), ("bf16", 4), ("f32", 3), ("f32", 8)])
 def test_weight_gradients_on_second_stream(dev, dtype, B):
-    """The dW products of a step run on a second HIP stream next to the dX chain (train.py:_fork/_join).  Same kernels, same
+    """The dW products of a step run on a second HIP stream next to the dX chain (schedule.py:StepSchedule.fork_point / side_stream / join).  Same kernels, same
     operands: the gradients equal the single-stream step's up to the order-free fp32 atomics of the scatter gradients
     (max_k / group / nn_distance, like the reference's) -- 1e-5 of each tensor's largest entry, run to run as well."""
     from dispu_amd import synth

@@ -76,6 +76,13 @@ def test_step_takes_the_path_it_was_chosen_for(case):
     assert (rec.count("dispu_linear_splitk_finish") == 0) == ((B, N) in NO_SPLITK)
     assert (tr.defer_side is False) == ((B, N) == (68, 64))
     assert rec.count("dispu_attention_fwd_lse") == 1 and rec.count("dispu_attention_bwd") == 1
+    # ... and Trainer.path states the same, without a device
+    path = tr.path(B, N)
+    assert path.stem == (rec.count("dispu_stem_block") == 4)
+    assert path.after_split == (0 if rec.count("dispu_linear_splitk_finish") == 0 else 8) and (path.after_split == 0) == ((B, N) in NO_SPLITK)
+    assert path.defer_side is tr.defer_side
+    assert path.attention == "flash" and path.local_bwd == "pair" and rec.count("dispu_ps_local_grad") == 0
+    assert path.split_skip and rec.count("dispu_ps_skip_max_grad") == 1
 
 
 def test_training_forward(case):
