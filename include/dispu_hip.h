@@ -59,7 +59,8 @@ extern "C" {
  * (dispu_geodesic_*), the ragged-batch entries (dispu_fps_segments, dispu_knn_patch_segments, dispu_normalize_segments) and the
  * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32), and the large-cloud sampling (dispu_fps_cells*,
  * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*), and the outlier filters (dispu_knn_mean_dist_*,
- * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*): additions only. */
+ * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*), and the cross-cloud search with the attribute transfer
+ * (dispu_knn_cross_*, dispu_transfer_attributes_segments): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -1030,6 +1031,36 @@ size_t dispu_compact_scratch_bytes(int C, const int* off_host);
 int dispu_compact_segments(int C, const int* off, const int* off_host, const float* cloud, int rule, const void* src, const double* stats,
                            int min_neighbors, const int* status, float* out_points, int* out_index, int* new_off, void* scratch,
                            size_t scratch_bytes, void* stream);
+
+/* ---- exact k-NN from one cloud into another, and per-point attributes carried across it: csrc/attributes.hip, dis-pu_amd/attributes.py.
+ * The reference interpolates over the three neighbours of a brute-force search (Common/pointnet_util.py:204-208); this is that
+ * interpolation at any k <= 32 on exact neighbours, for clouds of scan size.  C <= 65535 segments; segment c has q_c queries and m_c
+ * reference points, 1 <= q_c, m_c <= 2^24; queries [sum q_c, 3] and refs [sum m_c, 3] are packed, qoff / roff [C+1] device offsets,
+ * qoff_host / roff_host the same on the host; neighbourhoods never cross segments.  The neighbour rule is the project's: for query i of
+ * segment c the k' = min(k, m_c) reference points of segment c with the smallest (d2 bits, local reference index),
+ * d2 = ((dx*dx + dy*dy) + dz*dz) in fp32 (DISPU_ARITH_PLAIN); a reference point equal to the query counts like any other; 1 <= k <= 32.
+ * Both sides go through the Morton-cell pre-pass of dispu_fps_cells; one wave per cell of 64 queries walks the reference segment's box
+ * table and skips a cell only when its lower bound exceeds the k-th distance, so the result is exact whatever the geometry.
+ * status [C] (device): 0, or 1 for a segment whose queries or references hold a NaN or an infinite coordinate, for which nothing else is
+ * written.  scratch: 16-byte aligned, at least dispu_knn_cross_scratch_bytes (0 for an illegal C, illegal offsets or a segment above
+ * 2^24 points); the library never allocates; a refusal (hipErrorInvalidValue) touches no output.  Ordinary stores, no float atomics,
+ * identical bytes from run to run.  The yardstick is tests/attributes_oracle.py.  Additions only: dispu_version() stays 5. ----------- */
+size_t dispu_knn_cross_scratch_bytes(int C, const int* qoff_host, const int* roff_host);
+/* idx_out [sum q_c, k] int32: the neighbours' local reference indices in ascending key order, -1 beyond k';  d2_out [sum q_c, k] float:
+ * their d2, +inf beyond k'.  Either may be NULL, not both.  sum q_c * k >= 2^31 is refused. */
+int dispu_knn_cross_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k,
+                             const float* queries, const float* refs, int* idx_out, float* d2_out, int* status, void* scratch,
+                             size_t scratch_bytes, void* stream);
+/* The same search with the transfer done in the kernel: no [sum q_c, k] tensor reaches memory.  feat [sum m_c, F] float row-major,
+ * F >= 1 -> out_feat [sum q_c, F];  labels [sum m_c] int32 -> out_labels [sum q_c];  either pair may be NULL, not both.
+ * mode 0, inverse-distance weights in double:  w_j = 1.0 / max((double)d2_j, 1e-10),  den = sum_j w_j,  num_f = sum_j w_j *
+ * (double)feat[r_j][f], both added in ascending rank over the k' neighbours,  out_feat = (float)(num_f / den); every operation is one
+ * IEEE double operation, so the value can be reproduced bit for bit.  mode 1: the row of the rank-0 neighbour.  Labels always take the
+ * rank-0 neighbour's label (ties in d2 go to the smallest index).  Feature values are not inspected: a NaN propagates.
+ * mode outside {0, 1}, F < 1 or sum q_c * max(F, k) >= 2^31 is refused. */
+int dispu_transfer_attributes_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, int mode,
+                                       const float* queries, const float* refs, int F, const float* feat, float* out_feat,
+                                       const int* labels, int* out_labels, int* status, void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

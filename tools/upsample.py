@@ -22,7 +22,14 @@ renormalised, and a cube whose normals cancel orients nothing).
 reference has no counterpart): statistical removes the points whose mean distance to their --outliers_k nearest neighbours exceeds the
 cloud's mean + --outliers_std standard deviations of it, radius those with fewer than --outliers_min other points within
 --outliers_radius.  Input cleaning runs first of all (before --grid_size; with --orient input the input normals follow the kept
-points): one stray point shrinks its whole normalised patch.  Output cleaning runs on the upsampled cloud, before --normals."""
+points): one stray point shrinks its whole normalised patch.  Output cleaning runs on the upsampled cloud, before --normals.
+
+--attributes idw|nearest (off by default) carries per-point attributes (colour, intensity, labels) onto the output: every column beyond
+the third of each input file is an attribute, and each output point takes the inverse-distance weighted mean over its --attributes_k
+nearest points of the RAW input file (idw), or the row of the nearest one (nearest: labels stay labels), found by an exact search on
+the GPU (dis-pu_amd/attributes.py; the reference has no counterpart).  The sources are the file's points before --clean_input and
+--grid_size; the transfer runs after --clean_output and before --normals.  Output rows are x y z a1 .. aF [nx ny nz].  Not together
+with --orient input, which reads columns 4-6 as normals."""
 import argparse
 import glob
 import math
@@ -67,6 +74,20 @@ def load_xyz_normals(path):
 def save_xyz_normals(path, points, normals):
     """rows x y z nx ny nz at %.6f"""
     np.savetxt(path, np.concatenate([np.asarray(points, np.float32), np.asarray(normals, np.float32)], axis=1), fmt="%.6f")
+
+
+def load_xyz_attributes(path):
+    """(points [n, 3], attributes [n, F]) float32 of an .xyz file with rows x y z a1 .. aF, F >= 1; ValueError naming a file with only
+    three columns (or fewer)."""
+    rows = np.loadtxt(path, ndmin=2).astype(np.float32)
+    if rows.shape[1] < 4:
+        raise ValueError("%s: --attributes needs at least one column beyond x y z, got %d columns" % (path, rows.shape[1]))
+    return np.ascontiguousarray(rows[:, :3]), np.ascontiguousarray(rows[:, 3:])
+
+
+def save_xyz_columns(path, points, *more):
+    """rows x y z and then every further block of columns, at %.6f"""
+    np.savetxt(path, np.concatenate([np.asarray(points, np.float32)] + [np.asarray(m, np.float32) for m in more], axis=1), fmt="%.6f")
 
 
 def group_by_budget(sizes, max_points):
@@ -122,6 +143,11 @@ def parse_args(argv=None):
     ap.add_argument("--outliers_std", type=float, default=2.0, help="statistical: keep up to mean + this many standard deviations")
     ap.add_argument("--outliers_radius", type=positive_float, default=None, help="radius: the search radius (needed by `radius`)")
     ap.add_argument("--outliers_min", type=int, default=2, help="radius: keep points with at least this many others within the radius")
+    ap.add_argument("--attributes", choices=("none", "idw", "nearest"), default="none",
+                    help="carry every input column beyond x y z onto the output points: idw (inverse-distance weighted mean over the "
+                         "--attributes_k nearest raw input points) or nearest (the nearest one's row; for labels); the output rows are "
+                         "x y z a1 .. aF [nx ny nz]; not together with --orient input, which reads columns 4-6 as normals")
+    ap.add_argument("--attributes_k", type=int, default=3, help="neighbours per output point of --attributes, 1 .. 32")
     a = ap.parse_args(argv)
     if "radius" in (a.clean_input, a.clean_output) and a.outliers_radius is None:
         ap.error("--clean_input / --clean_output radius need --outliers_radius R")
@@ -139,6 +165,10 @@ def parse_args(argv=None):
         ap.error("--orient viewpoint and --viewpoint X Y Z go together")
     if a.viewpoint is not None and not all(math.isfinite(v) for v in a.viewpoint):
         ap.error("--viewpoint must be finite")
+    if not 1 <= a.attributes_k <= 32:
+        ap.error("--attributes_k must be in 1 .. 32, got %d" % a.attributes_k)
+    if a.attributes != "none" and a.orient == "input":
+        ap.error("--attributes and --orient input do not go together: columns 4-6 would be both attributes and normals")
     return a
 
 
@@ -156,6 +186,24 @@ def remove_outliers(kind, arrays, a, dev):
         kept += [t.cpu().numpy() for t in pts]
         index += [t.cpu().numpy() for t in idx]
     return kept, index
+
+
+def transfer_attributes(preds, src_points, src_attrs, a, dev):
+    """the --attributes step: numpy attributes [len(pred), F] for every cloud of `preds` from its raw input (points, attributes), in
+    groups of at most --max-points output points; clouds of one group with different column counts go in separate calls"""
+    import torch
+    from dispu_amd import attributes
+    out = [None] * len(preds)
+    for group in group_by_budget([p.shape[0] for p in preds], a.max_points):
+        for F in sorted({src_attrs[i].shape[1] for i in group}):
+            same = [i for i in group if src_attrs[i].shape[1] == F]
+            got = attributes.transfer_attributes([torch.from_numpy(np.ascontiguousarray(preds[i], np.float32)).to(dev) for i in same],
+                                                 [torch.from_numpy(src_points[i]).to(dev) for i in same],
+                                                 features=[torch.from_numpy(src_attrs[i]).to(dev) for i in same], k=a.attributes_k,
+                                                 mode=a.attributes)
+            for i, t in zip(same, got):
+                out[i] = t.cpu().numpy()
+    return out
 
 
 def main(argv=None):
@@ -177,6 +225,12 @@ def main(argv=None):
             clouds, in_normals = (list(t) for t in zip(*[load_xyz_normals(p) for p in paths]))
         except ValueError as e:
             sys.exit(str(e))
+    elif a.attributes != "none":
+        try:
+            clouds, src_attrs = (list(t) for t in zip(*[load_xyz_attributes(p) for p in paths]))
+        except ValueError as e:
+            sys.exit(str(e))
+        src_points = list(clouds)                       # the raw file's points: --clean_input and --grid_size replace clouds[i], not these
     else:
         clouds = [load_xyz(p) for p in paths]
 
@@ -235,6 +289,11 @@ def main(argv=None):
             for i, before, after in zip(group, preds, cleaned):
                 removed_out[i] = before.shape[0] - after.shape[0]
             preds = cleaned
+        if a.attributes != "none":
+            try:
+                attrs = transfer_attributes(preds, [src_points[i] for i in group], [src_attrs[i] for i in group], a, dev)
+            except ValueError as e:
+                sys.exit("%s: --attributes: %s" % (", ".join(paths[i] for i in group), e))
         if a.normals == "pca":
             from dispu_amd.normals import estimate_normals
             dpred = [torch.from_numpy(p).to(dev) for p in preds]
@@ -252,7 +311,9 @@ def main(argv=None):
                 sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
         for j, (i, pred) in enumerate(zip(group, preds)):
             out = os.path.join(out_dir, output_name(paths[i], a.final_ratio))
-            if a.normals == "pca":
+            if a.attributes != "none":
+                save_xyz_columns(out, pred, attrs[j], *([normals[j]] if a.normals == "pca" else []))
+            elif a.normals == "pca":
                 save_xyz_normals(out, pred, normals[j])
             else:
                 save_xyz(out, pred)
