@@ -21,8 +21,10 @@ POISSON_MAX_ROUNDS = 256    # include/dispu_hip.h: DISPU_POISSON_MAX_ROUNDS
 SORT_ROWS_MAX_K = 4096      # dispu_sort_rows_i32
 RADIX_TILE = 2048           # include/dispu_hip.h: DISPU_RADIX_TILE
 GRID_NONFINITE, GRID_AXIS_X, GRID_AXIS_Y, GRID_AXIS_Z, GRID_TOO_MANY_POINTS = 1, 2, 3, 4, 5   # include/dispu_hip.h: DISPU_GRID_*
+ORIENT_HOST_ROUNDS = 1      # include/dispu_hip.h: DISPU_ORIENT_HOST_ROUNDS (flags of dispu_orient_consistent_segments)
+ORIENT_PROFILE_FLOATS = 8   # include/dispu_hip.h: DISPU_ORIENT_PROFILE_FLOATS
 
-_vp, _i, _sz, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_long
+_vp, _i, _sz, _l =C.c_void_p, C.c_int, C.c_size_t, C.c_long
 
 # name -> (restype, argtypes); must list every symbol of include/dispu_hip.h (tests check this)
 SIGNATURES = {
@@ -41,6 +43,8 @@ SIGNATURES = {
     "dispu_fps_cells_wanted": (_i, [_i, _i]),
     "dispu_pca_normals_scratch_bytes": (_sz, [_i, _vp, _i]),
     "dispu_pca_normals_segments": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_orient_consistent_scratch_bytes": (_sz, [_i, _vp, _i]),
+    "dispu_orient_consistent_segments": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dispu_knn_mean_dist_scratch_bytes": (_sz, [_i, _vp, _i]),
     "dispu_knn_mean_dist_segments": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_radius_count_scratch_bytes": (_sz, [_i, _vp]),

@@ -5,7 +5,11 @@ x y z; what leaves the upsampler needs a normal per point for surface reconstruc
 The neighbourhood of a point is the k' = min(k, n) points of its own cloud with the smallest (d2, index), d2 in plain fp32 arithmetic,
 the point itself included: pc_util.py:83-92's k-NN made deterministic, the rule of upsample.knn_patch_segments.  The normal is the
 eigenvector of the smallest eigenvalue of the neighbourhood's covariance, computed in double around the point itself, so a scan at
-large coordinates with fine structure loses nothing.  The yardstick is tests/normals_oracle.py."""
+large coordinates with fine structure loses nothing.  The yardstick is tests/normals_oracle.py.
+
+orient_consistent makes the signs agree from point to point on shapes where no pointwise rule can (a torus, a handle): propagation
+along the minimum spanning forest of the neighbour graph (csrc/orient_consistent.hip, dispu_orient_consistent_segments; the yardstick
+is tests/orient_oracle.py)."""
 import numpy as np
 import torch
 
@@ -29,12 +33,26 @@ def _check_cloud(t, what):
     req(t.dim() == 2 and t.shape[1] == 3, "%s: expected an [n, 3] tensor, got shape %s" % (what, tuple(t.shape)))
 
 
+def _split_consistent(orient):
+    """('consistent',) or ('consistent', prior) -> (True, prior); any other orient -> (False, orient)"""
+    if not (isinstance(orient, (tuple, list)) and len(orient) >= 1 and isinstance(orient[0], str) and orient[0] == "consistent"):
+        return False, orient
+    req(len(orient) <= 2, "('consistent',) or ('consistent', prior) takes at most one argument")
+    prior = orient[1] if len(orient) == 2 else None
+    if len(orient) == 2:
+        req(isinstance(prior, (tuple, list)) and len(prior) >= 1 and isinstance(prior[0], str) and prior[0] in ORIENT_FORMS,
+            "the prior of ('consistent', prior) must be ('viewpoint', xyz), ('centroid',) or ('reference', ref_points, ref_normals), "
+            "got %r" % (prior,))
+    return True, prior
+
+
 def _check_orient(orient, clouds):
     """-> the form's name (or None) after every check that needs no launch"""
     if orient is None:
         return None
-    req(isinstance(orient, (tuple, list)) and len(orient) >= 1 and orient[0] in ORIENT_FORMS,
-        "orient must be None, ('viewpoint', xyz), ('centroid',) or ('reference', ref_points, ref_normals), got %r" % (orient,))
+    req(isinstance(orient, (tuple, list)) and len(orient) >= 1 and isinstance(orient[0], str) and orient[0] in ORIENT_FORMS,
+        "orient must be None, ('viewpoint', xyz), ('centroid',), ('reference', ref_points, ref_normals), ('consistent',) or "
+        "('consistent', prior), got %r" % (orient,))
     form, C = orient[0], len(clouds)
     if form == "centroid":
         req(len(orient) == 1, "('centroid',) takes no argument")
@@ -79,6 +97,9 @@ def estimate_normals(points, k=16, orient=None, return_variation=False, return_n
             ("centroid",) -- outwards, away from the cloud's mean (closed objects);
             ("reference", ref_points, ref_normals) -- in agreement with the normal of the nearest reference point (tensors, or lists
             of them, one pair per cloud).  Where the direction is orthogonal to the normal the sign of orient=None stays.
+            ("consistent",) -- signs that agree from point to point on any shape: orient_consistent(vote="anchor") on the orient=None
+            normals and the neighbours of this search;  ("consistent", prior), prior any of the three forms above -- the normals of
+            the prior, then orient_consistent(vote="majority"): consistent, and facing the way most of the prior does.
     return_variation: also the surface variation max(l0, 0) / (l0 + l1 + l2) [n] of the covariance's eigenvalues l0 <= l1 <= l2.
     return_neighbors: also the neighbours' indices [n, k] int32 in ascending (distance, index) order, -1 beyond min(k, n).
     Returns the normals, or a tuple (normals, variation, neighbors) with the parts asked for, in that order.
@@ -98,6 +119,8 @@ def estimate_normals(points, k=16, orient=None, return_variation=False, return_n
     sizes = [int(c.shape[0]) for c in clouds]
     total = sum(sizes)
     req(total * max(k, 3) < 2 ** 31, "a packed batch holds at most 2^31 - 1 output words, got %d points at k = %d" % (total, k))
+    consistent, orient = _split_consistent(orient)
+    want_neighbors, return_neighbors = return_neighbors, return_neighbors or consistent
     form = _check_orient(orient, clouds)
 
     dev = clouds[0].device
@@ -131,6 +154,9 @@ def estimate_normals(points, k=16, orient=None, return_variation=False, return_n
                                                 _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)), "dispu_pca_normals_segments")
         bad = np.nonzero(status.cpu().numpy())[0]
     req(len(bad) == 0, "cloud %d holds a NaN or an infinite coordinate" % (int(bad[0]) if len(bad) else -1))
+    if consistent:                                           # a prior keeps its overall direction: the majority decides per component
+        normal = _orient_launch(cloud, normal, neighbors, off, k, 0 if orient is None else 1, False, False)[0]
+        return_neighbors = want_neighbors
 
     def split(t):
         return t if single else [t[off[c]:off[c + 1]] for c in range(C)]
@@ -140,4 +166,103 @@ def estimate_normals(points, k=16, orient=None, return_variation=False, return_n
         res.append(split(variation))
     if return_neighbors:
         res.append(split(neighbors))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+VOTES = ("anchor", "majority")
+_STATUS_TEXT = ((1, "holds a NaN or an infinite normal"), (2, "holds a neighbour index outside -1 .. n - 1"),
+                (4, "did not converge (an iteration cap was reached)"))
+
+
+def _orient_launch(cloud, normal, neighbors, off, k, vote, want_flip, want_component):
+    """dispu_orient_consistent_segments on a packed batch (contiguous device tensors, host offsets) -> (normal_out, flip, component,
+    n_components); ValueError for a flagged cloud"""
+    dev, C, total = cloud.device, len(off) - 1, int(off[-1])
+    with torch.cuda.device(dev):
+        L = _lib.lib()
+        nbytes = L.dispu_orient_consistent_scratch_bytes(C, _host_ptr(off), k)
+        req(nbytes > 0, "dispu_orient_consistent_segments refuses these clouds")
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        d_off = torch.from_numpy(off).to(dev)
+        out = torch.empty((total, 3), dtype=torch.float32, device=dev)
+        flip = torch.zeros((total,), dtype=torch.uint8, device=dev) if want_flip else None
+        component = torch.zeros((total,), dtype=torch.int32, device=dev) if want_component else None
+        ncomp = torch.zeros((C,), dtype=torch.int32, device=dev) if want_component else None
+        status = torch.zeros((C,), dtype=torch.int32, device=dev)
+        _lib.check(L.dispu_orient_consistent_segments(C, _lib.ptr(d_off), _host_ptr(off), k, _lib.ptr(cloud), _lib.ptr(normal),
+                                                      _lib.ptr(neighbors), vote, 0, _lib.ptr(out), _lib.ptr(flip), _lib.ptr(component),
+                                                      _lib.ptr(ncomp), _lib.ptr(status), _lib.ptr(scratch), nbytes, None,
+                                                      _lib.stream_ptr(dev)),
+                   "dispu_orient_consistent_segments")
+        st = status.cpu().numpy()
+    bad = np.nonzero(st)[0]
+    if len(bad):
+        c, bits = int(bad[0]), int(st[bad[0]])
+        req(False, "cloud %d %s" % (c, " and ".join(text for bit, text in _STATUS_TEXT if bits & bit)))
+    return out, flip, component, ncomp
+
+
+def orient_consistent(points, normals, k=16, neighbors=None, vote="anchor", return_flips=False, return_components=False):
+    """Signs that agree from point to point (Hoppe et al. 1992): the sign is propagated along the minimum spanning forest of the k-NN
+    graph weighted by 1 - |n_u . n_v| (csrc/orient_consistent.hip, dispu_orient_consistent_segments in include/dispu_hip.h; the
+    yardstick is tests/orient_oracle.py).  The result is a pure function of the input: the forest is unique under the header's edge order.
+
+    points, normals: float32 [n, 3] tensors on a ROCm device, or lists of them (one packed launch sequence; 1 .. 2^24 points per cloud,
+    at most 65535 clouds).  Normals of any sign; a zero normal is carried along and never counts in a vote.
+    neighbors: int32 [n, k] local indices as estimate_normals(return_neighbors=True) returns them (-1 and the row's own index are
+    ignored), or lists of them; None: the lists of the exact search at k.  4 <= k <= 32; with neighbors given k must be their width.
+    vote: "anchor" -- per connected component the point with the largest (z, y, x) keeps or turns its normal so that the first non-zero
+    of (nz, ny, nx) is positive (on a closed surface: outwards), and the rest follows;  "majority" -- of the two consistent choices the one
+    that turns fewer normals: for input that already has a direction (a viewpoint, a centroid, a reference).
+    Returns the oriented normals; with return_flips also the flip bytes [n] uint8; with return_components also the component of every
+    point [n] int32 (the lowest index of its component) and the number of components (an int, or a list of ints), in that order.
+    ValueError for illegal arguments (before any launch) and for a cloud with a non-finite normal or an illegal index (after it)."""
+    single = isinstance(points, torch.Tensor)
+    clouds = [points] if single else list(points) if isinstance(points, (list, tuple)) else None
+    req(clouds is not None, "points must be a float32 [n, 3] tensor on a ROCm device or a list of them, got %s" % type(points).__name__)
+    nrms = [normals] if isinstance(normals, torch.Tensor) else list(normals) if isinstance(normals, (list, tuple)) else None
+    req(nrms is not None and isinstance(normals, torch.Tensor) == single, "normals must be a tensor or a list, as points is")
+    req(1 <= len(clouds) <= MAX_CLOUDS, "1 .. %d clouds per call, got %d" % (MAX_CLOUDS, len(clouds)))
+    req(len(nrms) == len(clouds), "%d clouds and %d sets of normals" % (len(clouds), len(nrms)))
+    req(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and K_MIN <= k <= K_MAX,
+        "k must be an integer in %d .. %d, got %r" % (K_MIN, K_MAX, k))
+    k = int(k)
+    req(isinstance(vote, str) and vote in VOTES, "vote must be 'anchor' or 'majority', got %r" % (vote,))
+    for i, (c, m) in enumerate(zip(clouds, nrms)):
+        _check_cloud(c, "cloud %d" % i)
+        _check_cloud(m, "normals %d" % i)
+        req(1 <= c.shape[0] <= MAX_POINTS, "cloud %d has %d points, expected 1 .. 2^24" % (i, c.shape[0]))
+        req(m.shape == c.shape, "cloud %d has %d points and %d normals" % (i, c.shape[0], m.shape[0]))
+        req(c.device == clouds[0].device and m.device == clouds[0].device, "cloud %d lives on another device than cloud 0" % i)
+    sizes = [int(c.shape[0]) for c in clouds]
+    total, C = sum(sizes), len(clouds)
+    req(total * k < 2 ** 31, "a packed batch holds at most 2^31 - 1 neighbour slots, got %d points at k = %d" % (total, k))
+    if neighbors is not None:
+        nbs = [neighbors] if isinstance(neighbors, torch.Tensor) else list(neighbors) if isinstance(neighbors, (list, tuple)) else None
+        req(nbs is not None and isinstance(neighbors, torch.Tensor) == single and len(nbs) == C,
+            "neighbors must be a tensor or a list of %d tensors, as points is" % C)
+        for i, (b, n) in enumerate(zip(nbs, sizes)):
+            req(isinstance(b, torch.Tensor) and b.is_cuda and b.device == clouds[0].device and b.dtype == torch.int32,
+                "neighbors %d must be an int32 tensor on the clouds' device" % i)
+            req(tuple(b.shape) == (n, k), "neighbors %d: expected shape (%d, %d), got %s" % (i, n, k, tuple(b.shape)))
+    else:
+        nbs = estimate_normals(clouds, k=k, return_neighbors=True)[1]
+    off = np.zeros(C + 1, np.int32)
+    np.cumsum(sizes, out=off[1:])
+
+    def pack(ts):
+        return (ts[0] if C == 1 else torch.cat(list(ts))).contiguous()
+
+    out, flip, component, ncomp = _orient_launch(pack(clouds), pack(nrms), pack(nbs), off, k, VOTES.index(vote), return_flips,
+                                                 return_components)
+
+    def split(t):
+        return t if single else [t[off[c]:off[c + 1]] for c in range(C)]
+
+    res = [split(out)]
+    if return_flips:
+        res.append(split(flip))
+    if return_components:
+        counts = [int(v) for v in ncomp.cpu().numpy()]
+        res += [split(component), counts[0] if single else counts]
     return res[0] if len(res) == 1 else tuple(res)

@@ -60,7 +60,7 @@ extern "C" {
  * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32), and the large-cloud sampling (dispu_fps_cells*,
  * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*), and the outlier filters (dispu_knn_mean_dist_*,
  * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*), and the cross-cloud search with the attribute transfer
- * (dispu_knn_cross_*, dispu_transfer_attributes_segments): additions only. */
+ * (dispu_knn_cross_*, dispu_transfer_attributes_segments), and the consistent orientation (dispu_orient_consistent_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -1061,6 +1061,39 @@ int dispu_knn_cross_segments(int C, const int* qoff, const int* qoff_host, const
 int dispu_transfer_attributes_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, int mode,
                                        const float* queries, const float* refs, int F, const float* feat, float* out_feat,
                                        const int* labels, int* out_labels, int* status, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- consistent normal orientation, csrc/orient_consistent.hip, dis-pu_amd/normals.py:orient_consistent (Hoppe et al. 1992): the sign
+ * is propagated along the minimum spanning forest of the k-NN graph.  The reference has no counterpart.  Batches as for
+ * dispu_pca_normals_segments: C <= 65535 clouds of 1 <= n_c <= 2^24 points packed in points / normal_in [sum n_c, 3] and neighbors
+ * [sum n_c, k] (int32 LOCAL indices, as dispu_pca_normals_segments' idx_out), 4 <= k <= 32, sum n_c * k < 2^31; off [C+1] on the device,
+ * off_host the same on the host.  An entry of neighbors equal to -1 or to its own row is ignored; duplicates are harmless.
+ * Edges: the undirected union of the lists.  dot = (nx_u*nx_v + ny_u*ny_v) + nz_u*nz_v in fp32, one rounding per operation
+ * (DISPU_ARITH_PLAIN);  w = max(0, 1 - |dot|) in fp32;  s(e) = [dot < 0].  Edges are strictly ordered by (bits of w as unsigned,
+ * min(u, v), max(u, v)); under a strict order the minimum spanning forest is unique, so the result does not depend on the algorithm
+ * (here: Boruvka rounds with a parity union-find, integer min / max / add atomics only).
+ * flip[x] = XOR of s(e) along the forest path from x to its component's anchor, XOR the anchor's own flip.  The anchor is the
+ * component's point with the largest (z, y, x), compared as fp32 in that order, ties to the lowest index.  vote 0: the anchor is flipped
+ * iff the first non-zero of (nz, ny, nx) of its input normal is negative.  vote 1: of the two global choices for the component the one
+ * that flips fewer points with a non-zero normal; on a tie the choice of vote 0.
+ * normal_out [sum n_c, 3] = normal_in with its three components negated where flip is set (it must not be normal_in);  flip [sum n_c]
+ * bytes;  component [sum n_c] = the lowest local index of the point's component;  n_components [C];  any of the last three may be NULL.
+ * status [C] (device): 0, or a sum of 1 (a NaN or an infinite normal), 2 (a neighbour index outside [-1, n_c)), 4 (a pointer-chasing
+ * loop reached its iteration cap: cannot happen under the strict order, and nothing ever spins); for a segment with status != 0 no
+ * other output is written, and the other segments are exact (an illegal index is never followed).
+ * flags: 0, or DISPU_ORIENT_HOST_ROUNDS: end the rounds by one 4-byte read-back per round instead of the device-side counter that
+ * makes the remaining launches return at once (same results; the call then synchronises the stream).
+ * profile_host: NULL, or DISPU_ORIENT_PROFILE_FLOATS host floats; the call then times its phases with events and synchronises:
+ * [0] rounds that hooked an edge, [1] setup ms, [2] propose ms, [3] hook ms, [4] compress ms, [5] finish ms, [6] rounds issued.
+ * scratch: 16-byte aligned, at least dispu_orient_consistent_scratch_bytes(C, off_host, k) (0 for an illegal C, k or offsets); the
+ * library never allocates; a refusal (hipErrorInvalidValue) touches no output.  Identical bytes from run to run.  The yardstick is
+ * tests/orient_oracle.py.  Additions only: dispu_version() stays 5. --------------------------------------------------------------- */
+#define DISPU_ORIENT_HOST_ROUNDS 1
+#define DISPU_ORIENT_PROFILE_FLOATS 8
+size_t dispu_orient_consistent_scratch_bytes(int C, const int* off_host, int k);
+int dispu_orient_consistent_segments(int C, const int* off, const int* off_host, int k, const float* points, const float* normal_in,
+                                     const int* neighbors, int vote, int flags, float* normal_out, unsigned char* flip, int* component,
+                                     int* n_components, int* status, void* scratch, size_t scratch_bytes, float* profile_host,
+                                     void* stream);
 
 #ifdef __cplusplus
 }

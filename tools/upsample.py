@@ -16,7 +16,11 @@ scan does not have.  The output then has final_ratio times the SUBSAMPLED count.
 nearest neighbours in the output cloud (dis-pu_amd/normals.py; the reference has no counterpart).  --orient picks the sign: none (the
 largest component positive), centroid (outwards), viewpoint (towards --viewpoint X Y Z) or input (in agreement with the normal of the
 nearest input point: every input file then needs six columns; with --grid_size the input normals are averaged per cube and
-renormalised, and a cube whose normals cancel orients nothing).
+renormalised, and a cube whose normals cancel orients nothing).  --orient consistent makes the signs agree from point to point on any
+shape, by propagation along the minimum spanning tree of the neighbour graph (normals.orient_consistent): alone, every connected piece
+is turned so that its topmost point faces up (outwards on a closed surface); with --orient_prior centroid|viewpoint|input the normals
+first take that hint and every piece then faces the way most of its points did.  The rules for --viewpoint and six-column inputs are
+those of the prior.
 
 --clean_input / --clean_output statistical|radius (both off by default) drop stray points on the GPU (dis-pu_amd/outliers.py; the
 reference has no counterpart): statistical removes the points whose mean distance to their --outliers_k nearest neighbours exceeds the
@@ -131,9 +135,13 @@ def parse_args(argv=None):
     ap.add_argument("--normals", choices=("none", "pca"), default="none",
                     help="pca: write six columns x y z nx ny nz, the normal from the PCA of the --normals_k nearest output points")
     ap.add_argument("--normals_k", type=int, default=16, help="neighbourhood size of --normals pca, 4 .. 32")
-    ap.add_argument("--orient", choices=("none", "centroid", "viewpoint", "input"), default="none",
+    ap.add_argument("--orient", choices=("none", "centroid", "viewpoint", "input", "consistent"), default="none",
                     help="sign of the normals: none (largest component positive), centroid (outwards), viewpoint (towards --viewpoint), "
-                         "input (as the nearest input point's normal; the inputs need six columns)")
+                         "input (as the nearest input point's normal; the inputs need six columns), consistent (signs that agree from "
+                         "point to point: propagation along the neighbour graph's minimum spanning tree)")
+    ap.add_argument("--orient_prior", choices=("none", "centroid", "viewpoint", "input"), default="none",
+                    help="with --orient consistent: orient by this hint first, then make the signs consistent and keep the direction "
+                         "most points had")
     ap.add_argument("--viewpoint", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None, help="the viewpoint of --orient viewpoint")
     ap.add_argument("--clean_input", choices=("none", "statistical", "radius"), default="none",
                     help="drop outliers from every input cloud first of all (before --grid_size)")
@@ -161,13 +169,16 @@ def parse_args(argv=None):
         ap.error("--orient and --viewpoint need --normals pca")
     if not 4 <= a.normals_k <= 32:
         ap.error("--normals_k must be in 4 .. 32, got %d" % a.normals_k)
-    if (a.orient == "viewpoint") != (a.viewpoint is not None):
+    if a.orient_prior != "none" and a.orient != "consistent":
+        ap.error("--orient_prior needs --orient consistent")
+    a.hint = a.orient_prior if a.orient == "consistent" else a.orient     # the pointwise rule: it decides what else is needed
+    if (a.hint == "viewpoint") != (a.viewpoint is not None):
         ap.error("--orient viewpoint and --viewpoint X Y Z go together")
     if a.viewpoint is not None and not all(math.isfinite(v) for v in a.viewpoint):
         ap.error("--viewpoint must be finite")
     if not 1 <= a.attributes_k <= 32:
         ap.error("--attributes_k must be in 1 .. 32, got %d" % a.attributes_k)
-    if a.attributes != "none" and a.orient == "input":
+    if a.attributes != "none" and a.hint == "input":
         ap.error("--attributes and --orient input do not go together: columns 4-6 would be both attributes and normals")
     return a
 
@@ -220,7 +231,7 @@ def main(argv=None):
     except ValueError as e:
         sys.exit(str(e))
     in_normals = None
-    if a.orient == "input":
+    if a.hint == "input":
         try:
             clouds, in_normals = (list(t) for t in zip(*[load_xyz_normals(p) for p in paths]))
         except ValueError as e:
@@ -298,13 +309,15 @@ def main(argv=None):
             from dispu_amd.normals import estimate_normals
             dpred = [torch.from_numpy(p).to(dev) for p in preds]
             orient = None
-            if a.orient == "centroid":
+            if a.hint == "centroid":
                 orient = ("centroid",)
-            elif a.orient == "viewpoint":
+            elif a.hint == "viewpoint":
                 orient = ("viewpoint", a.viewpoint)
-            elif a.orient == "input":
+            elif a.hint == "input":
                 orient = ("reference", [torch.from_numpy(clouds[i]).to(dev) for i in group],
                           [torch.as_tensor(in_normals[i], device=dev).contiguous() for i in group])
+            if a.orient == "consistent":
+                orient = ("consistent",) if orient is None else ("consistent", orient)
             try:
                 normals = [t.cpu().numpy() for t in estimate_normals(dpred, k=a.normals_k, orient=orient)]
             except ValueError as e:
