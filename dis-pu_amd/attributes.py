@@ -5,83 +5,51 @@ inverse-distance weighting (Common/pointnet_util.py:204-208) at any k <= 32, car
 
 The neighbours are the exact ones of the project's rule -- the k smallest (d2, reference index), d2 in plain fp32 arithmetic -- found by
 a cell-pruned search over both clouds; neighbourhoods never cross clouds.  The yardstick is tests/attributes_oracle.py."""
-import numpy as np
 import torch
 
 from . import _lib
 from ._util import req
-from .normals import MAX_CLOUDS, MAX_POINTS, _check_cloud, _host_ptr
+from .segments import Packed, check_int_range, host_ptr
 
 K_MIN, K_MAX = 1, 32
 MODES = {"idw": 0, "nearest": 1}
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
 class _Pair(object):
-    """queries and references, a tensor pair or two lists of equal length, checked, packed once"""
+    """queries and references, a tensor pair or two lists of equal length: two packed batches of one device, and what joins them"""
 
     def __init__(self, queries, refs, who):
         self.single = isinstance(queries, torch.Tensor)
         if self.single:
             req(isinstance(refs, torch.Tensor), "%s: queries is a tensor, so refs must be one too, got %s" % (who, type(refs).__name__))
-            qs, rs = [queries], [refs]
         else:
             req(isinstance(queries, (list, tuple)) and isinstance(refs, (list, tuple)),
                 "queries and refs must be float32 [n, 3] tensors on a ROCm device or two lists of them, got %s and %s"
                 % (type(queries).__name__, type(refs).__name__))
-            qs, rs = list(queries), list(refs)
-        req(len(qs) >= 1, "%s needs at least one cloud" % who)
-        req(len(qs) == len(rs), "%d query clouds but %d reference clouds" % (len(qs), len(rs)))
-        req(len(qs) <= MAX_CLOUDS, "at most %d clouds per call, got %d" % (MAX_CLOUDS, len(qs)))
-        for side, clouds in (("queries", qs), ("refs", rs)):
-            for i, c in enumerate(clouds):
-                _check_cloud(c, "%s of cloud %d" % (side, i))
-                req(1 <= c.shape[0] <= MAX_POINTS, "%s of cloud %d has %d points, expected 1 .. 2^24" % (side, i, c.shape[0]))
-                req(c.device == qs[0].device, "%s of cloud %d lives on another device than the queries of cloud 0" % (side, i))
-        self.qs, self.rs, self.C, self.dev = qs, rs, len(qs), qs[0].device
-        self.qoff, self.roff = np.zeros(self.C + 1, np.int64), np.zeros(self.C + 1, np.int64)
-        np.cumsum([int(c.shape[0]) for c in qs], out=self.qoff[1:])
-        np.cumsum([int(c.shape[0]) for c in rs], out=self.roff[1:])
-        req(self.roff[-1] < 2 ** 31, "a packed batch holds at most 2^31 - 1 reference points, got %d" % self.roff[-1])
-        self.nq, self.nr = int(self.qoff[-1]), int(self.roff[-1])
+            req(len(queries) >= 1, "%s needs at least one cloud" % who)
+            req(len(queries) == len(refs), "%d query clouds but %d reference clouds" % (len(queries), len(refs)))
+        self.queries = Packed(queries, who, label="queries of cloud %d", home="the queries of cloud 0")
+        self.refs = Packed(refs, who, label="refs of cloud %d", dev=self.queries.dev, home="the queries of cloud 0")
+        self.C, self.dev, self.nq = self.queries.C, self.queries.dev, self.queries.total
+        req(self.refs.total < 2 ** 31, "a packed batch holds at most 2^31 - 1 reference points, got %d" % self.refs.total)
 
     def width(self, w):
         req(self.nq * w < 2 ** 31, "a packed batch holds at most 2^31 - 1 output words, got %d queries x %d" % (self.nq, w))
 
     def pack(self):
         """after every check that needs no launch"""
-        self.qoff, self.roff = self.qoff.astype(np.int32), self.roff.astype(np.int32)
-        self.q = (self.qs[0] if self.C == 1 else torch.cat(self.qs)).contiguous()
-        self.r = (self.rs[0] if self.C == 1 else torch.cat(self.rs)).contiguous()
-        self.d_qoff = torch.from_numpy(self.qoff).to(self.dev)
-        self.d_roff = torch.from_numpy(self.roff).to(self.dev)
-        self.status = torch.zeros((self.C,), dtype=torch.int32, device=self.dev)
-        nbytes = _lib.lib().dispu_knn_cross_scratch_bytes(self.C, _host_ptr(self.qoff), _host_ptr(self.roff))
-        req(nbytes > 0, "dispu_knn_cross_scratch_bytes refuses these clouds")
-        self.nbytes = nbytes
-        self.scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
+        self.queries.pack()
+        self.refs.pack(status=False)
+        self.nbytes = _lib.lib().dispu_knn_cross_scratch_bytes(self.C, host_ptr(self.queries.off), host_ptr(self.refs.off))
+        self.scratch = self.queries.scratch(self.nbytes, "dispu_knn_cross_scratch_bytes")
 
     def head(self):
         """the arguments every entry starts with"""
-        return (self.C, _lib.ptr(self.d_qoff), _host_ptr(self.qoff), _lib.ptr(self.d_roff), _host_ptr(self.roff))
+        q, r = self.queries, self.refs
+        return (self.C, _lib.ptr(q.d_off), host_ptr(q.off), _lib.ptr(r.d_off), host_ptr(r.off))
 
     def tail(self):
-        return (_lib.ptr(self.status), _lib.ptr(self.scratch), self.nbytes, _lib.stream_ptr(self.dev))
-
-    def split(self, t):
-        return t if self.single else [t[self.qoff[c]:self.qoff[c + 1]] for c in range(self.C)]
-
-    def refuse_non_finite(self):
-        bad = np.nonzero(self.status.cpu().numpy())[0]
-        req(len(bad) == 0, "cloud %d holds a NaN or an infinite coordinate" % (int(bad[0]) if len(bad) else -1))
-
-
-def _check_k(k):
-    req(_is_int(k) and K_MIN <= k <= K_MAX, "k must be an integer in %d .. %d, got %r" % (K_MIN, K_MAX, k))
-    return int(k)
+        return (_lib.ptr(self.queries.status), _lib.ptr(self.scratch), self.nbytes, _lib.stream_ptr(self.dev))
 
 
 def knn_cross(queries, refs, k, return_distance=True):
@@ -91,16 +59,16 @@ def knn_cross(queries, refs, k, return_distance=True):
     the squared distances, +inf beyond min(k, m): (idx, d2).  Lists in give lists out.  1 <= k <= 32.  ValueError for illegal arguments
     (before any launch) and for a cloud with a NaN or an infinite coordinate (after it)."""
     b = _Pair(queries, refs, "knn_cross")
-    k = _check_k(k)
+    k = check_int_range(k, K_MIN, K_MAX, "k")
     b.width(k)
     b.pack()
     with torch.cuda.device(b.dev):
         idx = torch.empty((b.nq, k), dtype=torch.int32, device=b.dev)
         d2 = torch.empty((b.nq, k), dtype=torch.float32, device=b.dev) if return_distance else None
-        _lib.check(_lib.lib().dispu_knn_cross_segments(*(b.head() + (k, _lib.ptr(b.q), _lib.ptr(b.r), _lib.ptr(idx), _lib.ptr(d2)) + b.tail())),
+        _lib.check(_lib.lib().dispu_knn_cross_segments(*(b.head() + (k, _lib.ptr(b.queries.cloud), _lib.ptr(b.refs.cloud), _lib.ptr(idx), _lib.ptr(d2)) + b.tail())),
                    "dispu_knn_cross_segments")
-        b.refuse_non_finite()
-    return (b.split(idx), b.split(d2)) if return_distance else b.split(idx)
+        b.queries.refuse_non_finite()
+    return (b.queries.split(idx), b.queries.split(d2)) if return_distance else b.queries.split(idx)
 
 
 def _attr_list(b, value, name, dtype, dims):
@@ -111,7 +79,7 @@ def _attr_list(b, value, name, dtype, dims):
         req(isinstance(value, torch.Tensor), "%s must be a tensor when queries is one, got %s" % (name, type(value).__name__))
         value = [value]
     req(isinstance(value, (list, tuple)) and len(value) == b.C, "%s: expected %d tensors, one per cloud" % (name, b.C))
-    for i, (t, r) in enumerate(zip(value, b.rs)):
+    for i, (t, r) in enumerate(zip(value, b.refs.clouds)):
         what = "%s of cloud %d" % (name, i)
         req(isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == dims,
             "%s: expected a %s tensor of %d dimension(s)" % (what, str(dtype).replace("torch.", ""), dims))
@@ -131,7 +99,7 @@ def transfer_attributes(queries, refs, features=None, labels=None, k=3, mode="id
     ->  features [q, F] float32, or labels [q] int32, or the tuple (features, labels) when both are given.  Lists in give lists out.
     Feature values are not inspected (a NaN propagates).  ValueError as for knn_cross."""
     b = _Pair(queries, refs, "transfer_attributes")
-    k = _check_k(k)
+    k = check_int_range(k, K_MIN, K_MAX, "k")
     req(mode in MODES, "mode must be 'idw' or 'nearest', got %r" % (mode,))
     req(features is not None or labels is not None, "transfer_attributes needs features, labels or both")
     feats = _attr_list(b, features, "features", torch.float32, 2)
@@ -142,14 +110,14 @@ def transfer_attributes(queries, refs, features=None, labels=None, k=3, mode="id
     with torch.cuda.device(b.dev):
         feat = out_feat = lab = out_lab = None
         if feats is not None:
-            feat = (feats[0] if b.C == 1 else torch.cat(feats)).contiguous()
+            feat = b.refs.pack_like(feats)
             out_feat = torch.empty((b.nq, F), dtype=torch.float32, device=b.dev)
         if labs is not None:
-            lab = (labs[0] if b.C == 1 else torch.cat(labs)).contiguous()
+            lab = b.refs.pack_like(labs)
             out_lab = torch.empty((b.nq,), dtype=torch.int32, device=b.dev)
-        _lib.check(_lib.lib().dispu_transfer_attributes_segments(*(b.head() + (k, MODES[mode], _lib.ptr(b.q), _lib.ptr(b.r), F, _lib.ptr(feat),
+        _lib.check(_lib.lib().dispu_transfer_attributes_segments(*(b.head() + (k, MODES[mode], _lib.ptr(b.queries.cloud), _lib.ptr(b.refs.cloud), F, _lib.ptr(feat),
                                                                                _lib.ptr(out_feat), _lib.ptr(lab), _lib.ptr(out_lab)) + b.tail())),
                    "dispu_transfer_attributes_segments")
-        b.refuse_non_finite()
-    res = [b.split(t) for t in (out_feat, out_lab) if t is not None]
+        b.queries.refuse_non_finite()
+    res = [b.queries.split(t) for t in (out_feat, out_lab) if t is not None]
     return res[0] if len(res) == 1 else tuple(res)

@@ -7,9 +7,10 @@
 //              holds the 64 queries of one query cell -- spatially coherent, with a box -- and answers through the local index in .w
 //   seed       Morton keys are relative to each segment's own bounds: a query cell's number says nothing about the reference cells, and
 //              the wave has no cell of its own in the searched cloud.  One sweep of the reference segment's box table, 64 boxes per step,
-//              finds the cell with the smallest (box-to-box lower bound, cell number); the wave visits it and then its neighbours along
-//              the curve (s - 1, s + 1, s - 2, ...) until it has seen k' = min(k, m_c) points
-//   walk       the bounded table walk of knn_cells_search.h: a cell is visited unless its box-to-box bound exceeds the wave's largest k-th
+//              finds the cell s with the smallest (box-to-box lower bound, cell number).  Only this sweep is the kernel's own
+//   search     the text of knn_cells_search.h, the one the self-searching kernels include, started at s instead of the wave's own cell:
+//              the wave visits s and then its neighbours along the curve (s - 1, s + 1, s - 2, ...) until it has seen k' = min(k, m_c)
+//              points, then the bounded table walk: a cell is visited unless its box-to-box bound exceeds the wave's largest k-th
 //              distance, or its point-to-box bound exceeds the k-th distance of every lane.  A visit is dense: 64 queries x 64 points
 //   output     knn: the sorted list, padded with -1 / +inf beyond k'.  transfer: from the list in registers, in double and in ascending
 //              rank: w_j = 1 / max(d2_j, 1e-10), out_f = (sum_j w_j feat[r_j][f]) / (sum_j w_j); or the row of rank 0; labels of rank 0
@@ -57,23 +58,8 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
     const int qcnt = min(kNrmCell, nq - cb * kNrmCell);
     const bool valid = lane < qcnt;
     const float4 q = qspt[qbase + (size_t)(cb * kNrmCell + (valid ? lane : 0))];   // idle lanes repeat query 0 and store nothing
-    const int kp = min(k, n);
     const float4 qlo4 = *reinterpret_cast<const float4*>(qgt + (size_t)cb * 8);
     const float4 qhi4 = *reinterpret_cast<const float4*>(qgt + (size_t)cb * 8 + 4);
-    const float qlx = qlo4.x, qly = qlo4.y, qlz = qlo4.z, qhx = qlo4.w, qhy = qhi4.x, qhz = qhi4.y;
-
-    NrmBest<KMAX> best;
-    best.init();
-    auto visit = [&](int j) {                                                   // j wave-uniform: all 64 queries against cell j
-        const int cnt = min(kNrmCell, n - j * kNrmCell);
-        const float4 p = sp[j * kNrmCell + min(lane, cnt - 1)];
-        for (int i = 0; i < cnt; ++i) {
-            const float px = __shfl(p.x, i, kWave), py = __shfl(p.y, i, kWave), pz = __shfl(p.z, i, kWave);
-            const uint32_t pi = (uint32_t)__shfl(__float_as_int(p.w), i, kWave);
-            const float d = sqdist3<false>(px - q.x, py - q.y, pz - q.z);
-            best.push(((uint64_t)__float_as_uint(d) << 32) | pi, k);
-        }
-    };
 
     // the seed: the reference cell of the smallest (box-to-box bound, cell number).  Lane 0 always holds cell 0, so s < K
     uint64_t sk = kNrmNone;
@@ -82,43 +68,13 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
         if (j < K) {
             const float4 a = *reinterpret_cast<const float4*>(gt + (size_t)j * 8);
             const float4 b = *reinterpret_cast<const float4*>(gt + (size_t)j * 8 + 4);
-            const uint64_t key = ((uint64_t)__float_as_uint(cell_box_lb(a, b, qlx, qly, qlz, qhx, qhy, qhz)) << 32) | (uint32_t)j;
+            const float lb = cell_box_lb(a, b, qlo4.x, qlo4.y, qlo4.z, qlo4.w, qhi4.x, qhi4.y);
+            const uint64_t key = ((uint64_t)__float_as_uint(lb) << 32) | (uint32_t)j;
             sk = key < sk ? key : sk;
         }
     }
     const int s = min((int)(uint32_t)wave_min_u64(sk), K - 1);
-    visit(s);
-    int seen = min(kNrmCell, n - s * kNrmCell), vlo = s, vhi = s;
-    for (int d = 1; seen < kp; ++d) {                                           // kp <= n: ends at the latest with every cell visited
-        if (s - d >= 0) { visit(s - d); seen += kNrmCell; vlo = s - d; }        // only the last cell of a segment is short, and it
-        if (s + d < K) { visit(s + d); seen += min(kNrmCell, n - (s + d) * kNrmCell); vhi = s + d; }   // is never at s - d
-    }
-
-    uint32_t wk = (uint32_t)(wave_max_u64(best.thr) >> 32);                     // bits of the wave's largest k-th distance
-    for (int j0 = 0; j0 < K; j0 += kWave) {
-        const int j = j0 + lane;
-        uint32_t lbb = 0xFFFFFFFFu;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        const bool open = j < K && (j < vlo || j > vhi);
-        if (open) {
-            a = *reinterpret_cast<const float4*>(gt + (size_t)j * 8);
-            b = *reinterpret_cast<const float4*>(gt + (size_t)j * 8 + 4);
-            lbb = __float_as_uint(cell_box_lb(a, b, qlx, qly, qlz, qhx, qhy, qhz));
-        }
-        unsigned long long reach = __ballot(open && lbb <= wk);
-        while (reach) {
-            const int bl = (int)__builtin_ctzll(reach);
-            reach &= reach - 1;
-            const uint32_t lb1 = (uint32_t)__shfl((int)lbb, bl, kWave);
-            if (lb1 > wk) continue;                                             // the k-th distance shrank since the ballot
-            // the same bound per lane, the query point as its own box: a cell no lane can gain from is not visited either
-            const float4 a1 = make_float4(__shfl(a.x, bl, kWave), __shfl(a.y, bl, kWave), __shfl(a.z, bl, kWave), __shfl(a.w, bl, kWave));
-            const float4 b1 = make_float4(__shfl(b.x, bl, kWave), __shfl(b.y, bl, kWave), 0.f, 0.f);
-            if (!__any(__float_as_uint(cell_box_lb(a1, b1, q.x, q.y, q.z, q.x, q.y, q.z)) <= (uint32_t)(best.thr >> 32))) continue;
-            visit(j0 + bl);
-            wk = (uint32_t)(wave_max_u64(best.thr) >> 32);
-        }
-    }
+#include "knn_cells_search.h"  // the ramp around s and the walk, as text: defines `kp` and `best`
     if (!valid) return;
 
     const size_t row = qbase + (size_t)__float_as_int(q.w);
@@ -159,20 +115,11 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
     }
 }
 
-// -> 0 and the largest cell count of a query segment, or hipErrorInvalidValue: C outside 1 .. 65535, offsets that do not start at 0 or do
-// not grow, a segment above 2^24 points, on either side
-static int cross_plan(int C, const int* qoff_host, const int* roff_host, int* kqmax) {
-    int nall, nserved, krmax;
-    const int rc = fpc_plan(C, qoff_host, qoff_host, 0, kCellsFixed64, &nall, &nserved, kqmax);
-    if (rc != 0) return rc;
-    return fpc_plan(C, roff_host, roff_host, 0, kCellsFixed64, &nall, &nserved, &krmax);
-}
-
 static int cross_run(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, const float* queries,
                      const float* refs, int* idx_out, float* d2_out, const XferArgs* x, int width, int* status, void* scratch,
                      size_t scratch_bytes, hipStream_t st) {
-    int kqmax = 0;
-    const int rc = cross_plan(C, qoff_host, roff_host, &kqmax);
+    int rc = cells_batch_check(C, qoff_host);
+    if (rc == 0) rc = cells_batch_check(C, roff_host);
     if (rc != 0) return rc;
     if (k < 1 || k > 32 || !qoff || !roff || !queries || !refs || !status) return (int)hipErrorInvalidValue;
     if ((long long)qoff_host[C] * (long long)width >= (1ll << 31)) return (int)hipErrorInvalidValue;
@@ -181,28 +128,21 @@ static int cross_run(int C, const int* qoff, const int* qoff_host, const int* ro
     const float4 *rspt, *qspt;
     const float *rtab, *qtab;
     const uint32_t *rsegb, *qsegb;
-    int kr = 0;
+    int kr = 0, kqmax = 0;
     int rp = fps_cells_prepass(C, roff, roff_host, refs, scratch, rbytes, &rspt, &rtab, &rsegb, &kr, st);
     if (rp != 0) return rp;
     rp = fps_cells_prepass(C, qoff, qoff_host, queries, (char*)scratch + rbytes, qbytes, &qspt, &qtab, &qsegb, &kqmax, st);   // rbytes is a multiple of 256
     if (rp != 0) return rp;
     const dim3 grid((kqmax + kNrmWaves - 1) / kNrmWaves, C), block(kNrmThreads);
-#define DISPU_CROSS_LAUNCH(KMAX)                                                                                                        \
-    do {                                                                                                                                \
-        if (x)                                                                                                                          \
-            hipLaunchKernelGGL((knn_cross_kernel<KMAX, true>), grid, block, 0, st, qoff, roff, qsegb, rsegb, qspt, rspt, qtab, rtab, k, \
-                               (int*)nullptr, (float*)nullptr, *x, status);                                                             \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((knn_cross_kernel<KMAX, false>), grid, block, 0, st, qoff, roff, qsegb, rsegb, qspt, rspt, qtab, rtab, k, \
-                               idx_out, d2_out, XferArgs{0, 0, nullptr, nullptr, nullptr, nullptr}, status);                            \
-    } while (0)
-    if (k <= 8)
-        DISPU_CROSS_LAUNCH(8);
-    else if (k <= 16)
-        DISPU_CROSS_LAUNCH(16);
-    else
-        DISPU_CROSS_LAUNCH(32);
-#undef DISPU_CROSS_LAUNCH
+    dispatch_kmax(k, [&](auto kmax_c) {
+        constexpr int KMAX = decltype(kmax_c)::value;
+        if (x)
+            hipLaunchKernelGGL((knn_cross_kernel<KMAX, true>), grid, block, 0, st, qoff, roff, qsegb, rsegb, qspt, rspt, qtab, rtab, k,
+                               (int*)nullptr, (float*)nullptr, *x, status);
+        else
+            hipLaunchKernelGGL((knn_cross_kernel<KMAX, false>), grid, block, 0, st, qoff, roff, qsegb, rsegb, qspt, rspt, qtab, rtab, k,
+                               idx_out, d2_out, XferArgs{0, 0, nullptr, nullptr, nullptr, nullptr}, status);
+    });
     return (int)hipGetLastError();
 }
 
@@ -211,8 +151,6 @@ static int cross_run(int C, const int* qoff, const int* qoff_host, const int* ro
 using namespace dispu;
 
 DISPU_EXPORT size_t dispu_knn_cross_scratch_bytes(int C, const int* qoff_host, const int* roff_host) {
-    int kqmax;
-    if (cross_plan(C, qoff_host, roff_host, &kqmax) != 0) return 0;
     const size_t rbytes = fps_cells_prepass_scratch(C, roff_host), qbytes = fps_cells_prepass_scratch(C, qoff_host);
     return rbytes && qbytes ? rbytes + qbytes : 0;
 }

@@ -1,7 +1,9 @@
 // Every function of libdispu_hip.so that is defined in one translation unit and called from another, declared ONCE: the defining file
 // and every caller include this header, so the compiler checks each definition and each call against the same prototype (default
-// arguments live here only).  Declarations only; the exported C-ABI is include/dispu_hip.h.
+// arguments live here only).  Declarations, and one template; the exported C-ABI is include/dispu_hip.h.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace dispu {
@@ -91,6 +93,19 @@ size_t fps_cells_scratch(int C, const int* off_host, const int* moff_host, int c
 // boxes (lo x3, hi x3, -, -; segment c's first row is off[c] / 64 + c), segb [C][8] (word 6: the non-finite flag; such a segment has no
 // cells), kmax the largest cell count of a segment.  The scratch is refused, untouched, when NULL, misaligned or too small.
 size_t fps_cells_prepass_scratch(int C, const int* off_host);
+// What every entry over such a batch checks first: fpc_plan for cells of 64 (C in 1 .. 65535, offsets that start at 0 and grow, at most
+// 2^24 points per segment) -> 0 and, where asked for, the largest segment and the largest cell count of a segment; or hipErrorInvalidValue
+int cells_batch_check(int C, const int* off_host, int* nall = nullptr, int* kmax = nullptr);
+// The capacity of the search's register list (knn_cells.h: NrmBest<KMAX>) for a list of k <= 32 keys: f(integral_constant<int, 8 | 16 | 32>)
+template <class F>
+void dispatch_kmax(int k, F&& f) {
+    if (k <= 8)
+        f(std::integral_constant<int, 8>{});
+    else if (k <= 16)
+        f(std::integral_constant<int, 16>{});
+    else
+        f(std::integral_constant<int, 32>{});
+}
 int fps_cells_prepass(int C, const int* off, const int* off_host, const float* inp, void* scratch, size_t scratch_bytes,
                       const float4** spt, const float** tab, const uint32_t** segb, int* kmax, hipStream_t st);
 

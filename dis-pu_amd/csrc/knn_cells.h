@@ -1,6 +1,8 @@
 // The exact cell-pruned k-NN search over the Morton cells of morton_cells.hip, shared by its clients (normals.hip: the PCA normals;
-// outliers.hip: the mean neighbour distance, the radius count): here the sorted-register candidate list and the box bound; the search
-// itself -- the Morton-offset ramp, then the box-table walk -- is knn_cells_search.h, included as text inside each kernel.
+// outliers.hip: the mean neighbour distance, the radius count; attributes.hip: the search from one cloud into another): here the
+// sorted-register candidate list and the box bound.  The search itself -- the list, the visit, the Morton-offset ramp around a start
+// cell, then the box-table walk -- exists once, in knn_cells_search.h, included as text inside each kernel; the prologue of the kernels
+// that search their own segment (segment, cell, query) likewise once, in knn_cells_prologue.h.
 // normals.hip's header comment describes the search and proves why a skip is sound; cell_box_lb below is the bound it speaks of.
 #pragma once
 #include "morton_cells.h"
@@ -33,7 +35,9 @@ struct NrmBest {
 };
 
 // lower bound of d2 between any point of the box (lo, hi) and any point of the cell whose table row is (a, b) = (lo x3, hi.x | hi.y,
-// hi.z, -, -): lb <= d2 bit for bit (normals.hip); a query point is the box lo = hi = q.  The search body spells the same operations out
+// hi.z, -, -): lb <= d2 bit for bit (normals.hip); a query point is the box lo = hi = q.  knn_cells_search.h spells the same operations
+// out instead of calling this: with the call, the six shuffles of the per-lane bound issue in another order and the normals and mean-distance
+// kernels compile to other machine code than the measured one; the seed sweep of attributes.hip and the radius count call it
 __device__ __forceinline__ float cell_box_lb(const float4& a, const float4& b, float lx, float ly, float lz, float hx, float hy, float hz) {
     const float ex = fmaxf(fmaxf(a.x - hx, lx - a.w), 0.f);
     const float ey = fmaxf(fmaxf(a.y - hy, ly - b.x), 0.f);

@@ -4,14 +4,18 @@
 // 1228800 points (and 6 % faster on 64 x 8192) than the form written out in the kernel, the two measured alternately in one run (DESIGN
 // section 9).  Textual inclusion leaves the normals kernels' machine code exactly as it was.
 //
+// The one copy of the search: the kernels that search a segment's own cells (normals.hip, outliers.hip) start it at the wave's own cell,
+// s = cb after knn_cells_prologue.h; knn_cross_kernel (attributes.hip), whose queries come from another cloud, at the cell its seed
+// sweep picked.  Whatever s is, every cell outside the ramp [vlo, vhi] goes through the walk, so the result does not depend on it.
+//
 // Reads, from the including scope (one wave, one query per lane; all but lane and q wave-uniform):
-//   const float4* sp   the segment's sorted points (x, y, z, local index as bits)      const float* gt   its rows of the cell table
-//   int n, K, cb       the segment's points and cells, the wave's own cell             int lane, qcnt    lanes >= qcnt repeat query 0
-//   float4 q           the lane's query                                                int k, kp         list length, kp = min(k, n)
-// Defines NrmBest<KMAX> best: every lane's kp smallest keys (d2 bits << 32 | local index) over the segment, ascending.
-// No include guard on purpose: once per kernel.
-    const float4 qlo4 = *reinterpret_cast<const float4*>(gt + (size_t)cb * 8);
-    const float4 qhi4 = *reinterpret_cast<const float4*>(gt + (size_t)cb * 8 + 4);
+//   const float4* sp   the searched segment's sorted points (x, y, z, local index as bits)   const float* gt   its rows of the cell table
+//   int n, K           the searched segment's points and cells                               int s             the start cell, 0 <= s < K
+//   float4 q           the lane's query                                                      int lane, k       k: the list length
+//   float4 qlo4, qhi4  a box around the wave's 64 queries, as a table row (lo x3, hi.x | hi.y, hi.z, -, -)
+// Defines int kp = min(k, n) and NrmBest<KMAX> best: every lane's kp smallest keys (d2 bits << 32 | local index) over the segment,
+// ascending.  No include guard on purpose: once per kernel.
+    const int kp = min(k, n);
     const float qlx = qlo4.x, qly = qlo4.y, qlz = qlo4.z, qhx = qlo4.w, qhy = qhi4.x, qhz = qhi4.y;
 
     NrmBest<KMAX> best;
@@ -26,11 +30,11 @@
             best.push(((uint64_t)__float_as_uint(d) << 32) | pi, k);
         }
     };
-    visit(cb);
-    int seen = qcnt, vlo = cb, vhi = cb;
+    visit(s);
+    int seen = min(kNrmCell, n - s * kNrmCell), vlo = s, vhi = s;
     for (int d = 1; seen < kp; ++d) {                                           // kp <= n: ends at the latest with every cell visited
-        if (cb - d >= 0) { visit(cb - d); seen += kNrmCell; vlo = cb - d; }     // only the last cell of a segment is short, and it
-        if (cb + d < K) { visit(cb + d); seen += min(kNrmCell, n - (cb + d) * kNrmCell); vhi = cb + d; }   // is never at cb - d
+        if (s - d >= 0) { visit(s - d); seen += kNrmCell; vlo = s - d; }        // only the last cell of a segment is short, and it
+        if (s + d < K) { visit(s + d); seen += min(kNrmCell, n - (s + d) * kNrmCell); vhi = s + d; }   // is never at s - d
     }
     uint32_t wk = (uint32_t)(wave_max_u64(best.thr) >> 32);                     // bits of the wave's largest k-th distance
     for (int j0 = 0; j0 < K; j0 += kWave) {

@@ -225,9 +225,15 @@ int fpc_prepass(int C, const int* off, const int* moff, const float* inp, char* 
 }
 
 // the pre-pass for a client other than FPS (contract: internal.h)
+int cells_batch_check(int C, const int* off_host, int* nall, int* kmax) {
+    int na, nserved, km;
+    const int rc = fpc_plan(C, off_host, off_host, 0, kCellsFixed64, &na, &nserved, &km);
+    if (nall) *nall = na;
+    if (kmax) *kmax = km;
+    return rc;
+}
 size_t fps_cells_prepass_scratch(int C, const int* off_host) {
-    int nall, nserved, kmax;
-    if (fpc_plan(C, off_host, off_host, 0, kCellsFixed64, &nall, &nserved, &kmax) != 0) return 0;
+    if (cells_batch_check(C, off_host) != 0) return 0;
     return fpc_scratch((size_t)off_host[C], C).total;
 }
 int fps_cells_prepass(int C, const int* off, const int* off_host, const float* inp, void* scratch, size_t scratch_bytes,

@@ -6,15 +6,16 @@
 //
 //   pre-pass   morton_cells.hip (fps_cells_prepass):: segment boxes and non-finite flags, Morton keys with the segment id on top,
 //              one stable dispu_radix_sort_pairs, cells of 64 consecutive sorted positions with their boxes
-//   search     (knn_cells.h, knn_cells_search.h) one wave per cell, one query per lane; every lane keeps its k best keys (d2 bits << 32 | local index) sorted in
-//              registers.  The wave visits its own cell, then the cells at growing Morton offset (c - 1, c + 1, c - 2, ...) until it
+//   search     (knn_cells.h; the text of knn_cells_prologue.h and knn_cells_search.h, which exists there once for every kernel that
+//              searches) one wave per cell, one query per lane; every lane keeps its k best keys (d2 bits << 32 | local index) sorted in
+//              registers.  The wave visits its start cell (here its own; attributes.hip picks one by a sweep), then the cells at growing Morton offset (c - 1, c + 1, c - 2, ...) until it
 //              has seen k' points (every lane sees every point of a visited cell, so all lanes then hold k' candidates), then walks
 //              the segment's box table, 64 boxes per step (one per lane), and visits a cell only if its lower bound does not exceed
 //              the wave's largest current k-th distance.  A visit is dense: 64 queries x 64 points.
 //   normal     in the same kernel, from the neighbourhood in registers: q_j = p_j - p_i, mu = sum q_j / k', Cov = sum q_j q_j^T / k' -
 //              mu mu^T, all in double; cyclic Jacobi in double; the eigenvector of the smallest eigenvalue, stored as fp32.
 //
-// Why a skip is sound: per axis e := max(fl(lo_cell - hi_query), fl(lo_query - hi_cell), 0).  For a point p of the cell and a query q of
+// Why a skip is sound (of the walk in knn_cells_search.h, the only copy of it): per axis e := max(fl(lo_cell - hi_query), fl(lo_query - hi_cell), 0).  For a point p of the cell and a query q of
 // the wave, lo_cell <= p and q <= hi_query, and rounding is monotone, so fl(lo_cell - hi_query) <= fl(p - q); likewise fl(lo_query -
 // hi_cell) <= fl(q - p) = -fl(p - q): e <= |fl(p - q)| holds IN floating point.  The bound lb = ((ex*ex + ey*ey) + ez*ez) is the same
 // operations in the same order as d2, each of them (product of non-negatives, sum) monotone in its non-negative arguments, so lb <= d2
@@ -56,24 +57,9 @@ __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* _
                                                                   const float* __restrict__ orient, float* __restrict__ normal,
                                                                   float* __restrict__ variation, int* __restrict__ idx_out,
                                                                   int* __restrict__ status) {
-    const int c = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = off[c], n = off[c + 1] - b0;
-    const size_t base = (size_t)b0;
-    const uint32_t bad = segb[(size_t)c * 8 + 6];
-    if (blockIdx.x == 0 && tid == 0) status[c] = bad ? 1 : 0;
-    if (bad) return;                                                            // nothing is written for a non-finite segment
-    const int K = (n + kNrmCell - 1) / kNrmCell;
-    const int cb = blockIdx.x * kNrmWaves + wave;
-    if (cb >= K) return;                                                        // wave-uniform
-    const float4* __restrict__ sp = spt + base;
-    const float* __restrict__ gt = tab + (base / kNrmCell + (size_t)c) * 8;
-    const int qcnt = min(kNrmCell, n - cb * kNrmCell);
-    const bool valid = lane < qcnt;
-    const float4 q = sp[cb * kNrmCell + (valid ? lane : 0)];                    // idle lanes repeat query 0 and store nothing
-    const int kp = min(k, n);
-
-#include "knn_cells_search.h"  // the search, as text: defines `best`
+#include "knn_cells_prologue.h"  // segment, cell, query, as text: defines c, lane, n, base, cb, sp, gt, valid, q, qlo4, qhi4 ...
+    const int s = cb;                                                           // the search starts in the wave's own cell
+#include "knn_cells_search.h"    // the search, as text: defines `kp` and `best`
     if (!valid) return;
 
     const int qi = __float_as_int(q.w);
@@ -145,26 +131,20 @@ __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* _
     if (variation) variation[row] = var;
 }
 
-static int nrm_check(int C, const int* off_host, int k) {
-    if (C <= 0 || C > 65535 || !off_host || k < 4 || k > 32) return (int)hipErrorInvalidValue;
-    return 0;
-}
-
 }  // namespace dispu
 
 using namespace dispu;
 
 DISPU_EXPORT size_t dispu_pca_normals_scratch_bytes(int C, const int* off_host, int k) {
-    if (nrm_check(C, off_host, k) != 0) return 0;
-    return fps_cells_prepass_scratch(C, off_host);
+    return k < 4 || k > 32 ? 0 : fps_cells_prepass_scratch(C, off_host);
 }
 
 DISPU_EXPORT int dispu_pca_normals_segments(int C, const int* off, const int* off_host, int k, const float* cloud, int orient_mode,
                                             const float* orient, float* normal, float* variation, int* idx_out, int* status,
                                             void* scratch, size_t scratch_bytes, void* stream) {
-    const int rc = nrm_check(C, off_host, k);
+    const int rc = cells_batch_check(C, off_host);
     if (rc != 0) return rc;
-    if (orient_mode < 0 || orient_mode > 2 || (orient_mode != 0 && !orient) || !off || !cloud || !normal || !status)
+    if (k < 4 || k > 32 || orient_mode < 0 || orient_mode > 2 || (orient_mode != 0 && !orient) || !off || !cloud || !normal || !status)
         return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const float4* spt;
@@ -174,14 +154,9 @@ DISPU_EXPORT int dispu_pca_normals_segments(int C, const int* off, const int* of
     const int rp = fps_cells_prepass(C, off, off_host, cloud, scratch, scratch_bytes, &spt, &tab, &segb, &kmax, st);
     if (rp != 0) return rp;
     const dim3 grid((kmax + kNrmWaves - 1) / kNrmWaves, C), block(kNrmThreads);
-    if (k <= 8)
-        hipLaunchKernelGGL((pca_normals_kernel<8>), grid, block, 0, st, cloud, off, segb, spt, tab, k, orient_mode, orient, normal, variation,
-                           idx_out, status);
-    else if (k <= 16)
-        hipLaunchKernelGGL((pca_normals_kernel<16>), grid, block, 0, st, cloud, off, segb, spt, tab, k, orient_mode, orient, normal,
-                           variation, idx_out, status);
-    else
-        hipLaunchKernelGGL((pca_normals_kernel<32>), grid, block, 0, st, cloud, off, segb, spt, tab, k, orient_mode, orient, normal,
-                           variation, idx_out, status);
+    dispatch_kmax(k, [&](auto kmax_c) {
+        hipLaunchKernelGGL((pca_normals_kernel<decltype(kmax_c)::value>), grid, block, 0, st, cloud, off, segb, spt, tab, k, orient_mode, orient,
+                           normal, variation, idx_out, status);
+    });
     return (int)hipGetLastError();
 }

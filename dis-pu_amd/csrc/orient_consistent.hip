@@ -39,7 +39,7 @@
 // per-slot offer away.  A row whose slots all end inside its own component is marked dead and skipped from then on (components only
 // grow).  Measurements and the form this replaced: DESIGN.md section 9, "Consistent orientation".  Only integer min / max / add / or
 // atomics: order-free, identical bytes from run to run.  No float atomics.
-#include "common.h"
+#include "internal.h"
 
 namespace dispu {
 
@@ -427,15 +427,9 @@ static OrLayout or_layout(int C, size_t total, char* base) {
 
 // 0, or hipErrorInvalidValue; *nmax = the largest segment
 static int or_check(int C, const int* off_host, int k, int* nmax) {
-    if (C <= 0 || C > 65535 || !off_host || k < 4 || k > 32 || off_host[0] != 0) return (int)hipErrorInvalidValue;
-    int big = 0;
-    for (int c = 0; c < C; ++c) {
-        const long long n = (long long)off_host[c + 1] - (long long)off_host[c];
-        if (n < 1 || n > (1 << 24)) return (int)hipErrorInvalidValue;
-        big = n > big ? (int)n : big;
-    }
-    if ((long long)off_host[C] * k >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    *nmax = big;
+    const int rc = cells_batch_check(C, off_host, nmax);
+    if (rc != 0) return rc;
+    if (k < 4 || k > 32 || (long long)off_host[C] * k >= (1ll << 31)) return (int)hipErrorInvalidValue;
     return 0;
 }
 

@@ -6,7 +6,7 @@
 //   mean_dist  the search of knn_cells_search.h at k + 1 (the one behind the normals, morton_cells.hip's pre-pass before it), then from the
 //              neighbourhood in registers: s = sum of sqrt((double)d2_j) in ascending rank, mean = (float)(s / max(k' - 1, 1)).
 //              No [n, k] tensor reaches memory.
-//   count      one wave per cell, one query per lane; the segment's box table 64 boxes per step (one per lane).  A cell is visited
+//   count      (the prologue of knn_cells_prologue.h, not the search) one wave per cell, one query per lane; the segment's box table 64 boxes per step (one per lane).  A cell is visited
 //              unless its box-to-box lower bound exceeds r2 (cell_box_lb: lb <= d2 bit for bit, so no point within r2 is lost), or the
 //              point-to-box bound exceeds r2 on every lane that still counts.  A visit is dense, 64 x 64.  The walk ends once every
 //              live lane holds more than `cap` matches, its own (d2 = 0) included; the own match is subtracted at the end.
@@ -22,57 +22,26 @@ namespace dispu {
 constexpr int kOutThr = 1024, kOutThrWaves = kOutThr / kWave;    // the statistics workgroup
 constexpr int kOutCmp = 256;                                     // the compaction kernels
 
-// k: the list length, the caller's k + 1: the neighbourhood includes the point itself.  The prologue is pca_normals_kernel's, line for line (a shared helper that
-// returned it in a struct cost four VGPRs across the search: 98 for 94 at KMAX 16, a wave of occupancy).
+// k: the list length, the caller's k + 1: the neighbourhood includes the point itself
 template <int KMAX>
 __global__ __launch_bounds__(kNrmThreads) void knn_mean_dist_kernel(const int* __restrict__ off, const uint32_t* __restrict__ segb,
                                                                     const float4* __restrict__ spt, const float* __restrict__ tab, int k,
                                                                     float* __restrict__ mean_dist, int* __restrict__ status) {
-    const int c = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = off[c], n = off[c + 1] - b0;
-    const size_t base = (size_t)b0;
-    const uint32_t bad = segb[(size_t)c * 8 + 6];
-    if (blockIdx.x == 0 && tid == 0) status[c] = bad ? 1 : 0;
-    if (bad) return;                                                            // nothing is written for a non-finite segment
-    const int K = (n + kNrmCell - 1) / kNrmCell;
-    const int cb = blockIdx.x * kNrmWaves + wave;
-    if (cb >= K) return;                                                        // wave-uniform
-    const float4* __restrict__ sp = spt + base;
-    const float* __restrict__ gt = tab + fpc_cell_base(base, c) * 8;
-    const int qcnt = min(kNrmCell, n - cb * kNrmCell);
-    const bool valid = lane < qcnt;
-    const float4 q = sp[cb * kNrmCell + (valid ? lane : 0)];                    // idle lanes repeat query 0 and store nothing
-    const int kp = min(k, n);
-#include "knn_cells_search.h"  // the search, as text: defines `best`
+#include "knn_cells_prologue.h"  // segment, cell, query, as text
+    const int s = cb;                                                           // the search starts in the wave's own cell
+#include "knn_cells_search.h"    // the search, as text: defines `kp` and `best`
     if (!valid) return;
-    double s = 0.0;
+    double sum = 0.0;
 #pragma unroll
     for (int j = 0; j < KMAX; ++j)
-        if (j < kp) s += sqrt((double)__uint_as_float((uint32_t)(best.b[j] >> 32)));
-    mean_dist[base + (size_t)__float_as_int(q.w)] = (float)(s / (double)max(kp - 1, 1));
+        if (j < kp) sum += sqrt((double)__uint_as_float((uint32_t)(best.b[j] >> 32)));
+    mean_dist[base + (size_t)__float_as_int(q.w)] = (float)(sum / (double)max(kp - 1, 1));
 }
 
 __global__ __launch_bounds__(kNrmThreads) void radius_count_kernel(const int* __restrict__ off, const uint32_t* __restrict__ segb,
                                                                    const float4* __restrict__ spt, const float* __restrict__ tab, float r2,
                                                                    int cap, int* __restrict__ count, int* __restrict__ status) {
-    const int c = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = off[c], n = off[c + 1] - b0;
-    const size_t base = (size_t)b0;
-    const uint32_t bad = segb[(size_t)c * 8 + 6];
-    if (blockIdx.x == 0 && tid == 0) status[c] = bad ? 1 : 0;
-    if (bad) return;                                                            // nothing is written for a non-finite segment
-    const int K = (n + kNrmCell - 1) / kNrmCell;
-    const int cb = blockIdx.x * kNrmWaves + wave;
-    if (cb >= K) return;                                                        // wave-uniform
-    const float4* __restrict__ sp = spt + base;
-    const float* __restrict__ gt = tab + fpc_cell_base(base, c) * 8;
-    const int qcnt = min(kNrmCell, n - cb * kNrmCell);
-    const bool valid = lane < qcnt;
-    const float4 q = sp[cb * kNrmCell + (valid ? lane : 0)];                    // idle lanes repeat query 0 and store nothing
-    const float4 qlo4 = *reinterpret_cast<const float4*>(gt + (size_t)cb * 8);
-    const float4 qhi4 = *reinterpret_cast<const float4*>(gt + (size_t)cb * 8 + 4);
+#include "knn_cells_prologue.h"  // segment, cell, query, as text
     int raw = 0;                                                                // matches so far, the query's own among them: raw <= n
     for (int j0 = 0; j0 < K && __any(valid && raw <= cap); j0 += kWave) {
         const int j = j0 + lane;
@@ -205,32 +174,19 @@ static CmpScratch cmp_scratch(size_t N) {
     return s;
 }
 
-// -> 0 and the largest segment / the largest cell count, or hipErrorInvalidValue: C outside 1 .. 65535, offsets that do not start at 0
-// or do not grow, a segment above 2^24 points
-static int out_plan(int C, const int* off_host, int* nall, int* kmax) {
-    int nserved;
-    return fpc_plan(C, off_host, off_host, 0, kCellsFixed64, nall, &nserved, kmax);
-}
-static int mean_dist_check(int C, const int* off_host, int k) {
-    int nall, kmax;
-    if (k < 1 || k > 31) return (int)hipErrorInvalidValue;
-    return out_plan(C, off_host, &nall, &kmax);
-}
-
 }  // namespace dispu
 
 using namespace dispu;
 
 DISPU_EXPORT size_t dispu_knn_mean_dist_scratch_bytes(int C, const int* off_host, int k) {
-    if (mean_dist_check(C, off_host, k) != 0) return 0;
-    return fps_cells_prepass_scratch(C, off_host);
+    return k < 1 || k > 31 ? 0 : fps_cells_prepass_scratch(C, off_host);
 }
 
 DISPU_EXPORT int dispu_knn_mean_dist_segments(int C, const int* off, const int* off_host, int k, const float* cloud, float* mean_dist,
                                               int* status, void* scratch, size_t scratch_bytes, void* stream) {
-    const int rc = mean_dist_check(C, off_host, k);
+    const int rc = cells_batch_check(C, off_host);
     if (rc != 0) return rc;
-    if (!off || !cloud || !mean_dist || !status) return (int)hipErrorInvalidValue;
+    if (k < 1 || k > 31 || !off || !cloud || !mean_dist || !status) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const float4* spt;
     const float* tab;
@@ -240,31 +196,26 @@ DISPU_EXPORT int dispu_knn_mean_dist_segments(int C, const int* off, const int* 
     if (rp != 0) return rp;
     const dim3 grid((kmax + kNrmWaves - 1) / kNrmWaves, C), block(kNrmThreads);
     const int k1 = k + 1;
-    if (k1 <= 8)
-        hipLaunchKernelGGL((knn_mean_dist_kernel<8>), grid, block, 0, st, off, segb, spt, tab, k1, mean_dist, status);
-    else if (k1 <= 16)
-        hipLaunchKernelGGL((knn_mean_dist_kernel<16>), grid, block, 0, st, off, segb, spt, tab, k1, mean_dist, status);
-    else
-        hipLaunchKernelGGL((knn_mean_dist_kernel<32>), grid, block, 0, st, off, segb, spt, tab, k1, mean_dist, status);
+    dispatch_kmax(k1, [&](auto kmax_c) {
+        hipLaunchKernelGGL((knn_mean_dist_kernel<decltype(kmax_c)::value>), grid, block, 0, st, off, segb, spt, tab, k1, mean_dist, status);
+    });
     return (int)hipGetLastError();
 }
 
 DISPU_EXPORT size_t dispu_radius_count_scratch_bytes(int C, const int* off_host) {
-    int nall, kmax;
-    if (out_plan(C, off_host, &nall, &kmax) != 0) return 0;
     return fps_cells_prepass_scratch(C, off_host);
 }
 
 DISPU_EXPORT int dispu_radius_count_segments(int C, const int* off, const int* off_host, float radius, int cap, const float* cloud, int* count,
                                              int* status, void* scratch, size_t scratch_bytes, void* stream) {
-    int nall, kmax = 0;
-    const int rc = out_plan(C, off_host, &nall, &kmax);
+    const int rc = cells_batch_check(C, off_host);
     if (rc != 0) return rc;
     if (!(radius > 0.f) || !(radius <= 3.4028235e38f) || cap < 1 || !off || !cloud || !count || !status) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const float4* spt;
     const float* tab;
     const uint32_t* segb;
+    int kmax = 0;
     const int rp = fps_cells_prepass(C, off, off_host, cloud, scratch, scratch_bytes, &spt, &tab, &segb, &kmax, st);
     if (rp != 0) return rp;
     const float r2 = radius * radius;                                           // one fp32 rounding (the build does not contract)
@@ -275,8 +226,7 @@ DISPU_EXPORT int dispu_radius_count_segments(int C, const int* off, const int* o
 
 DISPU_EXPORT int dispu_outlier_threshold_segments(int C, const int* off, const int* off_host, const float* mean_dist, const int* status,
                                                   double ratio, double* stats, void* stream) {
-    int nall, kmax;
-    const int rc = out_plan(C, off_host, &nall, &kmax);
+    const int rc = cells_batch_check(C, off_host);
     if (rc != 0) return rc;
     if (!off || !mean_dist || !status || !stats || !(ratio >= -1.7976931348623157e308 && ratio <= 1.7976931348623157e308))
         return (int)hipErrorInvalidValue;
@@ -285,16 +235,15 @@ DISPU_EXPORT int dispu_outlier_threshold_segments(int C, const int* off, const i
 }
 
 DISPU_EXPORT size_t dispu_compact_scratch_bytes(int C, const int* off_host) {
-    int nall, kmax;
-    if (out_plan(C, off_host, &nall, &kmax) != 0) return 0;
+    if (cells_batch_check(C, off_host) != 0) return 0;
     return cmp_scratch((size_t)off_host[C]).total;
 }
 
 DISPU_EXPORT int dispu_compact_segments(int C, const int* off, const int* off_host, const float* cloud, int rule, const void* src,
                                         const double* stats, int min_neighbors, const int* status, float* out_points, int* out_index,
                                         int* new_off, void* scratch, size_t scratch_bytes, void* stream) {
-    int nall, kmax;
-    const int rc = out_plan(C, off_host, &nall, &kmax);
+    int nall;
+    const int rc = cells_batch_check(C, off_host, &nall);
     if (rc != 0) return rc;
     if (rule < 0 || rule > 2 || !off || !src || (rule == 1 && !stats) || (out_points && !cloud) || !out_index || !new_off)
         return (int)hipErrorInvalidValue;

@@ -15,22 +15,10 @@ import torch
 
 from . import _lib
 from ._util import req
+from .segments import MAX_CLOUDS, Packed, as_list, check_cloud, check_int_range, host_ptr
 
 K_MIN, K_MAX = 4, 32
-MAX_CLOUDS = 65535
-MAX_POINTS = 1 << 24
 ORIENT_FORMS = ("viewpoint", "centroid", "reference")
-
-
-def _host_ptr(a):
-    return _lib.C.c_void_p(a.ctypes.data)
-
-
-def _check_cloud(t, what):
-    req(isinstance(t, torch.Tensor), "%s: expected a float32 [n, 3] tensor on a ROCm device, got %s" % (what, type(t).__name__))
-    req(t.is_cuda, "%s must live on a ROCm device (dis-pu_amd has no CPU path)" % what)
-    req(t.dtype == torch.float32, "%s must be float32, got %s" % (what, t.dtype))
-    req(t.dim() == 2 and t.shape[1] == 3, "%s: expected an [n, 3] tensor, got shape %s" % (what, tuple(t.shape)))
 
 
 def _split_consistent(orient):
@@ -69,8 +57,8 @@ def _check_orient(orient, clouds):
         req(isinstance(rp, (list, tuple)) and isinstance(rn, (list, tuple)) and len(rp) == C and len(rn) == C,
             "reference: expected one (ref_points, ref_normals) pair per cloud (%d)" % C)
         for i, (p, m) in enumerate(zip(rp, rn)):
-            _check_cloud(p, "reference points %d" % i)
-            _check_cloud(m, "reference normals %d" % i)
+            check_cloud(p, "reference points %d" % i)
+            check_cloud(m, "reference normals %d" % i)
             req(p.shape[0] >= 1 and p.shape == m.shape, "reference %d: points %s and normals %s must be equal, non-empty shapes"
                 % (i, tuple(p.shape), tuple(m.shape)))
             req(p.device == clouds[i].device, "reference %d lives on another device than its cloud" % i)
@@ -104,68 +92,45 @@ def estimate_normals(points, k=16, orient=None, return_variation=False, return_n
     return_neighbors: also the neighbours' indices [n, k] int32 in ascending (distance, index) order, -1 beyond min(k, n).
     Returns the normals, or a tuple (normals, variation, neighbors) with the parts asked for, in that order.
     ValueError for illegal arguments (before any launch) and for a cloud with a NaN or an infinite coordinate (after it)."""
-    single = isinstance(points, torch.Tensor)
-    clouds = [points] if single else list(points) if isinstance(points, (list, tuple)) else None
-    req(clouds is not None, "points must be a float32 [n, 3] tensor on a ROCm device or a list of them, got %s" % type(points).__name__)
-    req(len(clouds) >= 1, "estimate_normals needs at least one cloud")
-    req(len(clouds) <= MAX_CLOUDS, "at most %d clouds per call, got %d" % (MAX_CLOUDS, len(clouds)))
-    for i, c in enumerate(clouds):
-        _check_cloud(c, "cloud %d" % i)
-        req(1 <= c.shape[0] <= MAX_POINTS, "cloud %d has %d points, expected 1 .. 2^24" % (i, c.shape[0]))
-        req(c.device == clouds[0].device, "cloud %d lives on another device than cloud 0" % i)
-    req(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and K_MIN <= k <= K_MAX,
-        "k must be an integer in %d .. %d, got %r" % (K_MIN, K_MAX, k))
-    k = int(k)
-    sizes = [int(c.shape[0]) for c in clouds]
-    total = sum(sizes)
-    req(total * max(k, 3) < 2 ** 31, "a packed batch holds at most 2^31 - 1 output words, got %d points at k = %d" % (total, k))
+    b = Packed(points, "estimate_normals")
+    k = check_int_range(k, K_MIN, K_MAX, "k")
+    b.limit(max(k, 3), tail=" at k = %d" % k)
     consistent, orient = _split_consistent(orient)
     want_neighbors, return_neighbors = return_neighbors, return_neighbors or consistent
-    form = _check_orient(orient, clouds)
+    form = _check_orient(orient, b.clouds)
 
-    dev = clouds[0].device
-    C = len(clouds)
-    off = np.zeros(C + 1, np.int32)
-    np.cumsum(sizes, out=off[1:])
-    cloud = (clouds[0] if C == 1 else torch.cat(clouds)).contiguous()
+    b.pack()
+    dev, C, total = b.dev, b.C, b.total
     with torch.cuda.device(dev):
         mode, direction = 0, None
         if form == "viewpoint":
             v = np.asarray(orient[1].detach().cpu() if isinstance(orient[1], torch.Tensor) else orient[1], np.float32)
             mode, direction = 2, torch.from_numpy(np.broadcast_to(v.reshape(-1, 3), (C, 3)).copy()).to(dev)
         elif form == "centroid":
-            mode, direction = 1, torch.cat([(c.double() - c.double().mean(dim=0, keepdim=True)).float() for c in clouds]).contiguous()
+            mode, direction = 1, torch.cat([(c.double() - c.double().mean(dim=0, keepdim=True)).float() for c in b.clouds]).contiguous()
         elif form == "reference":
             rp, rn = orient[1], orient[2]
             if isinstance(rp, torch.Tensor):
                 rp, rn = [rp], [rn]
-            mode, direction = 1, _reference_directions(clouds, rp, rn).contiguous()
+            mode, direction = 1, _reference_directions(b.clouds, rp, rn).contiguous()
         L = _lib.lib()
-        nbytes = L.dispu_pca_normals_scratch_bytes(C, _host_ptr(off), k)
-        req(nbytes > 0, "dispu_pca_normals_segments refuses these clouds")
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        d_off = torch.from_numpy(off).to(dev)
+        nbytes = L.dispu_pca_normals_scratch_bytes(C, host_ptr(b.off), k)
+        scratch = b.scratch(nbytes, "dispu_pca_normals_segments")
         normal = torch.zeros((total, 3), dtype=torch.float32, device=dev)
         variation = torch.zeros((total,), dtype=torch.float32, device=dev) if return_variation else None
         neighbors = torch.full((total, k), -1, dtype=torch.int32, device=dev) if return_neighbors else None
-        status = torch.zeros((C,), dtype=torch.int32, device=dev)
-        _lib.check(L.dispu_pca_normals_segments(C, _lib.ptr(d_off), _host_ptr(off), k, _lib.ptr(cloud), mode, _lib.ptr(direction),
-                                                _lib.ptr(normal), _lib.ptr(variation), _lib.ptr(neighbors), _lib.ptr(status),
+        _lib.check(L.dispu_pca_normals_segments(C, _lib.ptr(b.d_off), host_ptr(b.off), k, _lib.ptr(b.cloud), mode, _lib.ptr(direction),
+                                                _lib.ptr(normal), _lib.ptr(variation), _lib.ptr(neighbors), _lib.ptr(b.status),
                                                 _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)), "dispu_pca_normals_segments")
-        bad = np.nonzero(status.cpu().numpy())[0]
-    req(len(bad) == 0, "cloud %d holds a NaN or an infinite coordinate" % (int(bad[0]) if len(bad) else -1))
+        b.refuse_non_finite()
     if consistent:                                           # a prior keeps its overall direction: the majority decides per component
-        normal = _orient_launch(cloud, normal, neighbors, off, k, 0 if orient is None else 1, False, False)[0]
+        normal = _orient_launch(b, normal, neighbors, k, 0 if orient is None else 1, False, False)[0]
         return_neighbors = want_neighbors
-
-    def split(t):
-        return t if single else [t[off[c]:off[c + 1]] for c in range(C)]
-
-    res = [split(normal)]
+    res = [b.split(normal)]
     if return_variation:
-        res.append(split(variation))
+        res.append(b.split(variation))
     if return_neighbors:
-        res.append(split(neighbors))
+        res.append(b.split(neighbors))
     return res[0] if len(res) == 1 else tuple(res)
 
 
@@ -174,22 +139,20 @@ _STATUS_TEXT = ((1, "holds a NaN or an infinite normal"), (2, "holds a neighbour
                 (4, "did not converge (an iteration cap was reached)"))
 
 
-def _orient_launch(cloud, normal, neighbors, off, k, vote, want_flip, want_component):
-    """dispu_orient_consistent_segments on a packed batch (contiguous device tensors, host offsets) -> (normal_out, flip, component,
+def _orient_launch(b, normal, neighbors, k, vote, want_flip, want_component):
+    """dispu_orient_consistent_segments on a packed batch with its packed normals and neighbours -> (normal_out, flip, component,
     n_components); ValueError for a flagged cloud"""
-    dev, C, total = cloud.device, len(off) - 1, int(off[-1])
+    dev, C, total = b.dev, b.C, b.total
     with torch.cuda.device(dev):
         L = _lib.lib()
-        nbytes = L.dispu_orient_consistent_scratch_bytes(C, _host_ptr(off), k)
-        req(nbytes > 0, "dispu_orient_consistent_segments refuses these clouds")
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        d_off = torch.from_numpy(off).to(dev)
+        nbytes = L.dispu_orient_consistent_scratch_bytes(C, host_ptr(b.off), k)
+        scratch = b.scratch(nbytes, "dispu_orient_consistent_segments")
         out = torch.empty((total, 3), dtype=torch.float32, device=dev)
         flip = torch.zeros((total,), dtype=torch.uint8, device=dev) if want_flip else None
         component = torch.zeros((total,), dtype=torch.int32, device=dev) if want_component else None
         ncomp = torch.zeros((C,), dtype=torch.int32, device=dev) if want_component else None
         status = torch.zeros((C,), dtype=torch.int32, device=dev)
-        _lib.check(L.dispu_orient_consistent_segments(C, _lib.ptr(d_off), _host_ptr(off), k, _lib.ptr(cloud), _lib.ptr(normal),
+        _lib.check(L.dispu_orient_consistent_segments(C, _lib.ptr(b.d_off), host_ptr(b.off), k, _lib.ptr(b.cloud), _lib.ptr(normal),
                                                       _lib.ptr(neighbors), vote, 0, _lib.ptr(out), _lib.ptr(flip), _lib.ptr(component),
                                                       _lib.ptr(ncomp), _lib.ptr(status), _lib.ptr(scratch), nbytes, None,
                                                       _lib.stream_ptr(dev)),
@@ -217,52 +180,36 @@ def orient_consistent(points, normals, k=16, neighbors=None, vote="anchor", retu
     Returns the oriented normals; with return_flips also the flip bytes [n] uint8; with return_components also the component of every
     point [n] int32 (the lowest index of its component) and the number of components (an int, or a list of ints), in that order.
     ValueError for illegal arguments (before any launch) and for a cloud with a non-finite normal or an illegal index (after it)."""
-    single = isinstance(points, torch.Tensor)
-    clouds = [points] if single else list(points) if isinstance(points, (list, tuple)) else None
+    single, clouds, nrms = isinstance(points, torch.Tensor), as_list(points), as_list(normals)
     req(clouds is not None, "points must be a float32 [n, 3] tensor on a ROCm device or a list of them, got %s" % type(points).__name__)
-    nrms = [normals] if isinstance(normals, torch.Tensor) else list(normals) if isinstance(normals, (list, tuple)) else None
     req(nrms is not None and isinstance(normals, torch.Tensor) == single, "normals must be a tensor or a list, as points is")
     req(1 <= len(clouds) <= MAX_CLOUDS, "1 .. %d clouds per call, got %d" % (MAX_CLOUDS, len(clouds)))
     req(len(nrms) == len(clouds), "%d clouds and %d sets of normals" % (len(clouds), len(nrms)))
-    req(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and K_MIN <= k <= K_MAX,
-        "k must be an integer in %d .. %d, got %r" % (K_MIN, K_MAX, k))
-    k = int(k)
+    k = check_int_range(k, K_MIN, K_MAX, "k")
     req(isinstance(vote, str) and vote in VOTES, "vote must be 'anchor' or 'majority', got %r" % (vote,))
+    b = Packed(points, "orient_consistent")
     for i, (c, m) in enumerate(zip(clouds, nrms)):
-        _check_cloud(c, "cloud %d" % i)
-        _check_cloud(m, "normals %d" % i)
-        req(1 <= c.shape[0] <= MAX_POINTS, "cloud %d has %d points, expected 1 .. 2^24" % (i, c.shape[0]))
+        check_cloud(m, "normals %d" % i)
         req(m.shape == c.shape, "cloud %d has %d points and %d normals" % (i, c.shape[0], m.shape[0]))
-        req(c.device == clouds[0].device and m.device == clouds[0].device, "cloud %d lives on another device than cloud 0" % i)
-    sizes = [int(c.shape[0]) for c in clouds]
-    total, C = sum(sizes), len(clouds)
-    req(total * k < 2 ** 31, "a packed batch holds at most 2^31 - 1 neighbour slots, got %d points at k = %d" % (total, k))
+        req(m.device == b.dev, "cloud %d lives on another device than cloud 0" % i)
+    b.limit(k, unit="neighbour slots", tail=" at k = %d" % k)
     if neighbors is not None:
-        nbs = [neighbors] if isinstance(neighbors, torch.Tensor) else list(neighbors) if isinstance(neighbors, (list, tuple)) else None
-        req(nbs is not None and isinstance(neighbors, torch.Tensor) == single and len(nbs) == C,
-            "neighbors must be a tensor or a list of %d tensors, as points is" % C)
-        for i, (b, n) in enumerate(zip(nbs, sizes)):
-            req(isinstance(b, torch.Tensor) and b.is_cuda and b.device == clouds[0].device and b.dtype == torch.int32,
+        nbs = as_list(neighbors)
+        req(nbs is not None and isinstance(neighbors, torch.Tensor) == single and len(nbs) == b.C,
+            "neighbors must be a tensor or a list of %d tensors, as points is" % b.C)
+        for i, (t, c) in enumerate(zip(nbs, clouds)):
+            req(isinstance(t, torch.Tensor) and t.is_cuda and t.device == b.dev and t.dtype == torch.int32,
                 "neighbors %d must be an int32 tensor on the clouds' device" % i)
-            req(tuple(b.shape) == (n, k), "neighbors %d: expected shape (%d, %d), got %s" % (i, n, k, tuple(b.shape)))
+            req(tuple(t.shape) == (c.shape[0], k), "neighbors %d: expected shape (%d, %d), got %s" % (i, c.shape[0], k, tuple(t.shape)))
     else:
         nbs = estimate_normals(clouds, k=k, return_neighbors=True)[1]
-    off = np.zeros(C + 1, np.int32)
-    np.cumsum(sizes, out=off[1:])
-
-    def pack(ts):
-        return (ts[0] if C == 1 else torch.cat(list(ts))).contiguous()
-
-    out, flip, component, ncomp = _orient_launch(pack(clouds), pack(nrms), pack(nbs), off, k, VOTES.index(vote), return_flips,
+    b.pack(status=False)
+    out, flip, component, ncomp = _orient_launch(b, b.pack_like(nrms), b.pack_like(nbs), k, VOTES.index(vote), return_flips,
                                                  return_components)
-
-    def split(t):
-        return t if single else [t[off[c]:off[c + 1]] for c in range(C)]
-
-    res = [split(out)]
+    res = [b.split(out)]
     if return_flips:
-        res.append(split(flip))
+        res.append(b.split(flip))
     if return_components:
         counts = [int(v) for v in ncomp.cpu().numpy()]
-        res += [split(component), counts[0] if single else counts]
+        res += [b.split(component), counts[0] if single else counts]
     return res[0] if len(res) == 1 else tuple(res)

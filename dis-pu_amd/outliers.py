@@ -12,59 +12,11 @@ import torch
 
 from . import _lib
 from ._util import req
-from .normals import MAX_CLOUDS, MAX_POINTS, _check_cloud, _host_ptr
+from .segments import Packed, check_int_range, host_ptr, is_int
 
 K_MIN, K_MAX = 1, 31
 INT_MAX = 2 ** 31 - 1
 RULE_FLAGS, RULE_MEAN_DIST, RULE_COUNT = 0, 1, 2                 # dispu_compact_segments' rule
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
-class _Batch(object):
-    """a tensor or a list of tensors, checked, packed once"""
-
-    def __init__(self, points, who):
-        self.single = isinstance(points, torch.Tensor)
-        clouds = [points] if self.single else list(points) if isinstance(points, (list, tuple)) else None
-        req(clouds is not None, "points must be a float32 [n, 3] tensor on a ROCm device or a list of them, got %s" % type(points).__name__)
-        req(len(clouds) >= 1, "%s needs at least one cloud" % who)
-        req(len(clouds) <= MAX_CLOUDS, "at most %d clouds per call, got %d" % (MAX_CLOUDS, len(clouds)))
-        for i, c in enumerate(clouds):
-            _check_cloud(c, "cloud %d" % i)
-            req(1 <= c.shape[0] <= MAX_POINTS, "cloud %d has %d points, expected 1 .. 2^24" % (i, c.shape[0]))
-            req(c.device == clouds[0].device, "cloud %d lives on another device than cloud 0" % i)
-        sizes = [int(c.shape[0]) for c in clouds]
-        self.total = sum(sizes)
-        req(self.total * 3 < 2 ** 31, "a packed batch holds at most 2^31 - 1 output words, got %d points" % self.total)
-        self.clouds, self.C, self.dev = clouds, len(clouds), clouds[0].device
-        self.off = np.zeros(self.C + 1, np.int32)
-        np.cumsum(sizes, out=self.off[1:])
-
-    def pack(self):
-        """after every check that needs no launch"""
-        self.cloud = (self.clouds[0] if self.C == 1 else torch.cat(self.clouds)).contiguous()
-        self.d_off = torch.from_numpy(self.off).to(self.dev)
-        self.status = torch.zeros((self.C,), dtype=torch.int32, device=self.dev)
-
-    def split(self, t, off=None):
-        off = self.off if off is None else off
-        return t[off[0]:off[1]] if self.single else [t[off[c]:off[c + 1]] for c in range(self.C)]
-
-    def scratch(self, nbytes, what):
-        req(nbytes > 0, "%s refuses these clouds" % what)
-        return torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
-
-    def refuse_non_finite(self, status=None):
-        bad = np.nonzero((self.status if status is None else status).cpu().numpy())[0]
-        req(len(bad) == 0, "cloud %d holds a NaN or an infinite coordinate" % (int(bad[0]) if len(bad) else -1))
-
-
-def _check_k(k):
-    req(_is_int(k) and K_MIN <= k <= K_MAX, "k must be an integer in %d .. %d, got %r" % (K_MIN, K_MAX, k))
-    return int(k)
 
 
 def _check_radius(radius):
@@ -77,10 +29,10 @@ def _check_radius(radius):
 
 def _mean_dist(b, k):
     L = _lib.lib()
-    nbytes = L.dispu_knn_mean_dist_scratch_bytes(b.C, _host_ptr(b.off), k)
+    nbytes = L.dispu_knn_mean_dist_scratch_bytes(b.C, host_ptr(b.off), k)
     scratch = b.scratch(nbytes, "dispu_knn_mean_dist_segments")
     out = torch.zeros((b.total,), dtype=torch.float32, device=b.dev)
-    _lib.check(L.dispu_knn_mean_dist_segments(b.C, _lib.ptr(b.d_off), _host_ptr(b.off), k, _lib.ptr(b.cloud), _lib.ptr(out),
+    _lib.check(L.dispu_knn_mean_dist_segments(b.C, _lib.ptr(b.d_off), host_ptr(b.off), k, _lib.ptr(b.cloud), _lib.ptr(out),
                                               _lib.ptr(b.status), _lib.ptr(scratch), nbytes, _lib.stream_ptr(b.dev)),
                "dispu_knn_mean_dist_segments")
     return out
@@ -88,10 +40,10 @@ def _mean_dist(b, k):
 
 def _radius_count(b, radius, cap):
     L = _lib.lib()
-    nbytes = L.dispu_radius_count_scratch_bytes(b.C, _host_ptr(b.off))
+    nbytes = L.dispu_radius_count_scratch_bytes(b.C, host_ptr(b.off))
     scratch = b.scratch(nbytes, "dispu_radius_count_segments")
     out = torch.zeros((b.total,), dtype=torch.int32, device=b.dev)
-    _lib.check(L.dispu_radius_count_segments(b.C, _lib.ptr(b.d_off), _host_ptr(b.off), radius, cap, _lib.ptr(b.cloud), _lib.ptr(out),
+    _lib.check(L.dispu_radius_count_segments(b.C, _lib.ptr(b.d_off), host_ptr(b.off), radius, cap, _lib.ptr(b.cloud), _lib.ptr(out),
                                              _lib.ptr(b.status), _lib.ptr(scratch), nbytes, _lib.stream_ptr(b.dev)),
                "dispu_radius_count_segments")
     return out
@@ -100,12 +52,12 @@ def _radius_count(b, radius, cap):
 def _compact(b, rule, src, stats, min_neighbors):
     """-> (kept points [m, 3], kept local indices [m] int32, new offsets [C + 1] on the host, the status read back with them)"""
     L = _lib.lib()
-    nbytes = L.dispu_compact_scratch_bytes(b.C, _host_ptr(b.off))
+    nbytes = L.dispu_compact_scratch_bytes(b.C, host_ptr(b.off))
     scratch = b.scratch(nbytes, "dispu_compact_segments")
     pts = torch.empty((b.total, 3), dtype=torch.float32, device=b.dev)
     idx = torch.empty((b.total,), dtype=torch.int32, device=b.dev)
     tail = torch.zeros((2 * b.C + 1,), dtype=torch.int32, device=b.dev)         # new_off [C + 1], then a copy of status [C]: one read-back
-    _lib.check(L.dispu_compact_segments(b.C, _lib.ptr(b.d_off), _host_ptr(b.off), _lib.ptr(b.cloud), rule, _lib.ptr(src), _lib.ptr(stats),
+    _lib.check(L.dispu_compact_segments(b.C, _lib.ptr(b.d_off), host_ptr(b.off), _lib.ptr(b.cloud), rule, _lib.ptr(src), _lib.ptr(stats),
                                         min_neighbors, _lib.ptr(b.status), _lib.ptr(pts), _lib.ptr(idx), _lib.ptr(tail), _lib.ptr(scratch),
                                         nbytes, _lib.stream_ptr(b.dev)), "dispu_compact_segments")
     tail[b.C + 1:] = b.status
@@ -120,8 +72,8 @@ def knn_mean_distance(points, k=16):
     every point to its k nearest other points of its own cloud, 1 <= k <= 31; a cloud of n <= k points uses its n - 1 others, a cloud
     of one point gives 0.  ValueError for illegal arguments (before any launch) and for a cloud with a NaN or an infinite coordinate
     (after it)."""
-    b = _Batch(points, "knn_mean_distance")
-    k = _check_k(k)
+    b = Packed(points, "knn_mean_distance", words=3)
+    k = check_int_range(k, K_MIN, K_MAX, "k")
     b.pack()
     with torch.cuda.device(b.dev):
         out = _mean_dist(b, k)
@@ -135,8 +87,8 @@ def remove_statistical_outliers(points, k=16, std_ratio=2.0, return_index=False,
     return_index: also the kept indices [m] int64, ascending.  return_stats: also (mean, std, threshold) per cloud, a float64 [3]
     tensor on the host.  Returns the points, or a tuple (points, index, stats) with the parts asked for, in that order.
     A cloud whose points all coincide keeps everything.  ValueError as for knn_mean_distance; std_ratio must be finite."""
-    b = _Batch(points, "remove_statistical_outliers")
-    k = _check_k(k)
+    b = Packed(points, "remove_statistical_outliers", words=3)
+    k = check_int_range(k, K_MIN, K_MAX, "k")
     req(isinstance(std_ratio, (int, float, np.integer, np.floating)) and not isinstance(std_ratio, bool) and math.isfinite(float(std_ratio)),
         "std_ratio must be a finite number, got %r" % (std_ratio,))
     b.pack()
@@ -144,7 +96,7 @@ def remove_statistical_outliers(points, k=16, std_ratio=2.0, return_index=False,
         L = _lib.lib()
         md = _mean_dist(b, k)
         stats = torch.zeros((b.C, 3), dtype=torch.float64, device=b.dev)
-        _lib.check(L.dispu_outlier_threshold_segments(b.C, _lib.ptr(b.d_off), _host_ptr(b.off), _lib.ptr(md), _lib.ptr(b.status),
+        _lib.check(L.dispu_outlier_threshold_segments(b.C, _lib.ptr(b.d_off), host_ptr(b.off), _lib.ptr(md), _lib.ptr(b.status),
                                                       float(std_ratio), _lib.ptr(stats), _lib.stream_ptr(b.dev)),
                    "dispu_outlier_threshold_segments")
         pts, idx, new_off, status = _compact(b, RULE_MEAN_DIST, md, stats, 0)
@@ -163,9 +115,9 @@ def radius_neighbor_count(points, radius, cap=None):
     the boundary included; duplicates of a point count), at most `cap` (None: exact counts; the search ends early once every point of
     a cell has reached it).  radius is rounded to float32 and must then be finite and > 0; cap >= 1.  ValueError as for
     knn_mean_distance."""
-    b = _Batch(points, "radius_neighbor_count")
+    b = Packed(points, "radius_neighbor_count", words=3)
     r = _check_radius(radius)
-    req(cap is None or (_is_int(cap) and 1 <= cap <= INT_MAX), "cap must be None or an integer in 1 .. 2^31 - 1, got %r" % (cap,))
+    req(cap is None or (is_int(cap) and 1 <= cap <= INT_MAX), "cap must be None or an integer in 1 .. 2^31 - 1, got %r" % (cap,))
     b.pack()
     with torch.cuda.device(b.dev):
         out = _radius_count(b, r, INT_MAX if cap is None else int(cap))
@@ -177,9 +129,9 @@ def remove_radius_outliers(points, radius, min_neighbors=2, return_index=False):
     """Keep the points with at least min_neighbors other points of their cloud within radius (radius_neighbor_count at cap =
     min_neighbors)  ->  the kept points [m, 3] in input order, possibly [0, 3] (a list in gives lists out).  return_index: also the
     kept indices [m] int64, ascending.  min_neighbors >= 1.  ValueError as for radius_neighbor_count."""
-    b = _Batch(points, "remove_radius_outliers")
+    b = Packed(points, "remove_radius_outliers", words=3)
     r = _check_radius(radius)
-    req(_is_int(min_neighbors) and 1 <= min_neighbors <= INT_MAX, "min_neighbors must be an integer >= 1, got %r" % (min_neighbors,))
+    req(is_int(min_neighbors) and 1 <= min_neighbors <= INT_MAX, "min_neighbors must be an integer >= 1, got %r" % (min_neighbors,))
     b.pack()
     with torch.cuda.device(b.dev):
         cnt = _radius_count(b, r, int(min_neighbors))

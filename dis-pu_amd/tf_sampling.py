@@ -4,6 +4,7 @@ import torch
 
 from . import _lib
 from ._util import f32, i32, req
+from .segments import host_ptr, to_device
 
 
 FPS_PATHS = ("auto", "cells", "stream")
@@ -12,10 +13,6 @@ FPS_PATHS = ("auto", "cells", "stream")
 def _check_path(path):
     req(path in FPS_PATHS, "path must be one of %s, got %r" % (", ".join(repr(p) for p in FPS_PATHS), path))
     return path
-
-
-def _host_ptr(a):
-    return _lib.C.c_void_p(a.ctypes.data)
 
 
 def fps_ragged(inp, off, moff, arith=_lib.ARITH_CONTRACT, path="auto", cell=0):
@@ -35,13 +32,13 @@ def fps_ragged(inp, off, moff, arith=_lib.ARITH_CONTRACT, path="auto", cell=0):
     if C == 0:
         return out
     L = _lib.lib()
-    d_off, d_moff = torch.from_numpy(off).to(dev), torch.from_numpy(moff).to(dev)
+    d_off, d_moff = to_device(off, dev), to_device(moff, dev)
     st = _lib.stream_ptr(dev)
 
     def stream_call(o, mo, d_o, d_mo, x, res):
-        nbytes = L.dispu_fps_segments_scratch_bytes(len(o) - 1, _host_ptr(o), _host_ptr(mo))
+        nbytes = L.dispu_fps_segments_scratch_bytes(len(o) - 1, host_ptr(o), host_ptr(mo))
         temp = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev) if nbytes else None
-        _lib.check(L.dispu_fps_segments(len(o) - 1, _lib.ptr(d_o), _lib.ptr(d_mo), _host_ptr(o), _host_ptr(mo), _lib.ptr(x), _lib.ptr(temp),
+        _lib.check(L.dispu_fps_segments(len(o) - 1, _lib.ptr(d_o), _lib.ptr(d_mo), host_ptr(o), host_ptr(mo), _lib.ptr(x), _lib.ptr(temp),
                                         nbytes, _lib.ptr(res), int(arith), st), "dispu_fps_segments")
 
     if path == "stream":
@@ -49,29 +46,29 @@ def fps_ragged(inp, off, moff, arith=_lib.ARITH_CONTRACT, path="auto", cell=0):
         return out
     n_c, m_c = np.diff(off), np.diff(moff)
     if path == "cells":
-        nbytes = L.dispu_fps_cells_scratch_bytes(C, _host_ptr(off), _host_ptr(moff), int(cell))
+        nbytes = L.dispu_fps_cells_scratch_bytes(C, host_ptr(off), host_ptr(moff), int(cell))
         req(nbytes > 0, "dispu_fps_cells refuses these segments (illegal offsets or cell size, or a segment above 2^24 points)")
         uses_cells = True
     else:
         req(int(cell) == 0, "a forced cell size needs path='cells'")
         uses_cells = any(L.dispu_fps_cells_wanted(int(n), int(m)) for n, m in zip(n_c, m_c) if n > 24576)
-        nbytes = L.dispu_fps_segments_auto_scratch_bytes(C, _host_ptr(off), _host_ptr(moff))
+        nbytes = L.dispu_fps_segments_auto_scratch_bytes(C, host_ptr(off), host_ptr(moff))
         if uses_cells and nbytes == 0:           # a segment above 2^24 points: only the streaming kernel takes it
             stream_call(off, moff, d_off, d_moff, inp, out)
             return out
     temp = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
     status = torch.zeros((C,), dtype=torch.int32, device=dev) if uses_cells else None
     if path == "cells":
-        _lib.check(L.dispu_fps_cells(C, _lib.ptr(d_off), _lib.ptr(d_moff), _host_ptr(off), _host_ptr(moff), _lib.ptr(inp), _lib.ptr(temp),
+        _lib.check(L.dispu_fps_cells(C, _lib.ptr(d_off), _lib.ptr(d_moff), host_ptr(off), host_ptr(moff), _lib.ptr(inp), _lib.ptr(temp),
                                      nbytes, _lib.ptr(out), _lib.ptr(status), int(arith), int(cell), st), "dispu_fps_cells")
     else:
-        _lib.check(L.dispu_fps_segments_auto(C, _lib.ptr(d_off), _lib.ptr(d_moff), _host_ptr(off), _host_ptr(moff), _lib.ptr(inp),
+        _lib.check(L.dispu_fps_segments_auto(C, _lib.ptr(d_off), _lib.ptr(d_moff), host_ptr(off), host_ptr(moff), _lib.ptr(inp),
                                              _lib.ptr(temp), nbytes, _lib.ptr(out), _lib.ptr(status), int(arith), st),
                    "dispu_fps_segments_auto")
     if uses_cells:
         for c in np.nonzero(status.cpu().numpy())[0]:          # non-finite segments: the existing entry, one segment at a time
             o1, m1 = np.array([0, n_c[c]], np.int32), np.array([0, m_c[c]], np.int32)
-            stream_call(o1, m1, torch.from_numpy(o1).to(dev), torch.from_numpy(m1).to(dev), inp[int(off[c]):int(off[c + 1])],
+            stream_call(o1, m1, to_device(o1, dev), to_device(m1, dev), inp[int(off[c]):int(off[c + 1])],
                         out[int(moff[c]):int(moff[c + 1])])
     return out
 

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .segments import host_ptr, offsets as segment_offsets, to_device
 from .tf_sampling import farthest_point_sample, fps_ragged, gather_point
 
 
@@ -83,23 +84,6 @@ def upsample_clouds(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_r
 
 # ---- ragged batches: clouds of different sizes packed into one [sum n_c, 3] array, segment c = points [off[c], off[c + 1]) -----------
 
-def segment_offsets(counts):
-    """counts [C] -> int32 offsets [C + 1] (host), refused (ValueError) when the total does not fit an int32 offset."""
-    off = np.zeros(len(counts) + 1, np.int64)
-    np.cumsum(np.asarray(counts, np.int64), out=off[1:])
-    if off[-1] >= 2 ** 31:
-        raise ValueError("a packed batch holds at most 2^31 - 1 rows, got %d" % off[-1])
-    return off.astype(np.int32)
-
-
-def _host_ptr(a):
-    return _lib.C.c_void_p(a.ctypes.data)
-
-
-def _dev(a, device):
-    return torch.from_numpy(a).to(device)
-
-
 def fps_segments(inp, off, moff, arith=_lib.ARITH_CONTRACT, path="auto", cell=0):
     """farthest_point_sample per segment: inp [sum n_c, 3] (device), off / moff host offsets of the points and of the samples ->
     idx [sum m_c] int32, local to each segment.  Segment c equals farthest_point_sample(m_c, cloud_c) bit for bit.
@@ -112,8 +96,8 @@ def knn_patch_segments(cloud, off, queries, qoff, k):
     """knn_patch per segment: cloud [sum n_c, 3], queries [sum m_c, 3] (device), host offsets -> idx [sum m_c, k] int32, local."""
     off, qoff = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(qoff, np.int32)
     idx = torch.empty((int(qoff[-1]), k), dtype=torch.int32, device=cloud.device)
-    d_off, d_qoff = _dev(off, cloud.device), _dev(qoff, cloud.device)
-    _lib.check(_lib.lib().dispu_knn_patch_segments(len(off) - 1, _lib.ptr(d_off), _lib.ptr(d_qoff), _host_ptr(off), _host_ptr(qoff), k,
+    d_off, d_qoff = to_device(off, cloud.device), to_device(qoff, cloud.device)
+    _lib.check(_lib.lib().dispu_knn_patch_segments(len(off) - 1, _lib.ptr(d_off), _lib.ptr(d_qoff), host_ptr(off), host_ptr(qoff), k,
                                                    _lib.ptr(cloud.contiguous()), _lib.ptr(queries.contiguous()), _lib.ptr(idx),
                                                    _lib.stream_ptr(cloud.device)), "dispu_knn_patch_segments")
     return idx
@@ -126,8 +110,8 @@ def normalize_segments(p, off):
     out = torch.empty_like(p)
     c = torch.empty((C, 3), dtype=torch.float32, device=p.device)
     f = torch.empty((C,), dtype=torch.float32, device=p.device)
-    d_off = _dev(off, p.device)
-    _lib.check(_lib.lib().dispu_normalize_segments(C, _lib.ptr(d_off), _host_ptr(off), _lib.ptr(p.contiguous()), _lib.ptr(out), _lib.ptr(c),
+    d_off = to_device(off, p.device)
+    _lib.check(_lib.lib().dispu_normalize_segments(C, _lib.ptr(d_off), host_ptr(off), _lib.ptr(p.contiguous()), _lib.ptr(out), _lib.ptr(c),
                                                    _lib.ptr(f), _lib.stream_ptr(p.device)), "dispu_normalize_segments")
     return out, c, f
 
@@ -169,8 +153,8 @@ def upsample_ragged(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_r
                                            device=dev) for c in clouds])
     cloud = cloud.contiguous()
     # the segment base of every seed row (local indices -> rows of the packed cloud) and the cloud of every patch
-    sbase = _dev(np.repeat(off[:-1], seed_nums), dev)
-    pcloud = _dev(np.repeat(np.arange(len(sizes)), seed_nums), dev)
+    sbase = to_device(np.repeat(off[:-1], seed_nums), dev)
+    pcloud = to_device(np.repeat(np.arange(len(sizes)), seed_nums), dev)
 
     cloud_n, c0, f0 = normalize_segments(cloud, off)                            # model.py:364
     seeds = fps_segments(cloud_n, off, soff)                                     # model.py:323
@@ -182,7 +166,7 @@ def upsample_ragged(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_r
     pred = denormalize_patches(fine, pc_c, pc_f)                                 # model.py:310
     merged = denormalize_patches(pred, c0[pcloud].contiguous(), f0[pcloud].contiguous()).reshape(-1, 3)   # model.py:371-372
     sel = fps_segments(merged, moff, ooff)                                       # model.py:375
-    result = _gather_rows(merged, sel + _dev(np.repeat(moff[:-1], out_nums), dev)).cpu().numpy()
+    result = _gather_rows(merged, sel + to_device(np.repeat(moff[:-1], out_nums), dev)).cpu().numpy()
     outs = [result[ooff[c]:ooff[c + 1]] for c in range(len(sizes))]
     if return_stages:
         return outs, dict(cloud_n=cloud_n, off=off, seeds=seeds, seed_off=soff, pidx=pidx, patches_n=pn, fine=fine, merged=merged,

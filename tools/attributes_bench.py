@@ -86,16 +86,14 @@ def composed(queries, refs, feats):
 
 def abi_knn(queries, refs, k):
     """dispu_knn_cross_segments on the packed batch with every buffer allocated once: nothing of the host path in the time"""
-    import numpy as np
     import torch
     from dispu_amd import _lib
+    from dispu_amd.segments import host_ptr, offsets
     L, p = _lib.lib(), _lib.ptr
     q, r = torch.cat(queries).contiguous(), torch.cat(refs).contiguous()
     dev, c = q.device, len(queries)
-    qoff, roff = np.zeros(c + 1, np.int32), np.zeros(c + 1, np.int32)
-    np.cumsum([t.shape[0] for t in queries], out=qoff[1:])
-    np.cumsum([t.shape[0] for t in refs], out=roff[1:])
-    hq, hr = _lib.C.c_void_p(qoff.ctypes.data), _lib.C.c_void_p(roff.ctypes.data)
+    qoff, roff = offsets([t.shape[0] for t in queries]), offsets([t.shape[0] for t in refs])
+    hq, hr = host_ptr(qoff), host_ptr(roff)
     d_qoff, d_roff = torch.from_numpy(qoff).to(dev), torch.from_numpy(roff).to(dev)
     nb = L.dispu_knn_cross_scratch_bytes(c, hq, hr)
     assert nb > 0

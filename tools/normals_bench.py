@@ -62,14 +62,15 @@ class _Calls(object):
         import numpy as np
         import torch
         from dispu_amd import _lib
+        from dispu_amd.segments import host_ptr, offsets
         self.L, self._lib, self.c, self.n, self.k = _lib.lib(), _lib, c, n, k
         self.x = _ellipsoids(c, n, 7)
         dev = self.x.device
         self.st = _lib.stream_ptr(dev)
-        self.off = (np.arange(c + 1, dtype=np.int64) * n).astype(np.int32)
+        self.off = offsets([n] * c)
         self.moff = np.arange(c + 1, dtype=np.int32)
         self.d_off, self.d_moff = torch.from_numpy(self.off).to(dev), torch.from_numpy(self.moff).to(dev)
-        self.hp = lambda a: _lib.C.c_void_p(a.ctypes.data)
+        self.hp = host_ptr
         self.nb = self.L.dispu_pca_normals_scratch_bytes(c, self.hp(self.off), k)
         self.cb = self.L.dispu_fps_cells_scratch_bytes(c, self.hp(self.off), self.hp(self.moff), 0)
         assert self.nb > 0 and self.cb > 0

@@ -72,12 +72,13 @@ def step(c, n, k, reps):
     import numpy as np
     import torch
     from dispu_amd import _lib
+    from dispu_amd.segments import host_ptr, offsets
     L, p = _lib.lib(), _lib.ptr
     x = _ellipsoids(c, n, 7)
     dev, total = x.device, c * n
     st = _lib.stream_ptr(dev)
-    off = (np.arange(c + 1, dtype=np.int64) * n).astype(np.int32)
-    hp = _lib.C.c_void_p(off.ctypes.data)
+    off = offsets([n] * c)
+    hp = host_ptr(off)
     d_off = torch.from_numpy(off).to(dev)
     nb, ob = L.dispu_pca_normals_scratch_bytes(c, hp, k), L.dispu_orient_consistent_scratch_bytes(c, hp, k)
     assert nb > 0 and ob > 0

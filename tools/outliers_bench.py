@@ -119,15 +119,14 @@ def composed_radius(clouds, radius, min_neighbors):
 def abi_calls(clouds, k):
     """the two C entries on the packed batch with every buffer allocated once: dispu_knn_mean_dist_segments at k and
     dispu_pca_normals_segments at k + 1 -- the same search with a different tail, nothing of the host path in the time"""
-    import numpy as np
     import torch
     from dispu_amd import _lib
+    from dispu_amd.segments import host_ptr, offsets
     L, p = _lib.lib(), _lib.ptr
     x = torch.cat(clouds).contiguous()
     dev, c, total = x.device, len(clouds), x.shape[0]
-    off = np.zeros(c + 1, np.int32)
-    np.cumsum([t.shape[0] for t in clouds], out=off[1:])
-    hp = _lib.C.c_void_p(off.ctypes.data)
+    off = offsets([t.shape[0] for t in clouds])
+    hp = host_ptr(off)
     d_off = torch.from_numpy(off).to(dev)
     nb = max(L.dispu_knn_mean_dist_scratch_bytes(c, hp, k), L.dispu_pca_normals_scratch_bytes(c, hp, k + 1))
     assert nb > 0

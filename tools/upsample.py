@@ -217,6 +217,101 @@ def transfer_attributes(preds, src_points, src_attrs, a, dev):
     return out
 
 
+def stage(prefix, fn, *args, **kw):
+    """fn(*args, **kw); a ValueError ends the run with `prefix` (the files concerned, the option) before its text"""
+    try:
+        return fn(*args, **kw)
+    except ValueError as e:
+        sys.exit("%s%s" % (prefix, e))
+
+
+def load_inputs(a, paths):
+    """-> (clouds, in_normals or None, (src_points, src_attrs) or None), numpy, one entry per path"""
+    if a.hint == "input":
+        clouds, in_normals = (list(t) for t in zip(*[load_xyz_normals(p) for p in paths]))
+        return clouds, in_normals, None
+    if a.attributes != "none":
+        clouds, src_attrs = (list(t) for t in zip(*[load_xyz_attributes(p) for p in paths]))
+        return clouds, None, (list(clouds), src_attrs)   # the raw file's points: --clean_input and --grid_size replace clouds[i], not these
+    return [load_xyz(p) for p in paths], None, None
+
+
+def prepare_inputs(a, paths, clouds, in_normals, dev):
+    """--clean_input, then --grid_size, in place on clouds (and on in_normals, which follow their points) -> removed points per cloud"""
+    import torch
+    raw = [c.shape[0] for c in clouds]
+    removed = [0] * len(clouds)
+    if a.clean_input != "none":
+        kept, index = stage("--clean_input: ", remove_outliers, a.clean_input, clouds, a, dev)
+        for i, (k, ix) in enumerate(zip(kept, index)):
+            if k.shape[0] < a.patch_num_point:
+                sys.exit("%s: --clean_input %s leaves %d of %d points, fewer than --patch_num_point %d"
+                         % (paths[i], a.clean_input, k.shape[0], raw[i], a.patch_num_point))
+            removed[i] = raw[i] - k.shape[0]
+            clouds[i] = k
+            if in_normals is not None:
+                in_normals[i] = np.ascontiguousarray(in_normals[i][ix])
+    if a.grid_size is not None:
+        from dispu_amd import grid_subsampling
+        for i, c in enumerate(clouds):
+            if in_normals is None:
+                clouds[i] = stage("%s: " % paths[i], grid_subsampling.compute, c, sampleDl=a.grid_size)
+            else:                                        # the normals ride through as features: the mean per cube, renormalised below
+                pts, nrm = stage("%s: " % paths[i], grid_subsampling.compute, torch.from_numpy(c).to(dev),
+                                 features=torch.from_numpy(in_normals[i]).to(dev), sampleDl=a.grid_size)
+                length = nrm.norm(dim=1, keepdim=True)
+                in_normals[i] = torch.where(length > 0, nrm / length, torch.zeros_like(nrm))      # a zero mean stays zero
+                clouds[i] = pts.cpu().numpy()
+    return removed
+
+
+def orient_argument(a, group, clouds, in_normals, dev):
+    """estimate_normals' orient for the clouds of one group"""
+    import torch
+    orient = None
+    if a.hint == "centroid":
+        orient = ("centroid",)
+    elif a.hint == "viewpoint":
+        orient = ("viewpoint", a.viewpoint)
+    elif a.hint == "input":
+        orient = ("reference", [torch.from_numpy(clouds[i]).to(dev) for i in group],
+                  [torch.as_tensor(in_normals[i], device=dev).contiguous() for i in group])
+    if a.orient == "consistent":
+        orient = ("consistent",) if orient is None else ("consistent", orient)
+    return orient
+
+
+def process_group(a, gen, paths, group, clouds, in_normals, src, dev):
+    """upsample, --clean_output, --attributes, --normals for one group -> (preds, attrs or None, normals or None, removed per cloud)"""
+    import torch
+    from dispu_amd.upsample import upsample_ragged
+    names = ", ".join(paths[i] for i in group)
+    preds = stage("%s: " % names, upsample_ragged, gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
+    removed, attrs, normals = [0] * len(group), None, None
+    if a.clean_output != "none":
+        cleaned, _ = stage("%s: --clean_output: " % names, remove_outliers, a.clean_output, preds, a, dev)
+        removed = [before.shape[0] - after.shape[0] for before, after in zip(preds, cleaned)]
+        preds = cleaned
+    if a.attributes != "none":
+        attrs = stage("%s: --attributes: " % names, transfer_attributes, preds, [src[0][i] for i in group], [src[1][i] for i in group], a, dev)
+    if a.normals == "pca":
+        from dispu_amd.normals import estimate_normals
+        dpred = [torch.from_numpy(p).to(dev) for p in preds]
+        orient = orient_argument(a, group, clouds, in_normals, dev)
+        normals = [t.cpu().numpy() for t in stage("%s: " % names, estimate_normals, dpred, k=a.normals_k, orient=orient)]
+    return preds, attrs, normals, removed
+
+
+def write_output(out, pred, attrs, normals):
+    from dispu_amd.upsample import save_xyz
+    if attrs is not None:
+        save_xyz_columns(out, pred, attrs, *([normals] if normals is not None else []))
+    elif normals is not None:
+        save_xyz_normals(out, pred, normals)
+    else:
+        save_xyz(out, pred)
+
+
 def main(argv=None):
     a = parse_args(argv)
     if a.max_points <= 0:
@@ -226,30 +321,13 @@ def main(argv=None):
     paths = sorted(glob.glob(pattern))
     if not paths:
         sys.exit("no input matches %s" % pattern)
-    try:
-        refuse_unsupported(paths)
-    except ValueError as e:
-        sys.exit(str(e))
-    in_normals = None
-    if a.hint == "input":
-        try:
-            clouds, in_normals = (list(t) for t in zip(*[load_xyz_normals(p) for p in paths]))
-        except ValueError as e:
-            sys.exit(str(e))
-    elif a.attributes != "none":
-        try:
-            clouds, src_attrs = (list(t) for t in zip(*[load_xyz_attributes(p) for p in paths]))
-        except ValueError as e:
-            sys.exit(str(e))
-        src_points = list(clouds)                       # the raw file's points: --clean_input and --grid_size replace clouds[i], not these
-    else:
-        clouds = [load_xyz(p) for p in paths]
+    stage("", refuse_unsupported, paths)
+    clouds, in_normals, src = stage("", load_inputs, a, paths)
 
     sys.path.insert(0, ROOT)
     import torch
     import dispu_amd  # noqa: F401
     from dispu_amd.checkpoint import restore_generator
-    from dispu_amd.upsample import save_xyz, upsample_ragged
 
     if not torch.cuda.is_available():
         sys.exit("no ROCm device")
@@ -259,80 +337,15 @@ def main(argv=None):
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
     raw = [c.shape[0] for c in clouds]
-    removed_in, removed_out = [0] * len(clouds), [0] * len(clouds)
-    if a.clean_input != "none":
-        try:
-            kept, index = remove_outliers(a.clean_input, clouds, a, dev)
-        except ValueError as e:
-            sys.exit("--clean_input: %s" % e)
-        for i, (k, ix) in enumerate(zip(kept, index)):
-            if k.shape[0] < a.patch_num_point:
-                sys.exit("%s: --clean_input %s leaves %d of %d points, fewer than --patch_num_point %d"
-                         % (paths[i], a.clean_input, k.shape[0], raw[i], a.patch_num_point))
-            removed_in[i] = raw[i] - k.shape[0]
-            clouds[i] = k
-            if in_normals is not None:
-                in_normals[i] = np.ascontiguousarray(in_normals[i][ix])
-    if a.grid_size is not None:
-        from dispu_amd import grid_subsampling
-        for i, c in enumerate(clouds):
-            try:
-                if in_normals is None:
-                    clouds[i] = grid_subsampling.compute(c, sampleDl=a.grid_size)
-                else:                                    # the normals ride through as features: the mean per cube, renormalised below
-                    pts, nrm = grid_subsampling.compute(torch.from_numpy(c).to(dev), features=torch.from_numpy(in_normals[i]).to(dev),
-                                                        sampleDl=a.grid_size)
-                    length = nrm.norm(dim=1, keepdim=True)
-                    in_normals[i] = torch.where(length > 0, nrm / length, torch.zeros_like(nrm))      # a zero mean stays zero
-                    clouds[i] = pts.cpu().numpy()
-            except ValueError as e:
-                sys.exit("%s: %s" % (paths[i], e))
+    removed_in = prepare_inputs(a, paths, clouds, in_normals, dev)
     for group in group_by_budget([c.shape[0] for c in clouds], a.max_points):
-        try:
-            preds = upsample_ragged(gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
-        except ValueError as e:
-            sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
-        if a.clean_output != "none":
-            try:
-                cleaned, _ = remove_outliers(a.clean_output, preds, a, dev)
-            except ValueError as e:
-                sys.exit("%s: --clean_output: %s" % (", ".join(paths[i] for i in group), e))
-            for i, before, after in zip(group, preds, cleaned):
-                removed_out[i] = before.shape[0] - after.shape[0]
-            preds = cleaned
-        if a.attributes != "none":
-            try:
-                attrs = transfer_attributes(preds, [src_points[i] for i in group], [src_attrs[i] for i in group], a, dev)
-            except ValueError as e:
-                sys.exit("%s: --attributes: %s" % (", ".join(paths[i] for i in group), e))
-        if a.normals == "pca":
-            from dispu_amd.normals import estimate_normals
-            dpred = [torch.from_numpy(p).to(dev) for p in preds]
-            orient = None
-            if a.hint == "centroid":
-                orient = ("centroid",)
-            elif a.hint == "viewpoint":
-                orient = ("viewpoint", a.viewpoint)
-            elif a.hint == "input":
-                orient = ("reference", [torch.from_numpy(clouds[i]).to(dev) for i in group],
-                          [torch.as_tensor(in_normals[i], device=dev).contiguous() for i in group])
-            if a.orient == "consistent":
-                orient = ("consistent",) if orient is None else ("consistent", orient)
-            try:
-                normals = [t.cpu().numpy() for t in estimate_normals(dpred, k=a.normals_k, orient=orient)]
-            except ValueError as e:
-                sys.exit("%s: %s" % (", ".join(paths[i] for i in group), e))
+        preds, attrs, normals, removed_out = process_group(a, gen, paths, group, clouds, in_normals, src, dev)
         for j, (i, pred) in enumerate(zip(group, preds)):
             out = os.path.join(out_dir, output_name(paths[i], a.final_ratio))
-            if a.attributes != "none":
-                save_xyz_columns(out, pred, attrs[j], *([normals[j]] if a.normals == "pca" else []))
-            elif a.normals == "pca":
-                save_xyz_normals(out, pred, normals[j])
-            else:
-                save_xyz(out, pred)
+            write_output(out, pred, attrs[j] if attrs is not None else None, normals[j] if normals is not None else None)
             gone = ""
             if a.clean_input != "none" or a.clean_output != "none":
-                gone = ", outliers removed: %d input, %d output" % (removed_in[i], removed_out[i])
+                gone = ", outliers removed: %d input, %d output" % (removed_in[i], removed_out[j])
             if a.grid_size is None:
                 print("%s: %d -> %d points, %s%s" % (paths[i], clouds[i].shape[0], pred.shape[0], out, gone))
             else:
