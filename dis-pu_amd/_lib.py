@@ -55,6 +55,8 @@ SIGNATURES = {
     "dispu_knn_cross_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_knn_cross_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_transfer_attributes_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_mls_project_scratch_bytes": (_sz, [_i, _vp, _vp]),
+    "dispu_mls_project_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_fps_segments_auto_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_fps_segments_auto": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "dispu_prob_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

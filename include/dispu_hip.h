@@ -60,7 +60,8 @@ extern "C" {
  * mesh sampler (dispu_mesh_sample, dispu_poisson_disk_*, dispu_sort_rows_i32), and the large-cloud sampling (dispu_fps_cells*,
  * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*), and the outlier filters (dispu_knn_mean_dist_*,
  * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*), and the cross-cloud search with the attribute transfer
- * (dispu_knn_cross_*, dispu_transfer_attributes_segments), and the consistent orientation (dispu_orient_consistent_*): additions only. */
+ * (dispu_knn_cross_*, dispu_transfer_attributes_segments), and the consistent orientation (dispu_orient_consistent_*), and the
+ * moving-least-squares projection (dispu_mls_project_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -1094,6 +1095,36 @@ int dispu_orient_consistent_segments(int C, const int* off, const int* off_host,
                                      const int* neighbors, int vote, int flags, float* normal_out, unsigned char* flip, int* component,
                                      int* n_components, int* status, void* scratch, size_t scratch_bytes, float* profile_host,
                                      void* stream);
+
+/* ---- moving-least-squares projection of one cloud onto the surface another describes: csrc/mls_project.hip, dis-pu_amd/mls.py.
+ * Queries = references denoises a cloud; an upsampled cloud against its input snaps the output onto the input's surface.  The
+ * reference has no counterpart.  Batches, offsets, status and scratch as for dispu_knn_cross_segments; 4 <= k <= 32,
+ * 1 <= support <= 4, 1 <= iterations <= 8.  One step, for query x (fp32) of segment c against its m_c reference points P:
+ *  1. neighbours: the k' = min(k, m_c) points of P with the smallest (d2 bits, local index), d2 = ((dx*dx + dy*dy) + dz*dz) in fp32
+ *     (DISPU_ARITH_PLAIN): the project's rule; a reference point equal to the query counts like any other (d2 = 0).
+ *  2. weights, in double: D = the d2 of rank k' - 1, rho2 = (support * support) * D; per neighbour in ascending rank r2 = d2_j / rho2;
+ *     w_j = 0 if r2 >= 1, else r = sqrt(r2), w_j = (((1 - r)*(1 - r)) * ((1 - r)*(1 - r))) * (4 r + 1)   (Wendland).
+ *  3. fit, in double, around x: u_j = p_j - x (exact);  S0 = sum w_j,  c = (sum w_j u_j) / S0,  Cov = (sum w_j u_j u_j^T) / S0 - c c^T,
+ *     sums in ascending rank;  the cyclic Jacobi of dispu_pca_normals_segments (same rotation, at most 12 sweeps, same off-diagonal
+ *     drop rule);  e = the normalised eigenvector of the smallest eigenvalue (ties: the lowest column);  l0 <= l1 <= l2 the eigenvalues.
+ *  4. the query keeps its position BIT FOR BIT if k' < 3, or fewer than 3 weights are non-zero, or D == 0, or l2 <= 0, or
+ *     l1 <= 1e-12 * l2 (collinear neighbours: no plane).
+ *  5. otherwise t = (c.x*e.x + c.y*e.y) + c.z*e.z and every coordinate becomes (float)((double)x + t * e): the sign of e cancels.
+ * iterations = T repeats the step on the moved fp32 positions against the SAME references (in the self case too: the surface stays
+ * fixed), so T iterations equal T calls of one, byte for byte.  The reference pre-pass runs once, the query pre-pass before every
+ * iteration on the positions it searches from.
+ * out [sum q_c, 3]: the new positions at the queries' rows; it must not overlap queries or refs.  idx_out [sum q_c, k] int32 or NULL:
+ * the last iteration's neighbours in ascending key order, -1 beyond k'.  sum q_c * k >= 2^31 is refused.
+ * status [C] (device): 0, or 1 for a segment whose queries (at any iteration) or references hold a NaN or an infinite coordinate; the
+ * step that finds it and every later one write nothing for that segment.
+ * scratch: 16-byte aligned, at least dispu_mls_project_scratch_bytes (both pre-passes, one position buffer, two status rows; 0 for an
+ * illegal C, illegal offsets or a segment above 2^24 points); the library never allocates; a refusal (hipErrorInvalidValue) comes
+ * before any launch and touches no output.  Ordinary stores, no atomics, identical bytes from run to run.  The yardstick is
+ * tests/mls_oracle.py.  Additions only: dispu_version() stays 5. ---------------------------------------------------------------------- */
+size_t dispu_mls_project_scratch_bytes(int C, const int* qoff_host, const int* roff_host);
+int dispu_mls_project_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, double support,
+                               int iterations, const float* queries, const float* refs, float* out, int* idx_out, int* status,
+                               void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,14 @@ the third of each input file is an attribute, and each output point takes the in
 nearest points of the RAW input file (idw), or the row of the nearest one (nearest: labels stay labels), found by an exact search on
 the GPU (dis-pu_amd/attributes.py; the reference has no counterpart).  The sources are the file's points before --clean_input and
 --grid_size; the transfer runs after --clean_output and before --normals.  Output rows are x y z a1 .. aF [nx ny nz].  Not together
-with --orient input, which reads columns 4-6 as normals."""
+with --orient input, which reads columns 4-6 as normals.
+
+--denoise_input T / --project_output T (both 0 = off by default, T = 1 .. 8 steps) move points onto a moving-least-squares surface on
+the GPU (dis-pu_amd/mls.py; the reference has no counterpart): every point goes onto the plane fitted to its --mls_k nearest points of
+the surface cloud, weighted out to --mls_support times the distance of the farthest of them.  --denoise_input projects every input
+cloud onto its own surface, after --clean_input and --grid_size and before the generator (normals of --orient input stay with their
+points).  --project_output projects the upsampled cloud onto the surface of the cloud that went into the generator, after
+--clean_output and before --attributes and --normals."""
 import argparse
 import glob
 import math
@@ -156,7 +163,23 @@ def parse_args(argv=None):
                          "--attributes_k nearest raw input points) or nearest (the nearest one's row; for labels); the output rows are "
                          "x y z a1 .. aF [nx ny nz]; not together with --orient input, which reads columns 4-6 as normals")
     ap.add_argument("--attributes_k", type=int, default=3, help="neighbours per output point of --attributes, 1 .. 32")
+    ap.add_argument("--denoise_input", type=int, default=0, metavar="T",
+                    help="0: off; T = 1 .. 8: project every input cloud onto its own moving-least-squares surface in T steps (after "
+                         "--clean_input and --grid_size, before the generator)")
+    ap.add_argument("--project_output", type=int, default=0, metavar="T",
+                    help="0: off; T = 1 .. 8: project every upsampled cloud onto the moving-least-squares surface of the cloud that went "
+                         "into the generator in T steps (after --clean_output, before --attributes and --normals)")
+    ap.add_argument("--mls_k", type=int, default=16, help="neighbours per point of --denoise_input / --project_output, 4 .. 32")
+    ap.add_argument("--mls_support", type=float, default=1.0,
+                    help="the weights of --denoise_input / --project_output reach this many times the farthest neighbour's distance, 1 .. 4")
     a = ap.parse_args(argv)
+    for name in ("denoise_input", "project_output"):
+        if not 0 <= getattr(a, name) <= 8:
+            ap.error("--%s must be in 0 .. 8, got %d" % (name, getattr(a, name)))
+    if not 4 <= a.mls_k <= 32:
+        ap.error("--mls_k must be in 4 .. 32, got %d" % a.mls_k)
+    if not 1.0 <= a.mls_support <= 4.0:                                      # a NaN fails both comparisons
+        ap.error("--mls_support must be in 1 .. 4, got %s" % a.mls_support)
     if "radius" in (a.clean_input, a.clean_output) and a.outliers_radius is None:
         ap.error("--clean_input / --clean_output radius need --outliers_radius R")
     if not 1 <= a.outliers_k <= 31:
@@ -217,6 +240,21 @@ def transfer_attributes(preds, src_points, src_attrs, a, dev):
     return out
 
 
+def mls_project(points, surfaces, steps, a, dev):
+    """the --denoise_input / --project_output step: every numpy cloud of `points` projected onto the surface of its cloud of `surfaces`
+    in `steps` steps, in groups of at most --max-points points -> numpy clouds"""
+    import torch
+    from dispu_amd import mls
+    out = [None] * len(points)
+    for group in group_by_budget([p.shape[0] for p in points], a.max_points):
+        got = mls.mls_project([torch.from_numpy(np.ascontiguousarray(points[i], np.float32)).to(dev) for i in group],
+                              [torch.from_numpy(np.ascontiguousarray(surfaces[i], np.float32)).to(dev) for i in group],
+                              k=a.mls_k, support=a.mls_support, iterations=steps)
+        for i, t in zip(group, got):
+            out[i] = t.cpu().numpy()
+    return out
+
+
 def stage(prefix, fn, *args, **kw):
     """fn(*args, **kw); a ValueError ends the run with `prefix` (the files concerned, the option) before its text"""
     try:
@@ -262,6 +300,8 @@ def prepare_inputs(a, paths, clouds, in_normals, dev):
                 length = nrm.norm(dim=1, keepdim=True)
                 in_normals[i] = torch.where(length > 0, nrm / length, torch.zeros_like(nrm))      # a zero mean stays zero
                 clouds[i] = pts.cpu().numpy()
+    if a.denoise_input:
+        clouds[:] = stage("--denoise_input: ", mls_project, clouds, clouds, a.denoise_input, a, dev)
     return removed
 
 
@@ -292,6 +332,8 @@ def process_group(a, gen, paths, group, clouds, in_normals, src, dev):
         cleaned, _ = stage("%s: --clean_output: " % names, remove_outliers, a.clean_output, preds, a, dev)
         removed = [before.shape[0] - after.shape[0] for before, after in zip(preds, cleaned)]
         preds = cleaned
+    if a.project_output:
+        preds = stage("%s: --project_output: " % names, mls_project, preds, [clouds[i] for i in group], a.project_output, a, dev)
     if a.attributes != "none":
         attrs = stage("%s: --attributes: " % names, transfer_attributes, preds, [src[0][i] for i in group], [src[1][i] for i in group], a, dev)
     if a.normals == "pca":
