@@ -47,7 +47,12 @@ __device__ void tri_closest(T px, T py, T pz, T ax, T ay, T az, T bx, T by, T bz
     const T bpx = px - bx, bpy = py - by, bpz = pz - bz;
     const T d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
     if (d3 >= T(0) && d4 <= d3) { qx = bx; qy = by; qz = bz; return; }
-    const T vc = d1 * d4 - d3 * d2;
+    // The face-region weights as triple products with the normal, (ab x ac) . (ap x bp) and its two companions: by Lagrange's identity
+    // the d1 d4 - d3 d2 of the book, whose two products of about |ab| |ac| |ap| |bp| cancel down to |ab x ac| |ap x bp| and, in
+    // fp32, left nothing but rounding for a sliver (length 1, width 1e-4: the point 0.007 off its own face; found by
+    // tests/test_mesh_eval_ops_gpu.py::test_point_to_mesh[rungs]).  Here each cross product is rounded at its own size.
+    const T nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+    const T vc = nx * (apy * bpz - apz * bpy) + ny * (apz * bpx - apx * bpz) + nz * (apx * bpy - apy * bpx);
     if (vc <= T(0) && d1 >= T(0) && d3 <= T(0) && d1 - d3 > T(0)) {
         const T v = d1 / (d1 - d3);
         qx = ax + v * abx; qy = ay + v * aby; qz = az + v * abz; return;
@@ -55,12 +60,12 @@ __device__ void tri_closest(T px, T py, T pz, T ax, T ay, T az, T bx, T by, T bz
     const T cpx = px - cx, cpy = py - cy, cpz = pz - cz;
     const T d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
     if (d6 >= T(0) && d5 <= d6) { qx = cx; qy = cy; qz = cz; return; }
-    const T vb = d5 * d2 - d1 * d6;
+    const T vb = nx * (cpy * apz - cpz * apy) + ny * (cpz * apx - cpx * apz) + nz * (cpx * apy - cpy * apx);
     if (vb <= T(0) && d2 >= T(0) && d6 <= T(0) && d2 - d6 > T(0)) {
         const T w = d2 / (d2 - d6);
         qx = ax + w * acx; qy = ay + w * acy; qz = az + w * acz; return;
     }
-    const T va = d3 * d6 - d5 * d4;
+    const T va = nx * (bpy * cpz - bpz * cpy) + ny * (bpz * cpx - bpx * cpz) + nz * (bpx * cpy - bpy * cpx);
     if (va <= T(0) && (d4 - d3) >= T(0) && (d5 - d6) >= T(0) && (d4 - d3) + (d5 - d6) > T(0)) {
         const T w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
         qx = bx + w * (cx - bx); qy = by + w * (cy - by); qz = bz + w * (cz - bz); return;

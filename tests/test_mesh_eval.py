@@ -185,3 +185,128 @@ def test_oracle_analyze_uniform_by_hand():
     assert abs(nn - 0.1) < 1e-7
     assert np.isclose(got[0], want0, rtol=1e-6)                    # the 3-point disk of seed 1 is skipped (< 5)
     assert np.isnan(got[1])                                        # every r1 disk skipped -> NaN
+
+
+# ---- the oracle helpers and inputs of tests/test_mesh_eval_ops_gpu.py ------------------------------------------------------------------
+def test_uniform_terms_by_hand():
+    # six points on a line, 0.25 apart (exact in float32), the last a copy of the first: nn = 0 for the pair, 0.25 for the rest
+    pts = np.array([[0.25 * k, 0, 0] for k in range(5)] + [[0.0, 0, 0]] + [[9.0, 9, 9]] * 4, np.float32)
+    disks = [[0, 1, 2, 3, 4, 5], [0, 1, 2, 3], [6, 7, 8, 9], [4, 3, 2, 1, 0]]   # seed 0: (r0, r1); seed 1: (r0, r1)
+    r, pct, N = np.array([0.5, 0.75]), np.array([0.01, 0.02]), 400
+    kept, term, mean = MO.uniform_terms(disks, r, pts, pct, N)
+    assert kept.tolist() == [1, 0, 0, 1] and term[1] == 0.0 and term[2] == 0.0
+    ed0 = math.sqrt(2 * (math.pi * 0.25 / 6) / 1.732)
+    want0 = (6 - 4.0) ** 2 / 4.0 * ((2 * (0 - ed0) ** 2 + 4 * (0.25 - ed0) ** 2) / ed0 / 6)
+    ed3 = math.sqrt(2 * (math.pi * 0.5625 / 5) / 1.732)
+    want3 = (5 - 8.0) ** 2 / 8.0 * ((0.25 - ed3) ** 2 / ed3)
+    assert abs(term[0] - want0) <= 1e-15 * want0 and abs(term[3] - want3) <= 1e-15 * want3
+    assert mean[0] == term[0] and mean[1] == term[3]                # one kept disk per radius
+    _, _, none = MO.uniform_terms(disks[1:3], r, pts, pct, N)
+    assert np.isnan(none).all()
+
+
+def test_uniform_terms_against_analyze_uniform():
+    rng = np.random.default_rng(12)
+    pts = rng.random((600, 3)).astype(np.float32)
+    pts[17] = pts[5]
+    disks = [np.sort(rng.choice(600, c, replace=False)) for c in (300, 4, 5, 40, 0, 7, 257, 6, 64, 3)]   # S = 5, R = 2
+    r, pct = np.array([0.4, 0.15]), np.array([0.3, 0.02])
+    kept, term, mean = MO.uniform_terms(disks, r, pts, pct, 600)
+    assert kept.tolist() == [int(len(d) >= 5) for d in disks]
+    np.testing.assert_allclose(mean, MO.analyze_uniform(disks, r, pts, pct), rtol=1e-4)
+
+
+def test_geodesic_disk_members_by_hand():
+    r = np.array([0.1, 0.25], np.float32)
+    r0 = float(r[0])                                              # float64(float32(0.1)) = 0.10000000149..., not 0.1
+    off = np.array([0, 0, 4, 5])
+    cand = np.array([7, 3, 9, 1, 2], np.int32)
+    dist = np.array([r0, np.nextafter(r0, np.inf), np.inf, 0.0, 0.25])
+    rows = MO.geodesic_disk_members(off, cand, dist, r)
+    assert [x.tolist() for x in rows] == [[], [], [7, 1], [7, 3, 1], [], [2]]
+    assert 0.1 < r0 and MO.geodesic_disk_members(off, cand, np.full(5, 0.1), r)[2].tolist() == [7, 3, 9, 1]
+
+
+def test_geodesic_case_holds_its_special_distances():
+    r = np.array([0.25, 0.1, 0.4], np.float32)
+    off, cand, dist = MO.geodesic_case(MO.GEO_ROWS, r, seed=1)
+    assert off.tolist() == [0, 0, 1, 64, 128, 193, 393] and cand.shape == dist.shape == (393,)
+    r64 = r.astype(np.float64)
+    for i in range(2, 6):
+        row = dist[off[i]:off[i + 1]]
+        assert row[0] == r64[i % 3] and row[1] > r64[i % 3] and np.float32(row[1]) == r[i % 3] and np.isinf(row[2]) and row[3] == 0.0
+        assert np.all(np.diff(cand[off[i]:off[i + 1]]) > 0)
+    assert dist[0] == r64[1]                                       # the row of one candidate: exactly on a radius
+
+
+@pytest.mark.parametrize("case", [(1, 1, 1), (3, 63, 2), (6, 65, 3), (683, 65, 3)])
+def test_disk_case_sits_on_the_radius(case):
+    S, n, R = case
+    seeds, points, radii = MO.disk_case(S, n, R)
+    assert seeds.dtype == points.dtype == radii.dtype == np.float32 and radii[0] == 1e5
+    r2 = MO.DISK_R * MO.DISK_R
+    assert points[0, 0] * points[0, 0] == r2 and not seeds[0].any()
+    rows = MO.disk_members_fp32(seeds, points, radii)
+    assert all(np.array_equal(rows[i * R], np.arange(n)) for i in range(S))
+    if n > 1 and R > 1:
+        assert points[1, 0] * points[1, 0] > r2 and 0 in rows[1] and 1 not in rows[1]
+    if S > 1 and R > 2:
+        assert rows[1 * R + 2].tolist() == [n - 1]                 # radius 0: the point the seed copies, d2 = 0 <= 0
+
+
+def test_uniformity_rows_layout():
+    pts = MO.uniformity_points()
+    assert pts.shape == (1100, 3) and np.array_equal(pts[0], pts[1099]) and len(np.unique(pts, axis=0)) == 1099
+    for S in (1, 63, 65, 130):
+        rows = MO.uniformity_rows(S)
+        sizes = np.array([len(r) for r in rows]).reshape(S, 2)
+        assert all(len(set(r.tolist())) == len(r) and r.min() >= 0 and r.max() < 1100 for r in rows if len(r))
+        if S == 1:
+            assert sizes.tolist() == [[1025, 5]]
+            continue
+        assert set(sizes.reshape(-1).tolist()) == set(MO.UNI_SIZES_KEPT + MO.UNI_SIZES_SKIPPED)
+        assert (sizes[0::2, 0] >= 5).all() and (sizes[1::2, 0] < 5).all()                   # alternate along the seeds
+        if S == 65:
+            assert (sizes[:, 1] < 5).all()
+        else:
+            assert (sizes[1::2, 1] >= 5).all() and (sizes[0::2, 1] < 5).all()
+        big = [r for r in rows if len(r) == 1025]
+        paired = [r for r in big if r[0] == 0 and r[1024] == 1099]
+        plain = [r for r in big if 0 not in r and 1099 not in r]
+        assert len(paired) >= 1 and len(plain) >= 1 and len(paired) + len(plain) == len(big)
+
+
+def test_mesh_builders():
+    v, f = MO.icosphere_prefix(4, 4097)
+    assert f.shape == (4097, 3) and v.dtype == np.float32 and f.max() < v.shape[0]
+    v, f = MO.icosphere_prefix(2, None, 0.5, (37.5, -20.25, 11.0))
+    assert f.shape == (320, 3) and np.allclose(np.linalg.norm(v - np.float32([37.5, -20.25, 11.0]), axis=1), 0.5, atol=1e-5)
+    v, f = MO.sliver_rungs()
+    tv = v[f].astype(np.float64)
+    assert f.shape == (200, 3) and len(np.unique(f)) == 600
+    assert np.allclose(np.linalg.norm(tv[:, 1] - tv[:, 0], axis=1), 1.0) and np.allclose(np.linalg.norm(tv[:, 2] - tv[:, 1], axis=1), 1e-4, rtol=1e-2)
+    for extra, exact in ((MO.zero_area_faces(), True), (MO.near_collinear_faces(), False)):
+        t = extra.astype(np.float64)
+        area = 0.5 * np.linalg.norm(np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]), axis=1)
+        assert (area == 0.0).all() if exact else (area.max() < 1e-8 and (area > 0).any())
+        v2, f2 = MO.append_faces(v, f, extra)
+        assert np.array_equal(v2[f2[200:]], extra) and np.array_equal(f2[:200], f)
+    z = MO.zero_area_faces()
+    same = [[bool(np.array_equal(t[a], t[b])) for a, b in ((0, 1), (1, 2), (0, 2))] for t in z]
+    assert same == [[True, False, False], [False, True, False], [False, False, True], [True, True, True]] + [[False] * 3] * 3
+    dv_, df = MO.duplicated(v, f)
+    assert df.shape == (400, 3) and np.array_equal(df[:200], df[200:])
+
+
+@pytest.mark.parametrize("name", MO.P2F_MESHES + (MO.P2F_DUP_BASE,))
+def test_p2f_cases_leave_few_near_ties(name):
+    """what tests/test_mesh_eval_ops_gpu.py asserts of its inputs, from the oracle alone: at most a tenth of a mesh's points lie within
+    1e-6 x scale of a second face, and the meshes with appended faces have points that those faces decide."""
+    case = MO.p2f_case(name)
+    assert [len(s) for s in case["sets"]] == list(MO.P2F_POINT_COUNTS) and case["points"].shape == (333, 3)
+    clear = case["gap"] > 1e-6 * case["scale"]
+    assert 1.0 - clear.mean() <= 0.10
+    assert case["scale"] >= 1.0 and (case["scale"] > 37 if name == "offset" else case["scale"] < 7)
+    if case["favour"] is not None:
+        assert (np.isin(case["face"], case["favour"]) & clear).sum() >= 40
+        assert set(case["favour"].tolist()) <= set(case["face"][clear].tolist())   # every appended face decides a point
