@@ -18,6 +18,7 @@ MESH_TILE = 64         # faces per tile of point_to_mesh's face layout
 LINEAR_PLAN_INTS = 21  # include/dispu_hip.h: DISPU_LINEAR_PLAN_INTS
 POISSON_MAX_N = 49152       # include/dispu_hip.h: DISPU_POISSON_MAX_N
 POISSON_MAX_ROUNDS = 256    # include/dispu_hip.h: DISPU_POISSON_MAX_ROUNDS
+POISSON_CELLS_NONFINITE = 4 # include/dispu_hip.h: DISPU_POISSON_CELLS_NONFINITE (status bit of dispu_poisson_cells_*)
 SORT_ROWS_MAX_K = 4096      # dispu_sort_rows_i32
 RADIX_TILE = 2048           # include/dispu_hip.h: DISPU_RADIX_TILE
 GRID_NONFINITE, GRID_AXIS_X, GRID_AXIS_Y, GRID_AXIS_Z, GRID_TOO_MANY_POINTS = 1, 2, 3, 4, 5   # include/dispu_hip.h: DISPU_GRID_*
@@ -231,6 +232,9 @@ SIGNATURES = {
     "dispu_poisson_disk_keep": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dispu_poisson_disk_select": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dispu_sort_rows_i32": (_i, [_i, _i, _vp, _vp]),
+    "dispu_poisson_cells_scratch_bytes": (_sz, [_i, C.c_longlong]),
+    "dispu_poisson_cells_keep": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "dispu_poisson_cells_select": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dispu_radix_sort_scratch_bytes": (_sz, [C.c_longlong]),
     "dispu_radix_sort_pairs": (_i, [C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_grid_subsample_scratch_bytes": (_sz, [C.c_longlong, _i, _i]),

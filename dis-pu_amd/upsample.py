@@ -121,13 +121,20 @@ def _gather_rows(points, idx):
     return gather_point(points.reshape(1, -1, 3), idx.reshape(1, -1)).reshape(-1, 3)
 
 
-def upsample_ragged(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_ratio=4, return_stages=False):
+def upsample_ragged(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_ratio=4, return_stages=False, merge="fps", merge_seed=0):
     """Clouds of ANY sizes (a sequence of [n_c, 3] numpy arrays or device tensors) -> a list of [final_ratio * n_c, 3] float32 numpy
     arrays in input order, each bit-identical to upsample_cloud(gen, clouds[c]) (model.py:343-381 per cloud).  The clouds are packed
     into one [sum n_c, 3] array; whole-cloud normalisation, both FPS stages and the patch k-NN run as ONE launch (sequence) over all
     segments, and all patches of all clouds go through one generator batch.  With return_stages also a dict of the packed device
     stages and their host offsets: cloud_n / off, seeds / seed_off (= rows of pidx, patches_n and fine), merged / merged_off,
-    sel / out_off."""
+    sel / out_off.
+    merge: how the merged patch points of a cloud are thinned to final_ratio * n_c.  "fps" (the default) is the reference's exact FPS,
+    out_nums dependent rounds.  "poisson" replaces that one stage by poisson_cells.select(merged segments, out_nums,
+    poisson_cells.spacing_r_hi(inputs, final_ratio), shuffle_seed=merge_seed): a blue-noise set of exactly as many points in about ten
+    parallel rounds per radius, no longer the reference's output; the rows keep the merged cloud's order, and the stages gain
+    merge_r (the radius per cloud), merge_count (the points kept at it) and merge_r_hi (the start of the bisection)."""
+    if merge not in ("fps", "poisson"):
+        raise ValueError("merge must be 'fps' or 'poisson', got %r" % (merge,))
     clouds = list(clouds)
     if not clouds:
         raise ValueError("upsample_ragged needs at least one cloud")
@@ -165,12 +172,21 @@ def upsample_ragged(gen, clouds, patch_num_point=256, patch_num_ratio=3, final_r
     coarse, fine = generator_chain(gen, pn, final_ratio)
     pred = denormalize_patches(fine, pc_c, pc_f)                                 # model.py:310
     merged = denormalize_patches(pred, c0[pcloud].contiguous(), f0[pcloud].contiguous()).reshape(-1, 3)   # model.py:371-372
-    sel = fps_segments(merged, moff, ooff)                                       # model.py:375
+    extra = {}
+    if merge == "fps":
+        sel = fps_segments(merged, moff, ooff)                                   # model.py:375
+    else:
+        from . import poisson_cells
+        r_hi = poisson_cells.spacing_r_hi([cloud[off[c]:off[c + 1]] for c in range(len(sizes))], final_ratio)
+        idx, r, count = poisson_cells.select([merged[moff[c]:moff[c + 1]] for c in range(len(sizes))], out_nums, r_hi,
+                                             shuffle_seed=merge_seed)
+        sel = torch.cat(idx)
+        extra = dict(merge_r=torch.stack(r), merge_count=torch.stack(count), merge_r_hi=r_hi)
     result = _gather_rows(merged, sel + to_device(np.repeat(moff[:-1], out_nums), dev)).cpu().numpy()
     outs = [result[ooff[c]:ooff[c + 1]] for c in range(len(sizes))]
     if return_stages:
         return outs, dict(cloud_n=cloud_n, off=off, seeds=seeds, seed_off=soff, pidx=pidx, patches_n=pn, fine=fine, merged=merged,
-                          merged_off=moff, sel=sel, out_off=ooff)
+                          merged_off=moff, sel=sel, out_off=ooff, **extra)
     return outs
 
 

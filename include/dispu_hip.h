@@ -913,8 +913,8 @@ int dispu_mesh_sample(int V, int F, const float* verts, const int* faces, const 
  * smaller, and for n > DISPU_POISSON_MAX_N.
  * DISPU_POISSON_MAX_N: a cloud lives in ONE workgroup whose LDS holds the 16-bit offsets of the 32^3 cells (64 KB), one state byte per
  * point and one selection bit per point: 128 + 65536 + n + n / 8 bytes.  The 16-bit offsets bound n below 65536; 49152 (6 x 8192: up to
- * 6 x oversampling of an 8192-point cloud) needs 118 KB of the 160 KB a CU of this part has.  Larger clouds would need a
- * multi-workgroup tier, which does not exist. */
+ * 6 x oversampling of an 8192-point cloud) needs 118 KB of the 160 KB a CU of this part has.  Larger clouds take the
+ * device-wide cell tier below (dispu_poisson_cells_keep / _select), which returns the same bytes. */
 #define DISPU_POISSON_MAX_N 49152
 #define DISPU_POISSON_MAX_ROUNDS 256
 size_t dispu_poisson_disk_scratch_bytes(int b, int n);
@@ -930,6 +930,32 @@ int dispu_poisson_disk_select(int b, int n, int m, int steps, const float* point
 /* every row of idx [b,k] i32 ascending, in place (k <= 4096; one workgroup per row, bitonic network in LDS).  dispu_knn_patch returns
  * a region's points by distance; the greedy order of the selection must be the sample order, i.e. the index order. */
 int dispu_sort_rows_i32(int b, int k, int* idx, void* stream);
+/* The same selection for clouds of any size: the device-wide cell tier (csrc/poisson_disk_cells.hip, dis-pu_amd/poisson_cells.py).  The
+ * definition is dispu_poisson_disk_keep's, word for word (index order, d2 = (dx dx + dy dy) + dz dz in fp32, DISPU_ARITH_PLAIN, strict
+ * comparison, r <= 0 keeps everything), and the result is the sequential one bit for bit, whatever the timing, the launch shape or the
+ * packing, and identical from run to run (no float atomics).  Input: a packed ragged batch of C segments (1 <= C <= 65535, 1 .. 2^24
+ * points each, fewer than 2^31 in all) in points [off[C],3]; off [C+1] on the device, off_host the same on the host; radius [C] on the
+ * device, one per segment.  Per segment a uniform grid of cell side max(r, extent / 1024) (1 + 2^-10), keys (segment, z, y, x) through
+ * dispu_radix_sort_pairs' sorter, the 9 neighbour ranges kept per occupied cell; one launch per round over the still-active points,
+ * states updated in place (the kernel file says why that is safe), at most DISPU_POISSON_MAX_ROUNDS launches per evaluation.
+ * keep [off[C]] u8, count [C] i32, rounds (NULL: not written) [1] i32 = the rounds the evaluation took.  status [C] i32, written by
+ * the call: bit 0 = the segment was still active at the round bound (its outputs are then incomplete), bit 1 (select only) = fewer
+ * than m indices were written (only together with bit 0), bit 2 (DISPU_POISSON_CELLS_NONFINITE) = a non-finite coordinate or radius, or an extent beyond the float
+ * range (the segment is then not evaluated: its flags are all 1).  The call is synchronous: it reads ONE 4-byte word back per chunk of
+ * rounds to stop early.  scratch >= dispu_poisson_cells_scratch_bytes(C, off[C]) (0 for illegal sizes), 16-byte aligned; refused
+ * (hipErrorInvalidValue) when smaller, and for offsets that do not start at 0 or do not grow. */
+#define DISPU_POISSON_CELLS_NONFINITE 4
+size_t dispu_poisson_cells_scratch_bytes(int C, long long total_n);
+int dispu_poisson_cells_keep(int C, const int* off, const int* off_host, const float* points, const float* radius, unsigned char* keep,
+                             int* count, int* rounds, void* scratch, size_t scratch_bytes, int* status, void* stream);
+/* Exactly m_c = moff[c + 1] - moff[c] points per segment (1 <= m_c <= n_c; moff [C+1] on the device, moff_host on the host):
+ * dispu_poisson_disk_select's bisection bit for bit, per segment on the device (lo = 0, hi = r_hi[c]; steps times mid = 0.5f (lo + hi),
+ * the keep count at mid >= m_c ? lo = mid : hi = mid, fp32), the grid built once for r_hi, all segments in the same launches.
+ * idx [moff[C]] i32 = per segment its first m_c kept indices at r = lo, local to the segment, ascending; r_out [C] = lo;
+ * count_out [C] = the keep count at lo; rounds (NULL: not written) [steps + 1] i32 = the rounds of every evaluation.  steps >= 0. */
+int dispu_poisson_cells_select(int C, const int* off, const int* moff, const int* off_host, const int* moff_host, int steps,
+                               const float* points, const float* r_hi, int* idx, float* r_out, int* count_out, int* rounds,
+                               void* scratch, size_t scratch_bytes, int* status, void* stream);
 
 /* ---- grid subsampling: libs/cpp_wrappers/cpp_subsampling (compile_op.sh builds it with the other ops), the KPConv voxel-grid
  * subsampler.  dis-pu_amd/grid_subsampling.py, csrc/grid_subsample.hip, csrc/radix_sort.hip; the yardstick is the sequential float32 numpy restatement in

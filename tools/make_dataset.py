@@ -7,7 +7,8 @@
       published file.  The mesh name of every patch goes, one per line, into <out minus .h5>_names.txt.
   make_dataset.py clouds --mesh_dir DIR --out_dir DIR --num 2048
       per mesh a Poisson-disk cloud of --num points as <stem>.xyz (the text format of tools/upsample.py's outputs): --num 2048 makes the
-      inputs of tools/upsample.py, --num 8192 the ground truth of tools/evaluate.py.
+      inputs of tools/upsample.py, --num 8192 the ground truth of tools/evaluate.py.  --oversample x --num is at most 49152 candidates
+      (the one-workgroup selection); --cells lifts that to 2^24: larger clouds go through dis-pu_amd/poisson_cells.py.
 
 The reference's counterparts were made upstream with tools that are in neither tree, so the files are not the published ones: they
 are reproducible from (meshes, --seed) and close the loop meshes -> train -> upsample -> evaluate with nothing downloaded.
@@ -38,6 +39,9 @@ def parse_args(argv=None):
     c.add_argument("--out_dir", required=True)
     c.add_argument("--num", type=int, required=True, help="points per cloud (2048: upsampling inputs, 8192: ground truth)")
     c.add_argument("--oversample", type=int, default=4)
+    c.add_argument("--cells", action="store_true",
+                   help="allow more than %d candidates per cloud: above it the selection runs on the device-wide cell tier "
+                        "(dis-pu_amd/poisson_cells.py), below it on the one-workgroup kernel as without this flag" % 49152)
     c.add_argument("--seed", type=int, default=0)
     return ap.parse_args(argv)
 
@@ -73,9 +77,10 @@ def refuse_unsupported(a):
     else:
         if a.num <= 0:
             raise ValueError("--num must be positive, got %d" % a.num)
-        if a.oversample * a.num > _lib.POISSON_MAX_N:
-            raise ValueError("--oversample %d x --num %d = %d candidates, at most %d per cloud" % (a.oversample, a.num, a.oversample * a.num,
-                                                                                                  _lib.POISSON_MAX_N))
+        if a.oversample * a.num > (1 << 24 if a.cells else _lib.POISSON_MAX_N):
+            raise ValueError("--oversample %d x --num %d = %d candidates, at most %d per cloud%s"
+                             % (a.oversample, a.num, a.oversample * a.num, 1 << 24 if a.cells else _lib.POISSON_MAX_N,
+                                "" if a.cells else " (--cells lifts the limit: the device-wide cell tier)"))
     return mesh_files(a.mesh_dir)
 
 
@@ -92,7 +97,7 @@ def main(argv=None):
     import numpy as np
     import torch
     import dispu_amd  # noqa: F401
-    from dispu_amd import h5, mesh, mesh_sample, upsample
+    from dispu_amd import _lib, h5, mesh, mesh_sample, poisson_cells, upsample
 
     if not torch.cuda.is_available():
         sys.exit("no ROCm device")
@@ -117,7 +122,10 @@ def main(argv=None):
         os.makedirs(a.out_dir, exist_ok=True)
         for f, stem in zip(files, stems):
             m = mesh.Mesh.from_off(f, dev)
-            pts, r = mesh_sample.poisson_disk_cloud(m, a.num, oversample=a.oversample, seed=a.seed)
+            if a.oversample * a.num > _lib.POISSON_MAX_N:                # above the one-workgroup kernel: the device-wide cell tier
+                pts, r = poisson_cells.mesh_cloud(m, a.num, oversample=a.oversample, seed=a.seed)
+            else:
+                pts, r = mesh_sample.poisson_disk_cloud(m, a.num, oversample=a.oversample, seed=a.seed)
             upsample.save_xyz(os.path.join(a.out_dir, stem + ".xyz"), pts.cpu().numpy())
             print("%s: %d points, radius %.6g" % (stem, a.num, r))
 

@@ -8,6 +8,11 @@ its own), so clouds of different sizes share launches; the outputs do not depend
 points for its own n (the reference takes n from the first globbed file for all of them, model.py:356-359).  .xyz only: rows of
 >= 3 numbers, read like pc_util.load (np.loadtxt, first three columns).
 
+--merge poisson (default fps, the reference's exact farthest point sampling) thins the merged patches of every cloud to final_ratio * n
+points by a Poisson-disk selection instead (dis-pu_amd/poisson_cells.py: greedy dart throwing in a random priority order seeded by
+--merge_seed, the radius found by bisection): a blue-noise set of exactly as many points in about ten parallel rounds per radius where
+FPS takes final_ratio * n dependent ones; no longer the reference's output, and reproducible from --merge_seed.
+
 --grid_size G (off by default) first thins every cloud on the GPU to one barycentre per cube of edge G (dis-pu_amd/grid_subsampling.py,
 the reference's cpp_subsampling): FPS seeds and 256-NN patches only mean "a patch of surface" at a roughly even density, which a raw
 scan does not have.  The output then has final_ratio times the SUBSAMPLED count.
@@ -134,6 +139,10 @@ def parse_args(argv=None):
     ap.add_argument("--patch_num_ratio", type=int, default=3, help="patch seeds per patch_num_point input points")
     ap.add_argument("--max-points", dest="max_points", type=int, default=1 << 20,
                     help="input points per batch of clouds (bounds device memory and keeps packed offsets below 2^31)")
+    ap.add_argument("--merge", choices=("fps", "poisson"), default="fps",
+                    help="how the merged patches are thinned to final_ratio x N points: fps (the reference's exact farthest point sampling) "
+                         "or poisson (a Poisson-disk selection of exactly as many points, dis-pu_amd/poisson_cells.py)")
+    ap.add_argument("--merge_seed", type=int, default=0, help="--merge poisson: the seed of the greedy's random priority order")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32: the strict fp32 generator; bf16: after_conv as a bf16 product over F' stored as bf16 (Generator(dtype='bf16'))")
     ap.add_argument("--grid_size", type=positive_float, default=None,
@@ -326,7 +335,8 @@ def process_group(a, gen, paths, group, clouds, in_normals, src, dev):
     import torch
     from dispu_amd.upsample import upsample_ragged
     names = ", ".join(paths[i] for i in group)
-    preds = stage("%s: " % names, upsample_ragged, gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio)
+    preds = stage("%s: " % names, upsample_ragged, gen, [clouds[i] for i in group], a.patch_num_point, a.patch_num_ratio, a.final_ratio,
+                  merge=a.merge, merge_seed=a.merge_seed)
     removed, attrs, normals = [0] * len(group), None, None
     if a.clean_output != "none":
         cleaned, _ = stage("%s: --clean_output: " % names, remove_outliers, a.clean_output, preds, a, dev)
