@@ -22,6 +22,7 @@ POISSON_CELLS_NONFINITE = 4 # include/dispu_hip.h: DISPU_POISSON_CELLS_NONFINITE
 SORT_ROWS_MAX_K = 4096      # dispu_sort_rows_i32
 RADIX_TILE = 2048           # include/dispu_hip.h: DISPU_RADIX_TILE
 GRID_NONFINITE, GRID_AXIS_X, GRID_AXIS_Y, GRID_AXIS_Z, GRID_TOO_MANY_POINTS = 1, 2, 3, 4, 5   # include/dispu_hip.h: DISPU_GRID_*
+LATTICE_NONFINITE, LATTICE_RANGE = 1, 2   # include/dispu_hip.h: DISPU_LATTICE_*
 ORIENT_HOST_ROUNDS = 1      # include/dispu_hip.h: DISPU_ORIENT_HOST_ROUNDS (flags of dispu_orient_consistent_segments)
 ORIENT_PROFILE_FLOATS = 8   # include/dispu_hip.h: DISPU_ORIENT_PROFILE_FLOATS
 
@@ -58,6 +59,18 @@ SIGNATURES = {
     "dispu_transfer_attributes_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_mls_project_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_mls_project_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_signed_distance_scratch_bytes": (_sz, [_i, _vp, _vp]),
+    "dispu_signed_distance_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_lattice_voxels_scratch_bytes": (_sz, [C.c_longlong]),
+    "dispu_lattice_voxels": (_i, [C.c_longlong, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_lattice_dilate_scratch_bytes": (_sz, [C.c_longlong, _i]),
+    "dispu_lattice_dilate": (_i, [C.c_longlong, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_lattice_corners_scratch_bytes": (_sz, [C.c_longlong]),
+    "dispu_lattice_corners": (_i, [C.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_lattice_positions": (_i, [C.c_longlong, _vp, C.c_float, _vp, _vp]),
+    "dispu_contour_count_scratch_bytes": (_sz, [C.c_longlong, C.c_longlong]),
+    "dispu_contour_count": (_i, [C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_contour_emit": (_i, [C.c_longlong, C.c_longlong, C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _vp, _vp, _vp]),
     "dispu_fps_segments_auto_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_fps_segments_auto": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "dispu_prob_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -76,6 +76,20 @@ def load_off(path):
     return verts.astype(np.float32), faces.astype(np.int32)
 
 
+def save_off(path, verts, faces):
+    """(verts [V,3] float32, faces [F,3] int32) as arrays or tensors -> an OFF file that load_off reads back to the same arrays:
+    every coordinate with the 9 significant digits that name one float32."""
+    v = np.ascontiguousarray(verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else verts, dtype=np.float32)
+    f = np.ascontiguousarray(faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else faces)
+    req(v.ndim == 2 and v.shape[1] == 3, "verts: expected a [V, 3] array, got shape %s" % (v.shape,))
+    req(f.ndim == 2 and f.shape[1] == 3 and np.issubdtype(f.dtype, np.integer), "faces: expected an integer [F, 3] array, got %s %s" % (f.dtype, f.shape))
+    req(len(f) == 0 or (f.min() >= 0 and f.max() < len(v)), "faces: vertex index out of range")
+    with open(path, "w") as out:
+        out.write("OFF\n%d %d 0\n" % (len(v), len(f)))
+        out.writelines("%.9g %.9g %.9g\n" % (float(r[0]), float(r[1]), float(r[2])) for r in v)
+        out.writelines("3 %d %d %d\n" % (int(r[0]), int(r[1]), int(r[2])) for r in f)
+
+
 def _morton3(q):
     """interleave the low 10 bits of three non-negative ints -> 30-bit Morton code"""
     def spread(v):

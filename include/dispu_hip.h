@@ -61,7 +61,8 @@ extern "C" {
  * dispu_fps_segments_auto*), and the oriented normals (dispu_pca_normals_*), and the outlier filters (dispu_knn_mean_dist_*,
  * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*), and the cross-cloud search with the attribute transfer
  * (dispu_knn_cross_*, dispu_transfer_attributes_segments), and the consistent orientation (dispu_orient_consistent_*), and the
- * moving-least-squares projection (dispu_mls_project_*): additions only. */
+ * moving-least-squares projection (dispu_mls_project_*), and the surface reconstruction (dispu_signed_distance_*, dispu_lattice_*,
+ * dispu_contour_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -1151,6 +1152,88 @@ size_t dispu_mls_project_scratch_bytes(int C, const int* qoff_host, const int* r
 int dispu_mls_project_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, double support,
                                int iterations, const float* queries, const float* refs, float* out, int* idx_out, int* status,
                                void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- the signed distance to an oriented cloud (IMLS / Hoppe et al. 1992): csrc/signed_distance.hip, dis-pu_amd/reconstruct.py.  The
+ * implicit function the surface reconstruction below contours, at arbitrary positions.  The reference has no counterpart.  Batches,
+ * offsets, status and scratch as for dispu_mls_project_segments; normals [sum m_c, 3] are the references' rows, used as given (not
+ * normalised; a zero row contributes zero) and must be finite: that is the caller's duty, the entry does not look.  1 <= k <= 32,
+ * 1 <= support <= 4.  For query x (fp32) of segment c against its m_c reference points P:
+ *  1. neighbours: the k' = min(k, m_c) points of P with the smallest (d2 bits, local index), d2 = ((dx*dx + dy*dy) + dz*dz) in fp32
+ *     (DISPU_ARITH_PLAIN): the project's rule.
+ *  2. in double, one rounding per operation, in ascending rank: D = the d2 of rank k' - 1, rho2 = (support * support) * D; per
+ *     neighbour r2 = d2_j / rho2;  w_j = 0 unless r2 < 1 (so also when D == 0: r2 is a NaN), else r = sqrt(r2),
+ *     w_j = (((1 - r)*(1 - r)) * ((1 - r)*(1 - r))) * (4 r + 1)   (Wendland);  u = x - p_j (exact),
+ *     g_j = (u.x*n_j.x + u.y*n_j.y) + u.z*n_j.z;  S0 = sum w_j,  S1 = sum w_j * g_j.
+ *  3. f = S1 / S0 if S0 != 0, else g_0, the nearest point's tangent plane (k' = 1, coincident or equidistant neighbours, D == 0): f is
+ *     always defined.  out[x] = (float)f.
+ * Every operation is a correctly rounded IEEE one, so the value can be reproduced bit for bit (tests/reconstruct_oracle.py does).
+ * out [sum q_c] must not overlap queries, refs or normals.  status [C] (device): 0, or 1 for a segment whose queries or references hold
+ * a NaN or an infinite coordinate; nothing is written for it.  No [q, k] tensor reaches memory.  scratch: 16-byte aligned, at least
+ * dispu_signed_distance_scratch_bytes (both pre-passes; 0 for an illegal C, illegal offsets or a segment above 2^24 points); a refusal
+ * (hipErrorInvalidValue) comes before any launch and touches no output.  Ordinary stores, no atomics, identical bytes from run to run. */
+size_t dispu_signed_distance_scratch_bytes(int C, const int* qoff_host, const int* roff_host);
+int dispu_signed_distance_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, double support,
+                                   const float* queries, const float* refs, const float* normals, float* out, int* status, void* scratch,
+                                   size_t scratch_bytes, void* stream);
+
+/* ---- surface reconstruction, the lattice and the contouring: csrc/reconstruct.hip, dis-pu_amd/reconstruct.py:reconstruct_surface.
+ * f = 0 of the signed distance above, contoured on a sparse lattice by marching tetrahedra, vertices welded, every order pinned: one
+ * cloud per call, the output is unique.  The reference has no counterpart.  The entries are split where a count must reach the host to
+ * size the next buffer; each `*_host` count is written after the entry's work is done (the stream is synchronised).
+ * Lattice: h = voxel (fp32).  A point's voxel index per axis is floorf(p / h), the division correctly rounded; lattice vertex (i, j, l)
+ * sits at ((float)i*h, (float)j*h, (float)l*h), one rounding each.  Indices, after the band, stay in +-(2^20 - 1).  A voxel or vertex
+ * is the key ((l + 2^20 - 1) << 42) | ((j + 2^20 - 1) << 21) | (i + 2^20 - 1): ascending keys are ascending (l, j, i), z slowest.
+ *   dispu_lattice_voxels    occ_out [<= n]: the sorted unique keys of the voxels that hold a point, *count_host of them.
+ *                           *status_host: 0, DISPU_LATTICE_NONFINITE (a NaN or an infinite coordinate) or DISPU_LATTICE_RANGE (an index
+ *                           outside +-(2^20 - 1 - band)); then the count is 0.  1 <= n <= 2^24, voxel > 0 and finite, band in 1 .. 3.
+ *   dispu_lattice_dilate    act_out [<= nocc * (2 band + 1)^3]: the sorted unique keys of every occupied voxel's Chebyshev neighbours
+ *                           within band, the active voxels.  nocc * (2 band + 1)^3 < 2^31.
+ *   dispu_lattice_corners   lat_out [<= 8 nvox]: the sorted unique keys of the 8 corners of all active voxels, the lattice vertices,
+ *                           *count_host of them;  corner_out [nvox, 8]: the lattice-vertex number of corner b = bx + 2 by + 4 bz of
+ *                           every active voxel, by binary search.  8 nvox < 2^31.
+ *   dispu_lattice_positions pos_out [nlat, 3]: the vertices' positions.  1 <= nlat <= 2^24 (a query segment holds no more).
+ * Values: values [nlat] fp32, f at every lattice vertex (dispu_signed_distance_segments with queries = pos).  A vertex is negative iff
+ * f < 0 on the fp32 value; an exact zero is not.
+ * Tetrahedra: Kuhn's six per voxel around the diagonal 0 -> 7: for the axis permutations (a, b, c) in lexicographic order (xyz, xzy,
+ * yxz, yzx, zxy, zyx) the tetrahedron (0, e_a, e_a + e_b, 7), e = (1, 2, 4); translation-invariant, so neighbouring voxels agree on
+ * every shared face.  The edge between tet vertices t_i < t_j has lower endpoint A = t_i and direction code d = t_j - t_i in 1 .. 7;
+ * its global identity is slot = 7 * (lattice number of A) + d - 1.
+ * Cases: n0 < n1 the positions in the tet of its negative vertices, p0 < p1 of the others.  1 or 3 negative: v the odd vertex,
+ * o0 < o1 < o2 the rest, the triangle (E(v,o0), E(v,o1), E(v,o2)).  2 negative: the quad q = (E(n0,p0), E(n0,p1), E(n1,p1), E(n1,p0))
+ * as (q0, q1, q2) and (q0, q2, q3).  A triangle's last two vertices are swapped iff its normal (b - a) x (c - a), with every vertex at
+ * the MIDPOINT of its edge in the unit cube, does not point from the negative corners' centroid to the positive corners' centroid:
+ * a table per (tet, sign mask), never a decision on computed positions.
+ *   dispu_contour_count     slot_number [7 nlat]: a slot is used when an emitted triangle references it; the exclusive scan of the used
+ *                           flags, so mesh vertices are numbered in ascending (lattice vertex, d);  tri_start [nvox]: the exclusive
+ *                           scan of the voxels' triangle counts;  *nverts_host, *nfaces_host the totals.
+ *   dispu_contour_emit      verts_out [nverts, 3]: per axis and in double t = fa / (fa - fb), then A + t * (B - A), rounded to fp32,
+ *                           always from the lower endpoint A; fa, fb the stored fp32 values (fa < 0 <= fb or the reverse).
+ *                           faces_out [nfaces, 3] int32 in the order (active voxel ascending, tet 0 .. 5, triangle 0 .. 1).
+ *                           nverts, nfaces >= 1: an empty mesh needs no call.
+ * Zero-area faces appear when f is exactly 0 at a lattice vertex or fp32 collapses two vertices; they are kept: they keep the
+ * connectivity closed.  Outputs of one entry must not overlap its inputs or each other.  scratch: 16-byte aligned, at least the
+ * entry's *_scratch_bytes (0 for illegal sizes); the library never allocates; a refusal (hipErrorInvalidValue: NULL, illegal sizes,
+ * short or misaligned scratch, overlap) comes before any launch and touches nothing.  Used flags are plain stores of 1; no float
+ * atomics, every loop bounded, ordering by kernel boundaries only, identical bytes from run to run.  The yardstick is
+ * tests/reconstruct_oracle.py.  Additions only: dispu_version() stays 5. ------------------------------------------------------------ */
+#define DISPU_LATTICE_NONFINITE 1
+#define DISPU_LATTICE_RANGE 2
+size_t dispu_lattice_voxels_scratch_bytes(long long n);
+int dispu_lattice_voxels(long long n, const float* points, float voxel, int band, unsigned long long* occ_out, int* count_host,
+                         int* status_host, void* scratch, size_t scratch_bytes, void* stream);
+size_t dispu_lattice_dilate_scratch_bytes(long long nocc, int band);
+int dispu_lattice_dilate(long long nocc, const unsigned long long* occ, int band, unsigned long long* act_out, long long* count_host,
+                         void* scratch, size_t scratch_bytes, void* stream);
+size_t dispu_lattice_corners_scratch_bytes(long long nvox);
+int dispu_lattice_corners(long long nvox, const unsigned long long* act, unsigned long long* lat_out, int* corner_out,
+                          long long* count_host, void* scratch, size_t scratch_bytes, void* stream);
+int dispu_lattice_positions(long long nlat, const unsigned long long* lat, float voxel, float* pos_out, void* stream);
+size_t dispu_contour_count_scratch_bytes(long long nvox, long long nlat);
+int dispu_contour_count(long long nvox, long long nlat, const int* corner, const float* values, unsigned* slot_number, unsigned* tri_start,
+                        long long* nverts_host, long long* nfaces_host, void* scratch, size_t scratch_bytes, void* stream);
+int dispu_contour_emit(long long nvox, long long nlat, float voxel, const unsigned long long* lat, const int* corner, const float* values,
+                       const unsigned* slot_number, const unsigned* tri_start, long long nverts, long long nfaces, float* verts_out,
+                       int* faces_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -181,7 +181,26 @@ def parse_args(argv=None):
     ap.add_argument("--mls_k", type=int, default=16, help="neighbours per point of --denoise_input / --project_output, 4 .. 32")
     ap.add_argument("--mls_support", type=float, default=1.0,
                     help="the weights of --denoise_input / --project_output reach this many times the farthest neighbour's distance, 1 .. 4")
+    ap.add_argument("--mesh", choices=("none", "off"), default="none",
+                    help="off: also write <stem>_X<ratio>.off beside every cloud, the surface reconstructed from the written points and "
+                         "their oriented normals (needs --normals pca, an --orient other than none, and --mesh_voxel)")
+    ap.add_argument("--mesh_voxel", type=positive_float, default=None, help="--mesh: the lattice's edge H (no automatic choice)")
+    ap.add_argument("--mesh_k", type=int, default=8, help="--mesh: neighbours per lattice vertex of the signed distance, 1 .. 32")
+    ap.add_argument("--mesh_support", type=float, default=1.5,
+                    help="--mesh: the weights reach this many times the farthest neighbour's distance, 1 .. 4")
+    ap.add_argument("--mesh_band", type=int, default=1, help="--mesh: voxels followed around every occupied one, 1 .. 3")
     a = ap.parse_args(argv)
+    if a.mesh != "none":
+        if a.normals != "pca" or a.orient == "none":
+            ap.error("--mesh needs oriented normals: --normals pca with an --orient other than none")
+        if a.mesh_voxel is None:
+            ap.error("--mesh needs --mesh_voxel H")
+    if not 1 <= a.mesh_k <= 32:
+        ap.error("--mesh_k must be in 1 .. 32, got %d" % a.mesh_k)
+    if not 1.0 <= a.mesh_support <= 4.0:                                     # a NaN fails both comparisons
+        ap.error("--mesh_support must be in 1 .. 4, got %s" % a.mesh_support)
+    if not 1 <= a.mesh_band <= 3:
+        ap.error("--mesh_band must be in 1 .. 3, got %d" % a.mesh_band)
     for name in ("denoise_input", "project_output"):
         if not 0 <= getattr(a, name) <= 8:
             ap.error("--%s must be in 0 .. 8, got %d" % (name, getattr(a, name)))
@@ -364,6 +383,19 @@ def write_output(out, pred, attrs, normals):
         save_xyz(out, pred)
 
 
+def write_mesh(xyz_path, a, dev):
+    """the --mesh step: the surface of the cloud AS THE FILE HOLDS IT (x y z first, nx ny nz last, at the file's six decimals, so the
+    mesh can be reproduced from the file alone) -> the path of the .off beside it, vertex and face counts"""
+    import torch
+    from dispu_amd import mesh, reconstruct
+    rows = np.loadtxt(xyz_path, ndmin=2).astype(np.float32)
+    pts, nrm = (torch.from_numpy(np.ascontiguousarray(rows[:, c])).to(dev) for c in (slice(0, 3), slice(-3, None)))
+    verts, faces = reconstruct.reconstruct_surface(pts, nrm, a.mesh_voxel, k=a.mesh_k, support=a.mesh_support, band=a.mesh_band)
+    off = os.path.splitext(xyz_path)[0] + ".off"
+    mesh.save_off(off, verts, faces)
+    return off, verts.shape[0], faces.shape[0]
+
+
 def main(argv=None):
     a = parse_args(argv)
     if a.max_points <= 0:
@@ -403,6 +435,8 @@ def main(argv=None):
             else:
                 print("%s: %d -> %d (grid %g) -> %d points, %s%s" % (paths[i], raw[i], clouds[i].shape[0], a.grid_size, pred.shape[0], out,
                                                                    gone))
+            if a.mesh != "none":
+                print("%s: %d vertices, %d faces" % stage("%s: --mesh: " % out, write_mesh, out, a, dev))
     print("%d clouds in %.2f s" % (len(paths), time.time() - t0))
 
 
