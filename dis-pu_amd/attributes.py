@@ -9,47 +9,10 @@ import torch
 
 from . import _lib
 from ._util import req
-from .segments import Packed, check_int_range, host_ptr
+from .segments import Pair, check_int_range
 
 K_MIN, K_MAX = 1, 32
 MODES = {"idw": 0, "nearest": 1}
-
-
-class _Pair(object):
-    """queries and references, a tensor pair or two lists of equal length: two packed batches of one device, and what joins them"""
-
-    def __init__(self, queries, refs, who):
-        self.single = isinstance(queries, torch.Tensor)
-        if self.single:
-            req(isinstance(refs, torch.Tensor), "%s: queries is a tensor, so refs must be one too, got %s" % (who, type(refs).__name__))
-        else:
-            req(isinstance(queries, (list, tuple)) and isinstance(refs, (list, tuple)),
-                "queries and refs must be float32 [n, 3] tensors on a ROCm device or two lists of them, got %s and %s"
-                % (type(queries).__name__, type(refs).__name__))
-            req(len(queries) >= 1, "%s needs at least one cloud" % who)
-            req(len(queries) == len(refs), "%d query clouds but %d reference clouds" % (len(queries), len(refs)))
-        self.queries = Packed(queries, who, label="queries of cloud %d", home="the queries of cloud 0")
-        self.refs = Packed(refs, who, label="refs of cloud %d", dev=self.queries.dev, home="the queries of cloud 0")
-        self.C, self.dev, self.nq = self.queries.C, self.queries.dev, self.queries.total
-        req(self.refs.total < 2 ** 31, "a packed batch holds at most 2^31 - 1 reference points, got %d" % self.refs.total)
-
-    def width(self, w):
-        req(self.nq * w < 2 ** 31, "a packed batch holds at most 2^31 - 1 output words, got %d queries x %d" % (self.nq, w))
-
-    def pack(self):
-        """after every check that needs no launch"""
-        self.queries.pack()
-        self.refs.pack(status=False)
-        self.nbytes = _lib.lib().dispu_knn_cross_scratch_bytes(self.C, host_ptr(self.queries.off), host_ptr(self.refs.off))
-        self.scratch = self.queries.scratch(self.nbytes, "dispu_knn_cross_scratch_bytes")
-
-    def head(self):
-        """the arguments every entry starts with"""
-        q, r = self.queries, self.refs
-        return (self.C, _lib.ptr(q.d_off), host_ptr(q.off), _lib.ptr(r.d_off), host_ptr(r.off))
-
-    def tail(self):
-        return (_lib.ptr(self.queries.status), _lib.ptr(self.scratch), self.nbytes, _lib.stream_ptr(self.dev))
 
 
 def knn_cross(queries, refs, k, return_distance=True):
@@ -58,10 +21,10 @@ def knn_cross(queries, refs, k, return_distance=True):
     reference points of every query in ascending (d2, index) order, -1 beyond min(k, m); with return_distance also d2 [q, k] float32,
     the squared distances, +inf beyond min(k, m): (idx, d2).  Lists in give lists out.  1 <= k <= 32.  ValueError for illegal arguments
     (before any launch) and for a cloud with a NaN or an infinite coordinate (after it)."""
-    b = _Pair(queries, refs, "knn_cross")
+    b = Pair(queries, refs, "knn_cross")
     k = check_int_range(k, K_MIN, K_MAX, "k")
     b.width(k)
-    b.pack()
+    b.pack("dispu_knn_cross_scratch_bytes")
     with torch.cuda.device(b.dev):
         idx = torch.empty((b.nq, k), dtype=torch.int32, device=b.dev)
         d2 = torch.empty((b.nq, k), dtype=torch.float32, device=b.dev) if return_distance else None
@@ -98,7 +61,7 @@ def transfer_attributes(queries, refs, features=None, labels=None, k=3, mode="id
     nearest reference point.  Labels always come from the nearest reference point (equal distances: the smallest index).
     ->  features [q, F] float32, or labels [q] int32, or the tuple (features, labels) when both are given.  Lists in give lists out.
     Feature values are not inspected (a NaN propagates).  ValueError as for knn_cross."""
-    b = _Pair(queries, refs, "transfer_attributes")
+    b = Pair(queries, refs, "transfer_attributes")
     k = check_int_range(k, K_MIN, K_MAX, "k")
     req(mode in MODES, "mode must be 'idw' or 'nearest', got %r" % (mode,))
     req(features is not None or labels is not None, "transfer_attributes needs features, labels or both")
@@ -106,7 +69,7 @@ def transfer_attributes(queries, refs, features=None, labels=None, k=3, mode="id
     labs = _attr_list(b, labels, "labels", torch.int32, 1)
     F = int(feats[0].shape[1]) if feats is not None else 1
     b.width(max(F, k))
-    b.pack()
+    b.pack("dispu_knn_cross_scratch_bytes")
     with torch.cuda.device(b.dev):
         feat = out_feat = lab = out_lab = None
         if feats is not None:

@@ -3,11 +3,13 @@
 // interpolates features over three neighbours of a brute-force search (Common/pointnet_util.py:204-208, tf_interpolate's three_nn); this
 // is that interpolation at any k <= 32 on the exact neighbours of the project's rule, for clouds of scan size.
 //
-//   pre-pass   morton_cells.hip (fps_cells_prepass) TWICE: over the packed references and over the packed queries.  Each wave then
-//              holds the 64 queries of one query cell -- spatially coherent, with a box -- and answers through the local index in .w
-//   seed       Morton keys are relative to each segment's own bounds: a query cell's number says nothing about the reference cells, and
-//              the wave has no cell of its own in the searched cloud.  One sweep of the reference segment's box table, 64 boxes per step,
-//              finds the cell s with the smallest (box-to-box lower bound, cell number).  Only this sweep is the kernel's own
+// The frame -- two pre-passes, a seed, the shared search -- is the one of every kernel that searches another cloud (mls_project.hip,
+// signed_distance.hip); it exists once, the host side in knn_cross.h and the device side in knn_cross_prologue.h, and is described here.
+//
+//   pre-pass   morton_cells.hip (fps_cells_prepass) TWICE (knn_cross.h): over the packed references and over the packed queries.  Each
+//              wave then holds the 64 queries of one query cell -- spatially coherent, with a box -- and answers through the local index in .w
+//   seed       (knn_cross_prologue.h) the wave has no cell of its own in the searched cloud: one sweep of the reference segment's box
+//              table finds the cell s with the smallest (box-to-box lower bound, cell number)
 //   search     the text of knn_cells_search.h, the one the self-searching kernels include, started at s instead of the wave's own cell:
 //              the wave visits s and then its neighbours along the curve (s - 1, s + 1, s - 2, ...) until it has seen k' = min(k, m_c)
 //              points, then the bounded table walk: a cell is visited unless its box-to-box bound exceeds the wave's largest k-th
@@ -21,7 +23,7 @@
 // are, afterwards every cell outside [vlo, vhi] is tested, and skipped only on lb > k-th strictly (k-th = +inf while a list is short).
 //
 // Ordinary stores only, no atomics of its own, ordering by kernel boundaries only, identical bytes from run to run.
-#include "knn_cells.h"
+#include "knn_cross.h"
 
 namespace dispu {
 
@@ -41,39 +43,8 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
                                                                 int* __restrict__ idx_out, float* __restrict__ d2_out, XferArgs x,
                                                                 int* __restrict__ status) {
 #pragma clang fp contract(off)      // pinned here as well as by the build's -ffp-contract=off: the weights below round once per operation
-    const int c = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int qb0 = qoff[c], nq = qoff[c + 1] - qb0;
-    const int rb0 = roff[c], n = roff[c + 1] - rb0;
-    const size_t qbase = (size_t)qb0, rbase = (size_t)rb0;
-    const uint32_t bad = qsegb[(size_t)c * 8 + 6] | rsegb[(size_t)c * 8 + 6];
-    if (blockIdx.x == 0 && tid == 0) status[c] = bad ? 1 : 0;
-    if (bad) return;                                                            // nothing is written for a non-finite segment
-    const int KQ = (nq + kNrmCell - 1) / kNrmCell, K = (n + kNrmCell - 1) / kNrmCell;
-    const int cb = blockIdx.x * kNrmWaves + wave;
-    if (cb >= KQ) return;                                                       // wave-uniform
-    const float4* __restrict__ sp = rspt + rbase;
-    const float* __restrict__ gt = rtab + fpc_cell_base(rbase, c) * 8;
-    const float* __restrict__ qgt = qtab + fpc_cell_base(qbase, c) * 8;
-    const int qcnt = min(kNrmCell, nq - cb * kNrmCell);
-    const bool valid = lane < qcnt;
-    const float4 q = qspt[qbase + (size_t)(cb * kNrmCell + (valid ? lane : 0))];   // idle lanes repeat query 0 and store nothing
-    const float4 qlo4 = *reinterpret_cast<const float4*>(qgt + (size_t)cb * 8);
-    const float4 qhi4 = *reinterpret_cast<const float4*>(qgt + (size_t)cb * 8 + 4);
-
-    // the seed: the reference cell of the smallest (box-to-box bound, cell number).  Lane 0 always holds cell 0, so s < K
-    uint64_t sk = kNrmNone;
-    for (int j0 = 0; j0 < K; j0 += kWave) {
-        const int j = j0 + lane;
-        if (j < K) {
-            const float4 a = *reinterpret_cast<const float4*>(gt + (size_t)j * 8);
-            const float4 b = *reinterpret_cast<const float4*>(gt + (size_t)j * 8 + 4);
-            const float lb = cell_box_lb(a, b, qlo4.x, qlo4.y, qlo4.z, qlo4.w, qhi4.x, qhi4.y);
-            const uint64_t key = ((uint64_t)__float_as_uint(lb) << 32) | (uint32_t)j;
-            sk = key < sk ? key : sk;
-        }
-    }
-    const int s = min((int)(uint32_t)wave_min_u64(sk), K - 1);
+    const int* const status_in = nullptr;                                       // no status carried in
+#include "knn_cross_prologue.h"  // segment pair, query cell, query, seed, as text: defines c, lane, n, qbase, rbase, sp, gt, valid, q, s ...
 #include "knn_cells_search.h"  // the ramp around s and the walk, as text: defines `kp` and `best`
     if (!valid) return;
 
@@ -84,12 +55,12 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
         for (int j = 0; j < KMAX; ++j)
             if (j < k) {
                 const bool in = j < kp;
-                if (idx_out) idx_out[o + j] = in ? (int)(uint32_t)best.b[j] : -1;
-                if (d2_out) d2_out[o + j] = in ? __uint_as_float((uint32_t)(best.b[j] >> 32)) : __uint_as_float(0x7F800000u);
+                if (idx_out) idx_out[o + j] = in ? (int)best.index(j) : -1;
+                if (d2_out) d2_out[o + j] = in ? best.d2(j) : __uint_as_float(0x7F800000u);
             }
     } else {
         const size_t F = (size_t)x.F;
-        const size_t r0 = rbase + (size_t)(uint32_t)best.b[0];
+        const size_t r0 = rbase + (size_t)best.index(0);
         if (x.labels) x.out_labels[row] = x.labels[r0];
         if (!x.feat) return;
         float* __restrict__ out = x.out_feat + row * F;
@@ -100,14 +71,14 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
         double den = 0.0;
 #pragma unroll
         for (int j = 0; j < KMAX; ++j)
-            if (j < kp) den += 1.0 / fmax((double)__uint_as_float((uint32_t)(best.b[j] >> 32)), 1e-10);
+            if (j < kp) den += 1.0 / fmax((double)best.d2(j), 1e-10);
         for (size_t f = 0; f < F; ++f) {                                        // the weights again per column: 32 doubles would not stay in registers
             double num = 0.0;
 #pragma unroll
             for (int j = 0; j < KMAX; ++j)
                 if (j < kp) {
-                    const double w = 1.0 / fmax((double)__uint_as_float((uint32_t)(best.b[j] >> 32)), 1e-10);
-                    const double t = w * (double)x.feat[(rbase + (size_t)(uint32_t)best.b[j]) * F + f];
+                    const double w = 1.0 / fmax((double)best.d2(j), 1e-10);
+                    const double t = w * (double)x.feat[(rbase + (size_t)best.index(j)) * F + f];
                     num += t;
                 }
             out[f] = (float)(num / den);
@@ -118,30 +89,23 @@ __global__ __launch_bounds__(kNrmThreads) void knn_cross_kernel(const int* __res
 static int cross_run(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k, const float* queries,
                      const float* refs, int* idx_out, float* d2_out, const XferArgs* x, int width, int* status, void* scratch,
                      size_t scratch_bytes, hipStream_t st) {
-    int rc = cells_batch_check(C, qoff_host);
-    if (rc == 0) rc = cells_batch_check(C, roff_host);
-    if (rc != 0) return rc;
+    CrossPrepass p(C, qoff_host, roff_host);
+    if (p.rc != 0) return p.rc;
     if (k < 1 || k > 32 || !qoff || !roff || !queries || !refs || !status) return (int)hipErrorInvalidValue;
     if ((long long)qoff_host[C] * (long long)width >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const size_t rbytes = fps_cells_prepass_scratch(C, roff_host), qbytes = fps_cells_prepass_scratch(C, qoff_host);
-    if (!rbytes || !qbytes || !scratch || scratch_bytes < rbytes + qbytes || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
-    const float4 *rspt, *qspt;
-    const float *rtab, *qtab;
-    const uint32_t *rsegb, *qsegb;
-    int kr = 0, kqmax = 0;
-    int rp = fps_cells_prepass(C, roff, roff_host, refs, scratch, rbytes, &rspt, &rtab, &rsegb, &kr, st);
+    if (!p.fits(scratch, scratch_bytes)) return (int)hipErrorInvalidValue;
+    int rp = p.run_refs(roff, refs, scratch, st);
+    if (rp == 0) rp = p.run_queries(qoff, queries, scratch, st);
     if (rp != 0) return rp;
-    rp = fps_cells_prepass(C, qoff, qoff_host, queries, (char*)scratch + rbytes, qbytes, &qspt, &qtab, &qsegb, &kqmax, st);   // rbytes is a multiple of 256
-    if (rp != 0) return rp;
-    const dim3 grid((kqmax + kNrmWaves - 1) / kNrmWaves, C), block(kNrmThreads);
+    const dim3 grid = p.grid(), block(kNrmThreads);
     dispatch_kmax(k, [&](auto kmax_c) {
         constexpr int KMAX = decltype(kmax_c)::value;
         if (x)
-            hipLaunchKernelGGL((knn_cross_kernel<KMAX, true>), grid, block, 0, st, qoff, roff, qsegb, rsegb, qspt, rspt, qtab, rtab, k,
-                               (int*)nullptr, (float*)nullptr, *x, status);
+            hipLaunchKernelGGL((knn_cross_kernel<KMAX, true>), grid, block, 0, st, qoff, roff, p.qsegb, p.rsegb, p.qspt, p.rspt, p.qtab,
+                               p.rtab, k, (int*)nullptr, (float*)nullptr, *x, status);
         else
-            hipLaunchKernelGGL((knn_cross_kernel<KMAX, false>), grid, block, 0, st, qoff, roff, qsegb, rsegb, qspt, rspt, qtab, rtab, k,
-                               idx_out, d2_out, XferArgs{0, 0, nullptr, nullptr, nullptr, nullptr}, status);
+            hipLaunchKernelGGL((knn_cross_kernel<KMAX, false>), grid, block, 0, st, qoff, roff, p.qsegb, p.rsegb, p.qspt, p.rspt, p.qtab,
+                               p.rtab, k, idx_out, d2_out, XferArgs{0, 0, nullptr, nullptr, nullptr, nullptr}, status);
     });
     return (int)hipGetLastError();
 }
@@ -151,8 +115,7 @@ static int cross_run(int C, const int* qoff, const int* qoff_host, const int* ro
 using namespace dispu;
 
 DISPU_EXPORT size_t dispu_knn_cross_scratch_bytes(int C, const int* qoff_host, const int* roff_host) {
-    const size_t rbytes = fps_cells_prepass_scratch(C, roff_host), qbytes = fps_cells_prepass_scratch(C, qoff_host);
-    return rbytes && qbytes ? rbytes + qbytes : 0;
+    return CrossPrepass(C, qoff_host, roff_host).bytes();
 }
 
 DISPU_EXPORT int dispu_knn_cross_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int k,

@@ -32,6 +32,12 @@ constexpr int kWave = 64;
 // byte offsets inside a caller's scratch buffer advance in steps of 256
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// whether the byte ranges [a, a + na) and [b, b + nb) share a byte: what an entry refuses between an output and anything it still reads
+static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
 // "done once per DEVICE" flag for hipFuncSetAttribute (function attributes are per device: a process that drives several
 // GPUs must opt every one of them in to > 64 KB of dynamic LDS).  Two threads racing through the first call both set the
 // attribute, which is idempotent.

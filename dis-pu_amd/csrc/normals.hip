@@ -8,12 +8,12 @@
 //              one stable dispu_radix_sort_pairs, cells of 64 consecutive sorted positions with their boxes
 //   search     (knn_cells.h; the text of knn_cells_prologue.h and knn_cells_search.h, which exists there once for every kernel that
 //              searches) one wave per cell, one query per lane; every lane keeps its k best keys (d2 bits << 32 | local index) sorted in
-//              registers.  The wave visits its start cell (here its own; attributes.hip picks one by a sweep), then the cells at growing Morton offset (c - 1, c + 1, c - 2, ...) until it
+//              registers.  The wave visits its start cell (here its own; knn_cross_prologue.h picks one by a sweep), then the cells at growing Morton offset (c - 1, c + 1, c - 2, ...) until it
 //              has seen k' points (every lane sees every point of a visited cell, so all lanes then hold k' candidates), then walks
 //              the segment's box table, 64 boxes per step (one per lane), and visits a cell only if its lower bound does not exceed
 //              the wave's largest current k-th distance.  A visit is dense: 64 queries x 64 points.
 //   normal     in the same kernel, from the neighbourhood in registers: q_j = p_j - p_i, mu = sum q_j / k', Cov = sum q_j q_j^T / k' -
-//              mu mu^T, all in double; cyclic Jacobi in double; the eigenvector of the smallest eigenvalue, stored as fp32.
+//              mu mu^T, all in double; cyclic Jacobi in double (jacobi3.h); the eigenvector of the smallest eigenvalue, stored as fp32.
 //
 // Why a skip is sound (of the walk in knn_cells_search.h, the only copy of it): per axis e := max(fl(lo_cell - hi_query), fl(lo_query - hi_cell), 0).  For a point p of the cell and a query q of
 // the wave, lo_cell <= p and q <= hi_query, and rounding is monotone, so fl(lo_cell - hi_query) <= fl(p - q); likewise fl(lo_query -
@@ -28,27 +28,10 @@
 //
 // No [n, k] tensor reaches memory unless idx_out is asked for.  Every value is written with ordinary stores; no atomics of its own;
 // ordering between the pre-pass and the search by kernel boundaries only; identical bytes from run to run.
+#include "jacobi3.h"
 #include "knn_cells.h"
 
 namespace dispu {
-
-// one Jacobi rotation that zeroes a_pq of a symmetric 3x3 matrix; r is the third index: arp, arq its other two off-diagonals
-__device__ __forceinline__ void nrm_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
-                                           double& v1p, double& v1q, double& v2p, double& v2q) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-    arp = rp; arq = rq;
-    const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
-    const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
-    const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
-    v0p = a0; v0q = b0; v1p = a1; v1q = b1; v2p = a2; v2q = b2;
-}
 
 template <int KMAX>
 __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* __restrict__ xyz, const int* __restrict__ off,
@@ -68,7 +51,7 @@ __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* _
         int* __restrict__ o = idx_out + row * (size_t)k;
 #pragma unroll
         for (int j = 0; j < KMAX; ++j)
-            if (j < k) o[j] = j < kp ? (int)(uint32_t)best.b[j] : -1;
+            if (j < k) o[j] = j < kp ? (int)best.index(j) : -1;
     }
     // moments of q_j = p_j - p_i in double (the differences of the converted coordinates are exact)
     const double cx = (double)q.x, cy = (double)q.y, cz = (double)q.z;
@@ -76,7 +59,7 @@ __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* _
 #pragma unroll
     for (int j = 0; j < KMAX; ++j)
         if (j < kp) {
-            const size_t g = (base + (size_t)(uint32_t)best.b[j]) * 3;
+            const size_t g = (base + (size_t)best.index(j)) * 3;
             const double x = (double)xyz[g + 0] - cx, y = (double)xyz[g + 1] - cy, z = (double)xyz[g + 2] - cz;
             s1x += x; s1y += y; s1z += z;
             sxx += x * x; syy += y * y; szz += z * z;
@@ -86,21 +69,7 @@ __global__ __launch_bounds__(kNrmThreads) void pca_normals_kernel(const float* _
     const double mx = s1x * inv, my = s1y * inv, mz = s1z * inv;
     double a00 = sxx * inv - mx * mx, a11 = syy * inv - my * my, a22 = szz * inv - mz * mz;
     double a01 = sxy * inv - mx * my, a02 = sxz * inv - mx * mz, a12 = syz * inv - my * mz;
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;   // v[row][column]
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
-        nrm_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);      // (0, 1), r = 2
-        nrm_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);      // (0, 2), r = 1
-        nrm_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);      // (1, 2), r = 0
-        const double scale = fabs(a00) + fabs(a11) + fabs(a22);                 // off-diagonals that no longer change the diagonal
-        if (fabs(a01) + scale == scale) a01 = 0.0;
-        if (fabs(a02) + scale == scale) a02 = 0.0;
-        if (fabs(a12) + scale == scale) a12 = 0.0;
-    }
-    // the column of the smallest eigenvalue (ties: the lowest column), and the three in order
-    double l0 = a00, ex = v00, ey = v10, ez = v20;
-    if (a11 < l0) { l0 = a11; ex = v01; ey = v11; ez = v21; }
-    if (a22 < l0) { l0 = a22; ex = v02; ey = v12; ez = v22; }
+#include "jacobi3_sweep.h"  // the sweeps, as text: the eigenvalues in a00, a11, a22; defines l0, ex, ey, ez
     const double l2 = fmax(a00, fmax(a11, a22));
     const double sum = a00 + a11 + a22;
     float nx = 0.f, ny = 0.f, nz = 0.f, var = -1.0f;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kNrmThreads) void knn_mean_dist_kernel(const int* _
     double sum = 0.0;
 #pragma unroll
     for (int j = 0; j < KMAX; ++j)
-        if (j < kp) sum += sqrt((double)__uint_as_float((uint32_t)(best.b[j] >> 32)));
+        if (j < kp) sum += sqrt((double)best.d2(j));
     mean_dist[base + (size_t)__float_as_int(q.w)] = (float)(sum / (double)max(kp - 1, 1));
 }
 

@@ -278,10 +278,6 @@ static ContourScratch contour_scratch(size_t nvox, size_t nlat) {
     return s;
 }
 
-static bool recon_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 static bool recon_bad_scratch(const void* scratch, size_t have, size_t need) {
     return !need || !scratch || have < need || ((uintptr_t)scratch & 15);
 }
@@ -301,7 +297,7 @@ DISPU_EXPORT int dispu_lattice_voxels(long long n, const float* points, float vo
     const size_t N = (size_t)n;
     const KeyedScratch s = keyed_scratch(N);
     if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
-    if (recon_overlap(occ_out, 8 * N, points, 12 * N)) return (int)hipErrorInvalidValue;
+    if (ranges_overlap(occ_out, 8 * N, points, 12 * N)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)scratch;
     uint64_t* keys = (uint64_t*)(base + s.keys);
@@ -334,7 +330,7 @@ DISPU_EXPORT int dispu_lattice_dilate(long long nocc, const unsigned long long* 
     const size_t NK = (size_t)nk;
     const KeyedScratch s = keyed_scratch(NK);
     if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
-    if (recon_overlap(act_out, 8 * NK, occ, 8 * (size_t)nocc)) return (int)hipErrorInvalidValue;
+    if (ranges_overlap(act_out, 8 * NK, occ, 8 * (size_t)nocc)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)scratch;
     uint64_t* keys = (uint64_t*)(base + s.keys);
@@ -357,8 +353,8 @@ DISPU_EXPORT int dispu_lattice_corners(long long nvox, const unsigned long long*
     const size_t NK = (size_t)nvox * 8;
     const KeyedScratch s = keyed_scratch(NK);
     if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
-    if (recon_overlap(lat_out, 8 * NK, act, 8 * (size_t)nvox) || recon_overlap(corner_out, 4 * NK, act, 8 * (size_t)nvox) ||
-        recon_overlap(lat_out, 8 * NK, corner_out, 4 * NK))
+    if (ranges_overlap(lat_out, 8 * NK, act, 8 * (size_t)nvox) || ranges_overlap(corner_out, 4 * NK, act, 8 * (size_t)nvox) ||
+        ranges_overlap(lat_out, 8 * NK, corner_out, 4 * NK))
         return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)scratch;
@@ -377,7 +373,7 @@ DISPU_EXPORT int dispu_lattice_corners(long long nvox, const unsigned long long*
 
 DISPU_EXPORT int dispu_lattice_positions(long long nlat, const unsigned long long* lat, float voxel, float* pos_out, void* stream) {
     if (nlat <= 0 || nlat > (1ll << 24) || !lat || !pos_out || !(voxel > 0.0f) || !(voxel <= FLT_MAX)) return (int)hipErrorInvalidValue;
-    if (recon_overlap(pos_out, 12 * (size_t)nlat, lat, 8 * (size_t)nlat)) return (int)hipErrorInvalidValue;
+    if (ranges_overlap(pos_out, 12 * (size_t)nlat, lat, 8 * (size_t)nlat)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(recon_positions_kernel, dim3(rc_blocks((size_t)nlat)), dim3(kRsThreads), 0, (hipStream_t)stream, (const uint64_t*)lat,
                        (size_t)nlat, voxel, pos_out);
     return (int)hipGetLastError();
@@ -399,8 +395,8 @@ DISPU_EXPORT int dispu_contour_count(long long nvox, long long nlat, const int* 
     const void* ins[2] = {corner, values};
     const size_t inb[2] = {32 * NV, 4 * NL};
     for (int i = 0; i < 2; ++i)
-        if (recon_overlap(slot_number, 28 * NL, ins[i], inb[i]) || recon_overlap(tri_start, 4 * NV, ins[i], inb[i])) return (int)hipErrorInvalidValue;
-    if (recon_overlap(slot_number, 28 * NL, tri_start, 4 * NV)) return (int)hipErrorInvalidValue;
+        if (ranges_overlap(slot_number, 28 * NL, ins[i], inb[i]) || ranges_overlap(tri_start, 4 * NV, ins[i], inb[i])) return (int)hipErrorInvalidValue;
+    if (ranges_overlap(slot_number, 28 * NL, tri_start, 4 * NV)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)scratch;
     uint32_t *sums = (uint32_t*)(base + s.sums), *d_tot = (uint32_t*)(base + s.small);
@@ -431,8 +427,8 @@ DISPU_EXPORT int dispu_contour_emit(long long nvox, long long nlat, float voxel,
     const void* ins[5] = {lat, corner, values, slot_number, tri_start};
     const size_t inb[5] = {8 * NL, 32 * NV, 4 * NL, 28 * NL, 4 * NV};
     for (int i = 0; i < 5; ++i)
-        if (recon_overlap(verts_out, vb, ins[i], inb[i]) || recon_overlap(faces_out, fb, ins[i], inb[i])) return (int)hipErrorInvalidValue;
-    if (recon_overlap(verts_out, vb, faces_out, fb)) return (int)hipErrorInvalidValue;
+        if (ranges_overlap(verts_out, vb, ins[i], inb[i]) || ranges_overlap(faces_out, fb, ins[i], inb[i])) return (int)hipErrorInvalidValue;
+    if (ranges_overlap(verts_out, vb, faces_out, fb)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(recon_vertices_kernel, dim3(rc_blocks(7 * NL)), dim3(kRsThreads), 0, st, (const uint64_t*)lat, (uint32_t)NL, values, voxel,
                        (const uint32_t*)slot_number, (uint32_t)nverts, verts_out);

@@ -15,8 +15,7 @@ import torch
 
 from . import _lib
 from ._util import req
-from .mls import check_support
-from .segments import MAX_POINTS, Packed, check_cloud, check_int_range, host_ptr
+from .segments import MAX_POINTS, Pair, check_cloud, check_int_range, check_support, scratch_buffer
 
 K_MIN, K_MAX = 1, 32
 BAND_MIN, BAND_MAX = 1, 3
@@ -47,44 +46,25 @@ def signed_distance(queries, points, normals, k=8, support=1.5):
     ValueError for illegal arguments and non-finite normals (before any launch of the operator) and for a cloud with a NaN or an
     infinite coordinate (after it)."""
     who = "signed_distance"
-    if isinstance(queries, torch.Tensor):
-        req(isinstance(points, torch.Tensor), "%s: queries is a tensor, so points must be one too, got %s" % (who, type(points).__name__))
-    else:
-        req(isinstance(queries, (list, tuple)) and isinstance(points, (list, tuple)),
-            "queries and points must be float32 [n, 3] tensors on a ROCm device or two lists of them, got %s and %s"
-            % (type(queries).__name__, type(points).__name__))
-        req(len(queries) >= 1, "%s needs at least one cloud" % who)
-        req(len(queries) == len(points), "%d query clouds but %d reference clouds" % (len(queries), len(points)))
-    q = Packed(queries, who, label="queries of cloud %d", home="the queries of cloud 0")
-    r = Packed(points, who, label="points of cloud %d", dev=q.dev, home="the queries of cloud 0")
+    b = Pair(queries, points, who, name="points")
     k = check_int_range(k, K_MIN, K_MAX, "k")
     support = check_support(support)
-    nrm = _normals_list(normals, r.clouds, q.single, q.dev, who)
-    q.pack()
-    r.pack(status=False)
-    L = _lib.lib()
-    nbytes = L.dispu_signed_distance_scratch_bytes(q.C, host_ptr(q.off), host_ptr(r.off))
-    scratch = q.scratch(nbytes, "dispu_signed_distance_scratch_bytes")
-    with torch.cuda.device(q.dev):
-        packed_n = r.pack_like(nrm)
-        out = torch.empty((q.total,), dtype=torch.float32, device=q.dev)
-        _lib.check(L.dispu_signed_distance_segments(q.C, _lib.ptr(q.d_off), host_ptr(q.off), _lib.ptr(r.d_off), host_ptr(r.off), k, support,
-                                                    _lib.ptr(q.cloud), _lib.ptr(r.cloud), _lib.ptr(packed_n), _lib.ptr(out),
-                                                    _lib.ptr(q.status), _lib.ptr(scratch), nbytes, _lib.stream_ptr(q.dev)),
+    nrm = _normals_list(normals, b.refs.clouds, b.single, b.dev, who)
+    b.pack("dispu_signed_distance_scratch_bytes")
+    with torch.cuda.device(b.dev):
+        packed_n = b.refs.pack_like(nrm)
+        out = torch.empty((b.nq,), dtype=torch.float32, device=b.dev)
+        _lib.check(_lib.lib().dispu_signed_distance_segments(*(b.head() + (k, support, _lib.ptr(b.queries.cloud), _lib.ptr(b.refs.cloud),
+                                                                           _lib.ptr(packed_n), _lib.ptr(out)) + b.tail())),
                    "dispu_signed_distance_segments")
-        q.refuse_non_finite()
-    return q.split(out)
+        b.queries.refuse_non_finite()
+    return b.queries.split(out)
 
 
 def check_voxel(v):
     ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(float(v)) and float(v) > 0
     req(ok and 0 < float(np.float32(v)) < float("inf"), "voxel must be a positive finite number (as float32 too), got %r" % (v,))
     return float(np.float32(v))
-
-
-def _scratch(nbytes, what, dev):
-    req(nbytes > 0, "%s refuses these sizes" % what)
-    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
 
 
 def _mark(dev):
@@ -124,7 +104,7 @@ def reconstruct_surface(points, normals, voxel, k=8, support=1.5, band=1, max_ve
         marks = [_mark(dev)] if stages is not None else None
         # occupied voxels
         nb = L.dispu_lattice_voxels_scratch_bytes(n)
-        scratch = _scratch(nb, "dispu_lattice_voxels_scratch_bytes", dev)
+        scratch = scratch_buffer(nb, "dispu_lattice_voxels_scratch_bytes", dev, "sizes")
         occ = torch.empty((n,), **i64)
         cnt, status = C.c_int(0), C.c_int(0)
         _lib.check(L.dispu_lattice_voxels(n, _lib.ptr(points), h, band, _lib.ptr(occ), C.byref(cnt), C.byref(status), _lib.ptr(scratch), nb, st),
@@ -137,7 +117,7 @@ def reconstruct_surface(points, normals, voxel, k=8, support=1.5, band=1, max_ve
         nkeys = nocc * (2 * band + 1) ** 3
         nb = L.dispu_lattice_dilate_scratch_bytes(nocc, band)
         del scratch
-        scratch = _scratch(nb, "dispu_lattice_dilate_scratch_bytes", dev)
+        scratch = scratch_buffer(nb, "dispu_lattice_dilate_scratch_bytes", dev, "sizes")
         act = torch.empty((nkeys,), **i64)
         cnt64 = C.c_longlong(0)
         _lib.check(L.dispu_lattice_dilate(nocc, _lib.ptr(occ), band, _lib.ptr(act), C.byref(cnt64), _lib.ptr(scratch), nb, st), "dispu_lattice_dilate")
@@ -145,7 +125,7 @@ def reconstruct_surface(points, normals, voxel, k=8, support=1.5, band=1, max_ve
         # lattice vertices and the corner table
         nb = L.dispu_lattice_corners_scratch_bytes(nvox)
         del scratch
-        scratch = _scratch(nb, "dispu_lattice_corners_scratch_bytes", dev)
+        scratch = scratch_buffer(nb, "dispu_lattice_corners_scratch_bytes", dev, "sizes")
         lat = torch.empty((8 * nvox,), **i64)
         corner = torch.empty((nvox, 8), dtype=torch.int32, device=dev)
         _lib.check(L.dispu_lattice_corners(nvox, _lib.ptr(act), _lib.ptr(lat), _lib.ptr(corner), C.byref(cnt64), _lib.ptr(scratch), nb, st),
@@ -164,7 +144,7 @@ def reconstruct_surface(points, normals, voxel, k=8, support=1.5, band=1, max_ve
             marks.append(_mark(dev))
         # contouring
         nb = L.dispu_contour_count_scratch_bytes(nvox, nlat)
-        scratch = _scratch(nb, "dispu_contour_count_scratch_bytes", dev)
+        scratch = scratch_buffer(nb, "dispu_contour_count_scratch_bytes", dev, "sizes")
         num = torch.empty((7 * nlat,), dtype=torch.int32, device=dev)
         start = torch.empty((nvox,), dtype=torch.int32, device=dev)
         nv, nf = C.c_longlong(0), C.c_longlong(0)
