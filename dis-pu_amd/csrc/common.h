@@ -32,6 +32,29 @@ constexpr int kWave = 64;
 // byte offsets inside a caller's scratch buffer advance in steps of 256
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// A scratch layout, region by region: take(bytes) is the offset of the next region and steps past it to the next multiple of 256; after
+// the last region `off` is the size of the whole.  Every region is rounded on its own, so the total does not depend on their order.
+// base: the buffer the regions lie in, for ptr(); null where a layout is only sized.
+struct Carver {
+    char* base = nullptr;
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off += align256(bytes);
+        return o;
+    }
+    template <class T>
+    T* ptr(size_t bytes) {                           // the region itself; null without a base
+        const size_t o = take(bytes);
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+};
+
+// what every entry asks of a caller's scratch: not null, 16-byte aligned, at least `need` bytes
+static inline bool scratch_ok(const void* scratch, size_t have, size_t need) {
+    return scratch && have >= need && !((uintptr_t)scratch & 15);
+}
+
 // whether the byte ranges [a, a + na) and [b, b + nb) share a byte: what an entry refuses between an output and anything it still reads
 static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;

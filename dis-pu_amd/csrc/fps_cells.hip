@@ -128,7 +128,7 @@ int fps_cells_run(int C, const int* off, const int* moff, const int* off_host, c
     if (!off || !moff || !inp || !out || !status) return (int)hipErrorInvalidValue;
     const size_t N = (size_t)off_host[C];
     const FpcScratch s = fpc_scratch(N, C);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    if (!scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     char* base = (char*)scratch;
     const uint32_t* segb = (const uint32_t*)(base + s.segb);
     const float* tab = (const float*)(base + s.tab);

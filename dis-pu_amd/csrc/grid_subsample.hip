@@ -18,8 +18,8 @@
 //   labels    per label column, the same sorter on (voxel id << 32) | (label ^ 0x80000000), then per voxel the longest run of equal
 //             keys, the first such run winning: ties go to the smallest label (signed)
 //
-// Cross-workgroup ordering is by kernel boundaries only: no kernel waits on anything another workgroup writes.  The sorter and the
-// device-wide scan (histogram table there, the heads here) are those of radix_sort.hip.
+// Cross-workgroup ordering is by kernel boundaries only: no kernel waits on anything another workgroup writes.  The sorter, the
+// device-wide scan and the run heads (RadixSorter, exclusive_scan_u32, run_heads_scan) are those of radix_sort.hip.
 // Two small host readbacks per call (dispu_grid_subsample_plan): the bounds with the non-finite flag, and m.
 #include "internal.h"
 #include <math.h>
@@ -166,14 +166,8 @@ __global__ __launch_bounds__(kRsThreads) void iota_kernel(size_t n, uint32_t* __
     if (i < n) vals[i] = (uint32_t)i;
 }
 
-// ---- run heads ---------------------------------------------------------------------------------------------------------------------------
-// keys == nullptr: all keys are equal (the zero-pass path)
-__global__ __launch_bounds__(kRsThreads) void heads_kernel(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ head) {
-    const size_t j = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
-    if (j < n) head[j] = (j == 0 || (keys && keys[j] != keys[j - 1])) ? 1u : 0u;
-}
-
-// ex: the exclusive scan of the heads, replaced in place by the voxel id of every sorted position; start[v] = the first position of voxel
+// ---- runs --------------------------------------------------------------------------------------------------------------------------------
+// keys == nullptr: all keys are equal (the zero-pass path).  ex: run_heads_scan's exclusive scan of the heads, replaced in place by the voxel id of every sorted position; start[v] = the first position of voxel
 // v, start[m] = n
 __global__ __launch_bounds__(kRsThreads) void runs_kernel(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ ex,
                                                           uint32_t* __restrict__ start) {
@@ -240,27 +234,23 @@ __global__ __launch_bounds__(kRsThreads) void label_mode_kernel(uint32_t n, uint
 
 // ---- scratch of the whole operator -----------------------------------------------------------------------------------------------------------
 struct GridScratch {
-    size_t kA, kB, vA, vB, perm, vid, start, table, sums, partial, small, total;
+    RadixSorter sort;
+    uint32_t *perm, *vid, *start;
+    Bounds *partial, *bounds;                        // bounds: the Bounds result, and the voxel count m 128 bytes behind it
+    size_t total;
 };
-static GridScratch grid_scratch(size_t n) {
+static GridScratch grid_scratch(size_t n, void* base = nullptr) {
     GridScratch s;
-    size_t o = 0;
-    s.kA = o;      o += align256(8 * n);
-    s.kB = o;      o += align256(8 * n);
-    s.vA = o;      o += align256(4 * n);
-    s.vB = o;      o += align256(4 * n);
-    s.perm = o;    o += align256(4 * n);
-    s.vid = o;     o += align256(4 * n);
-    s.start = o;   o += align256(4 * (n + 1));
-    s.table = o;   o += align256(4 * rs_table_words(n));
-    s.sums = o;    o += align256(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
-    s.partial = o; o += align256(sizeof(Bounds) * kBoundsMaxBlocks);
-    s.small = o;   o += 256;                         // Bounds result, m
-    s.total = o;
+    Carver cv{(char*)base};
+    s.sort.carve(cv, n);
+    s.perm = cv.ptr<uint32_t>(4 * n);
+    s.vid = cv.ptr<uint32_t>(4 * n);
+    s.start = cv.ptr<uint32_t>(4 * (n + 1));
+    s.partial = cv.ptr<Bounds>(sizeof(Bounds) * kBoundsMaxBlocks);
+    s.bounds = cv.ptr<Bounds>(256);
+    s.total = cv.off;
     return s;
 }
-
-static inline unsigned blocks_for(size_t work) { return (unsigned)((work + kRsThreads - 1) / kRsThreads); }
 
 }  // namespace dispu
 
@@ -279,24 +269,17 @@ DISPU_EXPORT int dispu_grid_subsample_plan(long long n, const float* points, flo
     if (n >= (1ll << 31)) { *status_out = DISPU_GRID_TOO_MANY_POINTS; return 0; }   // before anything is touched
     if (n <= 0 || !points || !(dl > 0.0f) || !(dl <= FLT_MAX)) return (int)hipErrorInvalidValue;
     const size_t N = (size_t)n;
-    const GridScratch s = grid_scratch(N);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    GridScratch s = grid_scratch(N, scratch);
+    if (!scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)scratch;
-    uint64_t *kA = (uint64_t*)(base + s.kA), *kB = (uint64_t*)(base + s.kB);
-    uint32_t *vA = (uint32_t*)(base + s.vA), *vB = (uint32_t*)(base + s.vB);
-    uint32_t *perm = (uint32_t*)(base + s.perm), *vid = (uint32_t*)(base + s.vid), *start = (uint32_t*)(base + s.start);
-    uint32_t *table = (uint32_t*)(base + s.table), *sums = (uint32_t*)(base + s.sums);
-    Bounds* partial = (Bounds*)(base + s.partial);
-    Bounds* d_bounds = (Bounds*)(base + s.small);
-    uint32_t* d_m = (uint32_t*)(base + s.small + 128);
+    uint32_t* d_m = (uint32_t*)((char*)s.bounds + 128);
 
-    const int bblocks = (int)(blocks_for(N) < (unsigned)kBoundsMaxBlocks ? blocks_for(N) : (unsigned)kBoundsMaxBlocks);
-    hipLaunchKernelGGL(bounds_partial_kernel, dim3(bblocks), dim3(kRsThreads), 0, st, points, N, partial);
-    hipLaunchKernelGGL(bounds_finish_kernel, dim3(1), dim3(kRsThreads), 0, st, (const Bounds*)partial, bblocks, d_bounds);
+    const int bblocks = (int)(rs_blocks(N) < (unsigned)kBoundsMaxBlocks ? rs_blocks(N) : (unsigned)kBoundsMaxBlocks);
+    hipLaunchKernelGGL(bounds_partial_kernel, dim3(bblocks), dim3(kRsThreads), 0, st, points, N, s.partial);
+    hipLaunchKernelGGL(bounds_finish_kernel, dim3(1), dim3(kRsThreads), 0, st, (const Bounds*)s.partial, bblocks, s.bounds);
     DISPU_CHECK_LAUNCH();
     Bounds hb;
-    DISPU_TRY(hipMemcpyAsync(&hb, d_bounds, sizeof(Bounds), hipMemcpyDeviceToHost, st));      // readback 1
+    DISPU_TRY(hipMemcpyAsync(&hb, s.bounds, sizeof(Bounds), hipMemcpyDeviceToHost, st));      // readback 1
     DISPU_TRY(hipStreamSynchronize(st));
     if (hb.bad) { *status_out = DISPU_GRID_NONFINITE; return 0; }
     const GridParams g = grid_params(hb, dl);
@@ -309,20 +292,18 @@ DISPU_EXPORT int dispu_grid_subsample_plan(long long n, const float* points, flo
 
     const uint64_t* sorted = nullptr;                // null: one cell, every key equal
     if (g.passes == 0) {
-        hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, N, perm);
+        hipLaunchKernelGGL(iota_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, N, s.perm);
     } else {
-        hipLaunchKernelGGL(grid_keys_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, points, N, g.origin[0], g.origin[1], g.origin[2],
-                           dl, g.N[0], g.N[0] * g.N[1], g.key_min, kA, vA);
-        const int rc = radix_passes(N, g.passes, kA, vA, kB, vB, kA, vA, table, sums, st);
+        hipLaunchKernelGGL(grid_keys_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, points, N, g.origin[0], g.origin[1], g.origin[2],
+                           dl, g.N[0], g.N[0] * g.N[1], g.key_min, s.sort.k[0], s.sort.v[0]);
+        const int rc = s.sort.sort(N, g.passes, st);
         if (rc) return rc;
-        const bool odd = g.passes & 1;
-        sorted = odd ? kB : kA;
-        DISPU_TRY(hipMemcpyAsync(perm, odd ? vB : vA, 4 * N, hipMemcpyDeviceToDevice, st));
+        sorted = s.sort.keys();
+        DISPU_TRY(hipMemcpyAsync(s.perm, s.sort.vals(), 4 * N, hipMemcpyDeviceToDevice, st));
     }
-    hipLaunchKernelGGL(heads_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, sorted, N, vid);
-    const int rc = exclusive_scan_u32(vid, N, sums, d_m, st);
+    const int rc = run_heads_scan(sorted, N, s.vid, s.sort.sums, d_m, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(runs_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, sorted, N, vid, start);
+    hipLaunchKernelGGL(runs_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, sorted, N, s.vid, s.start);
     DISPU_CHECK_LAUNCH();
     uint32_t hm = 0;
     DISPU_TRY(hipMemcpyAsync(&hm, d_m, sizeof(hm), hipMemcpyDeviceToHost, st));               // readback 2
@@ -337,25 +318,20 @@ DISPU_EXPORT int dispu_grid_subsample_emit(long long n, int m, int fdim, int ldi
     if (n <= 0 || n >= (1ll << 31) || m <= 0 || m > n || fdim < 0 || ldim < 0 || !points || !out_points) return (int)hipErrorInvalidValue;
     if ((fdim > 0 && (!features || !out_features)) || (ldim > 0 && (!classes || !out_classes))) return (int)hipErrorInvalidValue;
     const size_t N = (size_t)n;
-    const GridScratch s = grid_scratch(N);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    GridScratch s = grid_scratch(N, scratch);
+    if (!scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)scratch;
-    uint64_t *kA = (uint64_t*)(base + s.kA), *kB = (uint64_t*)(base + s.kB);
-    uint32_t *vA = (uint32_t*)(base + s.vA), *vB = (uint32_t*)(base + s.vB);
-    const uint32_t *perm = (const uint32_t*)(base + s.perm), *vid = (const uint32_t*)(base + s.vid), *start = (const uint32_t*)(base + s.start);
-    uint32_t *table = (uint32_t*)(base + s.table), *sums = (uint32_t*)(base + s.sums);
-
-    hipLaunchKernelGGL(grid_reduce_kernel, dim3(blocks_for((size_t)m * (3 + fdim))), dim3(kRsThreads), 0, st, (uint32_t)N, (uint32_t)m, fdim, start, perm,
+    hipLaunchKernelGGL(grid_reduce_kernel, dim3(rs_blocks((size_t)m * (3 + fdim))), dim3(kRsThreads), 0, st, (uint32_t)N, (uint32_t)m, fdim, s.start, s.perm,
                        points, features, out_points, out_features);
     DISPU_CHECK_LAUNCH();
     const int lpasses = (32 + bit_length_u64((unsigned long long)m - 1) + 7) / 8;
     for (int col = 0; col < ldim; ++col) {
-        hipLaunchKernelGGL(label_keys_kernel, dim3(blocks_for(N)), dim3(kRsThreads), 0, st, N, vid, perm, classes, ldim, col, kA, vA);
-        const int rc = radix_passes(N, lpasses, kA, vA, kB, vB, kA, vA, table, sums, st);
+        hipLaunchKernelGGL(label_keys_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, N, s.vid, s.perm, classes, ldim, col, s.sort.k[0],
+                           s.sort.v[0]);
+        const int rc = s.sort.sort(N, lpasses, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(label_mode_kernel, dim3(blocks_for((size_t)m)), dim3(kRsThreads), 0, st, (uint32_t)N, (uint32_t)m, start,
-                           (const uint64_t*)((lpasses & 1) ? kB : kA), ldim, col, out_classes);
+        hipLaunchKernelGGL(label_mode_kernel, dim3(rs_blocks((size_t)m)), dim3(kRsThreads), 0, st, (uint32_t)N, (uint32_t)m, s.start, s.sort.keys(),
+                           ldim, col, out_classes);
     }
     return (int)hipGetLastError();
 }

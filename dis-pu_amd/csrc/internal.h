@@ -1,6 +1,6 @@
 // Every function of libdispu_hip.so that is defined in one translation unit and called from another, declared ONCE: the defining file
 // and every caller include this header, so the compiler checks each definition and each call against the same prototype (default
-// arguments live here only).  Declarations, and one template; the exported C-ABI is include/dispu_hip.h.
+// arguments live here only).  Declarations, the sorter's handle and one template; the exported C-ABI is include/dispu_hip.h.
 #pragma once
 #include <type_traits>
 
@@ -61,14 +61,30 @@ int fps_wave_launch(int b, int n, int m, const float* xyz, int* perm, int* out, 
 // ---- radix_sort.hip: the device-wide stable LSD radix sort of (uint64 key, uint32 value) pairs and its three-step scan -----------------
 constexpr int kRsThreads = 256, kRsWaves = kRsThreads / kWave;       // the block size of the sorter, its scans and its clients' kernels
 size_t scan_blocks(size_t L);                                        // words of `sums` a scan over L words needs
-size_t rs_table_words(size_t n);                                     // words of the digit-major histogram table of n pairs
 // exclusive scan of data[L] in place; sums: scan_blocks(L) words; the grand total -> *total_out (device, if not null)
 int exclusive_scan_u32(uint32_t* data, size_t L, uint32_t* sums, uint32_t* total_out, hipStream_t st);
-// `passes` stable 8-bit passes from (src_k, src_v), which is only read, alternating into (xk, xv), (yk, yv), (xk, xv), ...: the result
-// is in x when passes is odd and in y when it is even (passes >= 1).  table: rs_table_words(n) words, sums: scan_blocks of the larger
-// of rs_table_words(n) and n
-int radix_passes(size_t n, int passes, const uint64_t* src_k, const uint32_t* src_v, uint64_t* xk, uint32_t* xv, uint64_t* yk,
-                 uint32_t* yv, uint32_t* table, uint32_t* sums, hipStream_t st);
+static inline unsigned rs_blocks(size_t work) { return (unsigned)((work + kRsThreads - 1) / kRsThreads); }   // one lane per item
+// The sorter as its in-library clients hold it: both sides of the ping-pong, the histogram table and the scan's block sums.  A client
+// writes its pairs to k[0], v[0], calls sort() and reads keys(), vals(); which side that is stays in here.  All four buffers are
+// overwritten by a sort and are the client's again afterwards.
+struct RadixSorter {
+    uint64_t* k[2];
+    uint32_t* v[2];
+    uint32_t *table, *sums;
+    int side = 0;                                    // where the last sort() left its result
+    // the regions for n pairs, in the order k[0], k[1], v[0], v[1], table, sums.  THE sizing rule -- table: 256 words per tile of n;
+    // sums: scan_blocks of the larger of that and n, so it also serves any scan over up to n words (run_heads_scan)
+    void carve(Carver& cv, size_t n);
+    // `passes` >= 0 stable 8-bit passes over (k[0], v[0]); 0 leaves the pairs where they are
+    int sort(size_t n, int passes, hipStream_t st);
+    const uint64_t* keys() const { return k[side]; }
+    const uint32_t* vals() const { return v[side]; }
+};
+// Run numbering over sorted keys: ex[j] = the number of run heads (j == 0 or keys[j] != keys[j - 1]) before position j, the run count
+// -> *count (device).  keys == nullptr: all keys are equal, one run.  sums: scan_blocks(n) words (a RadixSorter's do)
+int run_heads_scan(const uint64_t* keys, size_t n, uint32_t* ex, uint32_t* sums, uint32_t* count, hipStream_t st);
+// The step after it -- start[e] = j at a head, start[the run count] = n, ex[j] -> the number of j's run -- stays written out in its two
+// kernels (runs_kernel, pc_cells_kernel): as a shared __forceinline__ function, with or without __restrict__, it changed both kernels' code
 
 // ---- morton_cells.hip: the Morton-cell pre-pass over a packed ragged batch (bounds, keys, ONE sort, cells) -----------------------------
 // Which segments the pre-pass (and the sampling kernel behind it) serves, and in what cells.  An int underneath: it is a kernel argument.

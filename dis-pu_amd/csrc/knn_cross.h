@@ -25,7 +25,7 @@ struct CrossPrepass {
     size_t bytes() const { return rbytes + qbytes; }
     // whether `scratch` holds the two regions and `extra` bytes behind them
     bool fits(const void* scratch, size_t scratch_bytes, size_t extra = 0) const {
-        return rc == 0 && scratch && scratch_bytes >= bytes() + extra && !((uintptr_t)scratch & 15);
+        return rc == 0 && scratch_ok(scratch, scratch_bytes, bytes() + extra);
     }
     int run_refs(const int* roff, const float* refs, void* scratch, hipStream_t st) {
         int kr = 0;

@@ -157,16 +157,16 @@ __global__ __launch_bounds__(kFpcPre) void fpc_cells_kernel(const float* __restr
 
 FpcScratch fpc_scratch(size_t N, int C) {
     FpcScratch s;
-    size_t o = 0;
-    s.kin = o;  o += align256(8 * N);
-    s.kout = o; o += align256(8 * N);
-    s.vin = o;  o += align256(4 * N);
-    s.vout = o; o += align256(4 * N);
+    Carver cv;
+    s.kin = cv.take(8 * N);                          // kin, kout adjacent and in this order: spt lies over both
+    s.kout = cv.take(8 * N);
+    s.vin = cv.take(4 * N);
+    s.vout = cv.take(4 * N);
     s.sort_bytes = dispu_radix_sort_scratch_bytes((long long)N);
-    s.sort = o; o += align256(s.sort_bytes);
-    s.tab = o;  o += align256(32 * (N / kFpcMinCell + (size_t)C));
-    s.segb = o; o += align256(32 * (size_t)C);
-    s.total = o;
+    s.sort = cv.take(s.sort_bytes);
+    s.tab = cv.take(32 * (N / kFpcMinCell + (size_t)C));
+    s.segb = cv.take(32 * (size_t)C);
+    s.total = cv.off;
     return s;
 }
 
@@ -244,7 +244,7 @@ int fps_cells_prepass(int C, const int* off, const int* off_host, const float* i
     if (!off || !inp) return (int)hipErrorInvalidValue;
     const size_t N = (size_t)off_host[C];
     const FpcScratch s = fpc_scratch(N, C);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    if (!scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     char* base = (char*)scratch;
     *spt = (const float4*)(base + s.kin);
     *tab = (const float*)(base + s.tab);

@@ -405,23 +405,22 @@ struct OrLayout {
 
 static OrLayout or_layout(int C, size_t total, char* base) {
     OrLayout L;
-    size_t o = 0;
-    auto take = [&](size_t b) { char* p = base + o; o += align256(b); return p; };
-    L.live = (int*)take((size_t)(kOrMaxRounds + kOrMaxRounds * kOrJumpLaunches + C) * 4);   // zero-filled together
+    Carver cv{base};
+    L.live = cv.ptr<int>((size_t)(kOrMaxRounds + kOrMaxRounds * kOrJumpLaunches + C) * 4);   // zero-filled together
     L.jflag = L.live + kOrMaxRounds;
     L.ncomp = L.jflag + kOrMaxRounds * kOrJumpLaunches;
-    L.head_bytes = o;
-    L.best1 = (uint64_t*)take(total * 8);
-    L.k1 = (uint64_t*)take(total * 8);
-    L.k2 = (uint64_t*)take(total * 8);
-    L.cnt = (uint64_t*)take(total * 8);
-    L.P = (uint32_t*)take(total * 4);
-    L.H = (uint32_t*)take(total * 4);
-    L.best2 = (uint32_t*)take(total * 4);
-    L.low = (uint32_t*)take(total * 4);
-    L.cid = (int*)take(total * 4);
-    L.dead = (unsigned char*)take(total);
-    L.bytes = o;
+    L.head_bytes = cv.off;
+    L.best1 = cv.ptr<uint64_t>(total * 8);
+    L.k1 = cv.ptr<uint64_t>(total * 8);
+    L.k2 = cv.ptr<uint64_t>(total * 8);
+    L.cnt = cv.ptr<uint64_t>(total * 8);
+    L.P = cv.ptr<uint32_t>(total * 4);
+    L.H = cv.ptr<uint32_t>(total * 4);
+    L.best2 = cv.ptr<uint32_t>(total * 4);
+    L.low = cv.ptr<uint32_t>(total * 4);
+    L.cid = cv.ptr<int>(total * 4);
+    L.dead = cv.ptr<unsigned char>(total);
+    L.bytes = cv.off;
     return L;
 }
 
@@ -478,11 +477,11 @@ DISPU_EXPORT int dispu_orient_consistent_segments(int C, const int* off, const i
     const int rc = or_check(C, off_host, k, &nmax);
     if (rc != 0) return rc;
     if (!off || !points || !normal_in || !neighbors || !normal_out || !status || normal_out == normal_in || vote < 0 || vote > 1 ||
-        (flags & ~DISPU_ORIENT_HOST_ROUNDS) != 0 || !scratch || (((uintptr_t)scratch) & 15) != 0)
+        (flags & ~DISPU_ORIENT_HOST_ROUNDS) != 0)
         return (int)hipErrorInvalidValue;
     const uint32_t total = (uint32_t)off_host[C];
     const OrLayout L = or_layout(C, total, (char*)scratch);
-    if (scratch_bytes < L.bytes) return (int)hipErrorInvalidValue;
+    if (!scratch_ok(scratch, scratch_bytes, L.bytes)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nslots = total * (uint32_t)k;
     const dim3 block(kOrThreads), gn((total + kOrThreads - 1) / kOrThreads), gs((nslots + kOrThreads - 1) / kOrThreads);

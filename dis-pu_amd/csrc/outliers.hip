@@ -163,14 +163,15 @@ __global__ __launch_bounds__(kOutCmp) void compact_scatter_kernel(const int* __r
 }
 
 struct CmpScratch {
-    size_t flags, sums, total;
+    uint32_t *flags, *sums;
+    size_t total;
 };
-static CmpScratch cmp_scratch(size_t N) {
+static CmpScratch cmp_scratch(size_t N, void* base = nullptr) {
     CmpScratch s;
-    size_t o = 0;
-    s.flags = o; o += align256(4 * N);
-    s.sums = o;  o += align256(4 * scan_blocks(N));
-    s.total = o;
+    Carver cv{(char*)base};
+    s.flags = cv.ptr<uint32_t>(4 * N);
+    s.sums = cv.ptr<uint32_t>(4 * scan_blocks(N));
+    s.total = cv.off;
     return s;
 }
 
@@ -248,17 +249,15 @@ DISPU_EXPORT int dispu_compact_segments(int C, const int* off, const int* off_ho
     if (rule < 0 || rule > 2 || !off || !src || (rule == 1 && !stats) || (out_points && !cloud) || !out_index || !new_off)
         return (int)hipErrorInvalidValue;
     const size_t N = (size_t)off_host[C];
-    const CmpScratch s = cmp_scratch(N);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
+    const CmpScratch s = cmp_scratch(N, scratch);
+    if (!scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    uint32_t* flags = (uint32_t*)((char*)scratch + s.flags);
-    uint32_t* sums = (uint32_t*)((char*)scratch + s.sums);
     const dim3 grid((nall + kOutCmp - 1) / kOutCmp, C), block(kOutCmp);
-    hipLaunchKernelGGL(compact_flags_kernel, grid, block, 0, st, off, rule, src, stats, min_neighbors, status, flags);
+    hipLaunchKernelGGL(compact_flags_kernel, grid, block, 0, st, off, rule, src, stats, min_neighbors, status, s.flags);
     DISPU_CHECK_LAUNCH();
-    const int rs = exclusive_scan_u32(flags, N, sums, (uint32_t*)(new_off + C), st);
+    const int rs = exclusive_scan_u32(s.flags, N, s.sums, (uint32_t*)(new_off + C), st);
     if (rs != 0) return rs;
-    hipLaunchKernelGGL(compact_scatter_kernel, grid, block, 0, st, off, cloud, rule, src, stats, min_neighbors, status, flags, out_points,
+    hipLaunchKernelGGL(compact_scatter_kernel, grid, block, 0, st, off, cloud, rule, src, stats, min_neighbors, status, s.flags, out_points,
                        out_index, new_off);
     return (int)hipGetLastError();
 }

@@ -315,7 +315,7 @@ DISPU_EXPORT int dispu_poisson_disk_keep(int b, int n, const float* points, cons
                                          void* scratch, size_t scratch_bytes, int* status, void* stream) {
     if (b < 0 || n <= 0 || n > DISPU_POISSON_MAX_N || !points || !radius || !keep || !count || !status) return (int)hipErrorInvalidValue;
     if (b == 0) return 0;
-    if (!scratch || (((uintptr_t)scratch) & 15) || scratch_bytes < dispu_poisson_disk_scratch_bytes(b, n)) return (int)hipErrorInvalidValue;
+    if (!scratch_ok(scratch, scratch_bytes, dispu_poisson_disk_scratch_bytes(b, n))) return (int)hipErrorInvalidValue;
     return pd_launch<false>(b, n, 0, 0, points, radius, keep, count, nullptr, nullptr, scratch, status, (hipStream_t)stream);
 }
 
@@ -325,7 +325,7 @@ DISPU_EXPORT int dispu_poisson_disk_select(int b, int n, int m, int steps, const
         !status)
         return (int)hipErrorInvalidValue;
     if (b == 0) return 0;
-    if (!scratch || (((uintptr_t)scratch) & 15) || scratch_bytes < dispu_poisson_disk_scratch_bytes(b, n)) return (int)hipErrorInvalidValue;
+    if (!scratch_ok(scratch, scratch_bytes, dispu_poisson_disk_scratch_bytes(b, n))) return (int)hipErrorInvalidValue;
     return pd_launch<true>(b, n, m, steps, points, r_hi, nullptr, count_out, idx, r_out, scratch, status, (hipStream_t)stream);
 }
 

@@ -26,7 +26,7 @@
 // coordinate is below 1024 * 2^-23 = 2^-13 of a cell per point, far inside the 2^-10 margin), and it is capped in number, so an outlier
 // cannot blow the grid up.  The cell key is (segment, z, y, x), x fastest, in a uint64; (key, packed index) goes through the stable
 // sorter of radix_sort.hip, so indices ascend inside a cell.  The grid is sparse (1024^3 cells cannot be tabulated): the occupied cells
-// are compacted (head flags + exclusive_scan_u32), and because x is fastest the three x-neighbours of a row are ONE contiguous range of
+// are compacted (run_heads_scan of radix_sort.hip), and because x is fastest the three x-neighbours of a row are ONE contiguous range of
 // the sorted cloud, so a point scans 9 ranges.  The 9 ranges are found ONCE per occupied cell by binary search over the compacted keys
 // and kept as a record of 20 words per cell; every round of every radius of a bisection reads them back (DESIGN section 9 says why
 // this variant and what it costs in memory).
@@ -65,8 +65,6 @@ __device__ __forceinline__ int pc_find_seg(const int* __restrict__ off, int C, u
 __device__ __forceinline__ uint32_t pc_cell1(float x, float lo, float inv) {
     return (uint32_t)(int)fminf(fmaxf((x - lo) * inv, 0.0f), (float)(PC_G - 1));         // NaN -> 0; always inside the grid
 }
-
-static inline unsigned pc_blocks(size_t work) { return (unsigned)((work + kRsThreads - 1) / kRsThreads); }
 
 // ---- bounds ----------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kRsThreads) void pc_seg_init_kernel(int C, uint32_t* __restrict__ segb, int* __restrict__ status) {
@@ -143,12 +141,7 @@ __global__ __launch_bounds__(kRsThreads) void pc_keys_kernel(uint32_t N, int C, 
     vals[i] = i;
 }
 
-__global__ __launch_bounds__(kRsThreads) void pc_heads_kernel(const uint64_t* __restrict__ keys, uint32_t N, uint32_t* __restrict__ head) {
-    const uint32_t j = blockIdx.x * kRsThreads + threadIdx.x;
-    if (j < N) head[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1u : 0u;
-}
-
-// ex: the exclusive scan of the heads, replaced in place by the cell number of every sorted position; cstart[v] = the first position of
+// ex: run_heads_scan's exclusive scan of the heads, replaced in place by the cell number of every sorted position; cstart[v] = the first position of
 // occupied cell v, cstart[ncell] = N; ckey[v] = its key; spt[j] = (x, y, z, packed index as bits) of sorted position j
 __global__ __launch_bounds__(kRsThreads) void pc_cells_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t N,
                                                               const float* __restrict__ points, uint32_t* __restrict__ ex,
@@ -346,31 +339,27 @@ __global__ __launch_bounds__(kRsThreads) void pc_finish_kernel(int C, const int*
 
 // ---- scratch ---------------------------------------------------------------------------------------------------------------------------
 struct PcScratch {
-    size_t kA, kB, vA, vB, table, sums, spt, cid, cstart, ckey, crec, state, flag, words, segb, segg, segr, segc, cnt, total;
+    RadixSorter sort;                                // after the sort its value buffers are the two lists of active points
+    size_t spt, cid, cstart, ckey, crec, state, flag, words, segb, segg, segr, segc, cnt, total;
 };
-static PcScratch pc_scratch(size_t N, size_t C) {
+static PcScratch pc_scratch(size_t N, size_t C, void* base = nullptr) {
     PcScratch s;
-    size_t o = 0;
-    s.kA = o;     o += align256(8 * N);
-    s.kB = o;     o += align256(8 * N);
-    s.vA = o;     o += align256(4 * N);              // after the sort: the two lists of active points
-    s.vB = o;     o += align256(4 * N);
-    s.table = o;  o += align256(4 * rs_table_words(N));
-    s.sums = o;   o += align256(4 * scan_blocks(rs_table_words(N) > N ? rs_table_words(N) : N));
-    s.spt = o;    o += align256(16 * N);
-    s.cid = o;    o += align256(4 * N);
-    s.cstart = o; o += align256(4 * (N + 1));
-    s.ckey = o;   o += align256(8 * N);
-    s.crec = o;   o += align256(4 * (size_t)PC_REC * N);      // one record per occupied cell, at most one cell per point
-    s.state = o;  o += align256(N);
-    s.flag = o;   o += align256(N);
-    s.words = o;  o += align256(4 * N);
-    s.segb = o;   o += align256(32 * C);
-    s.segg = o;   o += align256(16 * C);
-    s.segr = o;   o += align256(16 * C);
-    s.segc = o;   o += align256(4 * C);
-    s.cnt = o;    o += align256(4 * (size_t)PC_CNT_WORDS + 256);      // the round counters, then the cell count
-    s.total = o;
+    Carver cv{(char*)base};
+    s.sort.carve(cv, N);
+    s.spt = cv.take(16 * N);
+    s.cid = cv.take(4 * N);
+    s.cstart = cv.take(4 * (N + 1));
+    s.ckey = cv.take(8 * N);
+    s.crec = cv.take(4 * (size_t)PC_REC * N);        // one record per occupied cell, at most one cell per point
+    s.state = cv.take(N);
+    s.flag = cv.take(N);
+    s.words = cv.take(4 * N);
+    s.segb = cv.take(32 * C);
+    s.segg = cv.take(16 * C);
+    s.segr = cv.take(16 * C);
+    s.segc = cv.take(4 * C);
+    s.cnt = cv.take(4 * (size_t)PC_CNT_WORDS + 256); // the round counters, then the cell count
+    s.total = cv.off;
     return s;
 }
 
@@ -389,28 +378,23 @@ static int pc_prepare(const PcRun& R, const int* off, const float* points, const
     const uint32_t N = R.N;
     const int C = R.C;
     hipStream_t st = R.st;
-    uint64_t *kA = R.at<uint64_t>(R.s.kA), *kB = R.at<uint64_t>(R.s.kB);
-    uint32_t *vA = R.at<uint32_t>(R.s.vA), *vB = R.at<uint32_t>(R.s.vB);
+    RadixSorter sort = R.s.sort;
     uint32_t *segb = R.at<uint32_t>(R.s.segb), *cid = R.at<uint32_t>(R.s.cid), *cstart = R.at<uint32_t>(R.s.cstart);
     float* segg = R.at<float>(R.s.segg);
-    hipLaunchKernelGGL(pc_seg_init_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, st, C, segb, status);
-    hipLaunchKernelGGL(pc_bounds_kernel, dim3(pc_blocks(N)), dim3(kRsThreads), 0, st, N, C, off, points, segb);
-    hipLaunchKernelGGL(pc_grid_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, st, C, r_top, segb, segg);
-    hipLaunchKernelGGL(pc_keys_kernel, dim3(pc_blocks(N)), dim3(kRsThreads), 0, st, N, C, off, points, (const float*)segg, kA, vA);
+    hipLaunchKernelGGL(pc_seg_init_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, st, C, segb, status);
+    hipLaunchKernelGGL(pc_bounds_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, N, C, off, points, segb);
+    hipLaunchKernelGGL(pc_grid_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, st, C, r_top, segb, segg);
+    hipLaunchKernelGGL(pc_keys_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, N, C, off, points, (const float*)segg, sort.k[0], sort.v[0]);
     DISPU_CHECK_LAUNCH();
     int bits = PC_CELL_BITS;
     for (unsigned c = (unsigned)C - 1u; c; c >>= 1) ++bits;
-    const int passes = (bits + 7) / 8;
-    int rc = radix_passes(N, passes, kA, vA, kB, vB, kA, vA, R.at<uint32_t>(R.s.table), R.at<uint32_t>(R.s.sums), st);
+    int rc = sort.sort(N, (bits + 7) / 8, st);
     if (rc) return rc;
-    const uint64_t* sk = (passes & 1) ? kB : kA;
-    const uint32_t* sv = (passes & 1) ? vB : vA;
-    hipLaunchKernelGGL(pc_heads_kernel, dim3(pc_blocks(N)), dim3(kRsThreads), 0, st, sk, N, cid);
-    rc = exclusive_scan_u32(cid, N, R.at<uint32_t>(R.s.sums), R.ncell(), st);
+    rc = run_heads_scan(sort.keys(), N, cid, sort.sums, R.ncell(), st);
     if (rc) return rc;
-    hipLaunchKernelGGL(pc_cells_kernel, dim3(pc_blocks(N)), dim3(kRsThreads), 0, st, sk, sv, N, points, cid, cstart, R.at<uint64_t>(R.s.ckey),
-                       R.at<float4>(R.s.spt));
-    hipLaunchKernelGGL(pc_ranges_kernel, dim3(pc_blocks((size_t)N * 9)), dim3(kRsThreads), 0, st, (const uint32_t*)R.ncell(), N,
+    hipLaunchKernelGGL(pc_cells_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, sort.keys(), sort.vals(), N, points, cid, cstart,
+                       R.at<uint64_t>(R.s.ckey), R.at<float4>(R.s.spt));
+    hipLaunchKernelGGL(pc_ranges_kernel, dim3(rs_blocks((size_t)N * 9)), dim3(kRsThreads), 0, st, (const uint32_t*)R.ncell(), N,
                        (const uint64_t*)R.at<uint64_t>(R.s.ckey), (const uint32_t*)cstart, R.at<uint32_t>(R.s.crec));
     return (int)hipGetLastError();
 }
@@ -425,18 +409,18 @@ static int pc_eval(const PcRun& R, int* status) {
     const float* segr = R.at<float>(R.s.segr);
     uint8_t* state = R.at<uint8_t>(R.s.state);
     uint32_t *cnt = R.at<uint32_t>(R.s.cnt), *segc = R.at<uint32_t>(R.s.segc);
-    uint32_t* list[2] = {R.at<uint32_t>(R.s.vA), R.at<uint32_t>(R.s.vB)};     // round k reads list[k & 1] and fills list[(k + 1) & 1]
-    hipLaunchKernelGGL(pc_eval_init_kernel, dim3(pc_blocks(N > (uint32_t)PC_CNT_WORDS ? N : PC_CNT_WORDS)), dim3(kRsThreads), 0, st, N, C, cid,
+    uint32_t* const* list = R.s.sort.v;              // round k reads list[k & 1] and fills list[(k + 1) & 1]
+    hipLaunchKernelGGL(pc_eval_init_kernel, dim3(rs_blocks(N > (uint32_t)PC_CNT_WORDS ? N : PC_CNT_WORDS)), dim3(kRsThreads), 0, st, N, C, cid,
                        crec, (const uint32_t*)R.at<uint32_t>(R.s.segb), segr, state, cnt, segc);
     uint32_t active = N;                             // an upper bound of the list the next round reads
     int round = 0;
     while (active && round < DISPU_POISSON_MAX_ROUNDS) {
         for (int j = 0; j < PC_CHUNK && round < DISPU_POISSON_MAX_ROUNDS; ++j, ++round) {
             if (round == 0)
-                hipLaunchKernelGGL(pc_round_kernel<true>, dim3(pc_blocks(N)), dim3(kRsThreads), 0, st, N, C, round, spt, cid, crec, segr, state,
+                hipLaunchKernelGGL(pc_round_kernel<true>, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, N, C, round, spt, cid, crec, segr, state,
                                    (const uint32_t*)nullptr, list[1], cnt);
             else
-                hipLaunchKernelGGL(pc_round_kernel<false>, dim3(pc_blocks(active)), dim3(kRsThreads), 0, st, N, C, round, spt, cid, crec, segr,
+                hipLaunchKernelGGL(pc_round_kernel<false>, dim3(rs_blocks(active)), dim3(kRsThreads), 0, st, N, C, round, spt, cid, crec, segr,
                                    state, (const uint32_t*)list[round & 1], list[(round + 1) & 1], cnt);
         }
         DISPU_CHECK_LAUNCH();
@@ -445,9 +429,9 @@ static int pc_eval(const PcRun& R, int* status) {
         if (active > N) active = N;
     }
     if (active)
-        hipLaunchKernelGGL(pc_cap_kernel, dim3(pc_blocks(active)), dim3(kRsThreads), 0, st, N, C, (const uint32_t*)(cnt + round),
+        hipLaunchKernelGGL(pc_cap_kernel, dim3(rs_blocks(active)), dim3(kRsThreads), 0, st, N, C, (const uint32_t*)(cnt + round),
                            (const uint32_t*)list[round & 1], cid, crec, status);
-    hipLaunchKernelGGL(pc_count_kernel, dim3(pc_blocks(N)), dim3(kRsThreads), 0, st, N, C, cid, crec, (const uint8_t*)state, segc);
+    hipLaunchKernelGGL(pc_count_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, N, C, cid, crec, (const uint8_t*)state, segc);
     return (int)hipGetLastError();
 }
 
@@ -459,8 +443,8 @@ static bool pc_args(int C, const int* off, const int* off_host, const void* scra
     R->C = C;
     R->st = (hipStream_t)stream;
     R->base = (char*)const_cast<void*>(scratch);
-    R->s = pc_scratch((size_t)N, (size_t)C);
-    return scratch && !(((uintptr_t)scratch) & 15) && scratch_bytes >= R->s.total;
+    R->s = pc_scratch((size_t)N, (size_t)C, R->base);
+    return scratch_ok(scratch, scratch_bytes, R->s.total);
 }
 
 }  // namespace dispu
@@ -480,15 +464,15 @@ DISPU_EXPORT int dispu_poisson_cells_keep(int C, const int* off, const int* off_
         return (int)hipErrorInvalidValue;
     int rc = pc_prepare(R, off, points, radius, status);
     if (rc) return rc;
-    hipLaunchKernelGGL(pc_bisect_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, R.st, C, -1, 0, (const int*)nullptr, radius, R.at<float>(R.s.segr),
+    hipLaunchKernelGGL(pc_bisect_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, R.st, C, -1, 0, (const int*)nullptr, radius, R.at<float>(R.s.segr),
                        (const uint32_t*)R.at<uint32_t>(R.s.segc), (const uint32_t*)R.at<uint32_t>(R.s.cnt), rounds);
     rc = pc_eval(R, status);
     if (rc) return rc;
-    hipLaunchKernelGGL(pc_bisect_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, R.st, C, 0, 0, (const int*)nullptr, radius, R.at<float>(R.s.segr),
+    hipLaunchKernelGGL(pc_bisect_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, R.st, C, 0, 0, (const int*)nullptr, radius, R.at<float>(R.s.segr),
                        (const uint32_t*)R.at<uint32_t>(R.s.segc), (const uint32_t*)R.at<uint32_t>(R.s.cnt), rounds);
-    hipLaunchKernelGGL(pc_flags_kernel, dim3(pc_blocks(R.N)), dim3(kRsThreads), 0, R.st, R.N, (const float4*)R.at<float4>(R.s.spt),
+    hipLaunchKernelGGL(pc_flags_kernel, dim3(rs_blocks(R.N)), dim3(kRsThreads), 0, R.st, R.N, (const float4*)R.at<float4>(R.s.spt),
                        (const uint8_t*)R.at<uint8_t>(R.s.state), keep, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(pc_finish_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, R.st, C, (const int*)nullptr,
+    hipLaunchKernelGGL(pc_finish_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, R.st, C, (const int*)nullptr,
                        (const uint32_t*)R.at<uint32_t>(R.s.segb), (const float*)R.at<float>(R.s.segr), (const uint32_t*)R.at<uint32_t>(R.s.segc),
                        count, (float*)nullptr, status);
     return (int)hipGetLastError();
@@ -510,21 +494,21 @@ DISPU_EXPORT int dispu_poisson_cells_select(int C, const int* off, const int* mo
     if (rc) return rc;
     float* segr = R.at<float>(R.s.segr);
     const uint32_t *segc = R.at<uint32_t>(R.s.segc), *cnt = R.at<uint32_t>(R.s.cnt);
-    hipLaunchKernelGGL(pc_bisect_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, R.st, C, -1, steps, moff, r_hi, segr, segc, cnt, rounds);
+    hipLaunchKernelGGL(pc_bisect_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, R.st, C, -1, steps, moff, r_hi, segr, segc, cnt, rounds);
     for (int k = 0; k <= steps; ++k) {               // the last pass evaluates the set at lo itself
         rc = pc_eval(R, status);
         if (rc) return rc;
-        hipLaunchKernelGGL(pc_bisect_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, R.st, C, k, steps, moff, r_hi, segr, segc, cnt, rounds);
+        hipLaunchKernelGGL(pc_bisect_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, R.st, C, k, steps, moff, r_hi, segr, segc, cnt, rounds);
     }
     unsigned char* flag = R.at<unsigned char>(R.s.flag);
     uint32_t* words = R.at<uint32_t>(R.s.words);
-    hipLaunchKernelGGL(pc_flags_kernel, dim3(pc_blocks(R.N)), dim3(kRsThreads), 0, R.st, R.N, (const float4*)R.at<float4>(R.s.spt),
+    hipLaunchKernelGGL(pc_flags_kernel, dim3(rs_blocks(R.N)), dim3(kRsThreads), 0, R.st, R.N, (const float4*)R.at<float4>(R.s.spt),
                        (const uint8_t*)R.at<uint8_t>(R.s.state), flag, words);
-    rc = exclusive_scan_u32(words, R.N, R.at<uint32_t>(R.s.sums), nullptr, R.st);
+    rc = exclusive_scan_u32(words, R.N, R.s.sort.sums, nullptr, R.st);
     if (rc) return rc;
-    hipLaunchKernelGGL(pc_emit_kernel, dim3(pc_blocks(R.N)), dim3(kRsThreads), 0, R.st, R.N, C, (uint32_t)moff_host[C], off, moff, (const unsigned char*)flag,
+    hipLaunchKernelGGL(pc_emit_kernel, dim3(rs_blocks(R.N)), dim3(kRsThreads), 0, R.st, R.N, C, (uint32_t)moff_host[C], off, moff, (const unsigned char*)flag,
                        (const uint32_t*)words, idx);
-    hipLaunchKernelGGL(pc_finish_kernel, dim3(pc_blocks(C)), dim3(kRsThreads), 0, R.st, C, moff, (const uint32_t*)R.at<uint32_t>(R.s.segb),
+    hipLaunchKernelGGL(pc_finish_kernel, dim3(rs_blocks(C)), dim3(kRsThreads), 0, R.st, C, moff, (const uint32_t*)R.at<uint32_t>(R.s.segb),
                        (const float*)segr, segc, count_out, r_out, status);
     return (int)hipGetLastError();
 }

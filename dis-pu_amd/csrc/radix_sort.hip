@@ -1,6 +1,8 @@
-// Device-wide stable LSD radix sort of (uint64 key, uint32 value) pairs and the three-step exclusive scan it is built on: behind
-// dispu_radix_sort_pairs (include/dispu_hip.h), and through internal.h under grid_subsample.hip (voxel keys, label keys, run heads)
-// and morton_cells.hip (Morton keys).  Stable: equal keys keep their input order, which is what both clients' determinism rests on.
+// Device-wide stable LSD radix sort of (uint64 key, uint32 value) pairs, the three-step exclusive scan it is built on, and the run
+// numbering that follows a sort: behind dispu_radix_sort_pairs (include/dispu_hip.h), and through internal.h (RadixSorter,
+// exclusive_scan_u32, run_heads_scan) under grid_subsample.hip (voxel keys, label keys), poisson_disk_cells.hip (cell keys) and
+// reconstruct.hip (lattice keys); morton_cells.hip (Morton keys) calls the exported entry.  Stable: equal keys keep their input order,
+// which is what every client's determinism rests on.
 //
 //   8 bits per pass, ceil(bits / 8) passes, ping-pong buffers; per pass:
 //     histogram   256 bins per tile of kRsTile elements in LDS (integer LDS atomics: counts are order-free)
@@ -177,9 +179,11 @@ __global__ __launch_bounds__(kRsThreads) void radix_scatter_kernel(const uint64_
 }
 
 static inline unsigned rs_tiles(size_t n) { return (unsigned)((n + kRsTile - 1) / kRsTile); }
-size_t rs_table_words(size_t n) { return (size_t)256 * rs_tiles(n); }
+static size_t rs_table_words(size_t n) { return (size_t)256 * rs_tiles(n); }       // the digit-major histogram table of n pairs
 
-int radix_passes(size_t n, int passes, const uint64_t* src_k, const uint32_t* src_v, uint64_t* xk, uint32_t* xv, uint64_t* yk,
+// `passes` stable 8-bit passes from (src_k, src_v), which is only read, alternating into (xk, xv), (yk, yv), (xk, xv), ...: the result
+// is in x when passes is odd and in y when it is even (passes >= 1)
+static int radix_passes(size_t n, int passes, const uint64_t* src_k, const uint32_t* src_v, uint64_t* xk, uint32_t* xv, uint64_t* yk,
                         uint32_t* yv, uint32_t* table, uint32_t* sums, hipStream_t st) {
     const unsigned tiles = rs_tiles(n);
     const uint64_t* ck = src_k;
@@ -197,18 +201,49 @@ int radix_passes(size_t n, int passes, const uint64_t* src_k, const uint32_t* sr
     return (int)hipGetLastError();
 }
 
-// scratch of the sorter alone: alternate keys, alternate payload, table, scan sums
+static void carve_table_sums(Carver& cv, size_t n, uint32_t*& table, uint32_t*& sums) {
+    table = cv.ptr<uint32_t>(4 * rs_table_words(n));
+    sums = cv.ptr<uint32_t>(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
+}
+
+void RadixSorter::carve(Carver& cv, size_t n) {
+    k[0] = cv.ptr<uint64_t>(8 * n);
+    k[1] = cv.ptr<uint64_t>(8 * n);
+    v[0] = cv.ptr<uint32_t>(4 * n);
+    v[1] = cv.ptr<uint32_t>(4 * n);
+    carve_table_sums(cv, n, table, sums);
+}
+
+int RadixSorter::sort(size_t n, int passes, hipStream_t st) {
+    side = passes & 1;                               // pass p reads side p & 1 and writes the other
+    return passes ? radix_passes(n, passes, k[0], v[0], k[1], v[1], k[0], v[0], table, sums, st) : 0;
+}
+
+// ---- run numbering ---------------------------------------------------------------------------------------------------------------------
+// keys == nullptr: all keys are equal
+__global__ __launch_bounds__(kRsThreads) void run_heads_kernel(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ head) {
+    const size_t j = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+    if (j < n) head[j] = (j == 0 || (keys && keys[j] != keys[j - 1])) ? 1u : 0u;
+}
+
+int run_heads_scan(const uint64_t* keys, size_t n, uint32_t* ex, uint32_t* sums, uint32_t* count, hipStream_t st) {
+    hipLaunchKernelGGL(run_heads_kernel, dim3(rs_blocks(n)), dim3(kRsThreads), 0, st, keys, n, ex);
+    return exclusive_scan_u32(ex, n, sums, count, st);
+}
+
+// scratch of the exported sorter: alternate keys, alternate payload, table, scan sums
 struct SortScratch {
-    size_t keys, vals, table, sums, total;
+    uint64_t* keys;
+    uint32_t *vals, *table, *sums;
+    size_t total;
 };
-static SortScratch sort_scratch(size_t n) {
+static SortScratch sort_scratch(size_t n, void* base = nullptr) {
     SortScratch s;
-    size_t o = 0;
-    s.keys = o;  o += align256(8 * n);
-    s.vals = o;  o += align256(4 * n);
-    s.table = o; o += align256(4 * rs_table_words(n));
-    s.sums = o;  o += align256(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
-    s.total = o;
+    Carver cv{(char*)base};
+    s.keys = cv.ptr<uint64_t>(8 * n);
+    s.vals = cv.ptr<uint32_t>(4 * n);
+    carve_table_sums(cv, n, s.table, s.sums);
+    s.total = cv.off;
     return s;
 }
 
@@ -235,14 +270,11 @@ DISPU_EXPORT int dispu_radix_sort_pairs(long long n, int bits, const unsigned lo
         DISPU_TRY(hipMemcpyAsync(vals_out, vals_in, 4 * N, hipMemcpyDeviceToDevice, st));
         return 0;
     }
-    const SortScratch s = sort_scratch(N);
-    if (!scratch || scratch_bytes < s.total || ((uintptr_t)scratch & 15)) return (int)hipErrorInvalidValue;
-    char* base = (char*)scratch;
-    uint64_t* ak = (uint64_t*)(base + s.keys);
-    uint32_t* av = (uint32_t*)(base + s.vals);
+    const SortScratch s = sort_scratch(N, scratch);
+    if (!scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     uint64_t* ok = (uint64_t*)keys_out;
     uint32_t* ov = (uint32_t*)vals_out;
     const bool odd = passes & 1;                     // the result lands in x for an odd pass count, in y for an even one
-    return radix_passes(N, passes, (const uint64_t*)keys_in, (const uint32_t*)vals_in, odd ? ok : ak, odd ? ov : av, odd ? ak : ok,
-                        odd ? av : ov, (uint32_t*)(base + s.table), (uint32_t*)(base + s.sums), st);
+    return radix_passes(N, passes, (const uint64_t*)keys_in, (const uint32_t*)vals_in, odd ? ok : s.keys, odd ? ov : s.vals,
+                        odd ? s.keys : ok, odd ? s.vals : ov, s.table, s.sums, st);
 }

@@ -39,29 +39,21 @@ __constant__ uint8_t kTetCase[6][16][7] = {
     {{0,0,0,0,0,0,0}, {1,4,5,7,0,0,0}, {1,4,35,33,0,0,0}, {2,5,7,35,5,35,33}, {1,5,33,42,0,0,0}, {2,4,42,7,4,33,42}, {2,4,35,42,4,42,5}, {1,7,35,42,0,0,0}, {1,7,42,35,0,0,0}, {2,4,5,42,4,42,35}, {2,4,42,33,4,7,42}, {1,5,42,33,0,0,0}, {2,5,33,35,5,35,7}, {1,4,33,35,0,0,0}, {1,4,7,5,0,0,0}, {0,0,0,0,0,0,0}},
     {{0,0,0,0,0,0,0}, {1,4,7,6,0,0,0}, {1,4,34,35,0,0,0}, {2,6,35,7,6,34,35}, {1,6,49,34,0,0,0}, {2,4,7,49,4,49,34}, {2,4,49,35,4,6,49}, {1,7,49,35,0,0,0}, {1,7,35,49,0,0,0}, {2,4,49,6,4,35,49}, {2,4,34,49,4,49,7}, {1,6,34,49,0,0,0}, {2,6,35,34,6,7,35}, {1,4,35,34,0,0,0}, {1,4,6,7,0,0,0}, {0,0,0,0,0,0,0}}};
 
-static inline unsigned rc_blocks(size_t work) { return (unsigned)((work + kRsThreads - 1) / kRsThreads); }
-
 // ---- the sorted unique set of a key buffer -----------------------------------------------------------------------------------------------
+// the entry writes its n keys to sort.k[0]
 struct UniqScratch {
-    size_t kB, vA, vB, head, table, sums, small, total;
+    RadixSorter sort;
+    uint32_t *head, *small;                          // small: the count; 16 words in, two flag words of the entry that owns the scratch
+    size_t total;
 };
-static UniqScratch uniq_scratch(size_t n) {
+static UniqScratch uniq_scratch(size_t n, void* base = nullptr) {
     UniqScratch s;
-    size_t o = 0;
-    s.kB = o;    o += align256(8 * n);
-    s.vA = o;    o += align256(4 * n);
-    s.vB = o;    o += align256(4 * n);
-    s.head = o;  o += align256(4 * n);
-    s.table = o; o += align256(4 * rs_table_words(n));
-    s.sums = o;  o += align256(4 * scan_blocks(rs_table_words(n) > n ? rs_table_words(n) : n));
-    s.small = o; o += 256;                           // the count; two flag words of the entry that owns the scratch
-    s.total = o;
+    Carver cv{(char*)base};
+    s.sort.carve(cv, n);
+    s.head = cv.ptr<uint32_t>(4 * n);
+    s.small = cv.ptr<uint32_t>(256);
+    s.total = cv.off;
     return s;
-}
-
-__global__ __launch_bounds__(kRsThreads) void recon_heads_kernel(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ head) {
-    const size_t j = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
-    if (j < n) head[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1u : 0u;
 }
 
 // ex: the exclusive scan of the heads; a head's key goes to its number (below n: at most n heads)
@@ -72,20 +64,16 @@ __global__ __launch_bounds__(kRsThreads) void recon_compact_kernel(const uint64_
     if ((j == 0 || keys[j] != keys[j - 1]) && ex[j] < n) out[ex[j]] = keys[j];
 }
 
-// keys [n] (overwritten) -> out [<= n] sorted unique, the count -> *count_host (the stream is synchronised).  base: uniq_scratch(n)
-static int sorted_unique(uint64_t* keys, size_t n, uint64_t* out, char* base, const UniqScratch& s, uint32_t* count_host, hipStream_t st) {
-    uint64_t* kB = (uint64_t*)(base + s.kB);
-    uint32_t *vA = (uint32_t*)(base + s.vA), *vB = (uint32_t*)(base + s.vB), *head = (uint32_t*)(base + s.head);
-    uint32_t *table = (uint32_t*)(base + s.table), *sums = (uint32_t*)(base + s.sums), *d_count = (uint32_t*)(base + s.small);
-    DISPU_TRY(hipMemsetAsync(vA, 0, 4 * n, st));     // the sorter carries values along; nobody reads them here
-    int rc = radix_passes(n, kLatPasses, keys, vA, kB, vB, keys, vA, table, sums, st);      // an even pass count: the result is in `keys`
+// s.sort.k[0] [n] (overwritten) -> out [<= n] sorted unique, the count -> *count_host (the stream is synchronised)
+static int sorted_unique(UniqScratch& s, size_t n, uint64_t* out, uint32_t* count_host, hipStream_t st) {
+    DISPU_TRY(hipMemsetAsync(s.sort.v[0], 0, 4 * n, st));      // the sorter carries values along; nobody reads them here
+    int rc = s.sort.sort(n, kLatPasses, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(recon_heads_kernel, dim3(rc_blocks(n)), dim3(kRsThreads), 0, st, (const uint64_t*)keys, n, head);
-    rc = exclusive_scan_u32(head, n, sums, d_count, st);
+    rc = run_heads_scan(s.sort.keys(), n, s.head, s.sort.sums, s.small, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(recon_compact_kernel, dim3(rc_blocks(n)), dim3(kRsThreads), 0, st, (const uint64_t*)keys, n, (const uint32_t*)head, out);
+    hipLaunchKernelGGL(recon_compact_kernel, dim3(rs_blocks(n)), dim3(kRsThreads), 0, st, s.sort.keys(), n, (const uint32_t*)s.head, out);
     DISPU_CHECK_LAUNCH();
-    DISPU_TRY(hipMemcpyAsync(count_host, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DISPU_TRY(hipMemcpyAsync(count_host, s.small, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DISPU_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -245,19 +233,6 @@ __global__ __launch_bounds__(kRsThreads) void recon_faces_kernel(const int* __re
     }
 }
 
-// ---- scratch layouts: a key buffer in front of the unique stage's own ------------------------------------------------------------------------
-struct KeyedScratch {
-    size_t keys, uniq, total;
-    UniqScratch u;
-};
-static KeyedScratch keyed_scratch(size_t nkeys) {
-    KeyedScratch s;
-    s.keys = 0;
-    s.uniq = align256(8 * nkeys);
-    s.u = uniq_scratch(nkeys);
-    s.total = s.uniq + s.u.total;
-    return s;
-}
 constexpr long long kReconMaxKeys = (1ll << 31) - 1;
 
 static long long dilate_keys(long long nocc, int band) {
@@ -267,19 +242,16 @@ static long long dilate_keys(long long nocc, int band) {
 }
 
 struct ContourScratch {
-    size_t sums, small, total;
+    uint32_t *sums, *tot;
+    size_t total;
 };
-static ContourScratch contour_scratch(size_t nvox, size_t nlat) {
+static ContourScratch contour_scratch(size_t nvox, size_t nlat, void* base = nullptr) {
     ContourScratch s;
-    const size_t L = 7 * nlat > nvox ? 7 * nlat : nvox;
-    s.sums = 0;
-    s.small = align256(4 * scan_blocks(L));
-    s.total = s.small + 256;
+    Carver cv{(char*)base};
+    s.sums = cv.ptr<uint32_t>(4 * scan_blocks(7 * nlat > nvox ? 7 * nlat : nvox));
+    s.tot = cv.ptr<uint32_t>(256);
+    s.total = cv.off;
     return s;
-}
-
-static bool recon_bad_scratch(const void* scratch, size_t have, size_t need) {
-    return !need || !scratch || have < need || ((uintptr_t)scratch & 15);
 }
 
 }  // namespace dispu
@@ -287,7 +259,7 @@ static bool recon_bad_scratch(const void* scratch, size_t have, size_t need) {
 using namespace dispu;
 
 DISPU_EXPORT size_t dispu_lattice_voxels_scratch_bytes(long long n) {
-    return (n <= 0 || n > (1ll << 24)) ? 0 : keyed_scratch((size_t)n).total;
+    return (n <= 0 || n > (1ll << 24)) ? 0 : uniq_scratch((size_t)n).total;
 }
 
 DISPU_EXPORT int dispu_lattice_voxels(long long n, const float* points, float voxel, int band, unsigned long long* occ_out, int* count_host,
@@ -295,24 +267,22 @@ DISPU_EXPORT int dispu_lattice_voxels(long long n, const float* points, float vo
     if (n <= 0 || n > (1ll << 24) || !points || !occ_out || !count_host || !status_host) return (int)hipErrorInvalidValue;
     if (!(voxel > 0.0f) || !(voxel <= FLT_MAX) || band < 1 || band > 3) return (int)hipErrorInvalidValue;
     const size_t N = (size_t)n;
-    const KeyedScratch s = keyed_scratch(N);
-    if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
+    UniqScratch s = uniq_scratch(N, scratch);
+    if (!s.total || !scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     if (ranges_overlap(occ_out, 8 * N, points, 12 * N)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)scratch;
-    uint64_t* keys = (uint64_t*)(base + s.keys);
-    uint32_t* flags = (uint32_t*)(base + s.uniq + s.u.small + 64);
+    uint32_t* flags = s.small + 16;
     *count_host = 0;
     *status_host = 0;
     DISPU_TRY(hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(recon_point_keys_kernel, dim3(rc_blocks(N)), dim3(kRsThreads), 0, st, points, N, voxel, (float)(kLatBias - band), keys, flags);
+    hipLaunchKernelGGL(recon_point_keys_kernel, dim3(rs_blocks(N)), dim3(kRsThreads), 0, st, points, N, voxel, (float)(kLatBias - band), s.sort.k[0], flags);
     DISPU_CHECK_LAUNCH();
     uint32_t hf[2] = {0, 0};
     DISPU_TRY(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, st));
     DISPU_TRY(hipStreamSynchronize(st));
     if (hf[0] || hf[1]) { *status_host = hf[0] ? DISPU_LATTICE_NONFINITE : DISPU_LATTICE_RANGE; return 0; }
     uint32_t cnt = 0;
-    const int rc = sorted_unique(keys, N, (uint64_t*)occ_out, base + s.uniq, s.u, &cnt, st);
+    const int rc = sorted_unique(s, N, (uint64_t*)occ_out, &cnt, st);
     if (rc) return rc;
     *count_host = (int)cnt;
     return 0;
@@ -320,7 +290,7 @@ DISPU_EXPORT int dispu_lattice_voxels(long long n, const float* points, float vo
 
 DISPU_EXPORT size_t dispu_lattice_dilate_scratch_bytes(long long nocc, int band) {
     const long long nk = dilate_keys(nocc, band);
-    return nk ? keyed_scratch((size_t)nk).total : 0;
+    return nk ? uniq_scratch((size_t)nk).total : 0;
 }
 
 DISPU_EXPORT int dispu_lattice_dilate(long long nocc, const unsigned long long* occ, int band, unsigned long long* act_out,
@@ -328,43 +298,39 @@ DISPU_EXPORT int dispu_lattice_dilate(long long nocc, const unsigned long long* 
     const long long nk = dilate_keys(nocc, band);
     if (!nk || !occ || !act_out || !count_host) return (int)hipErrorInvalidValue;
     const size_t NK = (size_t)nk;
-    const KeyedScratch s = keyed_scratch(NK);
-    if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
+    UniqScratch s = uniq_scratch(NK, scratch);
+    if (!s.total || !scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     if (ranges_overlap(act_out, 8 * NK, occ, 8 * (size_t)nocc)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)scratch;
-    uint64_t* keys = (uint64_t*)(base + s.keys);
     *count_host = 0;
-    hipLaunchKernelGGL(recon_dilate_keys_kernel, dim3(rc_blocks(NK)), dim3(kRsThreads), 0, st, (const uint64_t*)occ, (size_t)nocc, band, keys);
+    hipLaunchKernelGGL(recon_dilate_keys_kernel, dim3(rs_blocks(NK)), dim3(kRsThreads), 0, st, (const uint64_t*)occ, (size_t)nocc, band, s.sort.k[0]);
     uint32_t cnt = 0;
-    const int rc = sorted_unique(keys, NK, (uint64_t*)act_out, base + s.uniq, s.u, &cnt, st);
+    const int rc = sorted_unique(s, NK, (uint64_t*)act_out, &cnt, st);
     if (rc) return rc;
     *count_host = (long long)cnt;
     return 0;
 }
 
 DISPU_EXPORT size_t dispu_lattice_corners_scratch_bytes(long long nvox) {
-    return (nvox <= 0 || nvox * 8 > kReconMaxKeys) ? 0 : keyed_scratch((size_t)nvox * 8).total;
+    return (nvox <= 0 || nvox * 8 > kReconMaxKeys) ? 0 : uniq_scratch((size_t)nvox * 8).total;
 }
 
 DISPU_EXPORT int dispu_lattice_corners(long long nvox, const unsigned long long* act, unsigned long long* lat_out, int* corner_out,
                                        long long* count_host, void* scratch, size_t scratch_bytes, void* stream) {
     if (nvox <= 0 || nvox * 8 > kReconMaxKeys || !act || !lat_out || !corner_out || !count_host) return (int)hipErrorInvalidValue;
     const size_t NK = (size_t)nvox * 8;
-    const KeyedScratch s = keyed_scratch(NK);
-    if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
+    UniqScratch s = uniq_scratch(NK, scratch);
+    if (!s.total || !scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     if (ranges_overlap(lat_out, 8 * NK, act, 8 * (size_t)nvox) || ranges_overlap(corner_out, 4 * NK, act, 8 * (size_t)nvox) ||
         ranges_overlap(lat_out, 8 * NK, corner_out, 4 * NK))
         return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)scratch;
-    uint64_t* keys = (uint64_t*)(base + s.keys);
     *count_host = 0;
-    hipLaunchKernelGGL(recon_corner_keys_kernel, dim3(rc_blocks(NK)), dim3(kRsThreads), 0, st, (const uint64_t*)act, (size_t)nvox, keys);
+    hipLaunchKernelGGL(recon_corner_keys_kernel, dim3(rs_blocks(NK)), dim3(kRsThreads), 0, st, (const uint64_t*)act, (size_t)nvox, s.sort.k[0]);
     uint32_t cnt = 0;
-    const int rc = sorted_unique(keys, NK, (uint64_t*)lat_out, base + s.uniq, s.u, &cnt, st);
+    const int rc = sorted_unique(s, NK, (uint64_t*)lat_out, &cnt, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(recon_corner_table_kernel, dim3(rc_blocks(NK)), dim3(kRsThreads), 0, st, (const uint64_t*)act, (size_t)nvox,
+    hipLaunchKernelGGL(recon_corner_table_kernel, dim3(rs_blocks(NK)), dim3(kRsThreads), 0, st, (const uint64_t*)act, (size_t)nvox,
                        (const uint64_t*)lat_out, cnt, corner_out);
     DISPU_CHECK_LAUNCH();
     *count_host = (long long)cnt;
@@ -374,7 +340,7 @@ DISPU_EXPORT int dispu_lattice_corners(long long nvox, const unsigned long long*
 DISPU_EXPORT int dispu_lattice_positions(long long nlat, const unsigned long long* lat, float voxel, float* pos_out, void* stream) {
     if (nlat <= 0 || nlat > (1ll << 24) || !lat || !pos_out || !(voxel > 0.0f) || !(voxel <= FLT_MAX)) return (int)hipErrorInvalidValue;
     if (ranges_overlap(pos_out, 12 * (size_t)nlat, lat, 8 * (size_t)nlat)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(recon_positions_kernel, dim3(rc_blocks((size_t)nlat)), dim3(kRsThreads), 0, (hipStream_t)stream, (const uint64_t*)lat,
+    hipLaunchKernelGGL(recon_positions_kernel, dim3(rs_blocks((size_t)nlat)), dim3(kRsThreads), 0, (hipStream_t)stream, (const uint64_t*)lat,
                        (size_t)nlat, voxel, pos_out);
     return (int)hipGetLastError();
 }
@@ -390,27 +356,25 @@ DISPU_EXPORT int dispu_contour_count(long long nvox, long long nlat, const int* 
     if (nvox <= 0 || nvox * 8 > kReconMaxKeys || nlat <= 0 || nlat > (1ll << 24)) return (int)hipErrorInvalidValue;
     if (!corner || !values || !slot_number || !tri_start || !nverts_host || !nfaces_host) return (int)hipErrorInvalidValue;
     const size_t NV = (size_t)nvox, NL = (size_t)nlat;
-    const ContourScratch s = contour_scratch(NV, NL);
-    if (recon_bad_scratch(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
+    const ContourScratch s = contour_scratch(NV, NL, scratch);
+    if (!s.total || !scratch_ok(scratch, scratch_bytes, s.total)) return (int)hipErrorInvalidValue;
     const void* ins[2] = {corner, values};
     const size_t inb[2] = {32 * NV, 4 * NL};
     for (int i = 0; i < 2; ++i)
         if (ranges_overlap(slot_number, 28 * NL, ins[i], inb[i]) || ranges_overlap(tri_start, 4 * NV, ins[i], inb[i])) return (int)hipErrorInvalidValue;
     if (ranges_overlap(slot_number, 28 * NL, tri_start, 4 * NV)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)scratch;
-    uint32_t *sums = (uint32_t*)(base + s.sums), *d_tot = (uint32_t*)(base + s.small);
     *nverts_host = 0;
     *nfaces_host = 0;
     DISPU_TRY(hipMemsetAsync(slot_number, 0, 28 * NL, st));
-    hipLaunchKernelGGL(recon_count_kernel, dim3(rc_blocks(NV)), dim3(kRsThreads), 0, st, corner, values, NV, (uint32_t)NL, (uint32_t*)slot_number,
+    hipLaunchKernelGGL(recon_count_kernel, dim3(rs_blocks(NV)), dim3(kRsThreads), 0, st, corner, values, NV, (uint32_t)NL, (uint32_t*)slot_number,
                        (uint32_t*)tri_start);
     DISPU_CHECK_LAUNCH();
-    int rc = exclusive_scan_u32((uint32_t*)slot_number, 7 * NL, sums, d_tot, st);
-    if (rc == 0) rc = exclusive_scan_u32((uint32_t*)tri_start, NV, sums, d_tot + 1, st);
+    int rc = exclusive_scan_u32((uint32_t*)slot_number, 7 * NL, s.sums, s.tot, st);
+    if (rc == 0) rc = exclusive_scan_u32((uint32_t*)tri_start, NV, s.sums, s.tot + 1, st);
     if (rc) return rc;
     uint32_t tot[2] = {0, 0};
-    DISPU_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    DISPU_TRY(hipMemcpyAsync(tot, s.tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     DISPU_TRY(hipStreamSynchronize(st));
     *nverts_host = (long long)tot[0];
     *nfaces_host = (long long)tot[1];
@@ -430,9 +394,9 @@ DISPU_EXPORT int dispu_contour_emit(long long nvox, long long nlat, float voxel,
         if (ranges_overlap(verts_out, vb, ins[i], inb[i]) || ranges_overlap(faces_out, fb, ins[i], inb[i])) return (int)hipErrorInvalidValue;
     if (ranges_overlap(verts_out, vb, faces_out, fb)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(recon_vertices_kernel, dim3(rc_blocks(7 * NL)), dim3(kRsThreads), 0, st, (const uint64_t*)lat, (uint32_t)NL, values, voxel,
+    hipLaunchKernelGGL(recon_vertices_kernel, dim3(rs_blocks(7 * NL)), dim3(kRsThreads), 0, st, (const uint64_t*)lat, (uint32_t)NL, values, voxel,
                        (const uint32_t*)slot_number, (uint32_t)nverts, verts_out);
-    hipLaunchKernelGGL(recon_faces_kernel, dim3(rc_blocks(NV)), dim3(kRsThreads), 0, st, corner, values, NV, (uint32_t)NL, (const uint32_t*)slot_number,
+    hipLaunchKernelGGL(recon_faces_kernel, dim3(rs_blocks(NV)), dim3(kRsThreads), 0, st, corner, values, NV, (uint32_t)NL, (const uint32_t*)slot_number,
                        (const uint32_t*)tri_start, (uint32_t)nfaces, faces_out);
     return (int)hipGetLastError();
 }

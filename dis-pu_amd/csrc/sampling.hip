@@ -440,7 +440,7 @@ DISPU_EXPORT int dispu_fps_segments_auto(int C, const int* off, const int* moff,
     const size_t a = (nmax[1] || nmax[2]) ? align256((size_t)off_host[C] * sizeof(float)) : 0;
     const size_t b = nmax[3] ? fps_cells_scratch(C, off_host, moff_host, 0, kCellsAuto) : 0;
     if (nmax[3] && (!b || !status)) return (int)hipErrorInvalidValue;
-    if ((a || b) && (!temp || temp_bytes < a + b || ((uintptr_t)temp & 15))) return (int)hipErrorInvalidValue;
+    if ((a || b) && !scratch_ok(temp, temp_bytes, a + b)) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     if (status) DISPU_TRY(hipMemsetAsync(status, 0, sizeof(int) * (size_t)C, s));
     return fps_segments_run(C, off, moff, off_host, moff_host, inp, temp, nmax, true, (char*)temp + a, b, status, out, arith, s);

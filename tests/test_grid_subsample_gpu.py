@@ -97,6 +97,48 @@ def test_compute_matches_the_oracle_bit_for_bit(dev, n, grid, fdim, ldim):
         assert same_bits(out[-1], oc[:, :ldim]), "classes"
 
 
+def edge_cloud(n, pattern):
+    """unit cells, one point per sorted position j (shuffled on input): "one_cell" puts all of them into one cell (no sorting pass, the
+    run heads come from the null-keys branch), "own_cell" each into its own (n runs of one), "straddle" gives the positions within 5 of
+    a multiple of the sorter's tile one cell per multiple, so that a run starts in one tile and ends in the next (below TILE + 1 points:
+    a run of several points at either end of the array)"""
+    rng = np.random.default_rng(n * 3 + len(pattern))
+    j = np.arange(n)
+    if pattern == "one_cell":
+        cell = np.zeros((n, 3), np.int64)
+    elif pattern == "own_cell":
+        cell = np.stack([j % 17, (j // 17) % 17, j // 289], axis=1)
+    else:
+        r = j % TILE
+        x = np.where(r >= TILE - 5, (j // TILE + 1) * TILE, np.where(r < 5, j - r, j))
+        cell = np.stack([x, 0 * x, 0 * x], axis=1)
+    p = (cell + 0.5 + (rng.random((n, 3)) - 0.5) * 0.5).astype(f32)                # inside the cell, away from its faces
+    order = rng.permutation(n)
+    f = (rng.standard_normal((n, 2)) * np.array([1, 1e3], f32)).astype(f32)
+    c = LABELS[rng.integers(0, 5, (n, 1))]
+    return np.ascontiguousarray(p[order]), f, c, f32(1.0)
+
+
+@pytest.mark.parametrize("pattern", ("one_cell", "own_cell", "straddle"))
+@pytest.mark.parametrize("n", (1, TILE - 1, TILE, TILE + 1, 2 * TILE + 1))
+def test_run_numbering_at_its_edges(dev, n, pattern):
+    p, f, c, dl = edge_cloud(n, pattern)
+    ks = np.sort(O.keys(p, dl))
+    runs = 1 + int(np.count_nonzero(np.diff(ks)))
+    if pattern == "one_cell":
+        assert O.grid(p, dl)[1] == [1, 1, 1] and runs == 1
+    elif pattern == "own_cell":
+        assert runs == n
+    else:
+        assert all(ks[b - 1] == ks[b] and ks[b - 5] != ks[b - 6] for b in range(TILE, n, TILE))      # a run across every tile boundary
+        assert n < 5 or (ks[0] == ks[4] and ks[n - 1] == ks[n - 2])                                  # and runs of several points at both ends
+    op, of, oc = O.compute(p, f, c, dl)
+    assert len(op) == runs
+    pts, feats, cls = compute(p, f, c, sampleDl=dl)
+    assert same_bits(pts, op), "points (or the row order)"
+    assert same_bits(feats, of) and same_bits(cls, oc)
+
+
 def test_one_dimensional_classes_and_empty_feature_columns(dev):
     p, f, c, dl, op, of, oc = case(TILE + 1, "dense")
     pts, feats, cls = compute(p, features=f[:, :0], classes=np.ascontiguousarray(c[:, 0]), sampleDl=dl)
