@@ -59,6 +59,9 @@ SIGNATURES = {
     "dispu_transfer_attributes_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_mls_project_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_mls_project_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_icp_scratch_bytes": (_sz, [_i, _vp, _vp]),
+    "dispu_icp_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_double] + [_vp] * 13 + [_sz, _vp]),
+    "dispu_rigid_apply_segments": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dispu_signed_distance_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_signed_distance_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_lattice_voxels_scratch_bytes": (_sz, [C.c_longlong]),

@@ -1,4 +1,4 @@
-// The host side of an entry that searches one packed batch from another (attributes.hip, mls_project.hip, signed_distance.hip): the two
+// The host side of an entry that searches one packed batch from another (attributes.hip, mls_project.hip, signed_distance.hip, icp.hip): the two
 // Morton-cell pre-passes, their regions at the front of the caller's scratch -- references first, then queries, then whatever the
 // operator adds behind -- and the launch grid.  The device side is knn_cross_prologue.h.  Host only: nothing of it is a kernel argument.
 #pragma once

@@ -1,4 +1,5 @@
-// The prologue of a kernel that searches ANOTHER cloud's Morton cells (knn_cross_kernel, mls_project_kernel, signed_distance_kernel):
+// The prologue of a kernel that searches ANOTHER cloud's Morton cells (knn_cross_kernel, mls_project_kernel, signed_distance_kernel,
+// icp_accumulate_kernel):
 // which pair of segments, which query cell, which query, and the reference cell the search starts at.  Included as TEXT at the top of the
 // kernel body, like knn_cells_prologue.h and for its reason.
 //

@@ -1176,6 +1176,60 @@ int dispu_signed_distance_segments(int C, const int* qoff, const int* qoff_host,
                                    const float* queries, const float* refs, const float* normals, float* out, int* status, void* scratch,
                                    size_t scratch_bytes, void* stream);
 
+/* ---- rigid registration (ICP) of one cloud onto another: csrc/icp.hip, dis-pu_amd/registration.py.  Brings several scans of one object
+ * into one frame.  The reference has no counterpart.  Batches, offsets, status and scratch as for dispu_mls_project_segments: pair c is
+ * a SOURCE segment (the queries, q_c points) and a TARGET segment (the references, m_c points); plane mode (mode 1) also takes unit
+ * target normals packed like the references (used as given, the caller's duty to keep finite; their sign cancels).  The entry
+ * estimates per pair a rigid motion T, [C, 4, 4] double, row-major, last row 0 0 0 1, that maps source coordinates into the target's
+ * frame.  Every operation below is one IEEE operation in the order written (the build and the kernels pin fp contract off).
+ *  apply      cur[i].x = (float)(((T00*x + T01*y) + T02*z) + T03), likewise y and z with rows 1 and 2, in double from the ORIGINAL
+ *             fp32 source point and the current T: never chained from rounded positions, so `aligned` can be recomputed from the
+ *             returned T bit for bit.  dispu_rigid_apply_segments is this step alone (out may be points itself).
+ *  match      the nearest target point of cur[i] under the project's rule: the smallest (fp32 d2 bits, local index), exactly rank 0
+ *             of dispu_knn_cross_segments.  The point is an INLIER iff d2 <= max_d2 (both fp32; +inf: no rejection).
+ *  equations  in double, about the origin o = the pair's first target point (row 0 of the target segment):  p = cur[i] - o,
+ *             qv = y - o for the matched target point y, d = p - qv, n the normal of y.  Unknowns (w, t) of p -> p + w x p + t.
+ *             mode 0 (point to point), three residuals d:   Aww = [[py*py + pz*pz, -(px*py), -(px*pz)], [., px*px + pz*pz, -(py*pz)],
+ *               [., ., px*px + py*py]],  Awt = [[0, -pz, py], [pz, 0, -px], [-py, px, 0]],  Att = I,
+ *               b = (py*dz - pz*dy, pz*dx - px*dz, px*dy - py*dx, dx, dy, dz),  e = (dx*dx + dy*dy) + dz*dz.
+ *             mode 1 (point to plane), one residual r = (dx*nx + dy*ny) + dz*nz:  J = (py*nz - pz*ny, pz*nx - px*nz, px*ny - py*nx,
+ *               nx, ny, nz),  A_ij = J_i * J_j,  b_i = J_i * r,  e = r * r.
+ *             A point that is no inlier contributes zeros.  The 29 sums -- the 21 upper entries of A row by row, the 6 of b, e and
+ *             the inlier count -- are formed per query cell (64 consecutive points of the source's Morton order, one per lane) by
+ *             the butterfly v += v[lane ^ o], o = 32, 16, 8, 4, 2, 1, and per pair over the cells: cell j goes to slot j mod 32, every
+ *             slot is summed in ascending j, the slots are added in ascending order.  No float atomics.
+ *  solve      the pair is DEGENERATE when it has fewer than 3 (mode 0) or 6 (mode 1) inliers, when a pivot of the Cholesky
+ *             factorisation of A is <= 1e-12 * its diagonal entry of A or is not finite, or when the solution is not finite: it keeps
+ *             its T and freezes.  Otherwise (w, t) = -A^-1 b,  R = I + a [w]x + c [w]x^2 with th = |w|, a = sin th / th,
+ *             c = (1 - cos th) / th^2 (for th < 1e-12: a = 1 - th^2 / 6, c = 0.5 - th^2 / 24),  U(x) = R (x - o) + o + t,  T <- U o T:
+ *             the rotation R * T_R, the translation ((R * (T_t - o)) + o) + t.
+ *  converged  after its update, iff tolerance > 0, |w| <= tolerance and |t| <= tolerance * D, D the diagonal of the target segment's
+ *             bounding box in double from its fp32 bounds: the pair freezes.  A frozen pair costs the batch-wide source pre-pass and
+ *             the apply only; its waves leave the accumulation after the prologue.
+ *  loop       the target pre-pass once; `iterations` times: apply, source pre-pass on cur, accumulate, solve; then the evaluation of
+ *             the returned T: apply, pre-pass, accumulate (frozen pairs included), no solve.  iterations = 0 evaluates init.  Every
+ *             launch is enqueued up front: the entry neither synchronises nor copies to the host, and k iterations equal k calls of
+ *             one, each given the transform of the last as init, byte for byte (at tolerance 0).
+ * init [C, 16] double or NULL (identity).  Outputs per pair: transform [C, 16];  aligned [sum q_c, 3] = cur under the returned T (it
+ * must not overlap source or target);  inliers [C] int;  rmse [C] double = sqrt(e / inliers), 0 without inliers;  iters [C] int, the
+ * updates applied;  flag [C] int: 0 out of iterations, 1 converged, 2 degenerate;  corr [sum q_c] int32 or NULL: the matched target
+ * point's local index, -1 for a point that is no inlier.
+ * status [C] (device): 0, or 1 for a pair either side of which holds a NaN or an infinite coordinate (at any iteration: a transform
+ * that overflows fp32 counts); nothing else is written for such a pair.
+ * Refused (hipErrorInvalidValue, before any launch, nothing touched): C or offsets as for dispu_knn_cross_segments, a NULL pointer
+ * (corr, init and, in mode 0, target_normals may be NULL), mode outside {0, 1}, iterations outside 0 .. 128, max_d2 NaN or negative,
+ * tolerance NaN, negative or infinite, a scratch that is NULL, misaligned or shorter than dispu_icp_scratch_bytes (both pre-passes, cur,
+ * two status rows, the working T and state, one row of 32 doubles per source cell; 0 for an illegal C or offsets), aligned overlapping
+ * source or target.  Ordinary stores only, identical bytes from run to run.  The yardstick is tests/icp_oracle.py.  Additions only:
+ * dispu_version() stays 5. ---------------------------------------------------------------------------------------------------------- */
+size_t dispu_icp_scratch_bytes(int C, const int* qoff_host, const int* roff_host);
+int dispu_icp_segments(int C, const int* qoff, const int* qoff_host, const int* roff, const int* roff_host, int mode, int iterations,
+                       float max_d2, double tolerance, const float* source, const float* target, const float* target_normals,
+                       const double* init, double* transform, float* aligned, int* corr, int* inliers, double* rmse, int* iters,
+                       int* flag, int* status, void* scratch, size_t scratch_bytes, void* stream);
+int dispu_rigid_apply_segments(int C, const int* off, const int* off_host, const float* points, const double* transform, float* out,
+                               void* stream);
+
 /* ---- surface reconstruction, the lattice and the contouring: csrc/reconstruct.hip, dis-pu_amd/reconstruct.py:reconstruct_surface.
  * f = 0 of the signed distance above, contoured on a sparse lattice by marching tetrahedra, vertices welded, every order pinned: one
  * cloud per call, the output is unique.  The reference has no counterpart.  The entries are split where a count must reach the host to
