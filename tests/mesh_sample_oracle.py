@@ -110,6 +110,30 @@ def poisson_keep(points, r):
     return greedy_keep(p.shape[0], nbr, dd, r)
 
 
+def lattice_with_close_pairs(side, extra, seed=0):
+    """A cloud whose greedy answer follows from how it is built, at any size: the side^3 lattice of spacing 1 plus `extra` planted
+    points, each beside a lattice point of its own -- every other one an exact duplicate, the rest 0.3 away along +x, +y or +z (seeded)
+    -- all in seeded index order.  At a radius well inside (0.3, 0.7) the only conflicts are the `extra` isolated pairs (a planted
+    point is at least 0.7 from every point but its host), so the later index of each pair is rejected and everything else is kept.
+    -> (points f32 [side^3 + extra, 3], keep bool).  tests/test_second_trips.py confirms the rule against poisson_keep at about 5000
+    points."""
+    rs = np.random.RandomState(seed)
+    g = np.arange(side, dtype=np.float32)
+    lattice = np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3)
+    host = rs.permutation(side ** 3)[:extra]
+    shift = np.zeros((extra, 3), np.float32)
+    near = np.arange(extra) % 2 == 1
+    shift[np.nonzero(near)[0], rs.randint(0, 3, int(near.sum()))] = np.float32(0.3)
+    pts = np.concatenate([lattice, lattice[host] + shift]).astype(np.float32)
+    n = len(pts)
+    perm = rs.permutation(n)                                                        # position j holds point perm[j]
+    pos = np.empty(n, np.int64)
+    pos[perm] = np.arange(n)
+    keep = np.ones(n, bool)
+    keep[np.maximum(pos[host], pos[side ** 3 + np.arange(extra)])] = False
+    return np.ascontiguousarray(pts[perm]), keep
+
+
 def poisson_select(points, m, r_hi, steps=12):
     """-> (idx [m] i32, r f32, count): lo = 0, hi = r_hi; steps times mid = 0.5f (lo + hi), count(mid) >= m ? lo = mid : hi = mid in
     fp32; the first m kept indices at lo."""

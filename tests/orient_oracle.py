@@ -6,6 +6,8 @@ the orientation tests.  Two programs that must agree bit for bit:
   orient_rounds()  the synchronous parallel rounds of the kernels (propose, hook with the cycle-break, pointer jumping with composed
                    parities), then the finish from the parities to the roots.
 
+jump_launch() / jump_model() restate the bounded pointer jump launch by launch (synchronously), for the deep chains of DEEP.
+
 Edges, weights and signs as the header states them: dot = (nx nx' + ny ny') + nz nz' in fp32 with one rounding per operation,
 w = max(0, 1 - |dot|) in fp32, s = [dot < 0]."""
 import functools
@@ -125,8 +127,63 @@ def orient(points, normals, nbr, vote=0, E=None):
     return out
 
 
-def boruvka_rounds(E):
-    """the kernels' rounds, synchronous -> (root [n], parity to the root [n], chosen edges [m] bool, rounds)"""
+JUMP_ITERS, JUMP_LAUNCHES = 64, 4                                  # kOrJumpIters, kOrJumpLaunches of csrc/orient_consistent.hip
+
+
+def jump_launch(parent, par):
+    """A synchronous model of ONE orient_jump_kernel launch: every thread reads the words the launch found, follows at most JUMP_ITERS
+    links with the parities composed, and rewrites its own word -> (parent, par, short); short: a thread ended short of its root, the
+    flag that lets the next launch work.  (The real launch rewrites in place while others read, so a thread may get further than
+    here, never less far.)"""
+    x = np.arange(len(parent))
+    p, q = parent.copy(), par.copy()
+    done = np.zeros(len(parent), bool)
+    for _ in range(JUMP_ITERS):
+        up = parent[p]
+        done |= (p == x) | (up == p)
+        act = np.nonzero(~done)[0]
+        if len(act) == 0:
+            break
+        q[act] ^= par[p[act]]
+        p[act] = up[act]
+    done |= (p == x) | (parent[p] == p)
+    return p, q, not done.all()
+
+
+def jump_model(parent, par):
+    """launches until one leaves no thread short, at most JUMP_LAUNCHES -> (parent, par, launches that worked, still short)"""
+    for used in range(1, JUMP_LAUNCHES + 1):
+        parent, par, short = jump_launch(parent, par)
+        if not short:
+            break
+    return parent, par, used, short
+
+
+def launches_for_depth(d):
+    """what the model needs for a tree of depth d, as arithmetic: a launch leaves no thread short iff d <= JUMP_ITERS + 1, and takes d
+    to ceil(d / (JUMP_ITERS + 1)) otherwise (tests/test_orient_oracle.py holds jump_launch to both on chains of up to 274628 nodes).
+    Sizes beyond that, 2^24 nodes among them, are bounded by this closed form, not by a run of the model."""
+    used = 1
+    while d > JUMP_ITERS + 1:
+        d = -(-d // (JUMP_ITERS + 1))
+        used += 1
+    return used
+
+
+def depths(parent):
+    """links from every node to its root, for a forest given by parent (roots point at themselves)"""
+    p = parent.copy()
+    d = (p != np.arange(len(parent))).astype(np.int64)             # links from x to p[x], doubled until p[x] is the root
+    while True:
+        up = p[p]
+        if (up == p).all():
+            return d
+        d, p = d + d[p], up
+
+
+def boruvka_rounds(E, launches=None):
+    """the kernels' rounds, synchronous -> (root [n], parity to the root [n], chosen edges [m] bool, rounds).  launches: a list; then
+    the flattening of every round is jump_model's, and the list receives (depth of the hooked forest, launches that worked) per round"""
     n, m = E.n, len(E.lo)
     lo, hi, s = E.lo, E.hi, E.s
     parent, par = np.arange(n, dtype=np.int64), np.zeros(n, np.uint8)
@@ -153,6 +210,12 @@ def boruvka_rounds(E):
         new_parent[roots[hook]] = rb[hook]
         new_par[roots[hook]] = par[a[hook]] ^ par[b[hook]] ^ s[e[hook]]
         parent, par = new_parent, new_par
+        if launches is not None:
+            depth = int(depths(parent).max())
+            parent, par, used, short = jump_model(parent, par)
+            assert not short, "a tree deeper than %d launches flatten" % JUMP_LAUNCHES
+            launches.append((depth, used))
+            continue
         for _ in range(64):                                         # pointer jumping, parities composed
             up = parent[parent]
             if (up == parent).all():
@@ -163,11 +226,11 @@ def boruvka_rounds(E):
     return parent, par, chosen, rounds
 
 
-def orient_rounds(points, normals, nbr, vote=0, E=None):
+def orient_rounds(points, normals, nbr, vote=0, E=None, launches=None):
     """the rounds, then the kernels' finish -> dict(normal, flip, component, n_components, tree, rounds)"""
     nrm = np.ascontiguousarray(normals, np.float32)
     E = E or Edges(nrm, nbr)
-    root, rel, chosen, rounds = boruvka_rounds(E)
+    root, rel, chosen, rounds = boruvka_rounds(E, launches)
     rel = rel.astype(np.int64)
     nonzero = (nrm != 0).any(axis=1).astype(np.int64)
     flip = np.zeros(E.n, np.uint8)
@@ -236,6 +299,41 @@ def sheet(rows=200, cols=100, seed=4):
     return p.astype(np.float32), np.take_along_axis(nbr, perm, axis=1)
 
 
+def chain_lists(n, rs):
+    """[n, 4] int32: {i - 1, i + 1, -1, -1} in seeded column order, -1 beyond either end"""
+    i = np.arange(n, dtype=np.int32)
+    nbr = np.stack([i - 1, np.where(i + 1 < n, i + 1, -1), np.full(n, -1, np.int32), np.full(n, -1, np.int32)], axis=1).astype(np.int32)
+    return np.take_along_axis(nbr, np.argsort(rs.random_sample(nbr.shape), axis=1), axis=1)
+
+
+def path(n, seed=19):
+    """n points on a line, normals (0, 0, +-1) with seeded signs: every weight is exactly 0, so (min, max) alone orders the edges and
+    every node's lightest edge is the one to its LOWER neighbour.  Round one hooks every node but 0 to its lower neighbour (0 and 1
+    choose the same edge: the lower root stays): one chain of depth n - 1, node i being i links from the root 0."""
+    rs = np.random.RandomState(seed)
+    p = np.zeros((n, 3), np.float32)
+    p[:, 0] = np.arange(n, dtype=np.float32) * np.float32(0.25)
+    sign = np.where(rs.random_sample(n) < 0.5, -1.0, 1.0).astype(np.float32)
+    nrm = np.stack([np.zeros_like(sign), np.zeros_like(sign), sign], axis=1)
+    return p, nrm, chain_lists(n, rs)
+
+
+def rising(n, seed=20):
+    """the same line with normals that turn in the xy-plane by increments falling from 1.2 to 0.3 rad, signs seeded: the weight
+    1 - |cos| falls along the line, so every node's lightest edge is the one to its HIGHER neighbour and the chain hooks upwards
+    (n - 1 and n - 2 choose the same edge: n - 2 stays, the root)"""
+    rs = np.random.RandomState(seed)
+    p = path(n)[0]
+    theta = np.concatenate([[0.0], np.cumsum(np.linspace(1.2, 0.3, n - 1))])
+    sign = np.where(rs.random_sample(n) < 0.5, -1.0, 1.0)
+    nrm = (np.stack([np.cos(theta), np.sin(theta), np.zeros(n)], axis=1) * sign[:, None]).astype(np.float32)
+    return p, nrm, chain_lists(n, rs)
+
+
+# the deep hook trees: 1, 2, 2, 3 and 4 launches of the pointer jump in the model (tests/test_orient_oracle.py: a launch flattens depth
+# 65, so 66 points are the last that need one launch), and a chain that hooks upwards
+DEEP = ("path_66", "path_67", "path_68", "path_4228", "path_274628", "rising_4300")
+
 # name -> (points, input normals, neighbour lists): the cases of tests/test_orient_gpu.py, which tests/test_orient_oracle.py runs
 # through both programs.  Input normals are seeded random unit vectors unless the case says otherwise.
 SMALL_N, SMALL_K = (1, 2, 3, 5, 63, 64, 65, 257), (4, 16, 32)
@@ -274,6 +372,10 @@ def case(name):
     if name == "sheet":
         p, nbr = sheet()
         return p, random_units(len(p), 18), nbr
+    if name.startswith("path_"):
+        return path(int(name[5:]))
+    if name.startswith("rising_"):
+        return rising(int(name[7:]))
     raise KeyError(name)
 
 

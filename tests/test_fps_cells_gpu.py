@@ -111,6 +111,64 @@ def test_more_than_1024_cells(dev, arith, n, m):
     _check(dev, [_sphere(np.random.default_rng(n), n)], [m], arith)
 
 
+SLOT_BOUNDARY = (262144, 262145)                         # 4096 cells of 64: the full slot loop; one point more: 2049 cells of 128
+MANY = {257: (1, 63, 64, 65, 130), 65535: (1, 2, 3)}     # segments: sizes in a cycle
+
+
+@pytest.mark.parametrize("arith", [0, 1])
+@pytest.mark.parametrize("n", SLOT_BOUNDARY)
+def test_at_the_slot_boundary(dev, arith, n):
+    """the automatic cell size: the last n that keeps cells of 64 (exactly 4096 of them: every slot of the sampling kernel's cell loop
+    is taken) and the first that doubles them (tests/test_second_trips.py restates both from the sources).  One planted point is the
+    strict maximum of all three axes: its Morton code is the largest, so it sorts into the last cell (at 262145 points that cell's only
+    point), and as the farthest point from everything it is the second pick -- a sampler that drops the last cell or slot misses it."""
+    pc = _sphere(np.random.default_rng(n), n)
+    plant = n // 7
+    pc[plant] = np.float32([3.0, 3.0, 3.0])                # the far corner of the box: Morton cell (1023, 1023, 1023)
+    assert (pc[plant] > np.delete(pc, plant, axis=0).max(axis=0)).all()
+    assert _want(pc, 64, arith)[1] == plant
+    _check(dev, [pc], [64], arith)
+
+
+def _cells_packed(dev, packed, off, moff, arith):
+    """dispu_fps_cells itself on packed arrays -> (idx, status)"""
+    from dispu_amd import _lib
+    L = _lib.lib()
+    hp = lambda a: _lib.C.c_void_p(a.ctypes.data)
+    nC = len(off) - 1
+    x = torch.from_numpy(packed).to(dev)
+    d_off, d_moff = torch.from_numpy(off).to(dev), torch.from_numpy(moff).to(dev)
+    need = L.dispu_fps_cells_scratch_bytes(nC, hp(off), hp(moff), 0)
+    assert need > 0
+    sc = torch.empty((need,), dtype=torch.uint8, device=dev)
+    out = torch.full((int(moff[-1]),), -1, dtype=torch.int32, device=dev)
+    status = torch.full((nC,), 9, dtype=torch.int32, device=dev)
+    _lib.check(L.dispu_fps_cells(nC, _lib.ptr(d_off), _lib.ptr(d_moff), hp(off), hp(moff), _lib.ptr(x), _lib.ptr(sc), need, _lib.ptr(out),
+                                 _lib.ptr(status), arith, 0, _lib.stream_ptr(dev)), "dispu_fps_cells")
+    torch.cuda.synchronize()
+    return N(out), N(status)
+
+
+@pytest.mark.parametrize("arith", [0, 1])
+@pytest.mark.parametrize("nC", sorted(MANY))
+def test_many_segments(dev, arith, nC):
+    """9 and 16 segment bits above the 30 Morton bits of the pre-pass's keys: sorting passes 5 and 6, c << 30 with large c.  One packed
+    call, m_c = min(n_c, 5); the oracle runs once per distinct cloud and is asserted for every repeat of it at its own offset."""
+    cycle = MANY[nC]
+    rng = np.random.default_rng(nC + arith)
+    distinct = {n: _cloud(rng, n) for n in cycle}
+    sizes = np.array(cycle)[np.arange(nC) % len(cycle)]
+    ms = np.minimum(sizes, 5)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    moff = np.concatenate([[0], np.cumsum(ms)]).astype(np.int32)
+    got, status = _cells_packed(dev, np.concatenate([distinct[n] for n in sizes]), off, moff, arith)
+    assert not status.any()
+    for n in cycle:
+        want = _want(distinct[n], min(n, 5), arith)
+        rows = moff[:-1][sizes == n][:, None] + np.arange(min(n, 5))[None, :]
+        assert (got[rows] == want[None, :]).all(), n
+
+
 @pytest.mark.parametrize("arith", [0, 1])
 def test_ragged_and_batched(dev, arith):
     from dispu_amd.tf_sampling import farthest_point_sample

@@ -31,10 +31,10 @@ def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def make_cloud(n, grid):
+def make_cloud(n, grid, dl=None):
     """points with negative coordinates, a fifth of them exactly on voxel faces of this grid, a tenth duplicated; features of mixed
     magnitude (the order of the adds shows); labels from five values including the int32 extremes, duplicates labelled differently"""
-    dl = GRIDS[grid]
+    dl = GRIDS[grid] if dl is None else f32(dl)
     rng = np.random.default_rng(n * 7 + len(grid))
     p = (rng.random((n, 3)) * 4 - 1.5).astype(f32)
     k = n // 5
@@ -134,6 +134,126 @@ def test_run_numbering_at_its_edges(dev, n, pattern):
         assert n < 5 or (ks[0] == ks[4] and ks[n - 1] == ks[n - 2])                                  # and runs of several points at both ends
     op, of, oc = O.compute(p, f, c, dl)
     assert len(op) == runs
+    pts, feats, cls = compute(p, f, c, sampleDl=dl)
+    assert same_bits(pts, op), "points (or the row order)"
+    assert same_bits(feats, of) and same_bits(cls, oc)
+
+
+# ---- past the second trips: the sizes at which a loop runs again or a scan tier splits its work (tests/test_second_trips.py restates the
+# thresholds from the sources), against the vectorised oracle, which tests/test_grid_subsample_oracle.py holds to O.compute ----------------
+BIG = ((262145, "four"), (524289, "four"), (524289, "one"))
+
+
+def four_dl(n):
+    """about four points per voxel: the cloud fills 4^3"""
+    return f32((256.0 / n) ** (1.0 / 3.0))
+
+
+STRIDE = 1024 * 256                  # points per trip of the bounds kernel's stride loop (tests/test_second_trips.py)
+
+
+def big_cloud(n, grid):
+    """make_cloud with, on the "four" grid, the extremes that decide the grid moved into the later trips of the bounds kernel: the last
+    point of the second trip (or the only one) lies a voxel and a half below the box on z and above it on x, and at 524289 points the
+    one point of the third trip the same below on x and above on y.  A bounds pass that drops a trip, strides wrongly or loses the
+    tail gets another origin and another N (tests/test_grid_subsample_oracle.py asserts that every prefix of whole trips does).  The
+    "one" grid cannot be made to depend on its later points: every subset of a cloud inside one cell has that cell's grid."""
+    p, f, c, dl = make_cloud(n, grid, four_dl(n) if grid == "four" else None)
+    if grid == "four":
+        below, above = f32(-1.5) - f32(1.5) * dl, f32(2.5) + f32(1.5) * dl
+        j = min(n, 2 * STRIDE) - 1
+        p[j, 2], p[j, 0] = below, above
+        if n > 2 * STRIDE:
+            p[n - 1, 0], p[n - 1, 1] = below, above
+    return p, f, c, dl
+
+
+def big_case(n, grid):
+    if (n, grid, "big") not in _CASES:
+        p, f, c, dl = big_cloud(n, grid)
+        f, c = np.ascontiguousarray(f[:, :1]), np.ascontiguousarray(c[:, :1])
+        _CASES[(n, grid, "big")] = (p, f, c, dl) + O.compute_fast(p, f, c, dl)
+    return _CASES[(n, grid, "big")]
+
+
+@pytest.mark.parametrize("n, grid", BIG)
+def test_past_the_bounds_stride_and_one_scan_sum_per_thread(dev, n, grid):
+    """262145 points: the bounds kernel's 1024 workgroups stride a second time, and the grid depends on what that trip sees
+    (big_cloud); 524289: a third trip the grid depends on as well, and 257 tile sums in the scan of the run heads, in the
+    voxel sort's table scan not yet (257 tiles), so the voxel sort, the label sort and the run numbering all run at that size; "one":
+    the zero-pass path, run heads without keys, one serial run of 524289 points"""
+    p, f, c, dl, op, of, oc = big_case(n, grid)
+    if grid == "one":
+        assert O.grid(p, dl)[1] == [1, 1, 1] and len(op) == 1 and O.passes(p, dl) == 0
+    else:
+        assert 3.0 < n / len(op) < 5.0 and O.passes(p, dl) == 3
+    pts, feats, cls = compute(p, f, c, sampleDl=dl)
+    assert same_bits(pts, op), "points (or the row order)"
+    assert same_bits(feats, of) and same_bits(cls, oc)
+
+
+# name: (dl, cells per axis, the axis that has points below the doubly rounded origin, sorting passes)
+WIDE = {"two": (0.1, (31, 33, 29), 0, 2), "four": (0.7, (1000, 1025, 999), 2, 4), "five": (0.1, (8000, 8200, 8100), 1, 5),
+        "six": (0.7, (65000, 66000, 32000), 2, 6), "seven": (0.1, (260000, 262000, 250000), 0, 7),
+        "eight": (0.7, (1048000, 1048500, 1040000), 2, 8)}
+
+
+def below_origin_min(dl):
+    """(x0, origin): a minimum x0 whose origin floor(x0 (1 / dl)) dl, rounded twice, lies ABOVE it: points at x0 get cell -1"""
+    inv = f32(1.0) / dl
+    for j in range(1, 100000):
+        x0 = np.nextafter(f32(-j) * dl, f32(-np.inf))
+        origin = f32(np.floor(f32(x0 * inv))) * dl
+        if origin > x0:
+            return x0, origin
+    raise AssertionError("no minimum below its rounded origin at dl = %r" % dl)
+
+
+def wide_cloud(name, n=5000):
+    """n points in 1500 occupied cells of a grid of up to 2^20 cells per axis (float32 still resolves a sixth of dl at its far end): the
+    first and the last cell of every axis, 40 points exactly on voxel faces, 3 points below the rounded origin of one axis"""
+    dl, cells, axis, _ = WIDE[name]
+    dl = f32(dl)
+    rng = np.random.default_rng(sum(cells))
+    x0, o_axis = below_origin_min(dl)
+    occupied = np.stack([rng.integers(0, cells[a], 1500) for a in range(3)], axis=1)
+    occupied[0], occupied[1] = 0, np.array(cells) - 1
+    cell = occupied[np.r_[0, 1, rng.integers(0, 1500, n - 2)]]
+    frac = 0.1 + 0.8 * rng.random((n, 3))
+    frac[np.arange(10, 50), rng.integers(0, 3, 40)] = 0.0                                     # on a face (as near as float32 comes to it)
+    origin = np.zeros(3)
+    origin[axis] = o_axis
+    p = (origin[None, :] + (cell + frac) * np.float64(dl)).astype(f32)
+    p[50] = p[0]                                                                   # one of them in the first cell of the other axes
+    p[50:53, axis] = x0
+    f = (rng.standard_normal((n, 2)) * np.array([1, 1e3], f32)).astype(f32)
+    c = LABELS[rng.integers(0, 5, (n, 1))]
+    return np.ascontiguousarray(p), f, c, dl
+
+
+def plan_info(dev, p, dl):
+    """(status, m, the 8 doubles dispu_grid_subsample_plan reports: origin, N, passes, key_min)"""
+    import torch
+    from dispu_amd import _lib
+    L = _lib.lib()
+    n = p.shape[0]
+    tp = torch.from_numpy(p).to(dev)
+    nbytes = L.dispu_grid_subsample_scratch_bytes(n, 0, 0)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    m, status, info = C.c_int(0), C.c_int(0), (C.c_double * 8)()
+    _lib.check(L.dispu_grid_subsample_plan(n, _lib.ptr(tp), float(dl), _lib.ptr(scratch), nbytes, C.byref(m), C.byref(status), info,
+                                           _lib.stream_ptr(dev)), "plan")
+    return status.value, m.value, list(info)
+
+
+@pytest.mark.parametrize("name", sorted(WIDE))
+def test_wide_grids_of_two_and_four_to_eight_passes(dev, name):
+    """key ranges of 15 to 60 bits on 5000 points: the pass counts between the suite's 0, 1 and 3, products NX NY iz far above 2^32,
+    and a negative key_min"""
+    p, f, c, dl = wide_cloud(name)
+    status, m, info = plan_info(dev, p, dl)
+    op, of, oc = O.compute(p, f, c, dl)
+    assert status == 0 and m == len(op) and int(info[6]) == WIDE[name][3] == O.passes(p, dl) and info[7] < 0
     pts, feats, cls = compute(p, f, c, sampleDl=dl)
     assert same_bits(pts, op), "points (or the row order)"
     assert same_bits(feats, of) and same_bits(cls, oc)

@@ -85,6 +85,81 @@ def test_origin_and_grid_size_with_negative_coordinates():
     assert N[0] == int(np.floor(f32(f32(f32(0.3) - origin[0]) / dl))) + 1 and N[1] == int(np.floor(f32(f32(f32(2.05) - origin[1]) / dl))) + 1
 
 
+# ---- the vectorised oracle and the wide grids of tests/test_grid_subsample_gpu.py (imported for its case builders only) -----------------
+def _same(a, b):
+    return all((x is None and y is None) or same_bits(x, y) for x, y in zip(a, b))
+
+
+def test_fast_oracle_equals_the_sequential_one_on_every_gpu_case():
+    import test_grid_subsample_gpu as T
+    for n in T.SIZES:
+        for grid in sorted(T.GRIDS):
+            p, f, c, dl = T.make_cloud(n, grid)
+            assert _same(O.compute_fast(p, f, c, dl), O.compute(p, f, c, dl)), (n, grid)
+    for n in (1, T.TILE + 1, 2 * T.TILE + 1):
+        for pattern in ("one_cell", "own_cell", "straddle"):
+            p, f, c, dl = T.edge_cloud(n, pattern)
+            assert _same(O.compute_fast(p, f, c, dl), O.compute(p, f, c, dl)), (n, pattern)
+    p, f, c, dl = T.make_cloud(T.TILE, "dense")
+    assert _same(O.compute_fast(p, None, None, dl), O.compute(p, None, None, dl))
+    assert _same(O.compute_fast(p, None, c[:, 0], dl), O.compute(p, None, c[:, 0], dl))
+    # forced label ties, negative labels, a lone -0.0 and sums whose order shows
+    p = np.zeros((8, 3), f32) + f32(0.25)
+    p[4:] += f32(1.0)
+    c = np.array([[5, -7], [-1, -7], [5, 3], [-1, 3], [2 ** 31 - 1, 0], [-2 ** 31, 0], [9, 1], [9, 2]], np.int32)
+    assert O.compute_fast(p, None, c, 1.0)[2].tolist() == [[-1, -7], [9, 0]] and _same(O.compute_fast(p, None, c, 1.0), O.compute(p, None, c, 1.0))
+    p6 = np.zeros((6, 3), f32) + f32(0.5)
+    c6 = np.array([[3, 7], [-2, 7], [3, -9], [-2, 0], [5, 0], [5, -9]], np.int32)
+    assert O.compute_fast(p6, None, c6, 1.0)[2].tolist() == [[-2, -9]]
+    big = np.array([[0.5, 0.5, 0.5]] * 3 + [[1.5, 0.5, 0.5]], f32)
+    fo = np.array([[1.0], [1e8], [-1e8], [-0.0]], f32)
+    assert O.compute_fast(big, fo, None, 1.0)[1].tolist() == [[0.0], [0.0]] and _same(O.compute_fast(big, fo, None, 1.0), O.compute(big, fo, None, 1.0))
+    assert _same(O.compute_fast(big[:3], fo[:3], None, 1.0), O.compute(big[:3], fo[:3], None, 1.0))      # the single-voxel branch
+
+
+def test_the_wide_grids_have_the_passes_they_claim():
+    import test_grid_subsample_gpu as T
+    assert sorted(w[3] for w in T.WIDE.values()) == [2, 4, 5, 6, 7, 8]
+    for name, (_, cells, axis, want) in T.WIDE.items():
+        p, f, c, dl = T.wide_cloud(name)
+        origin, N = O.grid(p, dl)
+        assert O.passes(p, dl) == want, name
+        below = np.floor((p[:, axis] - origin[axis]).astype(f32) / dl) == -1
+        assert origin[axis] > p[:, axis].min() and below.sum() == 3 and O.keys(p, dl).min() < 0, name
+        assert all(abs(N[a] - cells[a]) <= 2 for a in range(3)) and max(N) <= 1 << 20, (name, N)
+        k = O.keys(p, dl)
+        assert (np.bincount(np.unique(k, return_inverse=True)[1]) > 1).any()    # voxels of several points
+        far = np.abs(p).max()
+        assert np.nextafter(far, f32(np.inf)) - far <= dl / f32(6), name          # float32 still resolves dl at the far end
+    p, f, c, dl = T.wide_cloud("eight")
+    N = O.grid(p, dl)[1]
+    assert N[0] * N[1] > 1 << 39 and N[0] * N[1] * N[2] > 1 << 59                  # NX NY iz far above 2^32
+    for n, grid in T.BIG:                                                          # and what the large cases claim
+        if grid == "four":
+            assert 3.4 < n / (4.0 / float(T.four_dl(n))) ** 3 < 4.6
+
+
+def test_the_large_grids_depend_on_every_trip_of_the_bounds_loop():
+    """origin or N of the "four" cases changes when the points of the last trip are left out, and again without the last two"""
+    import test_grid_subsample_gpu as T
+
+    def grid(p, dl):
+        origin, N = O.grid(p, dl)
+        return origin.tolist(), N
+
+    for n, name in T.BIG:
+        p, f, c, dl = T.big_cloud(n, name)
+        trips = -(-n // T.STRIDE)
+        assert trips == (2 if n == T.STRIDE + 1 else 3)
+        seen = [grid(p[:t * T.STRIDE], dl) for t in range(1, trips)] + [grid(p, dl)]
+        if name == "one":
+            assert all(g == ([0.0, 0.0, 0.0], [1, 1, 1]) for g in seen)            # one cell whatever is left out: nothing to plant
+            continue
+        for a, b in zip(seen, seen[1:]):
+            assert a[0] != b[0] and a[1] != b[1], (n, a, b)                        # another origin AND another grid size per trip
+        assert O.passes(p, dl) == 3
+
+
 # ---- compute(): everything refused before the device is touched ------------------------------------------------------------------------
 def _compute(*a, **k):
     import dispu_amd  # noqa: F401

@@ -1,6 +1,7 @@
 """GPU tests of dispu_pca_normals_segments / dispu_amd.normals.estimate_normals (csrc/normals.hip) against tests/normals_oracle.py:
 the neighbour indices bit for bit, the normals against float64 eigh of the same neighbourhoods, degenerate and refused input, the sign
-rules, and tools/upsample.py --normals end to end.  Every cloud has at most 8193 points; an oracle run is shared through lru_cache."""
+rules, and tools/upsample.py --normals end to end.  Every cloud has at most 8193 points (a batch up to 65535 clouds of 1 to 3); an
+oracle run is shared through lru_cache."""
 import ctypes as C
 import functools
 import os
@@ -124,6 +125,28 @@ def test_ragged_batch_equals_each_cloud_alone(dev):
         assert np.array_equal(idx[o:o + n], idx1) and np.array_equal(idx1, oracle_idx("sphere", 16, n))
         assert np.array_equal(nrm[o:o + n].view(np.uint32), nrm1.view(np.uint32)) and np.array_equal(var[o:o + n], var1)
         o += n
+
+
+MANY = {257: (1, 63, 64, 65, 130), 65535: (1, 2, 3)}          # segments: sizes in a cycle
+
+
+@pytest.mark.parametrize("nC", sorted(MANY))
+def test_neighbours_with_many_segments(dev, nC):
+    """9 and 16 segment bits above the 30 Morton bits of the pre-pass's keys: sorting passes 5 and 6, c << 30 with large c.  One packed
+    call; the brute-force rule runs once per distinct cloud and is asserted for every repeat of it at its own offset."""
+    cycle = MANY[nC]
+    sizes = np.array(cycle)[np.arange(nC) % len(cycle)]
+    distinct, lo = {}, 0
+    for n in cycle:
+        distinct[n] = cloud("sphere")[lo:lo + n]
+        lo += n
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    rc, _, _, idx, status = run_abi(dev, [distinct[n] for n in sizes], 4, off=off)
+    assert rc == 0 and len(status) == nC and not status.any()
+    for n in cycle:
+        want = O.neighbors(distinct[n], 4)
+        rows = off[:-1][sizes == n][:, None] + np.arange(n)[None, :]
+        assert np.array_equal(idx[rows], np.broadcast_to(want[None], (rows.shape[0], n, 4))), n
 
 
 @pytest.mark.parametrize("name", ["lattice", "coincident", "clusters"])

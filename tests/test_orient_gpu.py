@@ -1,6 +1,7 @@
 """GPU tests of dispu_orient_consistent_segments / dispu_amd.normals.orient_consistent (csrc/orient_consistent.hip) against
 tests/orient_oracle.py.  Every result is an integer or a sign bit: all comparisons are array_equal, none has a tolerance.  The largest
-cloud has 20 000 points; an oracle run is shared through lru_cache (orient_oracle.expected)."""
+cloud from a neighbour search has 20 000 points, the deep chains (lists built without a search) up to 274 628; an oracle run is shared
+through lru_cache (orient_oracle.expected)."""
 import ctypes as C
 import os
 import subprocess
@@ -108,6 +109,18 @@ def test_rounds_ended_by_read_back_give_the_same(dev):
     from dispu_amd import _lib
     for name in ("helix", "clusters"):
         check_case(dev, name, 0, flags=_lib.ORIENT_HOST_ROUNDS)
+
+
+@pytest.mark.parametrize("name", O.DEEP)
+def test_deep_hook_trees(dev, name):
+    """one chain of 65 to 274627 links after round one: in the synchronous model (tests/test_orient_oracle.py) launches 2, 3 and 4 of
+    the pointer jump work and hand their flag on; 66 points are the last a single launch flattens.  The real launches race and may end
+    sooner, so only results are asserted: with the rounds ended on the device and by read-back, twice each.  rising: the chain hooks
+    towards the higher index, against the order of the workgroups."""
+    from dispu_amd import _lib
+    for flags in (0, _lib.ORIENT_HOST_ROUNDS):
+        for _ in range(2):
+            check_case(dev, name, 0, flags=flags)
 
 
 def test_outputs_that_are_not_asked_for(dev):

@@ -29,6 +29,64 @@ def test_rounds_equal_kruskal(name):
     assert got["rounds"] <= max(1, int(np.ceil(np.log2(max(len(p), 2)))))
 
 
+# ---- the deep hook trees and the model of the pointer jump's launches ------------------------------------------------------------------
+def hooked_chain(name):
+    """(depth of the forest round one hooks, launches the model needs to flatten it, rounds) of a DEEP case"""
+    p, nrm, nbr = O.case(name)
+    launches = []
+    out = O.orient_rounds(p, nrm, nbr, 0, launches=launches)
+    assert out["n_components"] == 1 and len(launches) == out["rounds"] == 1
+    return launches[0] + (out,)
+
+
+@pytest.mark.parametrize("name", O.DEEP)
+def test_deep_chains_both_programs_and_the_jump_model_agree(name):
+    """Kruskal, the rounds with pointer doubling and the rounds with the launch model give the same flips; the chain is as deep as the
+    case claims"""
+    p, nrm, nbr = O.case(name)
+    n = len(p)
+    E = O.Edges(nrm, nbr)
+    depth, used, modelled = hooked_chain(name)
+    assert depth == (n - 1 if name.startswith("path_") else n - 2)
+    for vote in (0, 1):
+        want = O.expected(name, vote)
+        assert same(O.orient_rounds(p, nrm, nbr, vote, E=E), want), (name, vote)
+    assert same(modelled, O.expected(name, 0))
+    assert 0.4 * n < O.expected(name, 0)["flip"].sum() < 0.6 * n + 2               # the parities are live: about half the normals turn
+    if name.startswith("path_"):
+        assert not E.wbits.any()                                    # every weight exactly 0
+    else:                                                           # the fp32 weight bits strictly decrease along the line
+        assert np.array_equal(E.lo[np.lexsort((E.hi, E.lo))] + 1, E.hi[np.lexsort((E.hi, E.lo))])
+        assert (np.diff(E.wbits[np.lexsort((E.hi, E.lo))].astype(np.int64)) < 0).all()
+
+
+def test_jump_model_launch_counts():
+    """A launch of the model follows 64 links from the parent, so it flattens depth 65 and leaves depth d at ceil(d / 65): a chain of n
+    points hooks to depth n - 1, so 66 points need one launch and 67 two (one size below where a count of n - 2 would put it), 4228
+    three, 274628 four.  65^4 > 2^24: no tree of 2^24 nodes needs a fifth."""
+    assert (O.JUMP_ITERS, O.JUMP_LAUNCHES) == (64, 4)
+    step = O.JUMP_ITERS + 1
+    for n, want in ((66, 1), (67, 2), (68, 2), (step ** 2 + 1, 2), (step ** 2 + 2, 3), (4228, 3), (step ** 3 + 1, 3), (step ** 3 + 2, 4),
+                    (274628, 4)):
+        depth, used, _ = hooked_chain("path_%d" % n)
+        assert (depth, used) == (n - 1, want) and O.launches_for_depth(depth) == want, n
+    assert hooked_chain("rising_4300")[:2] == (4298, 3)
+    # one launch on a chain: depth d -> ceil(d / 65), and short exactly when some d > 65
+    for n in (60, 66, 67, 4228):
+        parent = np.maximum(np.arange(n) - 1, 0)
+        par = np.random.RandomState(n).randint(0, 2, n).astype(np.uint8)
+        par[0] = 0
+        p1, q1, short = O.jump_launch(parent, par)
+        d = np.arange(n)
+        assert np.array_equal(p1, np.maximum(d - step, 0)) and short == (n - 1 > step)
+        assert np.array_equal(O.depths(p1), -(-d // step))
+        to_root = np.bitwise_xor.accumulate(par)                    # parity of node i to the root
+        assert np.array_equal(q1, to_root ^ to_root[p1])            # the composed parity is the parity to the new parent
+    # any tree's deepest node sees only its own chain of ancestors, so the chain is the worst tree of its depth
+    assert O.launches_for_depth((1 << 24) - 1) == 4 and O.launches_for_depth(step ** 4) == 4 and O.launches_for_depth(step ** 4 + 1) == 5
+    assert step ** O.JUMP_LAUNCHES > 1 << 24
+
+
 def prim(E):
     """the minimum spanning forest by Prim from every unvisited node, with the same strict order -> [m] bool"""
     import heapq

@@ -1,7 +1,7 @@
 """GPU tests of the outlier filters (csrc/outliers.hip, dispu_amd.outliers) against tests/outliers_oracle.py: the mean neighbour distance
 bit for bit, the radius counts exactly, the per-cloud statistics to 1e-10, the kept indices exactly, ragged batches, flagged and refused
-input, and tools/upsample.py --clean_output end to end.  Every cloud has at most 4127 points; the oracle's sorted distances are shared
-through lru_cache."""
+input, and tools/upsample.py --clean_output end to end.  Every cloud the search sees has at most 4127 points (the oracle's sorted
+distances are shared through lru_cache); the compaction alone also runs on a million rows, against a numpy mask."""
 import ctypes as C
 import functools
 import os
@@ -281,6 +281,38 @@ def test_compact_by_plain_flags(dev):
     assert np.array_equal(new_off, offsets(keep)) and new_off[1] == 0
     assert np.array_equal(idx[:new_off[-1]], np.concatenate(keep).astype(np.int32))
     assert np.array_equal(bits(pts[:new_off[-1]]), bits(np.concatenate([c[k] for c, k in zip(clouds, keep)])))
+
+
+SCAN_TOTALS = (524289, 1050625)                                # rows in all: 257 and 514 tile sums in the scan of the flags
+
+
+@pytest.mark.parametrize("total", SCAN_TOTALS)
+def test_compact_past_one_scan_sum_per_thread(dev, total):
+    """more than 256 tile sums in the device-wide scan of the flags: 257 sums (two per thread of the one-workgroup tier, the last threads
+    idle) and 514 (three per thread); tests/test_second_trips.py restates the thresholds.  Three ragged clouds: about half kept, nothing
+    kept, everything kept; the expected rows come from the numpy mask."""
+    import torch
+    sizes = (total - 4099 - 70001, 4099, 70001)
+    r = np.random.RandomState(total % 1000)
+    packed = r.random_sample((total, 3)).astype(np.float32)
+    off = np.zeros(4, np.int32)
+    np.cumsum(sizes, out=off[1:])
+    clouds = [packed[off[c]:off[c + 1]] for c in range(3)]
+    flags = (r.random_sample(total) < 0.5).astype(np.int32) * r.randint(1, 9, total).astype(np.int32)
+    flags[off[1]:off[2]] = 0                                    # a segment that keeps nothing
+    flags[off[2]:] = r.randint(-9, 0, sizes[2]).astype(np.int32)  # and one that keeps everything (any non-zero word is a flag)
+    a = Abi(dev, clouds)
+    rc, pts, idx, new_off = a.compact(0, torch.from_numpy(flags).to(dev), status=False)
+    assert rc == 0
+    mask = flags != 0
+    kept = int(mask.sum())
+    assert 0.45 * sizes[0] < mask[:off[1]].sum() < 0.55 * sizes[0]
+    local = np.arange(total, dtype=np.int64) - np.repeat(off[:-1].astype(np.int64), sizes)
+    want_off = np.concatenate([[0], np.cumsum([mask[off[c]:off[c + 1]].sum() for c in range(3)])]).astype(np.int32)
+    assert np.array_equal(new_off, want_off) and new_off[1] == new_off[2] and new_off[3] - new_off[2] == sizes[2] and new_off[3] == kept
+    assert np.array_equal(idx[:kept], local[mask].astype(np.int32))
+    assert np.array_equal(bits(pts[:kept]), bits(packed[mask]))
+    assert (pts[kept:] == 7).all() and (idx[kept:] == -7).all()                                       # nothing behind the kept rows is touched
 
 
 # ---- batches, repeats, flagged segments -------------------------------------------------------------------------------------------------

@@ -183,6 +183,63 @@ def test_keep_above_the_old_limit(dev):
     assert 0.2 * n < want.sum() < 0.5 * n
 
 
+BIG_LATTICE = (80, 12289)                                 # 80^3 + 12289 = 524289 points: 257 tile sums in the scans over the points
+MANY = (257, (1, 63, 64, 65, 130))                        # 9 segment bits above the 30 cell bits: a fifth sorting pass
+
+
+def test_keep_past_one_scan_sum_per_thread(dev):
+    """524289 points whose answer follows from their construction (SO.lattice_with_close_pairs, confirmed against the greedy oracle at
+    about 5000 points in tests/test_second_trips.py): the cell sort, the run numbering and the scan of the active list at a size where
+    the one-workgroup tier of the scan gives every thread two sums"""
+    from dispu_amd import poisson_cells as PC
+    pts, want = SO.lattice_with_close_pairs(*BIG_LATTICE)
+    assert pts.shape[0] == 524289 and int((~want).sum()) == BIG_LATTICE[1]
+    keep, count = PC.keep(D(pts, dev), 0.4)
+    got = N(keep)
+    assert got.dtype == np.uint8 and got.max() <= 1 and np.array_equal(got.astype(bool), want)
+    assert int(count.item()) == int(want.sum())
+
+
+def keep_abi(dev, packed, off, radii):
+    """dispu_poisson_cells_keep on a packed batch -> (flags u8 [N], count [C], status [C])"""
+    import ctypes as C
+    from dispu_amd import _lib
+    L = _lib.lib()
+    nC, total = len(off) - 1, packed.shape[0]
+    off = np.ascontiguousarray(off, np.int32)
+    d_off, d_pts, d_r = D(off, dev), D(packed, dev), D(np.asarray(radii, f32), dev)
+    flags = torch.full((total,), 9, dtype=torch.uint8, device=dev)
+    count = torch.full((nC,), -7, dtype=torch.int32, device=dev)
+    status = torch.zeros(nC, dtype=torch.int32, device=dev)
+    rounds = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = L.dispu_poisson_cells_scratch_bytes(nC, total)
+    assert nbytes > 0
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(L.dispu_poisson_cells_keep(nC, _lib.ptr(d_off), C.c_void_p(off.ctypes.data), _lib.ptr(d_pts), _lib.ptr(d_r), _lib.ptr(flags),
+                                          _lib.ptr(count), _lib.ptr(rounds), _lib.ptr(scratch), nbytes, _lib.ptr(status),
+                                          _lib.stream_ptr(dev)), "dispu_poisson_cells_keep")
+    torch.cuda.synchronize(dev)
+    return N(flags), N(count), N(status)
+
+
+def test_keep_with_257_segments(dev):
+    """one packed call; the oracle runs once per distinct cloud and is asserted for every repeat at its own offset"""
+    nC, cycle = MANY
+    rng = np.random.default_rng(257)
+    distinct = {n: _sphere(rng, n) for n in cycle}
+    radius = {n: 0.9 * math.sqrt(4 * math.pi / n) for n in cycle}                # about the mean spacing: a good part is rejected
+    sizes = np.array(cycle)[np.arange(nC) % len(cycle)]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    flags, count, status = keep_abi(dev, np.concatenate([distinct[n] for n in sizes]), off, [radius[n] for n in sizes])
+    assert not status.any()
+    for n in cycle:
+        want = SO.poisson_keep(distinct[n], f32(radius[n]))
+        assert n < 63 or 0.2 * n < want.sum() < 0.9 * n
+        rows = off[:-1][sizes == n][:, None] + np.arange(n)[None, :]
+        assert flags.max() <= 1 and (flags[rows].astype(bool) == want[None, :]).all(), n
+        assert (count[sizes == n] == int(want.sum())).all(), n
+
+
 # ------------------------------------------------------------------------------------------------------------------ 5. select --------
 def _check_selection(pts, idx, r, count, m, want, steps):
     widx, wr, wcount = want

@@ -1,6 +1,7 @@
 """GPU test of the device-wide stable radix sort alone (dispu_radix_sort_pairs, csrc/radix_sort.hip) against
 np.argsort(kind="stable"): keys and payload exact.  Sizes around the tile and the one-workgroup scan, every pass count the bits give
-(0 extra bits in a pass, a pass of one bit, all eight passes), and key sets where stability decides every position."""
+(0 extra bits in a pass, a pass of one bit, all eight passes), key sets where stability decides every position, and once 2049 tiles, where
+the scan of the digit table gives every thread of its one-workgroup tier two sums."""
 import numpy as np
 import pytest
 
@@ -52,6 +53,23 @@ def test_radix_sort_pairs_is_the_stable_argsort(dev, n, bits):
         ko, vo = _sort(dev, keys, vals, bits)
         assert np.array_equal(ko, keys[order]), "%s: keys" % name
         assert np.array_equal(vo, vals[order]), "%s: payload (stability)" % name
+
+
+BIG = TILE * TILE + 1         # 2049 tiles: the digit table [256][2049] has 257 scan chunks, so scan_sums_kernel's threads scan two sums each
+
+
+@pytest.mark.parametrize("bits", (8, 17))
+@pytest.mark.parametrize("name", ("random", "four_values"))
+def test_more_than_2048_tiles(dev, name, bits):
+    """the sorter's own scan tier past one sum per thread (tests/test_second_trips.py restates the threshold): one pass, and three
+    passes whose last has one bit"""
+    rng = np.random.default_rng(1000 * bits + BIG)
+    vals = (np.arange(BIG, dtype=np.uint32) * np.uint32(2654435761)) ^ np.uint32(0x5BD1E995)
+    keys = _key_sets(BIG, bits, rng)[name]
+    order = np.argsort(keys, kind="stable")
+    ko, vo = _sort(dev, keys, vals, bits)                                       # also asserts that the inputs were only read
+    assert np.array_equal(ko, keys[order]), "%s: keys" % name
+    assert np.array_equal(vo, vals[order]), "%s: payload (stability)" % name
 
 
 def test_zero_bits_copies_and_two_runs_agree(dev):
