@@ -1,5 +1,6 @@
-"""Where and when the launches of a training step are submitted (train.Trainer decides WHAT is launched): side and auxiliary streams,
-the events between them, the deferral of side work behind the chain's kernels, the grouped split reductions."""
+"""Where and when the launches of a training step are submitted (train.Trainer decides WHAT is launched, products.Products which GEMM
+entry a dense product goes to): side and auxiliary streams, the events between them, the deferral of side work behind the chain's
+kernels, the grouped split reductions."""
 # torch.cuda and the library are touched by the hooks at the head of StepSchedule only: a subclass that replaces them with recorders
 # runs the whole schedule without a device (tests/test_schedule.py).
 import contextlib
@@ -114,7 +115,7 @@ class StepSchedule(object):
             self._side_busy = [False] * n
 
     def fork_point(self):
-        """an event at the current position of the current stream, for side work queued later (see Trainer._lin_bwd)."""
+        """an event at the current position of the current stream, for side work queued later (see Trainer._lin_bwd, Products.tn)."""
         ev = self._event()
         self.rec(ev, self._current_stream())
         return ev

@@ -6,6 +6,8 @@ weight_fine(epoch) * 1000 CD(fine) + repulsion_w * repulsion(fine)), `setup_opti
 over epochs, Adam beta1 = opts.beta on every generator variable) and the per-batch body of `train` (:215-232).
 The reference obtains gradients from TF1 autodiff; here every backward op is an explicit C-ABI launch
 (include/dispu_hip.h, "training step").  torch supplies device memory, the stream and torch.distributed only.
+The Trainer names the layers and their order; which GEMM entry a dense product goes to is decided in products.py (Products),
+where and when a launch is submitted in schedule.py (StepSchedule).
 
 Execution differences from the reference (not results):
   * parameters, gradients and both Adam moments live in four flat fp32 buffers (1.05 M floats each): ONE RCCL
@@ -20,6 +22,7 @@ import contextlib
 import ctypes
 import math
 import os
+import weakref
 from collections import OrderedDict
 from functools import partial
 
@@ -29,6 +32,7 @@ import torch
 from . import _lib
 from ._util import f32, req
 from .generator import BN_EPS, DENSE_BLOCKS, GROWTH, K_NEIGH, _Opts, gen_grid
+from .products import Products, _p
 from .schedule import StepSchedule
 
 BN_DECAY = 0.95      # DisPU/generator.py:39 bn_decay
@@ -83,11 +87,6 @@ def learning_rate(opts, epoch):
     return lr
 
 
-def _p(t, off=0):
-    """Device pointer of element `off` of t's storage (in t's own element size: a bf16-stored activation advances 2 bytes per column)."""
-    return _lib.C.c_void_p(t.data_ptr() + t.element_size() * off) if t is not None else _lib.C.c_void_p(0)
-
-
 class _Step(object):
     """What forward() leaves for loss_backward(), _recompute_pair_tensors() and backward(): the shape, the input, the workspace, the path
     (Trainer.path) and the two flags of the current forward."""
@@ -101,8 +100,8 @@ class _Step(object):
         self.stash_ready = False          # the pair tensors of the local cell's backward are in place (_recompute_pair_tensors)
 
 
-def _sched_attr(name):                                   # a Trainer switch that lives on its StepSchedule
-    return property(lambda self: getattr(self.sched, name), lambda self, v: setattr(self.sched, name, v))
+def _attr_of(owner, name):                               # a Trainer switch that lives on its StepSchedule / its Products
+    return property(lambda self: getattr(getattr(self, owner), name), lambda self, v: setattr(getattr(self, owner), name, v))
 
 
 class Trainer(object):
@@ -130,11 +129,9 @@ class Trainer(object):
         self.epoch = 0
         self.global_step = 0
         self._ws = {}
-        self._scratch = {}                    # per stream: scratch of the split reductions / column sums
         self._bn_scratch = None
         self._step = None                     # the current forward's record (_Step)
         self._tapes = {}
-        self._packs = {}                      # bf16 images of the weights for the streaming kernel (_stream)
         self._ar = None                       # parallel.BucketedAllReduce over flat_g (data parallel only, see _reducer)
         self._ar_armed = False                # True inside train_step(): backward() may start a bucket's all-reduce as soon as it is complete
         # a ONE-rank process group normally means "no collectives".  True keeps them (a 1-rank RCCL communicator executes the real
@@ -162,13 +159,15 @@ class Trainer(object):
         # fp32 storage only): h1 / dz0 / wv / the inverted neighbour graph never exist in HBM.  Correct and tested, but 40 us slower per 8-patch
         # step than the five-launch path (1.595 vs 1.555 ms): OFF by default
         self.fused_local_bwd = False
-        self.bf16_stream = True    # dtype="bf16": the large dense products on the streaming bf16 kernel (csrc/linear_bf16_stream.hip) where its shape rules hold
-        self.bf16_min_macs = 1.5e9            # dtype="bf16": products below this many multiply-adds stay on the fp32 kernel (_use_bf16)
+        # the dense products: their GEMM entries, bf16 weight images and per-stream scratch (bf16_stream, bf16_min_macs: the properties below)
+        inv = weakref.WeakMethod(self._invalidate_recordings)     # weak: no cycle keeps a dropped Trainer's device memory until the collector runs
+        self.prod = Products(self.device, self.sched, self.bf16, lambda: inv()())
         self.P = None
         if params is not None:
             self.load_params(params)
 
-    overlap_dw, dw_streams, group_reduce, defer_side = (_sched_attr(n) for n in ("overlap_dw", "dw_streams", "group_reduce", "defer_side"))
+    overlap_dw, dw_streams, group_reduce, defer_side = (_attr_of("sched", n) for n in ("overlap_dw", "dw_streams", "group_reduce", "defer_side"))
+    bf16_stream, bf16_min_macs, _scratch = (_attr_of("prod", n) for n in ("bf16_stream", "bf16_min_macs", "scratch"))
     st = property(lambda self: self.sched.st)            # the stream pointer the launches go to
 
     # --------------------------------------------------------------------------------------------- parameters ----
@@ -176,13 +175,13 @@ class Trainer(object):
         """Launch tapes hold RAW device pointers (flat parameter / gradient / moment buffers, W^T copies,
         scratch, workspaces).  Whenever one of those buffers is re-allocated every recording is dropped, so the next
         train_step_taped records afresh instead of replaying launches onto freed memory.  The bf16 images of the weights
-        (_stream) are keyed by the weight's address: dropped with the tapes that point at them."""
+        (Products.packs) are keyed by the weight's address: dropped with the tapes that point at them."""
         self._tapes.clear()
         # the schedule's device copies of reduction tables: only tapes (dropped above) and the step being recorded point at them; a moved
         # scratch buffer makes new table contents anyway
-        if self._packs or self.sched.tables:
+        if self.prod.packs or self.sched.tables:
             torch.cuda.synchronize(self.device)
-        self._packs.clear()
+        self.prod.packs.clear()
         self.sched.drop_tables()
 
     def load_params(self, params):
@@ -289,18 +288,6 @@ class Trainer(object):
         self._ws[key] = ws
         return ws
 
-    def _scratch_floats(self, n, key=None):
-        """scratch of the launches queued on ONE stream (they run in order, so they can share it): a dW stream's (key "dw<i>"), or the
-        current stream's (main or a branch)."""
-        key = key if key else self.sched.key
-        cur = self._scratch.get(key)
-        if cur is None or cur.numel() < n:
-            if cur is not None:
-                torch.cuda.synchronize(self.device)          # a launch on that stream may still be using the old buffer
-                self._invalidate_recordings()                # ... and a tape recorded at a smaller shape points into it
-            cur = self._scratch[key] = torch.empty(max(int(n), 1 << 20), dtype=torch.float32, device=self.device)
-        return cur
-
     def _zero(self, t):
         """t.zero_() on the stream launches currently go to, as a memset through the library (a plain C call: tape-able, and cheaper
         than the torch op)."""
@@ -309,156 +296,16 @@ class Trainer(object):
         _lib.check(L.dispu_memset_async(_lib.C.c_void_p(t.data_ptr()), 0, t.numel() * t.element_size(), st), "memset")
 
     # ----------------------------------------------------------------------------------------------- helpers ----
-    def _dl(self, batch, M, K, N, *rest):
-        """dispu_linear, or its bf16-product twin when the trainer runs mixed precision (narrow 3-wide layers stay fp32)."""
-        L = _lib.tape_lib()
-        fn = L.dispu_linear_bf16 if self._use_bf16(batch, M, K, N) else L.dispu_linear
-        return fn(batch, M, K, N, *rest)
-
-    def _use_bf16(self, batch, M, K, N):
-        """bf16 products for this GEMM?  Mixed precision is per product: the narrow 3-wide layers always stay fp32, and so do products
-        below `bf16_min_macs` multiply-adds -- at 8192 rows the K <= 256 products are launch / prologue-bound and the bf16 kernel (fp32
-        operands rounded on their way into LDS) is no faster than the fp32 one, often slower (24 - 29 us vs 15 - 24 us)."""
-        return self.bf16 and K > 4 and N > 4 and float(batch) * M * K * N >= self.bf16_min_macs
-
-    def _stream(self, M, K, N, X, xoff, W, woff, transpose, bias, act, Y, yoff):
-        """Y[:, yoff:yoff+N] = act(X[:, xoff:xoff+K] . B + bias) on the streaming bf16 kernel; B = W[woff..] as [K][N] (transpose = 1: the
-        forward product) or W^T with W[woff..] as [N][K] (transpose = 0: dX = dZ . W^T).  Returns False -- nothing launched -- when the
-        kernel's shape rules do not hold (the caller keeps dispu_linear_bf16).  The weight is packed to bf16 [N][K] right here, on the
-        same stream (weights change every step; 0.5 M elements at most)."""
-        if not (self.bf16 and self.bf16_stream) or M % 128 or K % 32 or N % 128:
-            return False
-        xb, yb = X.dtype == torch.bfloat16, Y.dtype == torch.bfloat16
-        es = 2 if xb else 4
-        if (X.stride(0) * es) % 16 or (xoff * es) % 16 or X.stride(1) != 1 or Y.stride(1) != 1 or W.stride(1) != 1:
-            return False
-        L = _lib.tape_lib()
-        key = (W.data_ptr() + 4 * woff, K, N, transpose)
-        bt = self._packs.get(key)
-        if bt is None:
-            bt = self._packs[key] = torch.empty((N, K), dtype=torch.bfloat16, device=self.device)
-        if transpose:
-            _lib.check(L.dispu_bf16_pack(K, N, _p(W, woff), W.stride(0), 1, _p(bt), self.st), "dispu_bf16_pack")
-        else:
-            _lib.check(L.dispu_bf16_pack(N, K, _p(W, woff), W.stride(0), 0, _p(bt), self.st), "dispu_bf16_pack")
-        tiles = (M // 128) * (N // (256 if N % 256 == 0 else 128))
-        nsp = 1
-        if tiles < 192 and not yb:
-            while nsp < 8 and tiles * nsp < 256 and K % (64 * nsp) == 0 and K // (2 * nsp) >= 256:
-                nsp *= 2
-        if nsp > 1:
-            parts = self._scratch_floats(nsp * M * N)
-            _lib.check(L.dispu_linear_bf16_stream(M, K, N, _p(X, xoff), X.stride(0), int(xb), _p(bt), K, None, 0, _p(parts), N, 0, nsp, M * N, self.st),
-                       "dispu_linear_bf16_stream")
-            _lib.check(L.dispu_linear_splitk_finish(M, N, nsp, _p(parts), M * N, _p(bias), act, _p(Y, yoff), Y.stride(0), self.st), "splitk_finish")
-        else:
-            _lib.check(L.dispu_linear_bf16_stream(M, K, N, _p(X, xoff), X.stride(0), int(xb), _p(bt), K, _p(bias), act, _p(Y, yoff), Y.stride(0),
-                                                  int(yb), 1, 0, self.st), "dispu_linear_bf16_stream")
-        return True
-
     def _lin(self, X, xoff, K, wname, act, Y, yoff, N, M=None, bias=True, W=None, woff=0):
         """Y[:, yoff:yoff+N] = act(X[:, xoff:xoff+K] . W + b)"""
-        L = _lib.tape_lib()
-        M = X.shape[0] if M is None else M
         W = self.P[wname + "/weights"] if W is None else W
-        b = self.P[wname + "/biases"] if bias else None
-        sto = (1 if X.dtype == torch.bfloat16 else 0) | (4 if Y.dtype == torch.bfloat16 else 0)
-        if (sto or self._use_bf16(1, M, K, N)) and self._stream(M, K, N, X, xoff, W, woff, 1, b, act, Y, yoff):
-            return
-        if sto:
-            assert xoff == 0 and yoff == 0
-            _lib.check(L.dispu_linear_bf16s(1, M, K, N, _p(X), X.stride(0), 0, _p(W, woff), W.stride(0), 0, 0, _p(b), act, _p(Y), Y.stride(0), 0,
-                                            None, 0, 0, sto, self.st), "dispu_linear_bf16s")
-            return
-        _lib.check(self._dl(1, M, K, N, _p(X, xoff), X.stride(0), 0, _p(W, woff), W.stride(0), 0, 0, _p(b), act,
-                                  _p(Y, yoff), Y.stride(0), 0, None, 0, 0, None, 0, 0, self.st), "dispu_linear")
-
-    def _tn(self, batch, M, K, N, X, xoff, ldx, sx, Zt, zoff, ldz, sz, out, ooff, ldo, so, accumulate, dbias=None, side=False, after=None,
-            wgrad=False):
-        """out (+)= X^T . Zt.  side=True: on a side stream (the caller guarantees nothing overwrites X / Zt before join), ordered after
-        `after` (an event or a StepSchedule.fork_group()) / this point of the current stream; the launch itself may be deferred (StepSchedule.defer).
-        wgrad=True: `out` is a weight gradient -- nothing reads it before join(), so its split reduction may wait for the stream's
-        grouped launch (Trainer.group_reduce)."""
-        L = _lib.tape_lib()
-        side = side and self.overlap_dw
-        sto = (1 if X.dtype == torch.bfloat16 else 0) | (2 if Zt.dtype == torch.bfloat16 else 0)
-        bf = self._use_bf16(batch, M, K, N) or bool(sto)
-        need = (L.dispu_linear_tn_bf16_scratch_floats if bf else L.dispu_linear_tn_scratch_floats)(batch, M, K, N)
-        # the streaming TN kernel where its shape rules hold (after_conv's 2048 x 256: 37 vs 59 us at 8192 rows; the pair tensors' 128 x 128
-        # over 131072 bf16-stored rows: 22 vs 47 us)
-        tn_stream = 0
-        if (bf and self.bf16_stream and batch == 1 and sto in (0, 3) and K % 128 == 0 and N % 128 == 0 and xoff == 0 and zoff == 0):
-            tn_stream = L.dispu_linear_tn_bf16_stream_scratch_floats(M, K, N)
-            need = max(need, tn_stream)
-
-        def launch(st, key):
-            if not (self.group_reduce and wgrad and batch == 1 and (key is not None or self.sched.key == "main")):
-                return launch_product(st, self._scratch_floats(need, key))
-            # a descriptor slot of its stream and a scratch buffer of this product's own (it must survive until the grouped reduction)
-            slot, grp = self.sched.reduce_slot(st, out.data_ptr() + 4 * ooff, dbias.data_ptr() if dbias is not None else 0)
-            sc = self._scratch_floats(need, ("tn", out.data_ptr() + 4 * ooff, K, N))
-            _lib.check(L.dispu_tn_defer(slot), "dispu_tn_defer")
-            try:
-                launch_product(st, sc)
-            finally:
-                grp.commit()
-
-        def launch_product(st, sc):
-            if tn_stream:
-                _lib.check(L.dispu_linear_tn_bf16_stream(M, K, N, _p(X), ldx, _p(Zt), ldz, sto, _p(out, ooff), ldo, accumulate, _p(dbias), _p(sc),
-                                                         sc.numel(), st), "dispu_linear_tn_bf16_stream")
-                return
-            if sto:
-                assert bf and xoff == 0 and zoff == 0
-                _lib.check(L.dispu_linear_tn_bf16s(batch, M, K, N, _p(X), ldx, sx, _p(Zt), ldz, sz, _p(out, ooff), ldo, so, accumulate, _p(dbias), _p(sc),
-                                                   sc.numel(), sto, st), "dispu_linear_tn_bf16s")
-                return
-            fn = L.dispu_linear_tn_bf16 if bf else L.dispu_linear_tn
-            _lib.check(fn(batch, M, K, N, _p(X, xoff), ldx, sx, _p(Zt, zoff), ldz, sz, _p(out, ooff), ldo, so, accumulate, _p(dbias), _p(sc),
-                          sc.numel(), st), "dispu_linear_tn_bf16" if bf else "dispu_linear_tn")
-
-        if not side:
-            launch(self.st, None)
-            return
-        ev = after if after is not None else self.sched.fork_point()
-        self.sched.defer(lambda: launch(*self.sched.side_stream(ev)))
-
-    def _act_bias_grad(self, M, N, dY, dyoff, Y, yoff, act, dZ, dzoff, dbias):
-        L = _lib.tape_lib()
-        need = L.dispu_act_bias_grad_scratch_floats(M, N)
-        sc = self._scratch_floats(need)
-        _lib.check(L.dispu_act_bias_grad(M, N, _p(dY, dyoff), dY.stride(0), _p(Y, yoff) if Y is not None else None,
-                                         Y.stride(0) if Y is not None else 0, act, _p(dZ, dzoff) if dZ is not None else None,
-                                         dZ.stride(0) if dZ is not None else 0, _p(dbias), 1, _p(sc), sc.numel(), self.st),
-                   "dispu_act_bias_grad")
-
-    def _dx(self, M, N, K, dY, dyoff, W, woff, dX, dxoff, acc, WT=None):
-        """dX[:, dxoff:dxoff+K] (+)= dY[:, dyoff:dyoff+N] . W^T.
-        WT: the step's transposed copy of W ([N, K] row-major): the product then runs untransposed (the forward GEMM's fast path)."""
-        L = _lib.tape_lib()
-        bf = self._use_bf16(1, M, N, K)
-        r1 = _p(dX, dxoff) if acc else None
-        ldr = dX.stride(0) if acc else 0
-        if WT is not None:
-            wp, ldw, tb = _p(WT), WT.stride(0), 0
-        else:
-            wp, ldw, tb = _p(W, woff), W.stride(0), 1
-        sto = (1 if dY.dtype == torch.bfloat16 else 0) | (4 if dX.dtype == torch.bfloat16 else 0)
-        if (sto or bf) and not acc and self._stream(M, N, K, dY, dyoff, W, woff, 0, None, 0, dX, dxoff):
-            return
-        if sto:
-            assert self.bf16 and not acc and dyoff == 0 and dxoff == 0
-            _lib.check(L.dispu_linear_bf16s(1, M, N, K, _p(dY), dY.stride(0), 0, wp, ldw, 0, tb, None, 0, _p(dX), dX.stride(0), 0, None, 0, 0,
-                                            sto, self.st), "dispu_linear_bf16s(dX)")
-            return
-        fn = L.dispu_linear_bf16 if bf else L.dispu_linear
-        _lib.check(fn(1, M, N, K, _p(dY, dyoff), dY.stride(0), 0, wp, ldw, 0, tb, None, 0, _p(dX, dxoff), dX.stride(0), 0,
-                      r1, ldr, 0, None, 0, 0, self.st), "dispu_linear(dX)")
+        self.prod.linear(X.shape[0] if M is None else M, K, N, X, xoff, W, woff, 0, self.P[wname + "/biases"] if bias else None, act, Y, yoff)
 
     def _lin_bwd(self, X, xoff, K, wname, N, dY, dyoff, dX=None, dxoff=0, acc_dx=False, M=None, bias=True, W=None, dW=None, woff=0,
                  db=None, side=True, after=None):
         """backward of _lin given dZ = dY[:, dyoff:dyoff+N] ALREADY multiplied by the layer's own relu' (its producer did that):
-        db += colsum dZ and dW += X^T dZ on the second stream (ordered after `after`, see _tn), dX[:, dxoff:dxoff+K] (+)= dZ . W^T (see _dx)."""
+        db += colsum dZ and dW += X^T dZ on the second stream (ordered after `after`, see Products.tn), dX[:, dxoff:dxoff+K] (+)= dZ . W^T
+        (Products.linear; through the step's W^T copy where there is one)."""
         M = X.shape[0] if M is None else M
         W = self.P[wname + "/weights"] if W is None else W
         dW = self.G[wname + "/weights"] if dW is None else dW
@@ -469,9 +316,9 @@ class Trainer(object):
         ev = self.sched.fork_point() if (self.overlap_dw and dX is not None) else after
         if dX is not None:
             WT = self.PT.get(wname + "/weights") if (wname is not None and woff == 0 and K == W.shape[0]) else None
-            self._dx(M, N, K, dY, dyoff, W, woff, dX, dxoff, acc_dx, WT)
-        self._tn(1, M, K, N, X, xoff, X.stride(0), 0, dY, dyoff, dY.stride(0), 0, dW, woff, dW.stride(0), 0, 1, dbias=db, side=side, after=ev,
-                 wgrad=True)
+            self.prod.linear(M, N, K, dY, dyoff, W, woff, 1, None, 0, dX, dxoff, acc_dx, WT)
+        self.prod.tn(1, M, K, N, X, xoff, X.stride(0), 0, dY, dyoff, dY.stride(0), 0, dW, woff, dW.stride(0), 0, 1, dbias=db, side=side, after=ev,
+                     wgrad=True)
 
     # ------------------------------------------------------------------------------------------------- path ----
     def path(self, B, N):
@@ -495,7 +342,7 @@ class Trainer(object):
         req(M % 32 == 0, "the non-local cell's attention kernels work on 32-point tiles: %d * N must be a multiple of 32, got N = %d"
                          % (self.up_ratio, N))
         # after_conv's split: fp32 products only (its input hp is stored as fp32 in both dtypes; bf16 products have their own tiles)
-        split = rm <= 16384 and rm % 128 == 0 and not self._use_bf16(1, rm, 2048, 256)
+        split = rm <= 16384 and rm % 128 == 0 and not self.prod.use_bf16(1, rm, 2048, 256)
         # the fused local backward needs fp32 pair tensors (dtype "f32"); its other two conditions always hold here: whole 8-point groups
         # (rm * 16 % 64 == 0 follows from rm % 64 == 0) and conv1's W^T copy (128 x 128 passes load_params' rule)
         return Path(stem=N <= 256 and N % 2 == 0, after_split=(4 if rm >= 8192 else 8) if split else 0, defer_side=rm <= 16 * 1024,
@@ -631,11 +478,11 @@ class Trainer(object):
                                                  self.st), "attention_fwd_lse")
         else:
             S = ws["S"]
-            _lib.check(self._dl(B, M, 64, M, _p(q), 64, M * 64, _p(kv), 128, M * 128, 1, None, 0, _p(S), M, M * M,
-                                None, 0, 0, None, 0, 0, self.st), "scores")
+            _lib.check(self.prod.batched(B, M, 64, M, _p(q), 64, M * 64, _p(kv), 128, M * 128, 1, None, 0, _p(S), M, M * M,
+                                             None, 0, 0, None, 0, 0, self.st), "scores")
             _lib.check(L.dispu_softmax_rows(s.rm, M, 0.125, _p(S), M, self.st), "softmax")
-            _lib.check(self._dl(B, M, M, 64, _p(S), M, M * M, _p(kv, 64), 128, M * 128, 0, None, 0, _p(att), 64,
-                                M * 64, None, 0, 0, None, 0, 0, self.st), "att.V")
+            _lib.check(self.prod.batched(B, M, M, 64, _p(S), M, M * M, _p(kv, 64), 128, M * 128, 0, None, 0, _p(att), 64,
+                                             M * 64, None, 0, 0, None, 0, 0, self.st), "att.V")
         self._lin(att, 0, 64, PS + "PointShuffle/conv_back_project", 1, ws["nl"], 0, 256)
         # what the backward needs and nothing in the forward touches (zeroed accumulators, the W^T copies: ~45 us of kernels),
         # behind the branch's own kernels
@@ -864,7 +711,7 @@ class Trainer(object):
     def backward(self):
         """gradients of pu_loss w.r.t. every trainable variable, accumulated into the flat gradient buffer.
         ReLU gradients never run as separate passes: the kernel that produces a layer's dY applies that layer's mask (the fused head
-        chains, the gathers, _act_bias_grad), so every dY arriving at _lin_bwd is already the pre-activation gradient dZ."""
+        chains, the gathers, Products.act_bias_grad), so every dY arriving at _lin_bwd is already the pre-activation gradient dZ."""
         s = self._step
         if not s.fresh:
             # a second backward() on the same forward (new targets / loss weights): the atomics accumulators still hold the previous,
@@ -969,16 +816,16 @@ class Trainer(object):
                                              _p(ws["dvec"]), self.st), "attention_bwd")
         else:
             # dP = dO . V^T
-            _lib.check(self._dl(B, M, 64, M, _p(ws["datt"]), 64, M * 64, _p(kv, 64), 128, M * 128, 1, None, 0, _p(dS), M, M * M,
-                                None, 0, 0, None, 0, 0, self.st), "dP")
+            _lib.check(self.prod.batched(B, M, 64, M, _p(ws["datt"]), 64, M * 64, _p(kv, 64), 128, M * 128, 1, None, 0, _p(dS), M, M * M,
+                                             None, 0, 0, None, 0, 0, self.st), "dP")
             # dV = P^T . dO  -> dkv[:, 64:128]
-            self._tn(B, M, M, 64, S, 0, M, M * M, ws["datt"], 0, 64, M * 64, dkv, 64, 128, M * 128, 0)
+            self.prod.tn(B, M, M, 64, S, 0, M, M * M, ws["datt"], 0, 64, M * 64, dkv, 64, 128, M * 128, 0)
             _lib.check(L.dispu_softmax_rows_grad(s.rm, M, 0.125, _p(S), M, _p(dS), M, self.st), "softmax_grad")
             # dQ = dS . K
-            _lib.check(self._dl(B, M, M, 64, _p(dS), M, M * M, _p(kv), 128, M * 128, 0, None, 0, _p(ws["dq"]), 64, M * 64,
-                                None, 0, 0, None, 0, 0, self.st), "dQ")
+            _lib.check(self.prod.batched(B, M, M, 64, _p(dS), M, M * M, _p(kv), 128, M * 128, 0, None, 0, _p(ws["dq"]), 64, M * 64,
+                                             None, 0, 0, None, 0, 0, self.st), "dQ")
             # dK = dS^T . Q -> dkv[:, 0:64]
-            self._tn(B, M, M, 64, dS, 0, M, M * M, q, 0, 64, M * 64, dkv, 0, 128, M * 128, 0)
+            self.prod.tn(B, M, M, 64, dS, 0, M, M * M, q, 0, 64, M * 64, dkv, 0, 128, M * 128, 0)
         self._lin_bwd(ws["up128"], 0, 128, PS + "PointShuffle/conv_kv", 128, dkv, 0, dup128)
         self._lin_bwd(ws["up128"], 0, 128, PS + "PointShuffle/conv_query", 64, ws["dq"], 0, dup128, 0, acc_dx=True)
 
@@ -1057,8 +904,8 @@ class Trainer(object):
         self._lin_bwd(ws["c256"], 0, 256, CS + "fc_layer1", 64, ws["dc64"], 0, after=grp)
         self._lin_bwd(ws["up128"], 0, 128, CS + "fc_layer0", 256, ws["dc256"], 0, after=grp)
         self._lin_bwd(ws["up256"], 0, 256, c2, 128, dup128, 0, after=grp)
-        self._tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
-                 dbias=G[UP + "conv1/biases"], side=True, after=grp, wgrad=True)   # read by Adam only: off the chain like every other dW
+        self.prod.tn(1, rm, 2, 256, ws["gcode"], 0, 2, 0, ws["dup256"], 0, 256, 0, dw1, 480 * 256, 256, 0, 1,
+                     dbias=G[UP + "conv1/biases"], side=True, after=grp, wgrad=True)   # read by Adam only: off the chain like every other dW
         self._lin_bwd(ws["feat"], 0, 480, None, 256, ws["dh256"], 0, ws["dfeat"], 0, bias=False, W=w1, dW=dw1)
 
     def _bwd_block_partials(self, s, blk):
@@ -1066,7 +913,7 @@ class Trainer(object):
         d, C, col, _, _ = blk
         L, ws, rn = _lib.tape_lib(), s.ws, s.rn
         F, dF, off = (ws["feat"], ws["dfeat"], 456) if d == 1 else (ws["prep"][d], ws["dprep"][d], 0)      # (dprep: zero-filled in forward(), off the chain)
-        scr = self._scratch_floats(L.dispu_edge_dense_conv_grad_scratch_floats(rn, C), "edge%d" % d)
+        scr = self.prod.scratch_floats(L.dispu_edge_dense_conv_grad_scratch_floats(rn, C), "edge%d" % d)
         _lib.check(L.dispu_edge_dense_conv_grad_partials(rn, s.N, C, _p(F, off), F.stride(0), _p(ws["kidx"][d]), K_NEIGH + 1, 1, *self._dense_w(d),
                                                          _p(ws["dfeat"], col), 480, _p(dF, off), dF.stride(0), _p(scr), scr.numel(), self.st),
                    "edge_dense_conv_grad_partials")
@@ -1081,7 +928,7 @@ class Trainer(object):
         d, _, _, in_col, _ = blk
         if d > 1:
             F, dF = s.ws["prep"][d], s.ws["dprep"][d]
-            self._act_bias_grad(s.rn, 48, dF, 0, F, 0, 1, dF, 0, None)        # prep = relu(.): its mask (dF came from atomics)
+            self.prod.act_bias_grad(s.rn, 48, dF, 0, F, 0, 1, dF, 0, None)        # prep = relu(.): its mask (dF came from atomics)
             self._lin_bwd(s.ws["feat"], in_col, 480 - in_col, FE + "layer%d_prep" % d, 48, dF, 0, s.ws["dfeat"], in_col, acc_dx=True)
 
     # -------------------------------------------------------------------------------------------------- step ----

@@ -42,6 +42,11 @@ def cases():
     out.append(("f32 (4, 64) second loss_backward + backward on one forward", "f32", (4, 64, 4), {}, {}, ("loss_backward", "backward")))
     out.append(("f32 (4, 64) backward without loss_backward", "f32", (4, 64, 4), {}, {}, ("zero_grad", "forward", "backward")))
     out.append(("bf16 (8, 256) bf16_stream=False", "bf16", (8, 256, 5), {"bf16_stream": False}, {}, FULL))
+    # corners of the dense-product dispatch (products.py): every product bf16 at a small shape; rm = 192, no multiple of 128, so the
+    # ladder's fall-throughs run; the batched products and the batch-B TN of the gemm attention path in bf16 mode; TN without grouping / side streams
+    for shape, attrs in (((4, 64, 4), {"bf16_min_macs": 0.0}), ((2, 24, 2), {"bf16_min_macs": 0.0}), ((4, 64, 4), {"flash_attn": False}),
+                         ((4, 64, 4), {"group_reduce": False}), ((4, 64, 4), {"overlap_dw": False})):
+        out.append(("bf16 (%d, %d) %s" % (shape[0], shape[1], ", ".join("%s=%s" % kv for kv in attrs.items())), "bf16", shape, attrs, {}, FULL))
     return out
 
 
