@@ -8,7 +8,7 @@ Modules named like the reference's op wrappers:
   tf_sampling, tf_grouping, tf_interpolate, tf_nndistance, tf_approxmatch  (tf_ops/*/tf_*.py)
   nearest_neighbors                                                          (libs/nearest_neighbors/knn.pyx)
 Whole-cloud operations without a reference counterpart, imported by name like the rest (none is loaded here, so importing the
-package stays free of torch): grid_subsampling, outliers, normals, attributes, mls, registration.
+package stays free of torch): grid_subsampling, outliers, clusters, normals, attributes, mls, registration.
 """
 from . import _lib  # noqa: F401  (does not load the .so until first use)
 

@@ -25,6 +25,7 @@ GRID_NONFINITE, GRID_AXIS_X, GRID_AXIS_Y, GRID_AXIS_Z, GRID_TOO_MANY_POINTS = 1,
 LATTICE_NONFINITE, LATTICE_RANGE = 1, 2   # include/dispu_hip.h: DISPU_LATTICE_*
 ORIENT_HOST_ROUNDS = 1      # include/dispu_hip.h: DISPU_ORIENT_HOST_ROUNDS (flags of dispu_orient_consistent_segments)
 ORIENT_PROFILE_FLOATS = 8   # include/dispu_hip.h: DISPU_ORIENT_PROFILE_FLOATS
+CLUSTER_HEAD_INTS = 16      # include/dispu_hip.h: DISPU_CLUSTER_HEAD_INTS (the counters at the head of dispu_cluster_segments' scratch)
 
 _vp, _i, _sz, _l =C.c_void_p, C.c_int, C.c_size_t, C.c_long
 
@@ -54,6 +55,9 @@ SIGNATURES = {
     "dispu_outlier_threshold_segments": (_i, [_i, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
     "dispu_compact_scratch_bytes": (_sz, [_i, _vp]),
     "dispu_compact_segments": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_cluster_scratch_bytes": (_sz, [_i, _vp]),
+    "dispu_cluster_segments": (_i, [_i, _vp, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dispu_cluster_select_segments": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "dispu_knn_cross_scratch_bytes": (_sz, [_i, _vp, _vp]),
     "dispu_knn_cross_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dispu_transfer_attributes_segments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -62,7 +62,7 @@ extern "C" {
  * dispu_radius_count_*, dispu_outlier_threshold_segments, dispu_compact_*), and the cross-cloud search with the attribute transfer
  * (dispu_knn_cross_*, dispu_transfer_attributes_segments), and the consistent orientation (dispu_orient_consistent_*), and the
  * moving-least-squares projection (dispu_mls_project_*), and the surface reconstruction (dispu_signed_distance_*, dispu_lattice_*,
- * dispu_contour_*): additions only. */
+ * dispu_contour_*), and the clustering (dispu_cluster_*): additions only. */
 int dispu_version(void);
 /* Stream / event / memset operations on raw HIP handles (hipEventRecord, hipStreamWaitEvent, hipMemsetAsync): what a host that
  * re-issues a recorded launch sequence needs beside the kernels (dis-pu_amd/_lib.py:Tape; no reference counterpart: TF's executor). */
@@ -1059,6 +1059,38 @@ size_t dispu_compact_scratch_bytes(int C, const int* off_host);
 int dispu_compact_segments(int C, const int* off, const int* off_host, const float* cloud, int rule, const void* src, const double* stats,
                            int min_neighbors, const int* status, float* out_points, int* out_index, int* new_off, void* scratch,
                            size_t scratch_bytes, void* stream);
+
+/* ---- density-based clustering of whole clouds (exact DBSCAN), csrc/cluster.hip, dis-pu_amd/clusters.py.  The reference has no
+ * counterpart.  Batches, d2, status word, scratch rule and refusals as for the outlier filters above; everything is per segment, fp32.
+ *   r2       = eps * eps, rounded once in fp32; eps finite and > 0.
+ *   core     point i is core when #{ j in its segment : d2_ij <= r2 }, ITSELF INCLUDED and duplicates counted, is >= min_points
+ *            (min_points >= 1; the convention of scikit-learn and Open3D).
+ *   clusters the connected components of the graph on the core points with an edge wherever d2 <= r2 (d2 is symmetric bit for bit).
+ *   ids      0, 1, ... in ascending order of the cluster's smallest core input index.
+ *   border   a non-core point with a core point at d2 <= r2 takes the label of the core point with the smallest (d2 bits, input
+ *            index); every other non-core point is noise, label -1.  A non-core point never joins two clusters.
+ * The labels are a pure function of the input, so the bytes are identical from run to run although the components are found with
+ * integer atomics (min, add, or) whose order is free; no float atomics.  Every device loop is capped and none waits for another
+ * thread; the capped passes are launched a fixed number of times and return at once when the launch before left nothing to do.
+ * labels [sum n_c] int32 in input order;  core_or_null [sum n_c] bytes, 1 for a core point;  sizes_or_null [sum n_c] int32: the entry
+ * zero-fills it, then sizes[off[c] + k] = the number of points labelled k in segment c (border points included), k < nclusters[c];
+ * nclusters [C].  status [C] (device): 0, or 1 for a segment that holds a NaN or an infinite coordinate, or 2 when a capped loop was
+ * still short after the last launch (not reachable by the bounds in csrc/cluster.hip; the caller must treat it as an error); nothing
+ * else is written for a segment with status != 0.  Asynchronous: no read-back, no synchronisation.
+ * scratch: its first DISPU_CLUSTER_HEAD_INTS ints hold afterwards [0, 4) whether link launch 1 .. 4 ran short of a cap (so launch
+ * j + 1 did work iff [j - 1] != 0; launch 1 always works), [4, 8) the same for the four flatten launches, [8] the clusters of the batch.
+ * The yardstick is tests/cluster_oracle.py.  Additions only: dispu_version() stays 5. ------------------------------------------------- */
+#define DISPU_CLUSTER_HEAD_INTS 16
+size_t dispu_cluster_scratch_bytes(int C, const int* off_host);
+int dispu_cluster_segments(int C, const int* off, const int* off_host, float eps, int min_points, const float* cloud, int* labels,
+                           unsigned char* core_or_null, int* sizes_or_null, int* nclusters, int* status, void* scratch,
+                           size_t scratch_bytes, void* stream);
+/* Keep flags for the `keep` largest clusters of every segment among those of size >= min_size, 1 <= keep <= 32, min_size >= 1: the
+ * clusters ordered by size descending, then id ascending.  labels, sizes, nclusters, status as dispu_cluster_segments wrote them.
+ * flags [sum n_c] int32: 1 for a point whose cluster is kept, else 0 (noise, and every point of a segment with status != 0): the src
+ * of dispu_compact_segments at rule 0.  One workgroup per segment, `keep` rounds of a maximum taken in a fixed order. */
+int dispu_cluster_select_segments(int C, const int* off, const int* off_host, const int* labels, const int* sizes, const int* nclusters,
+                                  const int* status, int keep, int min_size, int* flags, void* stream);
 
 /* ---- exact k-NN from one cloud into another, and per-point attributes carried across it: csrc/attributes.hip, dis-pu_amd/attributes.py.
  * The reference interpolates over the three neighbours of a brute-force search (Common/pointnet_util.py:204-208); this is that

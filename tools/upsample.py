@@ -33,6 +33,12 @@ cloud's mean + --outliers_std standard deviations of it, radius those with fewer
 --outliers_radius.  Input cleaning runs first of all (before --grid_size; with --orient input the input normals follow the kept
 points): one stray point shrinks its whole normalised patch.  Output cleaning runs on the upsampled cloud, before --normals.
 
+--keep_clusters K --cluster_eps E (0 = off by default, K = 1 .. 32) keeps only the K largest density clusters of every input cloud on
+the GPU (dis-pu_amd/clusters.py, exact DBSCAN; the reference has no counterpart): a floating blob, the turntable or a second object
+passes both outlier filters and would be upsampled with the object.  A point is core with --cluster_min_points points within E, itself
+included (1, the default: plain Euclidean cluster extraction); clusters below --cluster_min_size points are ignored.  It runs after
+--clean_input and before --grid_size and --denoise_input; the run's log line reports the points dropped.
+
 --attributes idw|nearest (off by default) carries per-point attributes (colour, intensity, labels) onto the output: every column beyond
 the third of each input file is an attribute, and each output point takes the inverse-distance weighted mean over its --attributes_k
 nearest points of the RAW input file (idw), or the row of the nearest one (nearest: labels stay labels), found by an exact search on
@@ -167,6 +173,13 @@ def parse_args(argv=None):
     ap.add_argument("--outliers_std", type=float, default=2.0, help="statistical: keep up to mean + this many standard deviations")
     ap.add_argument("--outliers_radius", type=positive_float, default=None, help="radius: the search radius (needed by `radius`)")
     ap.add_argument("--outliers_min", type=int, default=2, help="radius: keep points with at least this many others within the radius")
+    ap.add_argument("--keep_clusters", type=int, default=0, metavar="K",
+                    help="0: off; K = 1 .. 32: keep only the K largest density clusters of every input cloud (after --clean_input, "
+                         "before --grid_size and --denoise_input); needs --cluster_eps")
+    ap.add_argument("--cluster_eps", type=positive_float, default=None, help="--keep_clusters: the neighbourhood radius E")
+    ap.add_argument("--cluster_min_points", type=int, default=1,
+                    help="--keep_clusters: points within E, the point itself included, that make a core point (1: plain Euclidean clusters)")
+    ap.add_argument("--cluster_min_size", type=int, default=1, help="--keep_clusters: ignore clusters of fewer points")
     ap.add_argument("--attributes", choices=("none", "idw", "nearest"), default="none",
                     help="carry every input column beyond x y z onto the output points: idw (inverse-distance weighted mean over the "
                          "--attributes_k nearest raw input points) or nearest (the nearest one's row; for labels); the output rows are "
@@ -216,6 +229,14 @@ def parse_args(argv=None):
         ap.error("--outliers_std must be finite")
     if a.outliers_min < 1:
         ap.error("--outliers_min must be >= 1, got %d" % a.outliers_min)
+    if not 0 <= a.keep_clusters <= 32:
+        ap.error("--keep_clusters must be in 0 .. 32, got %d" % a.keep_clusters)
+    if a.keep_clusters > 0 and a.cluster_eps is None:
+        ap.error("--keep_clusters K needs --cluster_eps E")
+    if a.cluster_min_points < 1:
+        ap.error("--cluster_min_points must be >= 1, got %d" % a.cluster_min_points)
+    if a.cluster_min_size < 1:
+        ap.error("--cluster_min_size must be >= 1, got %d" % a.cluster_min_size)
     if a.normals == "none" and (a.orient != "none" or a.viewpoint is not None):
         ap.error("--orient and --viewpoint need --normals pca")
     if not 4 <= a.normals_k <= 32:
@@ -245,6 +266,20 @@ def remove_outliers(kind, arrays, a, dev):
             pts, idx = outliers.remove_statistical_outliers(d, k=a.outliers_k, std_ratio=a.outliers_std, return_index=True)
         else:
             pts, idx = outliers.remove_radius_outliers(d, a.outliers_radius, min_neighbors=a.outliers_min, return_index=True)
+        kept += [t.cpu().numpy() for t in pts]
+        index += [t.cpu().numpy() for t in idx]
+    return kept, index
+
+
+def keep_largest_clusters(arrays, a, dev):
+    """the --keep_clusters step on a list of numpy clouds, in groups of at most --max-points -> (kept clouds, kept indices), numpy"""
+    import torch
+    from dispu_amd import clusters
+    kept, index = [], []
+    for group in group_by_budget([c.shape[0] for c in arrays], a.max_points):
+        d = [torch.from_numpy(np.ascontiguousarray(arrays[i], np.float32)).to(dev) for i in group]
+        pts, idx = clusters.keep_clusters(d, a.cluster_eps, min_points=a.cluster_min_points, keep=a.keep_clusters,
+                                          min_size=a.cluster_min_size, return_index=True)
         kept += [t.cpu().numpy() for t in pts]
         index += [t.cpu().numpy() for t in idx]
     return kept, index
@@ -303,10 +338,11 @@ def load_inputs(a, paths):
 
 
 def prepare_inputs(a, paths, clouds, in_normals, dev):
-    """--clean_input, then --grid_size, in place on clouds (and on in_normals, which follow their points) -> removed points per cloud"""
+    """--clean_input, --keep_clusters, --grid_size, then --denoise_input, in place on clouds (and on in_normals, which follow their
+    points) -> (outliers removed per cloud, points dropped with the smaller clusters per cloud)"""
     import torch
     raw = [c.shape[0] for c in clouds]
-    removed = [0] * len(clouds)
+    removed, dropped = [0] * len(clouds), [0] * len(clouds)
     if a.clean_input != "none":
         kept, index = stage("--clean_input: ", remove_outliers, a.clean_input, clouds, a, dev)
         for i, (k, ix) in enumerate(zip(kept, index)):
@@ -314,6 +350,16 @@ def prepare_inputs(a, paths, clouds, in_normals, dev):
                 sys.exit("%s: --clean_input %s leaves %d of %d points, fewer than --patch_num_point %d"
                          % (paths[i], a.clean_input, k.shape[0], raw[i], a.patch_num_point))
             removed[i] = raw[i] - k.shape[0]
+            clouds[i] = k
+            if in_normals is not None:
+                in_normals[i] = np.ascontiguousarray(in_normals[i][ix])
+    if a.keep_clusters > 0:
+        kept, index = stage("--keep_clusters: ", keep_largest_clusters, clouds, a, dev)
+        for i, (k, ix) in enumerate(zip(kept, index)):
+            if k.shape[0] < a.patch_num_point:
+                sys.exit("%s: --keep_clusters %d leaves %d of %d points, fewer than --patch_num_point %d"
+                         % (paths[i], a.keep_clusters, k.shape[0], clouds[i].shape[0], a.patch_num_point))
+            dropped[i] = clouds[i].shape[0] - k.shape[0]
             clouds[i] = k
             if in_normals is not None:
                 in_normals[i] = np.ascontiguousarray(in_normals[i][ix])
@@ -330,7 +376,7 @@ def prepare_inputs(a, paths, clouds, in_normals, dev):
                 clouds[i] = pts.cpu().numpy()
     if a.denoise_input:
         clouds[:] = stage("--denoise_input: ", mls_project, clouds, clouds, a.denoise_input, a, dev)
-    return removed
+    return removed, dropped
 
 
 def orient_argument(a, group, clouds, in_normals, dev):
@@ -421,7 +467,7 @@ def main(argv=None):
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
     raw = [c.shape[0] for c in clouds]
-    removed_in = prepare_inputs(a, paths, clouds, in_normals, dev)
+    removed_in, dropped_in = prepare_inputs(a, paths, clouds, in_normals, dev)
     for group in group_by_budget([c.shape[0] for c in clouds], a.max_points):
         preds, attrs, normals, removed_out = process_group(a, gen, paths, group, clouds, in_normals, src, dev)
         for j, (i, pred) in enumerate(zip(group, preds)):
@@ -430,6 +476,8 @@ def main(argv=None):
             gone = ""
             if a.clean_input != "none" or a.clean_output != "none":
                 gone = ", outliers removed: %d input, %d output" % (removed_in[i], removed_out[j])
+            if a.keep_clusters > 0:
+                gone += ", dropped with the smaller clusters: %d" % dropped_in[i]
             if a.grid_size is None:
                 print("%s: %d -> %d points, %s%s" % (paths[i], clouds[i].shape[0], pred.shape[0], out, gone))
             else:
