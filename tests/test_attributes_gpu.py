@@ -80,9 +80,11 @@ def attrs(m, F, seed=0):
 
 
 class Abi(object):
-    """one packed batch of (queries, references) pairs on the device and what the C entries need; outputs are pre-filled with sentinels"""
+    """one packed batch of (queries, references) pairs on the device and what the C entries need; outputs are pre-filled with sentinels.
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the zero-filled one"""
 
-    def __init__(self, dev, qs, rs, qoff=None, roff=None, C_arg=None):
+    def __init__(self, dev, qs, rs, qoff=None, roff=None, C_arg=None, scratch_buf=None):
+        self.scratch_buf = scratch_buf
         import torch
         import dispu_amd  # noqa: F401
         from dispu_amd import _lib
@@ -103,6 +105,9 @@ class Abi(object):
         full = self.L.dispu_knn_cross_scratch_bytes(len(self.gq) - 1, C.c_void_p(self.gq.ctypes.data), C.c_void_p(self.gr.ctypes.data))
         assert full > 0
         self.buf = self.torch.zeros((full + 64,), dtype=self.torch.uint8, device=self.dev)
+        if self.scratch_buf is not None:
+            assert how in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+            return self.scratch_buf.ptr(), self.scratch_buf.nbytes - (1 if how == "short" else 0)
         if how == "null":
             return C.c_void_p(0), full
         if how == "short":

@@ -46,6 +46,40 @@ def run(dev, p, eps, mp):
     return tuple(t.cpu().numpy() for t in M.dbscan(torch.from_numpy(p).to(dev), eps, mp, return_core=True, return_sizes=True))
 
 
+def run_abi(dev, clouds, eps, mp, scratch="ok", scratch_buf=None):
+    """dispu_cluster_segments itself on a packed batch (run() goes through clusters.py, which allocates its own scratch), every output
+    pre-filled with a sentinel -> dict(rc, labels, core, sizes, nclusters, status).  scratch_buf: the caller's own scratch
+    (tests/scratch_contract.py: .ptr(), .nbytes) in place of a zero-filled one; scratch "short": one byte less than that"""
+    import torch
+    import dispu_amd  # noqa: F401
+    from dispu_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    off = np.zeros(len(clouds) + 1, np.int32)
+    np.cumsum([len(c) for c in clouds], out=off[1:])
+    total, nC = int(off[-1]), len(clouds)
+    cloud_t = torch.from_numpy(np.concatenate(clouds).astype(np.float32)).to(dev)
+    d_off = torch.from_numpy(off).to(dev)
+    full = L.dispu_cluster_scratch_bytes(nC, C.c_void_p(off.ctypes.data))
+    assert full > 0
+    buf = torch.zeros((full,), dtype=torch.uint8, device=dev)
+    assert scratch in ("ok", "short")
+    sp, sb = (p(buf), full) if scratch_buf is None else (scratch_buf.ptr(), scratch_buf.nbytes)
+    if scratch == "short":
+        sb -= 1
+    labels = torch.full((total,), -7, dtype=torch.int32, device=dev)
+    core = torch.full((total,), 9, dtype=torch.uint8, device=dev)
+    sizes = torch.full((total,), -7, dtype=torch.int32, device=dev)
+    ncl = torch.full((nC,), -7, dtype=torch.int32, device=dev)
+    status = torch.full((nC,), -7, dtype=torch.int32, device=dev)
+    rc = L.dispu_cluster_segments(nC, p(d_off), C.c_void_p(off.ctypes.data), eps, mp, p(cloud_t), p(labels), p(core), p(sizes), p(ncl),
+                                  p(status), sp, sb, _lib.stream_ptr(dev))
+    torch.cuda.synchronize(dev)
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(cloud=cloud_t.cpu().numpy(), off=d_off.cpu().numpy())    # as the call left them
+    return dict(rc=rc, labels=labels.cpu().numpy(), core=core.cpu().numpy(), sizes=sizes.cpu().numpy(), nclusters=ncl.cpu().numpy(),
+                status=status.cpu().numpy())
+
+
 def check(got, want):
     labels, core, sizes = got
     assert labels.dtype == np.int32 and core.dtype == np.bool_ and sizes.dtype == np.int32

@@ -37,8 +37,9 @@ def offsets(clouds):
 
 
 def run_abi(dev, srcs, tgts, normals=None, init=None, iterations=1, max_distance=INF, tolerance=0.0, want_corr=True, mode=None,
-            max_d2=None, qoff=None, roff=None, scratch="ok", C_arg=None, null=(), alias=None):
+            max_d2=None, qoff=None, roff=None, scratch="ok", C_arg=None, null=(), alias=None, scratch_buf=None):
     """the C entry on a packed batch of pairs, every output pre-filled with a sentinel -> dict(rc and the names of OUTS).
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the zero-filled one.
     normals: a list like tgts (plane mode) or None;  init: a list of 4 x 4 arrays or None;  mode / max_d2 / qoff / roff / C_arg /
     scratch / null / alias: what a refusal test bends (null: names of pointers passed as NULL; alias: "source" or "target", the array
     `aligned` is made to share)"""
@@ -59,6 +60,9 @@ def run_abi(dev, srcs, tgts, normals=None, init=None, iterations=1, max_distance
     assert full > 0
     buf = torch.zeros((full + 16,), dtype=torch.uint8, device=dev)
     sp, sb = _lib.ptr(buf), full
+    if scratch_buf is not None:
+        assert scratch in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+        sp, sb, full = scratch_buf.ptr(), scratch_buf.nbytes, scratch_buf.nbytes
     if scratch == "null":
         sp = C.c_void_p(0)
     elif scratch == "short":
@@ -87,6 +91,8 @@ def run_abi(dev, srcs, tgts, normals=None, init=None, iterations=1, max_distance
                               _lib.stream_ptr(dev))
     torch.cuda.synchronize(dev)
     assert np.array_equal(N(q).view(np.uint32), q0.view(np.uint32)) and np.array_equal(N(r).view(np.uint32), r0.view(np.uint32))   # inputs are only read
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(queries=N(q), refs=N(r), qoff=N(d_qoff), roff=N(d_roff))    # as the call left them
     res = {name: (N(t) if t is not None else None) for name, t in o.items()}
     res["rc"] = rc
     return res

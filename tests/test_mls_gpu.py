@@ -38,8 +38,10 @@ def offsets(clouds):
     return off
 
 
-def run_abi(dev, qs, rs, k, support=1.0, iterations=1, want_idx=True, qoff=None, roff=None, scratch="ok", C_arg=None, null=(), alias=None):
+def run_abi(dev, qs, rs, k, support=1.0, iterations=1, want_idx=True, qoff=None, roff=None, scratch="ok", C_arg=None, null=(), alias=None,
+            scratch_buf=None):
     """the C entry on a packed batch of pairs, every output pre-filled with a sentinel -> (return code, out, idx, status).
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the zero-filled one.
     qoff / roff / C_arg / scratch / null / alias: what a refusal test bends (null: names of pointers passed as NULL; alias: "queries"
     or "refs", the array `out` is made to share)"""
     import torch
@@ -57,6 +59,9 @@ def run_abi(dev, qs, rs, k, support=1.0, iterations=1, want_idx=True, qoff=None,
     assert full > 0
     buf = torch.zeros((full + 16,), dtype=torch.uint8, device=dev)
     sp, sb = _lib.ptr(buf), full
+    if scratch_buf is not None:
+        assert scratch in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+        sp, sb, full = scratch_buf.ptr(), scratch_buf.nbytes, scratch_buf.nbytes
     if scratch == "null":
         sp = C.c_void_p(0)
     elif scratch == "short":
@@ -78,6 +83,8 @@ def run_abi(dev, qs, rs, k, support=1.0, iterations=1, want_idx=True, qoff=None,
                                       ptrs["out"], _lib.ptr(idx), ptrs["status"], sp, sb, _lib.stream_ptr(dev))
     torch.cuda.synchronize(dev)
     assert np.array_equal(N(q).view(np.uint32), q0.view(np.uint32)) and np.array_equal(N(r).view(np.uint32), r0.view(np.uint32))   # inputs are only read
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(queries=N(q), refs=N(r), qoff=N(d_qoff), roff=N(d_roff))    # as the call left them
     return rc, N(out), (N(idx) if want_idx else None), N(status)
 
 

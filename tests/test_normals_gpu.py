@@ -24,8 +24,9 @@ def N(t):
     return t.detach().cpu().numpy()
 
 
-def run_abi(dev, clouds, k, mode=0, orient=None, want_var=True, want_idx=True, off=None, scratch="ok", C_arg=None):
-    """the C entry on a packed batch, every output pre-filled with a sentinel -> (return code, normal, variation, idx, status)"""
+def run_abi(dev, clouds, k, mode=0, orient=None, want_var=True, want_idx=True, off=None, scratch="ok", C_arg=None, scratch_buf=None):
+    """the C entry on a packed batch, every output pre-filled with a sentinel -> (return code, normal, variation, idx, status).
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the zero-filled one"""
     import torch
     import dispu_amd  # noqa: F401
     from dispu_amd import _lib
@@ -49,6 +50,9 @@ def run_abi(dev, clouds, k, mode=0, orient=None, want_var=True, want_idx=True, o
         sp, sb = C.c_void_p(0), full
     else:                                                       # one byte short
         sp, sb = _lib.ptr(buf), full - 1
+    if scratch_buf is not None:
+        assert scratch in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+        sp, sb = scratch_buf.ptr(), scratch_buf.nbytes - (0 if scratch == "ok" else 1)
     normal = torch.full((total, 3), 7.0, dtype=torch.float32, device=dev)
     var = torch.full((total,), 7.0, dtype=torch.float32, device=dev) if want_var else None
     idx = torch.full((total, k), -7, dtype=torch.int32, device=dev) if want_idx else None
@@ -58,6 +62,8 @@ def run_abi(dev, clouds, k, mode=0, orient=None, want_var=True, want_idx=True, o
     rc = L.dispu_pca_normals_segments(nC, _lib.ptr(d_off), hp, k, _lib.ptr(cloud), mode, _lib.ptr(d_or), _lib.ptr(normal), _lib.ptr(var),
                                       _lib.ptr(idx), _lib.ptr(status), sp, sb, _lib.stream_ptr(dev))
     torch.cuda.synchronize(dev)
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(cloud=N(cloud), off=N(d_off))               # as the call left them
     return rc, N(normal), (N(var) if want_var else None), (N(idx) if want_idx else None), N(status)
 
 

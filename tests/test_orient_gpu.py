@@ -25,9 +25,10 @@ def N(t):
 
 
 def run_abi(dev, cases, k, vote=0, flags=0, want=("flip", "component", "ncomp"), off=None, scratch="ok", C_arg=None, alias=False,
-            drop=None):
+            drop=None, scratch_buf=None):
     """the C entry on a packed batch of (points, normals, neighbours) triples, every output pre-filled with a sentinel
-    -> dict(rc, normal, flip, component, ncomp, status)"""
+    -> dict(rc, normal, flip, component, ncomp, status).  scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(),
+    .nbytes) in place of the zero-filled one"""
     import torch
     import dispu_amd  # noqa: F401
     from dispu_amd import _lib
@@ -52,6 +53,9 @@ def run_abi(dev, cases, k, vote=0, flags=0, want=("flip", "component", "ncomp"),
         sp, sb = C.c_void_p(buf.data_ptr() + 4), full
     else:                                                       # one byte short of what this call needs
         sp, sb = _lib.ptr(buf), L.dispu_orient_consistent_scratch_bytes(len(cases), C.c_void_p(good.ctypes.data), k) - 1
+    if scratch_buf is not None:
+        assert scratch in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+        sp, sb = scratch_buf.ptr(), scratch_buf.nbytes - (0 if scratch == "ok" else 1)
     out = torch.full((total, 3), 7.0, dtype=torch.float32, device=dev)
     flip = torch.full((total,), 9, dtype=torch.uint8, device=dev) if "flip" in want else None
     comp = torch.full((total,), -7, dtype=torch.int32, device=dev) if "component" in want else None
@@ -66,6 +70,8 @@ def run_abi(dev, cases, k, vote=0, flags=0, want=("flip", "component", "ncomp"),
                                             args["normal_out"], _lib.ptr(flip), _lib.ptr(comp), _lib.ptr(ncomp), args["status"], sp, sb,
                                             None, _lib.stream_ptr(dev))
     torch.cuda.synchronize(dev)
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(points=N(pts), normal_in=N(nrm), neighbors=N(nbr), off=N(d_off))   # as the call left them
     return dict(rc=rc, normal=N(out), flip=None if flip is None else N(flip), component=None if comp is None else N(comp),
                 ncomp=None if ncomp is None else N(ncomp), status=N(status), normal_in=N(nrm))
 

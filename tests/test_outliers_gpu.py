@@ -33,9 +33,11 @@ def offsets(clouds):
 
 
 class Abi(object):
-    """one packed batch on the device and what every C entry needs; outputs are pre-filled with sentinels"""
+    """one packed batch on the device and what every C entry needs; outputs are pre-filled with sentinels.
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the zero-filled one"""
 
-    def __init__(self, dev, clouds, off=None, C_arg=None):
+    def __init__(self, dev, clouds, off=None, C_arg=None, scratch_buf=None):
+        self.scratch_buf = scratch_buf
         import torch
         import dispu_amd  # noqa: F401
         from dispu_amd import _lib
@@ -53,6 +55,9 @@ class Abi(object):
     def scratch(self, full, how):
         """-> (pointer, size) of a scratch that is right ("ok"), NULL, one byte short or misaligned"""
         self.buf = self.torch.zeros((full + 64,), dtype=self.torch.uint8, device=self.dev)
+        if self.scratch_buf is not None:
+            assert how in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+            return self.scratch_buf.ptr(), self.scratch_buf.nbytes - (1 if how == "short" else 0)
         if how == "null":
             return C.c_void_p(0), full
         if how == "short":

@@ -25,7 +25,8 @@ def _key_sets(n, bits, rng):
     return sets
 
 
-def _sort(dev, keys, vals, bits):
+def _sort(dev, keys, vals, bits, scratch_buf=None):
+    """scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the uninitialised one"""
     import torch
     from dispu_amd import _lib
     L = _lib.lib()
@@ -36,9 +37,14 @@ def _sort(dev, keys, vals, bits):
     ko, vo = torch.empty_like(k), torch.empty_like(v)
     nbytes = L.dispu_radix_sort_scratch_bytes(n)
     scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    _lib.check(L.dispu_radix_sort_pairs(n, bits, _lib.ptr(k), _lib.ptr(v), _lib.ptr(ko), _lib.ptr(vo), _lib.ptr(scratch), nbytes,
+    sp = _lib.ptr(scratch)
+    if scratch_buf is not None:
+        sp, nbytes = scratch_buf.ptr(), scratch_buf.nbytes
+    _lib.check(L.dispu_radix_sort_pairs(n, bits, _lib.ptr(k), _lib.ptr(v), _lib.ptr(ko), _lib.ptr(vo), sp, nbytes,
                                         _lib.stream_ptr(dev)), "dispu_radix_sort_pairs")
     torch.cuda.synchronize()
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(keys=k.cpu().numpy().view(np.uint64), vals=v.cpu().numpy().view(np.uint32))   # as the call left them
     assert np.array_equal(k.cpu().numpy().view(np.uint64), keys) and np.array_equal(v.cpu().numpy().view(np.uint32), vals), "inputs were written"
     return ko.cpu().numpy().view(np.uint64), vo.cpu().numpy().view(np.uint32)
 

@@ -79,8 +79,9 @@ def sd_oracle(k, support):
     return [R.signed_distance(q, p, n, k, support) for q, p, n in sd_batch()]
 
 
-def run_sd(dev, qs, ps, ns, k, support, qoff=None, roff=None, scratch="ok", C_arg=None, null=(), alias=None):
-    """the C entry on a packed batch, outputs pre-filled with sentinels -> (rc, out, status); inputs must keep their bits"""
+def run_sd(dev, qs, ps, ns, k, support, qoff=None, roff=None, scratch="ok", C_arg=None, null=(), alias=None, scratch_buf=None):
+    """the C entry on a packed batch, outputs pre-filled with sentinels -> (rc, out, status); inputs must keep their bits.
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .nbytes) in place of the zero-filled one"""
     import torch
     import dispu_amd  # noqa: F401
     from dispu_amd import _lib
@@ -93,6 +94,9 @@ def run_sd(dev, qs, ps, ns, k, support, qoff=None, roff=None, scratch="ok", C_ar
     assert full > 0
     buf = torch.zeros((full + 16,), dtype=torch.uint8, device=dev)
     sp, sb = _lib.ptr(buf), full
+    if scratch_buf is not None:
+        assert scratch in ("ok", "short"), "with scratch_buf only a right or a one-byte-short size can be asked for"
+        sp, sb, full = scratch_buf.ptr(), scratch_buf.nbytes, scratch_buf.nbytes
     if scratch == "null":
         sp = C.c_void_p(0)
     elif scratch == "short":
@@ -114,6 +118,8 @@ def run_sd(dev, qs, ps, ns, k, support, qoff=None, roff=None, scratch="ok", C_ar
                                           ptrs["out"], ptrs["status"], sp, sb, _lib.stream_ptr(dev))
     torch.cuda.synchronize(dev)
     assert all(same_bits(N(x), b) for x, b in zip((q, p, n), before))           # inputs are only read
+    if scratch_buf is not None:
+        scratch_buf.inputs = dict(queries=N(q), refs=N(p), normals=N(n), qoff=N(d_qoff), roff=N(d_roff))   # as the call left them
     return rc, N(out), N(status)
 
 

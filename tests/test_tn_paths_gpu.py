@@ -81,8 +81,12 @@ def upload(dev, c, ops):
     return host, t, base
 
 
-def launch(dev, _lib, c, t, base, desc=None):
+def launch(dev, _lib, c, t, base, desc=None, scratch_buf=None):
+    """scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .floats) in place of the case's sentinel-filled one"""
     L = _lib.lib()
+    if scratch_buf is not None:
+        assert c.scratch == "exact" and scratch_buf.floats >= TP.scratch_floats(c) and scratch_buf.ptr().value % 16 == 0
+        base = dict(base, s=scratch_buf.ptr().value)
     args = TP.entry_args(c, base)
     p = TP.plan(c, base)
     assert p == TP.case_plan(c), (c, p, TP.case_plan(c))           # the plan the CPU census saw

@@ -127,10 +127,11 @@ def _cloud(rng, B, n, k):
 # today's shape; the trainer's (8192 rows: the statistics kernels' 1024 workgroups walk eight rows each); 3 clouds of 100; 17408 rows:
 # above the 2048 workgroups x 8 rows of the gradient's apply kernel
 @pytest.mark.parametrize("B,n", [(2, 256), (8, 1024), (3, 100), (17, 1024)])
-def test_wnet_bn_stats_and_grad(dev, L, B, n):
+def test_wnet_bn_stats_and_grad(dev, L, B, n, scratch_buf=None, seed=0):
     """weight_net_hidden in training mode (ops.py:181-191) without its stored input: batch statistics / folded scale+shift / moving
-    statistics against float64, then every gradient (dWw, dbw ~ 0, dgamma, dbeta, dxyz of both points of a pair)."""
-    rng = np.random.default_rng(3)
+    statistics against float64, then every gradient (dWw, dbw ~ 0, dgamma, dbeta, dxyz of both points of a pair).
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr()) in place of the uninitialised one; seed: other inputs"""
+    rng = np.random.default_rng(3 + seed)
     k, t = 16, 16
     xyz, idx = _cloud(rng, B, n, k)
     Ww = (rng.standard_normal((3, t)) * 2).astype(np.float32)
@@ -147,8 +148,9 @@ def test_wnet_bn_stats_and_grad(dev, L, B, n):
     scale, shift = torch.empty(16, dtype=torch.float32, device=dev), torch.empty(16, dtype=torch.float32, device=dev)
     nb = lib.dispu_ps_wnet_scratch_bytes(rows)
     sc = torch.empty(nb // 8 + 1, dtype=torch.float64, device=dev)
+    scp = p(sc) if scratch_buf is None else scratch_buf.ptr()
     L.check(lib.dispu_ps_wnet_bn_stats(rows, n, k, t, p(di), p(dx), p(tw), p(tb), p(tg), p(tbe), 1e-3, 0.95, p(stats), p(scale), p(shift),
-                                       p(mm), p(mv), p(sc), nb, st), "wnet_bn_stats")
+                                       p(mm), p(mv), scp, nb, st), "wnet_bn_stats")
     # float64 reference through the oracle's batch_norm
     xt = torch.tensor(xyz, dtype=F64, requires_grad=True)
     it = torch.tensor(idx.astype(np.int64))
@@ -176,7 +178,7 @@ def test_wnet_bn_stats_and_grad(dev, L, B, n):
     dxyz = torch.zeros((rows, 3), dtype=torch.float32, device=dev)
     sums = torch.empty(32, dtype=torch.float32, device=dev)
     L.check(lib.dispu_ps_wnet_grad(rows, n, k, t, p(di), p(dx), p(tw), p(tb), p(stats), p(scale), p(shift), p(tg), p(dv(g.reshape(-1, t), dev)),
-                                   p(dWw), p(dbw), p(dga), p(dbe), p(dxyz), p(sums), p(sc), nb, st), "wnet_grad")
+                                   p(dWw), p(dbw), p(dga), p(dbe), p(dxyz), p(sums), scp, nb, st), "wnet_grad")
     close(N_(dWw), wt.grad.numpy(), 2e-5, "dWw")
     close(N_(dga), Pt["s/gamma"].grad.numpy(), 1e-5, "dgamma")
     close(N_(dbe), Pt["s/beta"].grad.numpy(), 1e-5, "dbeta")
@@ -444,11 +446,12 @@ def test_mlp_chain_grad(dev, L, shape, fine, rows):
 
 
 @pytest.mark.parametrize("C,B,n", [(24, 2, 256), (48, 2, 256), (48, 1, 100), (24, 3, 36)])
-def test_edge_dense_conv_grad(dev, L, C, B, n):
+def test_edge_dense_conv_grad(dev, L, C, B, n, scratch_buf=None, seed=0):
     """dense_conv + get_edge_feature backward in one launch (csrc/edge_bwd.hip: forward recomputed on chip) against float64 autograd
     of oracle/train_oracle.py:dense_conv; duplicate neighbours make exact arg-max ties (shared evenly); n * B not a multiple of the
-    8-point tile exercises the ragged last tile."""
-    rng = np.random.default_rng(C + n)
+    8-point tile exercises the ragged last tile.
+    scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr()) in place of the uninitialised one; seed: other inputs"""
+    rng = np.random.default_rng(C + n + seed)
     k = 16
     F = rng.standard_normal((B, n, C)).astype(np.float32)
     idx = rng.integers(0, n, (B, n, k + 1)).astype(np.int32)                  # column 0 = "self" (dropped: ioff = 1), as knn_feat returns
@@ -477,11 +480,12 @@ def test_edge_dense_conv_grad(dev, L, C, B, n):
     dW = {kk: torch.zeros(v.shape, dtype=torch.float32, device=dev) for kk, v in P.items()}
     need = lib.dispu_edge_dense_conv_grad_scratch_floats(rows, C)
     sc = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    scp = p(sc) if scratch_buf is None else scratch_buf.ptr()
     for rep in range(2):                                                      # accumulating entry: the second call doubles everything
         L.check(lib.dispu_edge_dense_conv_grad(rows, n, C, p(tF), C, p(ti), k + 1, 1, p(tp["s/l0/weights"]), p(tp["s/l0/biases"]),
                                                p(tp["s/l1/weights"]), p(tp["s/l1/biases"]), p(tp["s/l2/weights"]), p(tp["s/l2/biases"]),
                                                p(dv(g, dev)), 72 + C, p(dF), C, p(dW["s/l0/weights"]), p(dW["s/l0/biases"]), p(dW["s/l1/weights"]),
-                                               p(dW["s/l1/biases"]), p(dW["s/l2/weights"]), p(dW["s/l2/biases"]), p(sc), need, st),
+                                               p(dW["s/l1/biases"]), p(dW["s/l2/weights"]), p(dW["s/l2/biases"]), scp, need, st),
                 "edge_dense_conv_grad")
         close(N_(dF).reshape(B, n, C), (rep + 1) * ft.grad.numpy(), 2e-5, "dF")
         for kk in P:
@@ -493,11 +497,11 @@ def test_edge_dense_conv_grad(dev, L, C, B, n):
     for rep in range(2):
         L.check(lib.dispu_edge_dense_conv_grad_partials(rows, n, C, p(tF), C, p(ti), k + 1, 1, p(tp["s/l0/weights"]), p(tp["s/l0/biases"]),
                                                         p(tp["s/l1/weights"]), p(tp["s/l1/biases"]), p(tp["s/l2/weights"]), p(tp["s/l2/biases"]),
-                                                        p(dv(g, dev)), 72 + C, p(dF2), C, p(sc), need, st), "edge_dense_conv_grad_partials")
+                                                        p(dv(g, dev)), 72 + C, p(dF2), C, scp, need, st), "edge_dense_conv_grad_partials")
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
         side.wait_event(ev)
-        L.check(lib.dispu_edge_dense_conv_grad_reduce(rows, C, p(sc), need, p(dW2["s/l0/weights"]), p(dW2["s/l0/biases"]), p(dW2["s/l1/weights"]),
+        L.check(lib.dispu_edge_dense_conv_grad_reduce(rows, C, scp, need, p(dW2["s/l0/weights"]), p(dW2["s/l0/biases"]), p(dW2["s/l1/weights"]),
                                                       p(dW2["s/l1/biases"]), p(dW2["s/l2/weights"]), p(dW2["s/l2/biases"]),
                                                       ctypes.c_void_p(side.cuda_stream)), "edge_dense_conv_grad_reduce")
         torch.cuda.current_stream(dev).wait_stream(side)                      # the next pass overwrites the partials

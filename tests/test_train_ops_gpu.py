@@ -81,8 +81,9 @@ def ids(cases):
 
 
 # ----------------------------------------------------------------------------------------- dispu_act_bias_grad ----
-def abg(dev, L, rows, n, act, dz, dbias, acc, ld=(None, None, None), off=(0, 0, 0), seed=0, short=0, expect=0):
-    """one call and every check of it.  dz: "none" (NULL), "alias" (dZ = dY's own window) or "sep"; ld / off: stride and column offset
+def abg(dev, L, rows, n, act, dz, dbias, acc, ld=(None, None, None), off=(0, 0, 0), seed=0, short=0, expect=0, scratch_buf=None):
+    """one call and every check of it.  scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(), .floats,
+    .guards_intact()) in place of the sentinel-filled one.  dz: "none" (NULL), "alias" (dZ = dY's own window) or "sep"; ld / off: stride and column offset
     of dY, Y, dZ (an offset of 1 under a stride that is a multiple of 4 is a pointer that is not 16-byte aligned); short: floats
     withheld from the scratch.  expect != 0: the call must be refused and write nothing."""
     rng = np.random.default_rng(1000 * seed + n)
@@ -96,8 +97,11 @@ def abg(dev, L, rows, n, act, dz, dbias, acc, ld=(None, None, None), off=(0, 0, 
     need = L.lib().dispu_act_bias_grad_scratch_floats(rows, n) if dbias else 0
     assert need > 0 or not dbias or rows == 0
     sc = Guarded(dev, max(need - short, 0))
+    scn = sc.n
+    if scratch_buf is not None:
+        sc, scn = scratch_buf, scratch_buf.floats - short
     rc = run(L, dev, "dispu_act_bias_grad", rows, n, sdy.ptr(), ld[0], sy.ptr(), ld[1], act, sdz.ptr() if sdz else None,
-             sdz.ld if sdz else 0, gdb.ptr() if dbias else None, acc, sc.ptr(), sc.n)
+             sdz.ld if sdz else 0, gdb.ptr() if dbias else None, acc, sc.ptr(), scn)
     assert rc == expect, "returned %d" % rc
     assert sy.untouched() and sc.guards_intact()
     what = "act_bias_grad %d x %d act %d dZ %s acc %d" % (rows, n, act, dz, acc)
@@ -387,9 +391,10 @@ def bn_scratch(dev, L, rows, c):
     return Guarded(dev, nb // 4), nb
 
 
-def bn_both(dev, L, rows, c, ldx, ldy, lddy, lddx, act, alias, moving, dgb, special=None, what=""):
-    """bn_train, then bn_train_grad on its outputs."""
-    rng = np.random.default_rng(rows + c)
+def bn_both(dev, L, rows, c, ldx, ldy, lddy, lddx, act, alias, moving, dgb, special=None, what="", scratch_buf=None, seed=0):
+    """bn_train, then bn_train_grad on its outputs.  scratch_buf: the caller's own scratch (tests/scratch_contract.py: .ptr(),
+    .guards_intact()) in place of the sentinel-filled one; seed: other inputs of the same sizes"""
+    rng = np.random.default_rng(rows + c + seed)
     X, gamma, beta = bn_inputs(rng, rows, c, special)
     mm0, mv0 = rng.standard_normal(c).astype(F32), rng.uniform(0.5, 1.5, c).astype(F32)
     f = TO.bn_train(X, gamma, beta, EPS, DECAY, act, mm0, mv0)
@@ -399,6 +404,8 @@ def bn_both(dev, L, rows, c, ldx, ldy, lddy, lddx, act, alias, moving, dgb, spec
     gm, gv = (Guarded(dev, c, fill=mm0), Guarded(dev, c, fill=mv0)) if moving else (None, None)
     ga, be = dv(gamma, dev), dv(beta, dev)
     sc, nb = bn_scratch(dev, L, rows, c)
+    if scratch_buf is not None:
+        sc = scratch_buf
     ok(L, dev, "dispu_bn_train", rows, c, sx.ptr(), sx.ld, p(ga), p(be), EPS, DECAY, act, sy.ptr(), sy.ld, stats.ptr(),
        gm.ptr() if moving else None, gv.ptr() if moving else None, sc.ptr(), nb)
     what = "bn %d x %d act %d %s" % (rows, c, act, what)
